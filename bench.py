@@ -56,6 +56,12 @@ VALU_PEAK_SOURCE = 'profiles/r06_valu_rate.txt (measured: v_pk_* 4.15 cycles per
 K3_FLOOR_OPS = 22                           # packed operations per cell pair of K3's recurrences, nothing else counted (see FullStep.launches)
 WINDOW = 2000
 B_ASCII = np.frombuffer(b'ACGTN', dtype=np.uint8)
+# --dump-outputs: the fields of an alignment row the call path asks for (no second best, no CIGAR), the seeded sample of reads whose
+# consensus bases are written (all of them would be ~50 MB as float32), and the cap on everything written
+CALL_ROW_FIELDS = ('score1', 'ref_begin1', 'ref_end1', 'read_begin1', 'read_end1', 'status')
+DUMP_SEED = 20211015
+DUMP_CCS_READS = 2048
+DUMP_MAX_BYTES = 64 << 20
 
 
 def clip_len(n):
@@ -349,7 +355,25 @@ class FullStep(object):
                                           'clip_base': cb, 'host_mask': self.zeros32}, 10, 3, True)     # 6. K6
         t3 = time.perf_counter()
         self.t_k5 += t1 - t0; self.t_fetch += t2 - t1; self.t_k6 += t3 - t2
-        self.last = {'rows': rows, 'sig': sig, 'keep': keep, 'clips': d_clips}
+        self.last = {'rows': rows, 'sig': sig, 'keep': keep, 'clips': d_clips, 'ncount': ncount}
+
+    def outputs(self):
+        """what the last step handed its caller, for --dump-outputs (call it before anything else runs the consensus plan): the consensus
+        of every read (K2 + K3: row, segments, the bases of a seeded sample of reads), and per read with a consensus the N count of its
+        window (K5), its alignment row (K1) and its splice-signal row (K6)"""
+        crow, csegs, ccs = self.ccs_plan.fetch()
+        nseg = np.clip(crow['nseg'], 0, csegs.shape[1])
+        sample = np.sort(np.random.Generator(np.random.PCG64(DUMP_SEED)).choice(self.nreads, min(DUMP_CCS_READS, self.nreads), replace=False))
+        bases = [ccs[self.ro[k]:self.ro[k] + max(int(crow['ccs_len'][k]), 0)] if nseg[k] > 0 else ccs[:0] for k in sample]
+        rows = self.last['rows']
+        return {'consensus_rows': np.stack([crow[f] for f in crow.dtype.names], axis=1).astype(np.float64),
+                'consensus_segments': csegs[np.arange(csegs.shape[1])[None, :] < nseg[:, None]].astype(np.float64),
+                'consensus_sample_reads': sample.astype(np.float64),
+                'consensus_sample_lengths': np.array([len(b) for b in bases], dtype=np.float64),
+                'consensus_sample_bases': np.concatenate(bases).astype(np.float32),
+                'window_n_count': self.last['ncount'].astype(np.float64),
+                'ssw_rows': np.stack([rows[f] for f in CALL_ROW_FIELDS], axis=1).astype(np.float64),
+                'splice_signals': self.last['sig'].astype(np.float64)}
 
     def counters(self):
         """the seven counters of `call` (main.py:50-51, 96-100) as this step fills them"""
@@ -409,7 +433,7 @@ class FullStep(object):
         return out, valu
 
 
-def run_full(torch, dist, hip, synth, ctx, wl, nreads, rank, world, steps, warmup, expect, use_dist=False, prod_windows=False):
+def run_full(torch, dist, hip, synth, ctx, wl, nreads, rank, world, steps, warmup, expect, use_dist=False, prod_windows=False, outputs=False):
     fs = FullStep(torch, hip, synth, ctx, wl, nreads, rank, expect, prod_windows)
     for _ in range(warmup):
         fs.step()
@@ -424,6 +448,7 @@ def run_full(torch, dist, hip, synth, ctx, wl, nreads, rank, world, steps, warmu
     if use_dist:
         dist.barrier()
     el = time.perf_counter() - t0
+    dumped = fs.outputs() if outputs else None
     counters = fs.counters()
     if use_dist:
         t = torch.tensor([el], dtype=torch.float64, device='cuda')
@@ -475,11 +500,13 @@ def run_full(torch, dist, hip, synth, ctx, wl, nreads, rank, world, steps, warmu
         res['prefilter'] = pf_stats
     if pf_check:
         res['prefilter_check'] = pf_check
+    if outputs:
+        res['outputs'] = dumped
     fs.genome.close()
     return res
 
 
-def run_c2(torch, dist, hip, synth, ctx, nreads, rank, world, steps, warmup, expect, use_dist=False):
+def run_c2(torch, dist, hip, synth, ctx, nreads, rank, world, steps, warmup, expect, use_dist=False, outputs=False):
     reads, wins = make_batch(synth, 'c2', nreads, rank)
     rd, ro = hip.pack(reads)
     fd, fo = hip.pack(wins)
@@ -509,14 +536,17 @@ def run_c2(torch, dist, hip, synth, ctx, nreads, rank, world, steps, warmup, exp
     lanes = [(ssw_plan, stream), (plan_b, tstream_b.cuda_stream)]
 
     def run_steps(k):
+        """-> (rows, CIGARs) of the last step"""
+        got = None
         if k <= 0:
-            return
+            return got
         lanes[0][0].run(d_reads.data_ptr(), d_wins.data_ptr(), lanes[0][1])
         for s_ in range(k):
             if s_ + 1 < k:
                 pl, st_ = lanes[(s_ + 1) & 1]
                 pl.run(d_reads.data_ptr(), d_wins.data_ptr(), st_)
-            lanes[s_ & 1][0].fetch()                # rows and CIGARs on the host inside the timed region
+            got = lanes[s_ & 1][0].fetch()          # rows and CIGARs on the host inside the timed region
+        return got
 
     # both lanes warm (events created, first launches done) whatever --warmup is, and the second plan's answers checked against the first's
     # (the oracle spot check above saw only ssw_plan; plan_b produces half of the timed fetches)
@@ -528,7 +558,7 @@ def run_c2(torch, dist, hip, synth, ctx, nreads, rank, world, steps, warmup, exp
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    run_steps(steps)
+    last = run_steps(steps)
     torch.cuda.synchronize()
     if use_dist:
         dist.barrier()
@@ -538,8 +568,13 @@ def run_c2(torch, dist, hip, synth, ctx, nreads, rank, world, steps, warmup, exp
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
     launches, valu = k1_launches(ssw_plan, lambda: ssw_plan.run(d_reads.data_ptr(), d_wins.data_ptr(), stream), ro, np.diff(fo), c2=True)
-    return {'value': world * nreads * steps / el, 'ms_per_step': el / steps * 1e3, 'launches': launches, 'valu_roofline': valu,
-            'roofline': roofline_of(launches)}
+    res = {'value': world * nreads * steps / el, 'ms_per_step': el / steps * 1e3, 'launches': launches, 'valu_roofline': valu,
+           'roofline': roofline_of(launches)}
+    if outputs:         # the complete s_align of every read: every field of its row, and the CIGARs (len << 4 | op: exact in float32)
+        rows, cig = last
+        assert not len(cig) or int(cig.max()) < 1 << 24
+        res['outputs'] = {'ssw_rows': np.stack([rows[f] for f in rows.dtype.names], axis=1).astype(np.float64), 'cigar': cig.astype(np.float32)}
+    return res
 
 
 # ---- the further lines of `extra` (N = 1 only) -------------------------------------------------------------------------
@@ -1019,6 +1054,16 @@ def emit(out, detail_path=None):
     sys.stdout.flush()
 
 
+def dump_outputs(arrays, path):
+    """--dump-outputs: every array as path/<name>.npy; float32 / float64 only, DUMP_MAX_BYTES in all"""
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, 'outputs of %d bytes: over the %d-byte cap' % (total, DUMP_MAX_BYTES)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, name + '.npy'), a)
+
+
 # ------------------------------------------------------------------------------------------------------------------
 def under_profiler():
     """rocprofv3 (or another HSA tool library) is preloaded into this process: the GPU is initialised already"""
@@ -1064,7 +1109,11 @@ def main():
     ap.add_argument('--prod-windows', action='store_true', help='c3 / c4 with the reference\'s own clip window (hit +- 200 kb, find_bsj.py:196-197) instead of 2 kb: the extra line c3_production_windows as the main workload (for profiling)')
     ap.add_argument('--detail', default=None, help='where the full record goes (default: bench_detail.json beside bench.py); stdout carries one short line')
     ap.add_argument('--no-extra', action='store_true', help='skip the extra lines (c2, c4, production shape, collapse, stage 1)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the last timed step computed as DIR/<name>.npy (float32/float64, '
+                    'rank 0\'s shard), so that two builds can be compared output for output on the same seeded inputs')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     wl = args.workload
     full = wl != 'c2'            # c3 / c4: the whole device part of `call`; c2: Smith-Waterman only
     nreads = args.reads or {'c3': 100000, 'c2': 10000, 'c4': 125000}[wl]
@@ -1116,10 +1165,14 @@ def main():
     from ciri_long_amd import hip, synth
     expect = cpu.pop('_expect') if cpu else None     # None: no CPU leg in this run (multi-GPU, --no-cpu, profiler): no spot check
     ctx = hip.Context(local_rank)
+    dump = args.dump_outputs is not None and rank == 0
     if full:
-        res = run_full(torch, dist, hip, synth, ctx, wl, nreads, rank, world, args.steps, args.warmup, None if args.prod_windows else expect, use_dist, prod_windows=args.prod_windows)
+        res = run_full(torch, dist, hip, synth, ctx, wl, nreads, rank, world, args.steps, args.warmup, None if args.prod_windows else expect, use_dist,
+                       prod_windows=args.prod_windows, outputs=dump)
     else:
-        res = run_c2(torch, dist, hip, synth, ctx, nreads, rank, world, args.steps, args.warmup, expect, use_dist)
+        res = run_c2(torch, dist, hip, synth, ctx, nreads, rank, world, args.steps, args.warmup, expect, use_dist, outputs=dump)
+    if dump:
+        dump_outputs(res.pop('outputs'), args.dump_outputs)
 
     step_text = ('through the device part of the call path, start to finish in every timed step: cyclic consensus (K2+K3) of every '
                  'read; the clipped part of each consensus gathered on the device from that step\'s K3 output; N count of the candidate '

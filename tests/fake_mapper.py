@@ -43,6 +43,12 @@ class FakeGenome(object):
         return None if g is None else g[max(start, 0):end]
 
 
+# (contig, query) -> the alignment, shared by every mapper of the process and inherited by forked workers.  Without the reference's
+# library (oracle/_ref) the scalar checker aligns some 16 times slower; the same reads are mapped again and again by the tests (once per
+# stage route), so each is aligned once, and a double that holds the interpreter lock (test_mapper_pool.py) spends its time in that lock.
+_ALIGNED = {}
+
+
 class FakeMapper(object):
     def __init__(self, genome, min_score=40):
         self.genome = genome
@@ -51,6 +57,12 @@ class FakeMapper(object):
         self._codes = {k: oracle_lib.encode(v) for k, v in genome.genome.items()}
         self.calls = 0
 
+    def _aligned(self, ctg, q):
+        key = (self.genome.genome[ctg], q)
+        if key not in _ALIGNED:
+            _ALIGNED[key] = self._align(self._codes[ctg], q, *SCHEME)
+        return _ALIGNED[key]
+
     def map(self, seq):
         self.calls += 1
         if not seq:
@@ -58,7 +70,7 @@ class FakeMapper(object):
         hits = []
         for ctg in sorted(self._codes):
             for strand, q in ((1, seq), (-1, rc(seq))):
-                res = self._align(self._codes[ctg], q, *SCHEME)
+                res = self._aligned(ctg, q)
                 if res is not None and res['score'] >= self.min_score and res['cigar']:
                     hits.append(FakeHit(ctg, strand, res, len(seq)))
         if not hits:
