@@ -139,7 +139,7 @@ struct clh_plan {
     clh::SswParams params;          // device pointers filled at run time
     bool quirk = false, do_cigar = false;
     std::vector<clh::SswTask> tasks;    // launch order
-    struct Seg { int rv, begin, count; int64_t ws_off = 0; int ws_slot = 0, ws_wgs = 0; };      // ws_*: K1w classes, the workspaces of their persistent workgroups
+    struct Seg { int rv, begin, count; int64_t ws_off = 0; int ws_slot = 0, ws_wgs = 0; int lmax = 0; };      // ws_*: K1w classes, the workspaces of their persistent workgroups; lmax: K1a classes, longest read
     void* d_seg_ctr = nullptr;               // one work counter per segment
     std::vector<clh::ScanSlice> slices;      // window slices of the sliced scan class (one segment at most)
     void *d_slices = nullptr, *d_parts = nullptr;
@@ -173,6 +173,8 @@ struct clh_plan {
     int64_t refs_bytes = -1;                 // size of the caller's refs buffer if stated (clh_plan_set_refs_bytes), else -1
     std::vector<hipEvent_t> chain_ev;   // between the parts of a split K1w class
     std::vector<hipEvent_t> ev;     // per segment: K1 start, K1 stop; then K1b small-window start/stop, large-window start/stop
+    bool alpha = false;             // matrix edge 6..32: every alignment in the K1a classes (ssw_alpha.hip)
+    void* d_alpha_mat = nullptr;    // their n x n matrix
 };
 
 extern "C" void clh_plan_destroy(clh_plan* pl)
@@ -182,7 +184,7 @@ extern "C" void clh_plan_destroy(clh_plan* pl)
     (void)hipSetDevice(c->device);
     if (pl->ran) (void)hipStreamSynchronize(pl->last_stream);
     void* bufs[] = {pl->d_tasks, pl->d_results, pl->d_colmax, pl->d_cigars, pl->d_cigar_len, pl->d_pool, pl->d_pool_head,
-                    pl->d_reads, pl->d_refs, pl->d_strips, pl->d_slices, pl->d_parts, pl->d_slice_base, pl->d_seg_ctr};
+                    pl->d_reads, pl->d_refs, pl->d_strips, pl->d_slices, pl->d_parts, pl->d_slice_base, pl->d_seg_ctr, pl->d_alpha_mat};
     for (void* b : bufs) c->release(b);
     for (auto& f : pl->pf) { void* pb[] = {f.d_win, f.d_pieces, f.d_work, f.d_dmin, f.d_queue, f.d_out, f.d_ctl, f.d_bound, f.d_parts, f.d_q2}; for (void* b : pb) c->release(b); }
     for (hipEvent_t e : pl->ev) (void)hipEventDestroy(e);
@@ -190,6 +192,14 @@ extern "C" void clh_plan_destroy(clh_plan* pl)
     for (hipEvent_t e : pl->chain_ev) (void)hipEventDestroy(e);
     if (pl->done_ev) (void)hipEventDestroy(pl->done_ev);
     delete pl;
+}
+
+// K1a (ssw_alpha.hip): the read-length bucket of an alignment over a matrix of edge 6..32
+static int alpha_class_for(int64_t L)
+{
+    for (int b = 0; b < clh::kNumAlphaBuckets - 1; ++b)
+        if (L <= clh::kAlphaRows[b]) return clh::kRvAlpha - b;
+    return clh::kRvAlpha - (clh::kNumAlphaBuckets - 1);
 }
 
 static int rv_class_for(int rows)
@@ -279,18 +289,22 @@ static clh_plan* ssw_plan_build(clh_ctx* ctx, int32_t n, const int64_t* read_off
                                 const int32_t* mask_len, const clh_ssw_opts* o)
 {
     if (!ctx || n < 0 || !read_off || (!ref_off && (!win_off || !win_len)) || !o || !o->mat) { fail(CLH_E_ARG, "clh_ssw_plan: null argument"); return nullptr; }
-    if (o->n_mat < 1 || o->n_mat > 5) { fail(CLH_E_UNSUPPORTED, "substitution matrix edge must be 1..5"); return nullptr; }
+    if (o->n_mat < 1) { fail(CLH_E_UNSUPPORTED, "substitution matrix edge must be 1..32"); return nullptr; }
     if (o->gap_open < o->gap_extend) {
         fail(CLH_E_UNSUPPORTED, "gap_open < gap_extend: the reference's 8-bit lazy-F loop is not a plain recurrence there; not implemented");
         return nullptr;
     }
+    if (o->n_mat > 32) { fail(CLH_E_UNSUPPORTED, "substitution matrix edge must be 1..32"); return nullptr; }
+    // matrix edge 6..32 (protein alphabets): the K1a classes take every alignment; the resident genome is DNA
+    const bool alpha = o->n_mat > 5;
+    if (alpha && !ref_off) { fail(CLH_E_UNSUPPORTED, "windows of a resident genome take substitution matrices of edge 1..5 only"); return nullptr; }
     if (hipSetDevice(ctx->device) != hipSuccess) { fail(CLH_E_HIP, "hipSetDevice failed"); return nullptr; }
     clh_plan* pl = new clh_plan();
     pl->ctx = ctx; pl->n = n; pl->opts = *o;
     clh::SswParams& P = pl->params;
     memset(&P, 0, sizeof(P));
     int mn = 0, mx = -128;
-    for (int i = 0; i < o->n_mat * o->n_mat; ++i) { P.mat[i] = o->mat[i]; mn = std::min(mn, (int)o->mat[i]); mx = std::max(mx, (int)o->mat[i]); }
+    for (int i = 0; i < o->n_mat * o->n_mat; ++i) { if (!alpha) P.mat[i] = o->mat[i]; mn = std::min(mn, (int)o->mat[i]); mx = std::max(mx, (int)o->mat[i]); }
     P.n = o->n_mat; P.gapO = o->gap_open; P.gapE = o->gap_extend; P.bias = -mn; P.max_match = mx; P.score_size = o->score_size;
     P.flag = o->flag; P.filters = o->filters; P.filterd = o->filterd;
     P.null_code = 5;
@@ -300,6 +314,7 @@ static clh_plan* ssw_plan_build(clh_ctx* ctx, int32_t n, const int64_t* read_off
         if (z) P.null_code = 4;
     }
     pl->opts.mat = nullptr;
+    pl->alpha = alpha;
     pl->quirk = o->gap_open <= o->gap_extend;
     pl->do_cigar = o->want_cigar && (o->flag & 7) != 0;
     if (!(o->score_size == 0 || o->score_size == 1 || o->score_size == 2)) {
@@ -314,7 +329,7 @@ static clh_plan* ssw_plan_build(clh_ctx* ctx, int32_t n, const int64_t* read_off
     int n_short_ref = 0;                     // alignments K1l could take: enough of them fill the GPU's lanes whatever their read length
     for (int a = 0; a < n; ++a) {
         const int64_t L = read_off[a + 1] - read_off[a], R = ref_off ? ref_off[a + 1] - ref_off[a] : (int64_t)win_len[a];
-        n_short_ref += lanes_class_for(L, R, o, mx, -mn, P.null_code, true) != 0;
+        n_short_ref += !alpha && lanes_class_for(L, R, o, mx, -mn, P.null_code, true) != 0;
     }
     const bool many_short_ref = n_short_ref >= 32768;
     for (int a = 0; a < n; ++a) {
@@ -322,8 +337,9 @@ static clh_plan* ssw_plan_build(clh_ctx* ctx, int32_t n, const int64_t* read_off
         if (L < 1 || R < 0 || L > 0x7fffffff || R > 0x7fffffff) { fail(CLH_E_ARG, "empty read or negative length in batch"); delete pl; return nullptr; }
         const int rc = (!ref_off && win_rc && win_rc[a]) ? 1 : 0;
         const int rows = (int)((L + 15) / 16) * 16;
-        const int lanes_rv = lanes_class_for(L, R, o, mx, -mn, P.null_code, many_short_ref);
-        const int rv = lanes_rv ? lanes_rv : scan_class_ok(L, o, mx, -mn) ? (scan_sliced(R, o) ? clh::kRvScanSliced : clh::kRvScan)
+        const int lanes_rv = alpha ? 0 : lanes_class_for(L, R, o, mx, -mn, P.null_code, many_short_ref);
+        const int rv = alpha ? alpha_class_for(L)
+                     : lanes_rv ? lanes_rv : scan_class_ok(L, o, mx, -mn) ? (scan_sliced(R, o) ? clh::kRvScanSliced : clh::kRvScan)
                                                     : (scanw_class_ok(L, R, o, mx) ? clh::kRvScanWide
                                                        : (scanw_sliced_ok(L, R, o, mx) ? clh::kRvScanWideSliced : rv_class_for(rows)));
         cls[a] = rv;
@@ -358,7 +374,7 @@ static clh_plan* ssw_plan_build(clh_ctx* ctx, int32_t n, const int64_t* read_off
     // (started that far before its owned columns) computes the whole-window H there; a later slice that sees the same cell
     // in its overlap can only underestimate, and loses the tie.  The reverse pass of the owning slice runs inside the slice.
     int n_all = n;
-    if (!o->want_score2 && o->gap_extend >= 1 && !getenv("CLH_NO_SLICES")) {
+    if (!alpha && !o->want_score2 && o->gap_extend >= 1 && !getenv("CLH_NO_SLICES")) {
         for (int a = 0; a < n; ++a) {
             if (cls[a] < 1 || cls[a] == clh::kRvStrips || pl->tasks[a].ref_len < kSliceMinWindow) continue;
             const clh::SswTask par = pl->tasks[a];
@@ -422,6 +438,24 @@ static clh_plan* ssw_plan_build(clh_ctx* ctx, int32_t n, const int64_t* read_off
         pl->strip_bytes = (pl->strip_bytes + 255) & ~(size_t)255;
         sg.ws_off = (int64_t)pl->strip_bytes;
         pl->strip_bytes += (size_t)sg.ws_slot * (size_t)sg.ws_wgs;
+    }
+    for (auto& sg : pl->segs) {
+        if (!clh::rv_is_alpha(sg.rv)) continue;
+        for (int k = 0; k < sg.count; ++k) sg.lmax = std::max(sg.lmax, (int)pl->tasks[sg.begin + k].read_len);
+        if (sg.lmax <= clh::kAlphaLdsRows) continue;
+        // the global form: pass state of the longest read per persistent workgroup
+        sg.ws_slot = (int)((clh::alpha_lds_bytes(sg.lmax) + 255) & ~(size_t)255);
+        sg.ws_wgs = std::min(sg.count, ctx->n_cu * 8);
+        pl->strip_bytes = (pl->strip_bytes + 255) & ~(size_t)255;
+        sg.ws_off = (int64_t)pl->strip_bytes;
+        pl->strip_bytes += (size_t)sg.ws_slot * (size_t)sg.ws_wgs;
+    }
+    if (alpha) {
+        pl->d_alpha_mat = ctx->alloc((size_t)o->n_mat * (size_t)o->n_mat);
+        if (!pl->d_alpha_mat || hipMemcpy(pl->d_alpha_mat, o->mat, (size_t)o->n_mat * (size_t)o->n_mat, hipMemcpyHostToDevice) != hipSuccess) {
+            fail(CLH_E_HIP, "out of device memory while building the plan");
+            clh_plan_destroy(pl); return nullptr;
+        }
     }
     pl->d_seg_ctr = ctx->alloc(sizeof(int) * std::max<size_t>(pl->segs.size(), 1));
     for (const auto& sg : pl->segs) {
@@ -755,7 +789,7 @@ extern "C" int clh_ssw_run(clh_plan* pl, const void* d_reads, const void* d_refs
     std::vector<size_t> ord(pl->segs.size());
     for (size_t k = 0; k < ord.size(); ++k) ord[k] = k;
     std::sort(ord.begin(), ord.end(), [&](size_t x, size_t y) {
-        auto weight = [](int rv) { return rv == clh::kRvStrips ? 1000 : (rv == clh::kRvScanWide ? 900 : (rv == clh::kRvScanWideSliced ? 800 : (rv == clh::kRvScanTr ? 700 : rv))); };      // (K1w: whole long reads, one wave each)
+        auto weight = [](int rv) { return rv == clh::kRvStrips ? 1000 : (rv == clh::kRvScanWide ? 900 : (rv == clh::kRvScanWideSliced ? 800 : (rv == clh::kRvScanTr ? 700 : (clh::rv_is_alpha(rv) ? 600 + clh::kRvAlpha - rv : rv)))); };      // (K1w: whole long reads, one wave each; K1a: longest reads first)
         const int rx = weight(pl->segs[x].rv), ry = weight(pl->segs[y].rv);
         return rx > ry;
     });
@@ -828,7 +862,8 @@ extern "C" int clh_ssw_run(clh_plan* pl, const void* d_reads, const void* d_refs
         } else if (s.rv == clh::kRvScanSliced) {
             P.slices = (const clh::ScanSlice*)pl->d_slices; P.parts = (clh::ScanPart*)pl->d_parts;
             HIPCHK(clh::launch_ssw_scan_sliced(pl->quirk, P, s.count, (int)pl->slices.size(), ls));
-        } else if (clh::rv_is_lanes(s.rv)) HIPCHK(clh::launch_ssw_lanes(clh::rv_lanes_columns(s.rv), P, s.count, ls));
+        } else if (clh::rv_is_alpha(s.rv)) HIPCHK(clh::launch_ssw_alpha(P, (const int8_t*)pl->d_alpha_mat, s.count, s.lmax, s.ws_wgs, (long long)s.ws_off, s.ws_slot, ls));
+        else if (clh::rv_is_lanes(s.rv)) HIPCHK(clh::launch_ssw_lanes(clh::rv_lanes_columns(s.rv), P, s.count, ls));
         else if (s.rv == clh::kRvScan) HIPCHK(clh::launch_ssw_scan(pl->quirk, P, s.count, ls));
         else if (s.rv == clh::kRvScanTr) {
             int* ctr = (int*)pl->d_seg_ctr + k;
@@ -848,7 +883,12 @@ extern "C" int clh_ssw_run(clh_plan* pl, const void* d_reads, const void* d_refs
             ls = c->side[(i_wide - 1) % 3];
             HIPCHK(hipStreamWaitEvent(ls, pl->chain_ev[i_wide - 1], 0));
         }
-        if (tb && !pl->profiling) { if (int rc = traceback(s.begin, s.count, (int)(k % clh::kTbMaxSeg), s.rv, ls)) return rc; }
+        if (tb && !pl->profiling) {
+            if (clh::rv_is_alpha(s.rv))
+                HIPCHK(clh::launch_ssw_alpha_traceback(PG, (const int8_t*)pl->d_alpha_mat, s.begin, s.count, pl->n_all, (int)(k % clh::kTbMaxSeg), s.lmax,
+                                                       pool, head, pl->pool_bytes, ls));
+            else if (int rc = traceback(s.begin, s.count, (int)(k % clh::kTbMaxSeg), s.rv, ls)) return rc;
+        }
     }
     if (fan)
         for (int i = 0; i < 3; ++i) {
@@ -864,7 +904,15 @@ extern "C" int clh_ssw_run(clh_plan* pl, const void* d_reads, const void* d_refs
         if (pl->profiling) HIPCHK(hipEventRecord(pl->ev[2 * k + 1], st));
         if (tb && !pl->profiling) { if (int rc = traceback(s.begin, s.count, (int)(k % clh::kTbMaxSeg), rv_all, st)) return rc; }
     }
-    if (tb && pl->profiling) {   // profiling runs: the traceback of all classes as serial launches after the score kernels
+    if (tb && pl->profiling && pl->alpha) {   // profiling runs of the K1a classes: their tracebacks after the score kernels, as one span
+        HIPCHK(hipEventRecord(pl->ev[eb + 0], st));
+        for (size_t k = 0; k < pl->segs.size(); ++k)
+            HIPCHK(clh::launch_ssw_alpha_traceback(PG, (const int8_t*)pl->d_alpha_mat, pl->segs[k].begin, pl->segs[k].count, pl->n_all,
+                                                   (int)(k % clh::kTbMaxSeg), pl->segs[k].lmax, pool, head, pl->pool_bytes, st));
+        HIPCHK(hipEventRecord(pl->ev[eb + 1], st));
+        HIPCHK(hipEventRecord(pl->ev[eb + 2], st));
+        HIPCHK(hipEventRecord(pl->ev[eb + 3], st));
+    } else if (tb && pl->profiling) {   // profiling runs: the traceback of all classes as serial launches after the score kernels
         const int rvmax = 32;
         HIPCHK(hipEventRecord(pl->ev[eb + 0], st));
         if (tb_rows_on()) HIPCHK(clh::launch_traceback_rows(PG, 0, pl->n_all, pl->n_all, 0, pool, head, pl->pool_bytes, st));
@@ -1002,6 +1050,10 @@ extern "C" int clh_ssw_fetch(clh_plan* pl, clh_align_t* out, uint32_t* cigar_buf
     std::vector<clh::SswResult> res((size_t)std::max(n, 1));
     std::vector<int32_t> clen((size_t)std::max(n, 1), 0);
     if (n > 0) HIPCHK(hipMemcpy(res.data(), pl->d_results, sizeof(clh::SswResult) * (size_t)n, hipMemcpyDeviceToHost));
+    if (pl->alpha)
+        for (int a = 0; a < n; ++a)
+            if (res[a].status & clh::CLH_STATUS_BAD_CODE)
+                return fail(CLH_E_ARG, "alignment " + std::to_string(a) + ": a read or reference code outside [0, " + std::to_string(pl->opts.n_mat) + ")");
     if (pl->do_cigar && n > 0) HIPCHK(hipMemcpy(clen.data(), pl->d_cigar_len, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
     std::vector<int32_t> share_off((size_t)std::max(n, 1), 0), glen((size_t)std::max(n, 1), 0);
     std::vector<int64_t> dst_off((size_t)std::max(n, 1), 0);
@@ -1059,14 +1111,33 @@ extern "C" int clh_ssw_fetch(clh_plan* pl, clh_align_t* out, uint32_t* cigar_buf
     return 0;
 }
 
+// the return code of a batch call whose plan was refused: what the plan builder reported as unsupported stays so
+static int plan_fail_code()
+{
+    if (g_err.empty()) return CLH_E_ARG;
+    const bool unsupported = g_err.find("not implemented") != std::string::npos || g_err.find("matrix edge must be") != std::string::npos ||
+                             g_err.find("resident genome take") != std::string::npos;
+    return unsupported ? CLH_E_UNSUPPORTED : CLH_E_ARG;
+}
+
 extern "C" int clh_ssw_batch(clh_ctx* ctx, int32_t n, const int8_t* reads, const int64_t* read_off, const int8_t* refs,
                              const int64_t* ref_off, const int32_t* mask_len, const clh_ssw_opts* opts, clh_align_t* out,
                              uint32_t* cigar_buf, int64_t cigar_cap, int64_t* cigar_used)
 {
     if (!ctx || !reads || !refs || !read_off || !ref_off) return fail(CLH_E_ARG, "clh_ssw_batch: null argument");
     clh_plan* pl = clh_ssw_plan(ctx, n, read_off, ref_off, mask_len, opts);
-    if (!pl) return g_err.empty() ? CLH_E_ARG : (g_err.find("not implemented") != std::string::npos ? CLH_E_UNSUPPORTED : CLH_E_ARG);
+    if (!pl) return plan_fail_code();
     int rc = 0;
+    if (pl->alpha) {       // codes outside the matrix: named here, before anything runs (the kernel checks them too)
+        const int nm = pl->opts.n_mat;
+        for (int a = 0; a < n && !rc; ++a) {
+            bool bad = false;
+            for (int64_t k = read_off[a]; k < read_off[a + 1] && !bad; ++k) bad = reads[k] < 0 || reads[k] >= nm;
+            for (int64_t k = ref_off[a]; k < ref_off[a + 1] && !bad; ++k) bad = refs[k] < 0 || refs[k] >= nm;
+            if (bad) rc = fail(CLH_E_ARG, "alignment " + std::to_string(a) + ": a read or reference code outside [0, " + std::to_string(nm) + ")");
+        }
+        if (rc) { clh_plan_destroy(pl); return rc; }
+    }
     const size_t rb = (size_t)read_off[n], fb = (size_t)ref_off[n];
     pl->d_reads = ctx->alloc(rb + 64);
     pl->d_refs = ctx->alloc(fb + 64);
@@ -1089,7 +1160,7 @@ extern "C" int clh_ssw_windows_batch(clh_genome* genome, int32_t n, const int8_t
         if (win_off[i] < 0 || win_len[i] < 0 || win_off[i] + win_len[i] > genome->len) return fail(CLH_E_ARG, "clh_ssw_windows_batch: window outside the genome");
     clh_ctx* ctx = genome->ctx;
     clh_plan* pl = clh_ssw_plan_windows(ctx, n, read_off, win_off, win_len, win_rc, mask_len, opts);
-    if (!pl) return g_err.empty() ? CLH_E_ARG : (g_err.find("not implemented") != std::string::npos ? CLH_E_UNSUPPORTED : CLH_E_ARG);
+    if (!pl) return plan_fail_code();
     int rc = 0;
     const size_t rb = (size_t)read_off[n];
     pl->d_reads = ctx->alloc(rb + 64);

@@ -12,7 +12,8 @@ enum {
     CLH_STATUS_TRACE_ERR = 4,   // traceback left the band (reference: "Trace back error", ssw.c:674-682)
     CLH_STATUS_NO_CIGAR = 8,    // CIGAR not requested / filtered by flag (ssw.c:850)
     CLH_STATUS_CIGAR_TRUNC = 16, // CIGAR buffer share / traceback pool exhausted
-    CLH_STATUS_NEED_BIG = 32     // internal: traceback must be redone with the large LDS window
+    CLH_STATUS_NEED_BIG = 32,    // internal: traceback must be redone with the large LDS window
+    CLH_STATUS_BAD_CODE = 64     // K1a: a read or reference code outside [0, n) (clh_ssw_fetch turns it into CLH_E_ARG)
 };
 
 // One alignment = one workgroup of one wavefront.  Offsets are into the packed batch arrays.
@@ -254,6 +255,18 @@ static constexpr int kRvLanes20 = -5, kRvLanes32 = -6, kRvLanes52 = -7, kRvLanes
 inline bool rv_is_lanes(int rv) { return rv <= kRvLanes20 && rv >= kRvLanes64; }
 inline int rv_lanes_columns(int rv) { return rv == kRvLanes20 ? 20 : (rv == kRvLanes32 ? 32 : (rv == kRvLanes52 ? 52 : 64)); }
 hipError_t launch_ssw_lanes(int rmax, const SswParams& p, int ntasks, hipStream_t stream);
+// pseudo classes: K1a, alphabets of 6..32 letters (ssw_alpha.hip), one class per read-length bucket: kRvAlpha - b holds reads
+// of at most kAlphaRows[b] rows; the last bucket (longer reads) keeps its pass state in global memory (persistent workgroups,
+// workspace slots inside `dirs`).  The matrix travels as its own device copy (SswParams.mat holds 32 bytes).
+static constexpr int kRvAlpha = -10, kNumAlphaBuckets = 5;
+static constexpr int kAlphaRows[kNumAlphaBuckets - 1] = {256, 1024, 4096, 8192};
+static constexpr int kAlphaLdsRows = 8192;
+inline bool rv_is_alpha(int rv) { return rv <= kRvAlpha && rv > kRvAlpha - kNumAlphaBuckets; }
+size_t alpha_lds_bytes(int lcap);
+hipError_t launch_ssw_alpha(const SswParams& p, const int8_t* d_mat, int ntasks, int lcap, int nworkgroups, long long ws_off, int ws_slot,
+                            hipStream_t stream);
+hipError_t launch_ssw_alpha_traceback(const SswParams& p, const int8_t* d_mat, int task_base, int ntasks, int n_total, int seg, int lmax,
+                                      uint8_t* pool_base, unsigned long long* pool_head, unsigned long long pool_size, hipStream_t stream);
 // K1b launches.  All take the plan's WHOLE task table in p.tasks and work on the tasks [task_base, task_base + ntasks) of launch
 // class `seg` (every class has its own hand-over counters and list regions, so the classes' launch chains run on different
 // streams at once).  Words behind the pool's bump pointer: [4 + seg] alignments the row kernel handed to its wide form,

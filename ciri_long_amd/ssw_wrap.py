@@ -12,7 +12,9 @@ Differences, all additive:
   * ``Aligner.align_batch(queries)`` and the module-level ``align_pairs(refs, queries, ...)`` issue ONE call for many
     alignments -- what a GPU needs, and what ``find_bsj.align_clip_segments`` / ``collapse`` are restructured around;
   * sequences are encoded with a 256-entry table instead of the reference's per-base Python loop (ssw_wrap.py:234-252);
-    the resulting codes are identical (A/a 0, C/c 1, G/g 2, T/t 3, everything else 4).
+    the resulting codes are identical (A/a 0, C/c 1, G/g 2, T/t 3, everything else 4);
+  * ``align_pairs_matrix`` aligns over any alphabet of up to 32 letters with its own substitution matrix (``BLOSUM62`` for
+    proteins), what the reference's ssw_init / ssw_align take and its Python wrapper does not expose.
 """
 import numpy as np
 
@@ -222,3 +224,91 @@ class Aligner(object):
         msg += "".join(self.int_to_base[int(self.ref_seq[i])] for i in range(shown)) + ("...\n" if self.ref_len > 50 else "\n")
         msg += " Lenght :{} nucleotides\n".format(self.ref_len)
         return msg
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# alphabets of up to 32 letters (ssw_init takes an n x n matrix for any n; libclh.so up to n = 32)
+# ---------------------------------------------------------------------------------------------------------------------------
+BLOSUM62_ALPHABET = 'ARNDCQEGHILKMFPSTWYVBZX*'
+# the published NCBI BLOSUM62 table, rows and columns in BLOSUM62_ALPHABET order
+_BLOSUM62_ROWS = """
+ 4 -1 -2 -2  0 -1 -1  0 -2 -1 -1 -1 -1 -2 -1  1  0 -3 -2  0 -2 -1  0 -4
+-1  5  0 -2 -3  1  0 -2  0 -3 -2  2 -1 -3 -2 -1 -1 -3 -2 -3 -1  0 -1 -4
+-2  0  6  1 -3  0  0  0  1 -3 -3  0 -2 -3 -2  1  0 -4 -2 -3  3  0 -1 -4
+-2 -2  1  6 -3  0  2 -1 -1 -3 -4 -1 -3 -3 -1  0 -1 -4 -3 -3  4  1 -1 -4
+ 0 -3 -3 -3  9 -3 -4 -3 -3 -1 -1 -3 -1 -2 -3 -1 -1 -2 -2 -1 -3 -3 -2 -4
+-1  1  0  0 -3  5  2 -2  0 -3 -2  1  0 -3 -1  0 -1 -2 -1 -2  0  3 -1 -4
+-1  0  0  2 -4  2  5 -2  0 -3 -3  1 -2 -3 -1  0 -1 -3 -2 -2  1  4 -1 -4
+ 0 -2  0 -1 -3 -2 -2  6 -2 -4 -4 -2 -3 -3 -2  0 -2 -2 -3 -3 -1 -2 -1 -4
+-2  0  1 -1 -3  0  0 -2  8 -3 -3 -1 -2 -1 -2 -1 -2 -2  2 -3  0  0 -1 -4
+-1 -3 -3 -3 -1 -3 -3 -4 -3  4  2 -3  1  0 -3 -2 -1 -3 -1  3 -3 -3 -1 -4
+-1 -2 -3 -4 -1 -2 -3 -4 -3  2  4 -2  2  0 -3 -2 -1 -2 -1  1 -4 -3 -1 -4
+-1  2  0 -1 -3  1  1 -2 -1 -3 -2  5 -1 -3 -1  0 -1 -3 -2 -2  0  1 -1 -4
+-1 -1 -2 -3 -1  0 -2 -3 -2  1  2 -1  5  0 -2 -1 -1 -1 -1  1 -3 -1 -1 -4
+-2 -3 -3 -3 -2 -3 -3 -3 -1  0  0 -3  0  6 -4 -2 -2  1  3 -1 -3 -3 -1 -4
+-1 -2 -2 -1 -3 -1 -1 -2 -2 -3 -3 -1 -2 -4  7 -1 -1 -4 -3 -2 -2 -1 -2 -4
+ 1 -1  1  0 -1  0  0  0 -1 -2 -2  0 -1 -2 -1  4  1 -3 -2 -2  0  0  0 -4
+ 0 -1  0 -1 -1 -1 -1 -2 -2 -1 -1 -1 -1 -2 -1  1  5 -2 -2  0 -1 -1  0 -4
+-3 -3 -4 -4 -2 -2 -3 -2 -2 -3 -2 -3 -1  1 -4 -3 -2 11  2 -3 -4 -3 -2 -4
+-2 -2 -2 -3 -2 -1 -2 -3  2 -1 -1 -2 -1  3 -3 -2 -2  2  7 -1 -3 -2 -1 -4
+ 0 -3 -3 -3 -1 -2 -2 -3 -3  3  1 -2  1 -1 -2 -2  0 -3 -1  4 -3 -2 -1 -4
+-2 -1  3  4 -3  0  1 -1  0 -3 -4  0 -3 -3 -2  0 -1 -4 -3 -3  4  1 -1 -4
+-1  0  0  1 -3  3  4 -2  0 -3 -3  1 -1 -3 -1  0 -1 -3 -2 -2  1  4 -1 -4
+ 0 -1 -1 -1 -2 -1 -1 -1 -1 -1 -1 -1 -1 -1 -2  0  0 -2 -1 -1 -1 -1 -1 -4
+-4 -4 -4 -4 -4 -4 -4 -4 -4 -4 -4 -4 -4 -4 -4 -4 -4 -4 -4 -4 -4 -4 -4  1
+"""
+BLOSUM62 = np.array([int(x) for x in _BLOSUM62_ROWS.split()], dtype=np.int8).reshape(24, 24)
+
+
+def encode_alphabet(seq, alphabet, unknown=None):
+    """str / bytes -> int8 codes: the index of each letter in `alphabet`, upper and lower case alike.  A letter outside the
+    alphabet raises ValueError, unless `unknown` names a letter of the alphabet to stand for it."""
+    if len(alphabet) > 32 or len(alphabet) < 1:
+        raise ValueError('encode_alphabet: alphabets of 1..32 letters')
+    lut = np.full(256, -1, dtype=np.int16)
+    for i, ch in enumerate(alphabet):
+        for c in {ch.upper(), ch.lower()}:
+            if lut[ord(c)] < 0:
+                lut[ord(c)] = i
+    if isinstance(seq, str):
+        seq = seq.encode('latin-1')
+    codes = lut[np.frombuffer(bytes(seq), dtype=np.uint8)]
+    if codes.size and codes.min() < 0:
+        if unknown is None:
+            bad = bytes(seq)[int(np.argmax(codes < 0))]
+            raise ValueError('encode_alphabet: letter %r is not in the alphabet' % chr(bad))
+        k = alphabet.find(unknown) if len(unknown) == 1 else -1
+        if k < 0:
+            k = alphabet.upper().find(unknown.upper()) if len(unknown) == 1 else -1
+        if k < 0:
+            raise ValueError('encode_alphabet: unknown=%r is not a letter of the alphabet' % (unknown,))
+        codes = np.where(codes < 0, k, codes)
+    return np.ascontiguousarray(codes, dtype=np.int8)
+
+
+def align_pairs_matrix(ref_seqs, query_seqs, matrix, alphabet, gap_open, gap_extend, report_secondary=False,
+                       report_cigar=False, min_score=0, min_len=0, context=None):
+    """align_pairs over an alphabet of up to 32 letters: element k is what the reference's ssw_init(query k, matrix) +
+    ssw_align(reference k, gap_open, gap_extend, flag 1) + its Python wrapper's filter would give, as a PyAlignRes or None.
+    matrix: n x n (row = reference letter), n = len(alphabet); sequences are str (letters of `alphabet`, any case) or
+    int8 code arrays."""
+    if len(ref_seqs) != len(query_seqs):
+        raise ValueError('align_pairs_matrix: %d references vs %d queries' % (len(ref_seqs), len(query_seqs)))
+    mat = np.ascontiguousarray(matrix, dtype=np.int8).reshape(-1)
+    n = len(alphabet)
+    if mat.size != n * n:
+        raise ValueError('align_pairs_matrix: a %d-letter alphabet needs a %d x %d matrix' % (n, n, n))
+    if not ref_seqs:
+        return []
+    enc = lambda s: encode_alphabet(s, alphabet) if isinstance(s, (str, bytes)) else np.asarray(s, dtype=np.int8)
+    qd, qo = hip.pack([enc(q) for q in query_seqs])
+    rd, ro = hip.pack([enc(r) for r in ref_seqs])
+    ctx = context or hip.default_context()
+    rows, cig = ctx.ssw_batch(qd, qo, rd, ro, mat, gap_open, gap_extend, flag=1, score_size=2,
+                              want_score2=bool(report_secondary), want_cigar=bool(report_cigar))
+    out = []
+    for k in range(len(rows)):
+        r = rows[k]
+        c = cig[r['cigar_off']:r['cigar_off'] + r['cigar_len']] if r['cigar_len'] > 0 else ()
+        out.append(_filter(r, c, int(qo[k + 1] - qo[k]), min_score, min_len, report_secondary, report_cigar))
+    return out

@@ -69,7 +69,7 @@ int clh_device_of(const clh_ctx* ctx);
 /* Scoring and reporting options; meaning and defaults follow ssw_init/ssw_align (ssw.h:54-120). */
 typedef struct {
     const int8_t* mat;     /* n_mat x n_mat substitution matrix, row = reference code (ssw.c:621) */
-    int32_t n_mat;         /* <= 5 */
+    int32_t n_mat;         /* 1..32; 6..32 (protein alphabets): the K1a class, packed references only, codes in [0, n_mat) */
     uint8_t gap_open;      /* absolute values, gap_open >= gap_extend required */
     uint8_t gap_extend;
     uint8_t flag;          /* ssw_align flag; ssw_wrap.py always passes 1 */

@@ -14,7 +14,8 @@
  * Conventions kept: the profile BORROWS `read` and `mat` (ssw.c:766-767); s_align and its cigar are malloc'd by
  * the library and released by align_destroy; errors return NULL with a message on stderr (ssw.c:810-813,818-821,
  * 857-860); maskLen < 15 prints the reference's warning and zeroes score2 (ssw.c:799-801,826-832).
- * Differences: one extra failure mode (no usable GPU -> NULL + message) and gap_open < gap_extend is rejected.
+ * Differences: one extra failure mode (no usable GPU -> NULL + message), gap_open < gap_extend is rejected, the matrix edge n of
+ * ssw_init must be 1..32 (any alphabet up to 32 letters), and codes outside [0, n) give NULL + message (undefined in the reference).
  * The device is chosen by the environment variable CIRI_LONG_DEVICE (default 0).
  */
 #ifndef CLH_SSW_LEGACY_H
