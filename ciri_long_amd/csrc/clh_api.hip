@@ -1308,6 +1308,420 @@ extern "C" int clh_edit_distance_batch(clh_ctx* ctx, int32_t n, const uint8_t* a
     return rc;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// K4m / K4t: edlib.align -- modes NW / SHW / HW, end and start locations, CIGARs (edit_align.hip)
+// ---------------------------------------------------------------------------------------------------------------
+struct clh_edit_align_plan {
+    clh_ctx* ctx = nullptr;
+    int n = 0, nk = 0, planes = 3, mode = 0, task = 0, k = -1;
+    bool eq = false, starts = false;
+    std::vector<int32_t> qlen, tlen, alpha, kidx;     // per pair; kidx: index among the pairs that reach the kernels, -1 trivial
+    std::vector<clh::EaPair> kp;
+    std::vector<clh::EaTask> tasks;                  // K4m, launch order (by lane-group class, longest text first)
+    int64_t ends_total = 0, nslots = 0;
+    struct Launch { int64_t a, b; int G; };
+    std::vector<Launch> rev;                         // reverse-pass launches over slot ranges
+    std::vector<clh::EaPath> paths;                  // K4t tasks, by chunk, then lane-group class
+    std::vector<int64_t> cig_of;                     // per kernel pair: its CIGAR's first op in the device buffer, -1 none
+    struct Chunk { int a, b; std::vector<Launch> cls; };
+    std::vector<Chunk> chunks;
+    int64_t cig_total = 0, ws_bytes = 0, carry_score = 0, carry_rev = 0, carry_path = 0;
+    void *d_sym = nullptr, *d_tasks = nullptr, *d_pairs = nullptr, *d_best = nullptr, *d_cnt = nullptr, *d_ends = nullptr, *d_rev_out = nullptr,
+         *d_slot_pair = nullptr, *d_rev_tasks = nullptr, *d_paths = nullptr, *d_path_tasks = nullptr, *d_ws = nullptr, *d_cig = nullptr,
+         *d_cig_len = nullptr, *d_carry_score = nullptr, *d_carry_rev = nullptr, *d_carry_path = nullptr, *d_eq_off = nullptr,
+         *d_eq_list = nullptr, *d_eqm = nullptr;
+    hipStream_t last_stream = nullptr;
+    bool ran = false;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+};
+
+static int ea_group(int m) { int B = (m + 63) >> 6, G = 1; while (G < B && G < 64) G <<= 1; return G; }
+static int64_t ea_pad(int64_t n) { return ((n + 63) & ~(int64_t)63) + 64; }   // one between-pass delta buffer (as K4)
+
+extern "C" void clh_edit_align_plan_destroy(clh_edit_align_plan* pl)
+{
+    if (!pl) return;
+    (void)hipSetDevice(pl->ctx->device);
+    if (pl->ran) (void)hipStreamSynchronize(pl->last_stream);
+    for (void* p : {pl->d_sym, pl->d_tasks, pl->d_pairs, pl->d_best, pl->d_cnt, pl->d_ends, pl->d_rev_out, pl->d_slot_pair, pl->d_rev_tasks,
+                    pl->d_paths, pl->d_path_tasks, pl->d_ws, pl->d_cig, pl->d_cig_len, pl->d_carry_score, pl->d_carry_rev, pl->d_carry_path,
+                    pl->d_eq_off, pl->d_eq_list, pl->d_eqm})
+        pl->ctx->release(p);
+    for (hipEvent_t e : pl->ev) if (e) (void)hipEventDestroy(e);
+    delete pl;
+}
+
+extern "C" clh_edit_align_plan* clh_edit_align_plan_create(clh_ctx* ctx, int32_t n, const uint8_t* q, const int64_t* q_off, const uint8_t* t,
+                                                           const int64_t* t_off, const clh_edit_align_opts* opts)
+{
+    if (!ctx || n < 0 || !q_off || !t_off || !opts || (n > 0 && (!q || !t))) { fail(CLH_E_ARG, "clh_edit_align_plan_create: null argument"); return nullptr; }
+    if (opts->mode < CLH_EA_NW || opts->mode > CLH_EA_HW) { fail(CLH_E_ARG, "clh_edit_align_plan_create: mode must be NW, SHW or HW"); return nullptr; }
+    if (opts->task < CLH_EA_DISTANCE || opts->task > CLH_EA_PATH) { fail(CLH_E_ARG, "clh_edit_align_plan_create: task must be distance, locations or path"); return nullptr; }
+    if (opts->n_eq < 0 || (opts->n_eq > 0 && !opts->eq) || opts->workspace_bytes < 0) { fail(CLH_E_ARG, "clh_edit_align_plan_create: bad equalities or workspace"); return nullptr; }
+    if (hipSetDevice(ctx->device) != hipSuccess) { fail(CLH_E_HIP, "hipSetDevice failed"); return nullptr; }
+    const int64_t tq = n ? q_off[n] - q_off[0] : 0, tt = n ? t_off[n] - t_off[0] : 0;
+    if (tq < 0 || tt < 0) { fail(CLH_E_ARG, "clh_edit_align_plan_create: offsets must ascend"); return nullptr; }
+    for (int k = 0; k < n; ++k)
+        if (q_off[k + 1] < q_off[k] || t_off[k + 1] < t_off[k] || q_off[k + 1] - q_off[k] > INT32_MAX / 4 || t_off[k + 1] - t_off[k] > INT32_MAX / 4) {
+            fail(CLH_E_ARG, "clh_edit_align_plan_create: offsets must ascend, strings below 2^29 bytes"); return nullptr;
+        }
+    clh_edit_align_plan* pl = new clh_edit_align_plan();
+    pl->ctx = ctx; pl->n = n; pl->mode = opts->mode; pl->task = opts->task; pl->k = opts->k;
+    pl->starts = opts->mode == CLH_EA_HW && opts->task >= CLH_EA_LOCATIONS;
+    const int64_t ws_limit = opts->workspace_bytes > 0 ? opts->workspace_bytes : ((int64_t)1 << 30);
+    // the batch's alphabet -> dense codes (bit planes: 3 for <= 8 letters, else 8), as K4
+    int code[256];
+    for (int& c : code) c = -1;
+    int nsym = 0;
+    auto learn = [&](const uint8_t* p, int64_t len) { for (int64_t i = 0; i < len; ++i) if (code[p[i]] < 0) code[p[i]] = nsym++; };
+    if (n) { learn(q + q_off[0], tq); learn(t + t_off[0], tt); }
+    pl->planes = nsym <= 8 ? 3 : 8;
+    // additionalEqualities over the codes: partner lists (score pass) and a bit matrix (traceback); absent letters drop out
+    std::vector<std::vector<uint8_t>> part(256);
+    std::vector<uint32_t> eqm(256 * 8, 0);
+    for (int e = 0; e < opts->n_eq; ++e) {
+        const int a = code[opts->eq[2 * e]], b = code[opts->eq[2 * e + 1]];
+        if (a < 0 || b < 0 || a == b || ((eqm[a * 8 + (b >> 5)] >> (b & 31)) & 1u)) continue;
+        eqm[a * 8 + (b >> 5)] |= 1u << (b & 31); eqm[b * 8 + (a >> 5)] |= 1u << (a & 31);
+        part[a].push_back((uint8_t)b); part[b].push_back((uint8_t)a);
+        pl->eq = true;
+    }
+    std::vector<int32_t> eq_off(257, 0);
+    std::vector<uint8_t> eq_list;
+    for (int c = 0; c < 256; ++c) { eq_list.insert(eq_list.end(), part[c].begin(), part[c].end()); eq_off[c + 1] = (int32_t)eq_list.size(); }
+    eq_list.push_back(0);
+    // symbols: queries, targets, then (HW with starts) the reversed strings of the pairs that reach the kernels
+    pl->qlen.resize(n); pl->tlen.resize(n); pl->alpha.resize(n); pl->kidx.assign(n, -1);
+    int64_t rev_bytes = 0;
+    for (int k = 0; k < n; ++k) {
+        const int m = (int)(q_off[k + 1] - q_off[k]), L = (int)(t_off[k + 1] - t_off[k]);
+        pl->qlen[k] = m; pl->tlen[k] = L;
+        uint64_t seen[4] = {0, 0, 0, 0};
+        for (int i = 0; i < m; ++i) { const int c = q[q_off[k] + i]; seen[c >> 6] |= 1ull << (c & 63); }
+        for (int i = 0; i < L; ++i) { const int c = t[t_off[k] + i]; seen[c >> 6] |= 1ull << (c & 63); }
+        pl->alpha[k] = __builtin_popcountll(seen[0]) + __builtin_popcountll(seen[1]) + __builtin_popcountll(seen[2]) + __builtin_popcountll(seen[3]);
+        if (m > 0 && L > 0) { pl->kidx[k] = pl->nk++; if (pl->starts) rev_bytes += m + L; }
+    }
+    std::vector<uint8_t> sym((size_t)(tq + tt + rev_bytes) + 32, 0);
+    for (int64_t i = 0; i < tq; ++i) sym[(size_t)i] = (uint8_t)code[q[q_off[0] + i]];
+    for (int64_t i = 0; i < tt; ++i) sym[(size_t)(tq + i)] = (uint8_t)code[t[t_off[0] + i]];
+    int64_t rpos = tq + tt;
+    pl->kp.resize(pl->nk);
+    for (int k = 0; k < n; ++k) {
+        if (pl->kidx[k] < 0) continue;
+        clh::EaPair& p = pl->kp[pl->kidx[k]];
+        p.m = pl->qlen[k]; p.n = pl->tlen[k];
+        p.q_off = q_off[k] - q_off[0]; p.t_off = tq + (t_off[k] - t_off[0]);
+        p.rq_off = p.rt_off = 0;
+        if (pl->starts) {
+            p.rq_off = rpos; for (int i = 0; i < p.m; ++i) sym[(size_t)(rpos + i)] = sym[(size_t)(p.q_off + p.m - 1 - i)]; rpos += p.m;
+            p.rt_off = rpos; for (int i = 0; i < p.n; ++i) sym[(size_t)(rpos + i)] = sym[(size_t)(p.t_off + p.n - 1 - i)]; rpos += p.n;
+        }
+        p.locbase = pl->ends_total; pl->ends_total += (int64_t)p.n + 1;
+        p.slot_base = 0; p.rev_carry_stride = 0; p.rev_chunk = 1; p.rev_s0 = 0;
+    }
+    // K4m tasks (the carry buffers of patterns above 4096 symbols as K4's)
+    for (int j = 0; j < pl->nk; ++j) {
+        const clh::EaPair& p = pl->kp[j];
+        clh::EaTask tk;
+        tk.pat_off = p.q_off; tk.txt_off = p.t_off; tk.out_off = p.locbase; tk.carry_off = -1;
+        tk.pat_len = p.m; tk.txt_len = p.n; tk.pair = j; tk.hin0 = pl->mode == CLH_EA_HW ? 0 : 1;
+        if (p.m > 4096) { tk.carry_off = pl->carry_score; pl->carry_score += 2 * ea_pad(p.n); }
+        pl->tasks.push_back(tk);
+    }
+    std::stable_sort(pl->tasks.begin(), pl->tasks.end(), [&](const clh::EaTask& x, const clh::EaTask& y) {
+        const int gx = ea_group(x.pat_len), gy = ea_group(y.pat_len);
+        if (gx != gy) return gx < gy;
+        return x.txt_len > y.txt_len;
+    });
+    // reverse-pass slots: n + 1 per pair (one per possible optimal column), in K4m's order; patterns above 4096 symbols
+    // take their carry buffers per slot, at most kRevCarry bytes per launch
+    std::vector<int32_t> slot_pair;
+    if (pl->starts) {
+        const int64_t kRevCarry = (int64_t)256 << 20;
+        for (size_t i = 0; i < pl->tasks.size();) {
+            const int G = ea_group(pl->tasks[i].pat_len);
+            size_t j = i;
+            int64_t s0 = pl->nslots, pmax = 0;
+            for (; j < pl->tasks.size() && ea_group(pl->tasks[j].pat_len) == G; ++j) {
+                clh::EaPair& p = pl->kp[pl->tasks[j].pair];
+                p.slot_base = pl->nslots; pl->nslots += (int64_t)p.n + 1;
+                for (int64_t s = 0; s <= p.n; ++s) slot_pair.push_back(pl->tasks[j].pair);
+                if (p.m > 4096) pmax = std::max<int64_t>(pmax, std::min<int64_t>(p.n, 2 * (int64_t)p.m + 1));
+            }
+            const int64_t s1 = pl->nslots;
+            int64_t chunk = s1 - s0;
+            if (pmax > 0) {
+                const int64_t cs = 2 * ea_pad(pmax);
+                chunk = std::max<int64_t>(1, kRevCarry / cs);
+                for (size_t x = i; x < j; ++x) {
+                    clh::EaPair& p = pl->kp[pl->tasks[x].pair];
+                    p.rev_chunk = chunk; p.rev_s0 = s0; p.rev_carry_stride = p.m > 4096 ? cs : 0;
+                }
+                pl->carry_rev = std::max(pl->carry_rev, std::min(chunk, s1 - s0) * cs);
+            }
+            for (int64_t a = s0; a < s1; a += chunk) pl->rev.push_back({a, std::min(a + chunk, s1), G});
+            i = j;
+        }
+    }
+    // K4t: per pair Pv, Mv, bottom score per block and column of target[start..end]; end - start + 1 <= n, and <= 2m
+    // outside NW (an optimal alignment of cost <= m spans at most 2m columns).  Chunks of the batch within ws_limit.
+    pl->cig_of.assign((size_t)pl->nk, -1);
+    if (pl->task == CLH_EA_PATH) {
+        std::vector<clh::EaPath> all;
+        std::vector<int64_t> wsb;
+        for (int k = 0; k < n; ++k) {
+            const int j = pl->kidx[k];
+            if (j < 0) continue;
+            const clh::EaPair& p = pl->kp[j];
+            const int64_t lmax = pl->mode == CLH_EA_NW ? p.n : std::min<int64_t>(p.n, 2 * (int64_t)p.m);
+            const int64_t B = (p.m + 63) >> 6;
+            const int64_t b = (20 * B * lmax + 255) & ~(int64_t)255;
+            if (b > ws_limit) {
+                fail(CLH_E_CAPACITY, "clh_edit_align_plan_create: the path of pair " + std::to_string(k) + " needs " + std::to_string(b) +
+                                     " bytes of workspace, above the limit of " + std::to_string(ws_limit));
+                delete pl; return nullptr;
+            }
+            clh::EaPath ph;
+            ph.pair = j; ph.lmax = (int32_t)lmax; ph.cig_cap = (int32_t)(p.m + lmax + 1); ph.pad = 0;
+            ph.cig_off = pl->cig_total; pl->cig_total += ph.cig_cap;
+            pl->cig_of[(size_t)j] = ph.cig_off;
+            ph.ws_off = 0; ph.carry_off = -1;
+            all.push_back(ph); wsb.push_back(b);
+        }
+        for (size_t i = 0; i < all.size();) {
+            size_t j = i;
+            int64_t used = 0, cused = 0;
+            while (j < all.size() && (j == i || used + wsb[j] <= ws_limit)) { used += wsb[j]; ++j; }
+            std::vector<clh::EaPath> part_(all.begin() + i, all.begin() + j);
+            std::stable_sort(part_.begin(), part_.end(), [&](const clh::EaPath& x, const clh::EaPath& y) {
+                const int gx = ea_group(pl->kp[x.pair].m), gy = ea_group(pl->kp[y.pair].m);
+                if (gx != gy) return gx < gy;
+                return x.lmax > y.lmax;
+            });
+            clh_edit_align_plan::Chunk ch;
+            ch.a = (int)pl->paths.size();
+            used = 0;
+            for (clh::EaPath ph : part_) {
+                const clh::EaPair& p = pl->kp[ph.pair];
+                ph.ws_off = used; used += (20 * (((int64_t)p.m + 63) >> 6) * ph.lmax + 255) & ~(int64_t)255;
+                if (p.m > 4096) { ph.carry_off = cused; cused += 2 * ea_pad(ph.lmax); }
+                const int G = ea_group(p.m);
+                const int64_t x = (int64_t)pl->paths.size();
+                if (ch.cls.empty() || ch.cls.back().G != G) ch.cls.push_back({x, x + 1, G}); else ch.cls.back().b = x + 1;
+                pl->paths.push_back(ph);
+            }
+            ch.b = (int)pl->paths.size();
+            pl->chunks.push_back(ch);
+            pl->ws_bytes = std::max(pl->ws_bytes, used);
+            pl->carry_path = std::max(pl->carry_path, cused);
+            i = j;
+        }
+    }
+    const size_t nk = (size_t)std::max(pl->nk, 1);
+    pl->d_sym = ctx->alloc(sym.size());
+    pl->d_tasks = ctx->alloc(sizeof(clh::EaTask) * std::max<size_t>(pl->tasks.size(), 1));
+    pl->d_pairs = ctx->alloc(sizeof(clh::EaPair) * nk);
+    pl->d_best = ctx->alloc(4 * nk); pl->d_cnt = ctx->alloc(4 * nk); pl->d_cig_len = ctx->alloc(4 * nk);
+    pl->d_ends = ctx->alloc(4 * (size_t)std::max<int64_t>(pl->ends_total, 1));
+    pl->d_rev_out = ctx->alloc(4 * (size_t)(pl->starts ? std::max<int64_t>(pl->ends_total, 1) : 1));
+    pl->d_slot_pair = ctx->alloc(4 * (size_t)std::max<int64_t>(pl->nslots, 1));
+    pl->d_rev_tasks = ctx->alloc(sizeof(clh::EaTask) * (size_t)std::max<int64_t>(pl->nslots, 1));
+    pl->d_paths = ctx->alloc(sizeof(clh::EaPath) * std::max<size_t>(pl->paths.size(), 1));
+    pl->d_path_tasks = ctx->alloc(sizeof(clh::EaTask) * std::max<size_t>(pl->paths.size(), 1));
+    pl->d_ws = ctx->alloc((size_t)std::max<int64_t>(pl->ws_bytes, 256));
+    pl->d_cig = ctx->alloc(4 * (size_t)std::max<int64_t>(pl->cig_total, 1));
+    pl->d_carry_score = ctx->alloc((size_t)pl->carry_score + 64);
+    pl->d_carry_rev = ctx->alloc((size_t)pl->carry_rev + 64);
+    pl->d_carry_path = ctx->alloc((size_t)pl->carry_path + 64);
+    pl->d_eq_off = ctx->alloc(4 * eq_off.size()); pl->d_eq_list = ctx->alloc(eq_list.size()); pl->d_eqm = ctx->alloc(4 * eqm.size());
+    bool ok = pl->d_sym && pl->d_tasks && pl->d_pairs && pl->d_best && pl->d_cnt && pl->d_cig_len && pl->d_ends && pl->d_rev_out && pl->d_slot_pair &&
+              pl->d_rev_tasks && pl->d_paths && pl->d_path_tasks && pl->d_ws && pl->d_cig && pl->d_carry_score && pl->d_carry_rev && pl->d_carry_path &&
+              pl->d_eq_off && pl->d_eq_list && pl->d_eqm;
+    ok = ok && hipMemcpy(pl->d_sym, sym.data(), sym.size(), hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && (pl->tasks.empty() || hipMemcpy(pl->d_tasks, pl->tasks.data(), sizeof(clh::EaTask) * pl->tasks.size(), hipMemcpyHostToDevice) == hipSuccess);
+    ok = ok && (pl->kp.empty() || hipMemcpy(pl->d_pairs, pl->kp.data(), sizeof(clh::EaPair) * pl->kp.size(), hipMemcpyHostToDevice) == hipSuccess);
+    ok = ok && (slot_pair.empty() || hipMemcpy(pl->d_slot_pair, slot_pair.data(), 4 * slot_pair.size(), hipMemcpyHostToDevice) == hipSuccess);
+    ok = ok && (pl->paths.empty() || hipMemcpy(pl->d_paths, pl->paths.data(), sizeof(clh::EaPath) * pl->paths.size(), hipMemcpyHostToDevice) == hipSuccess);
+    ok = ok && hipMemcpy(pl->d_eq_off, eq_off.data(), 4 * eq_off.size(), hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(pl->d_eq_list, eq_list.data(), eq_list.size(), hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(pl->d_eqm, eqm.data(), 4 * eqm.size(), hipMemcpyHostToDevice) == hipSuccess;
+    if (!ok) {
+        fail(CLH_E_HIP, "out of device memory or upload failed while building the edit-align plan");
+        clh_edit_align_plan_destroy(pl); return nullptr;
+    }
+    return pl;
+}
+
+static clh::EaParams ea_params(const clh_edit_align_plan* pl)
+{
+    clh::EaParams p;
+    p.sym = (const uint8_t*)pl->d_sym;
+    p.best = (int32_t*)pl->d_best; p.cnt = (int32_t*)pl->d_cnt; p.ends = (int32_t*)pl->d_ends; p.ends_cap = pl->ends_total;
+    p.rev_out = (int32_t*)pl->d_rev_out; p.rev_cap = pl->starts ? pl->ends_total : 0;
+    p.ws = (uint8_t*)pl->d_ws; p.ws_cap = pl->ws_bytes;
+    p.carry = nullptr; p.carry_cap = 0;
+    p.eq_off = (const int32_t*)pl->d_eq_off; p.eq_list = (const uint8_t*)pl->d_eq_list; p.eqm = (const uint32_t*)pl->d_eqm;
+    p.mode = pl->mode; p.k = pl->k;
+    return p;
+}
+
+extern "C" int clh_edit_align_plan_run(clh_edit_align_plan* pl, void* stream_)
+{
+    if (!pl) return fail(CLH_E_ARG, "clh_edit_align_plan_run: null argument");
+    HIPCHK(hipSetDevice(pl->ctx->device));
+    hipStream_t st = stream_ ? (hipStream_t)stream_ : pl->ctx->stream;
+    if (!pl->ev[0]) for (auto& e : pl->ev) HIPCHK(hipEventCreate(&e));
+    HIPCHK(hipEventRecord(pl->ev[0], st));
+    const size_t nk = (size_t)std::max(pl->nk, 1);
+    HIPCHK(hipMemsetAsync(pl->d_cnt, 0xff, 4 * nk, st));       // -1: no result (a kernel that left a pair out is caught by fetch)
+    HIPCHK(hipMemsetAsync(pl->d_cig_len, 0xff, 4 * nk, st));
+    if (pl->starts) HIPCHK(hipMemsetAsync(pl->d_rev_out, 0xff, 4 * (size_t)std::max<int64_t>(pl->ends_total, 1), st));
+    clh::EaParams p = ea_params(pl);
+    const int nt = (int)pl->tasks.size();
+    p.carry = (int8_t*)pl->d_carry_score; p.carry_cap = pl->carry_score;
+    for (int i = 0; i < nt;) {
+        const int G = ea_group(pl->tasks[(size_t)i].pat_len);
+        int j = i;
+        while (j < nt && ea_group(pl->tasks[(size_t)j].pat_len) == G) ++j;
+        HIPCHK(clh::launch_edit_align(p, clh::EA_SCORE, (const clh::EaTask*)pl->d_tasks + i, j - i, G, pl->planes, pl->eq, st));
+        i = j;
+    }
+    if (pl->starts && pl->nslots) {
+        clh::EaTask* rt = (clh::EaTask*)pl->d_rev_tasks;
+        HIPCHK(clh::launch_edit_align_build_rev(p, (const clh::EaPair*)pl->d_pairs, (const int32_t*)pl->d_slot_pair, pl->nslots, rt, st));
+        p.carry = (int8_t*)pl->d_carry_rev; p.carry_cap = pl->carry_rev;
+        for (const auto& l : pl->rev)
+            HIPCHK(clh::launch_edit_align(p, clh::EA_REVERSE, rt + l.a, (int)(l.b - l.a), l.G, pl->planes, pl->eq, st));
+    }
+    p.carry = (int8_t*)pl->d_carry_path; p.carry_cap = pl->carry_path;
+    for (const auto& ch : pl->chunks) {
+        const clh::EaPath* ph = (const clh::EaPath*)pl->d_paths + ch.a;
+        clh::EaTask* pt = (clh::EaTask*)pl->d_path_tasks + ch.a;
+        HIPCHK(clh::launch_edit_align_build_path(p, (const clh::EaPair*)pl->d_pairs, ph, ch.b - ch.a, pt, st));
+        for (const auto& l : ch.cls)
+            HIPCHK(clh::launch_edit_align(p, clh::EA_STORE, (const clh::EaTask*)pl->d_path_tasks + l.a, (int)(l.b - l.a), l.G, pl->planes, pl->eq, st));
+        HIPCHK(clh::launch_edit_align_traceback(p, ph, pt, ch.b - ch.a, (uint32_t*)pl->d_cig, (int32_t*)pl->d_cig_len, st));
+    }
+    HIPCHK(hipEventRecord(pl->ev[1], st));
+    pl->last_stream = st; pl->ran = true;
+    return 0;
+}
+
+// capacities: a pair has at most n + 1 optimal columns; its CIGAR at most m + n ops
+static void ea_caps(const clh_edit_align_plan* pl, int64_t* lc, int64_t* cc)
+{
+    *lc = 0; *cc = 0;
+    for (int k = 0; k < pl->n; ++k) { *lc += (int64_t)pl->tlen[k] + 1; *cc += (int64_t)pl->qlen[k] + pl->tlen[k] + 1; }
+}
+
+extern "C" int clh_edit_align_plan_caps(clh_edit_align_plan* pl, int64_t* locs_cap, int64_t* cigar_cap)
+{
+    if (!pl || !locs_cap || !cigar_cap) return fail(CLH_E_ARG, "clh_edit_align_plan_caps: null argument");
+    ea_caps(pl, locs_cap, cigar_cap);
+    return 0;
+}
+
+extern "C" int clh_edit_align_plan_fetch(clh_edit_align_plan* pl, clh_edit_align_row* rows, int32_t* locs, int64_t locs_cap, int64_t* locs_used,
+                                         uint32_t* cigar, int64_t cigar_cap, int64_t* cigar_used)
+{
+    if (!pl || !rows || !locs_used || !cigar_used || (locs_cap > 0 && !locs) || (cigar_cap > 0 && !cigar))
+        return fail(CLH_E_ARG, "clh_edit_align_plan_fetch: null argument");
+    if (!pl->ran) return fail(CLH_E_ARG, "clh_edit_align_plan_fetch before clh_edit_align_plan_run");
+    HIPCHK(hipSetDevice(pl->ctx->device));
+    HIPCHK(hipStreamSynchronize(pl->last_stream));
+    const size_t nk = (size_t)std::max(pl->nk, 1);
+    std::vector<int32_t> best(nk), cnt(nk), cl(nk), ends((size_t)std::max<int64_t>(pl->ends_total, 1)), rev(pl->starts ? ends.size() : 0);
+    std::vector<uint32_t> cig((size_t)std::max<int64_t>(pl->cig_total, 1));
+    if (pl->nk) {
+        HIPCHK(hipMemcpy(best.data(), pl->d_best, 4 * nk, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(cnt.data(), pl->d_cnt, 4 * nk, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(cl.data(), pl->d_cig_len, 4 * nk, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(ends.data(), pl->d_ends, 4 * ends.size(), hipMemcpyDeviceToHost));
+        if (pl->starts) HIPCHK(hipMemcpy(rev.data(), pl->d_rev_out, 4 * rev.size(), hipMemcpyDeviceToHost));
+        if (pl->cig_total) HIPCHK(hipMemcpy(cig.data(), pl->d_cig, 4 * (size_t)pl->cig_total, hipMemcpyDeviceToHost));
+    }
+    const bool want_start = pl->task >= CLH_EA_LOCATIONS, want_path = pl->task == CLH_EA_PATH;
+    int64_t lu = 0, cu = 0;
+    std::vector<int32_t> le;     // this pair's (start, end)
+    std::vector<uint32_t> ops;
+    for (int k = 0; k < pl->n; ++k) {
+        const int m = pl->qlen[k], L = pl->tlen[k], j = pl->kidx[k];
+        int d;
+        le.clear(); ops.clear();
+        if (j < 0) {
+            // an empty side: the dynamic programme's own answer (column -1 = before the first target letter)
+            if (L == 0) { d = m; le = {0, -1}; if (m) ops.push_back(((uint32_t)m << 4) | 1u); }
+            else if (pl->mode == CLH_EA_NW) { d = L; le = {0, L - 1}; ops.push_back(((uint32_t)L << 4) | 2u); }
+            else if (pl->mode == CLH_EA_SHW) { d = 1; le = {0, 0}; ops.push_back((1u << 4) | 2u); }
+            else { d = 0; for (int e = -1; e < L; ++e) { le.push_back(e + 1); le.push_back(e); } }
+        } else {
+            d = best[(size_t)j];
+            const int c = cnt[(size_t)j];
+            const int64_t base = pl->kp[(size_t)j].locbase;
+            if (c < 1 || c > L + 1) return fail(CLH_E_HIP, "edit_align: the score pass left pair " + std::to_string(k) + " without a result");
+            const bool above = pl->k >= 0 && d > pl->k;
+            for (int i = 0; i < c && !above; ++i) {
+                const int e = ends[(size_t)(base + i)];
+                int s = 0;
+                if (pl->starts && e >= 0) {
+                    const int p = rev[(size_t)(base + i)];
+                    if (p < 0) return fail(CLH_E_HIP, "edit_align: the reverse pass left pair " + std::to_string(k) + " without a start");
+                    s = e - p;
+                }
+                le.push_back(s); le.push_back(e);
+            }
+            if (want_path && !above) {
+                const int n_ops = cl[(size_t)j];
+                if (n_ops < 0) return fail(CLH_E_HIP, "edit_align: the traceback failed for pair " + std::to_string(k));
+                const int64_t co = pl->cig_of[(size_t)j];
+                if (co < 0) return fail(CLH_E_HIP, "edit_align: no path task for pair " + std::to_string(k));
+                ops.assign(cig.begin() + co, cig.begin() + co + n_ops);
+            }
+        }
+        clh_edit_align_row& r = rows[k];
+        const bool above = pl->k >= 0 && d > pl->k;
+        r.distance = above ? -1 : d;
+        r.status = above ? CLH_EA_ST_ABOVE_K : 0;
+        r.alphabet_len = pl->alpha[(size_t)k];
+        r.reserved = 0;
+        if (above) { le.clear(); ops.clear(); }
+        r.nlocs = (int32_t)(le.size() / 2);
+        r.loc_off = lu;
+        if (lu + r.nlocs > locs_cap) return fail(CLH_E_CAPACITY, "clh_edit_align_plan_fetch: locs_cap too small");
+        for (size_t i = 0; i < le.size(); i += 2) { locs[2 * lu] = want_start ? le[i] : -1; locs[2 * lu + 1] = le[i + 1]; ++lu; }
+        r.cigar_off = want_path && !above ? cu : -1;
+        r.cigar_len = want_path && !above ? (int32_t)ops.size() : 0;
+        if (want_path && !above) {
+            if (cu + (int64_t)ops.size() > cigar_cap) return fail(CLH_E_CAPACITY, "clh_edit_align_plan_fetch: cigar_cap too small");
+            for (uint32_t o : ops) cigar[cu++] = o;
+        }
+    }
+    *locs_used = lu; *cigar_used = cu;
+    return 0;
+}
+
+extern "C" int clh_edit_align_plan_timing(clh_edit_align_plan* pl, float* ms)
+{
+    if (!pl || !ms || !pl->ran) return fail(CLH_E_ARG, "clh_edit_align_plan_timing: no run to time");
+    HIPCHK(hipEventSynchronize(pl->ev[1]));
+    HIPCHK(hipEventElapsedTime(ms, pl->ev[0], pl->ev[1]));
+    return 0;
+}
+
+extern "C" int clh_edit_align_batch(clh_ctx* ctx, int32_t n, const uint8_t* q, const int64_t* q_off, const uint8_t* t, const int64_t* t_off,
+                                    const clh_edit_align_opts* opts, clh_edit_align_row* rows, int32_t* locs, int64_t locs_cap, int64_t* locs_used,
+                                    uint32_t* cigar, int64_t cigar_cap, int64_t* cigar_used)
+{
+    if (!rows || !locs_used || !cigar_used) return fail(CLH_E_ARG, "clh_edit_align_batch: null argument");
+    clh_edit_align_plan* pl = clh_edit_align_plan_create(ctx, n, q, q_off, t, t_off, opts);
+    if (!pl) return g_err.find("workspace") != std::string::npos ? CLH_E_CAPACITY : CLH_E_ARG;
+    int rc = clh_edit_align_plan_run(pl, nullptr);
+    if (!rc) rc = clh_edit_align_plan_fetch(pl, rows, locs, locs_cap, locs_used, cigar, cigar_cap, cigar_used);
+    clh_edit_align_plan_destroy(pl);
+    return rc;
+}
+
 extern "C" void clh_encode_dna(const char* seq, int64_t len, int8_t* out)
 {
     static int8_t lut[256];

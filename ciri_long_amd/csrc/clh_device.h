@@ -225,6 +225,40 @@ hipError_t launch_genome_count_n(const uint8_t* codes, const unsigned int* pre_n
 static constexpr int kGenomeBlock = 256;     // bases per entry of the N prefix table
 hipError_t launch_edit_distance(const uint8_t* seqs, const EdTask* tasks, int ntasks, int G, int planes, int32_t* out, int8_t* carry_ws, hipStream_t stream);
 
+// K4m / K4t (edit_align.hip): edlib.align's modes on K4's block scheme; the query is always the pattern
+struct EaTask {
+    int64_t pat_off, txt_off;   // into the packed symbol array
+    int64_t out_off;            // K4m: first end slot of the pair; reverse pass: index into rev_out; K4t: byte offset into the workspace
+    int64_t carry_off;          // pattern above 4096 symbols: byte offset of its two between-pass delta buffers; else -1
+    int32_t pat_len, txt_len;   // no work when either is <= 0 (txt_len < 0: K4t pair left without a path)
+    int32_t pair, hin0;         // hin0: horizontal delta entering block 0 (+1 NW / SHW, 0 HW)
+};
+struct EaPair {                 // per pair that reaches the kernels (both strings non-empty)
+    int64_t q_off, t_off, rq_off, rt_off;   // query, target, and their reversed copies (rq/rt: HW with starts only)
+    int64_t locbase, slot_base;             // first end slot (capacity n + 1); first reverse-pass slot
+    int64_t rev_carry_stride, rev_chunk, rev_s0;   // reverse passes of patterns above 4096: carry per slot, slots per launch, class start
+    int32_t m, n;
+};
+struct EaPath {                 // one K4t task
+    int64_t ws_off, carry_off, cig_off;
+    int32_t pair, lmax, cig_cap, pad;
+};
+enum { EA_SCORE = 0, EA_REVERSE = 1, EA_STORE = 2 };
+struct EaParams {
+    const uint8_t* sym;
+    int32_t *best, *cnt, *ends; int64_t ends_cap;      // K4m: best last-row score, number of optimal columns, the columns
+    int32_t* rev_out; int64_t rev_cap;                 // reverse pass: last optimal column, per end slot
+    uint8_t* ws; int64_t ws_cap;                       // K4t: Pv, Mv (uint64) and bottom score (int32) per block and column
+    int8_t* carry; int64_t carry_cap;
+    const int32_t* eq_off; const uint8_t* eq_list;     // additionalEqualities: partners of code c are eq_list[eq_off[c] .. eq_off[c + 1])
+    const uint32_t* eqm;                               // the same as a 256 x 256 bit matrix (traceback)
+    int mode, k;                                       // 0 NW, 1 SHW, 2 HW; k < 0: no bound
+};
+hipError_t launch_edit_align(const EaParams& p, int kind, const EaTask* tasks, int ntasks, int G, int planes, bool eq, hipStream_t stream);
+hipError_t launch_edit_align_build_rev(const EaParams& p, const EaPair* pairs, const int32_t* slot_pair, int64_t nslots, EaTask* tasks, hipStream_t stream);
+hipError_t launch_edit_align_build_path(const EaParams& p, const EaPair* pairs, const EaPath* paths, int n, EaTask* tasks, hipStream_t stream);
+hipError_t launch_edit_align_traceback(const EaParams& p, const EaPath* paths, const EaTask* tasks, int n, uint32_t* cigar, int32_t* cig_len, hipStream_t stream);
+
 static constexpr int kRvStrips = 1000;   // pseudo class: RV = 32 with row strips (reads longer than 4096 bases)
 extern const int kRvClasses[];
 extern const int kNumRvClasses;

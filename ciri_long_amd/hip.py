@@ -45,6 +45,18 @@ class SswOpts(C.Structure):
                 ('want_score2', C.c_int32), ('want_cigar', C.c_int32)]
 
 
+class EditAlignOpts(C.Structure):
+    _fields_ = [('mode', C.c_int32), ('task', C.c_int32), ('k', C.c_int32), ('n_eq', C.c_int32), ('eq', C.c_void_p),
+                ('workspace_bytes', C.c_int64)]
+
+
+EDIT_ALIGN_DTYPE = np.dtype([('distance', '<i4'), ('nlocs', '<i4'), ('loc_off', '<i8'), ('cigar_off', '<i8'), ('cigar_len', '<i4'),
+                             ('status', '<i4'), ('alphabet_len', '<i4'), ('reserved', '<i4')])
+EA_MODES = {'NW': 0, 'SHW': 1, 'HW': 2}
+EA_TASKS = {'distance': 0, 'locations': 1, 'path': 2}
+EA_ST_ABOVE_K = 1
+
+
 _lib = None
 _gpu_used = False         # set when this process creates its first device context (clh_create: the first call that initialises the HIP runtime);
                           # loading libclh.so and its host-only entry points (fastx_index, fastx_count, encode) do not
@@ -112,6 +124,17 @@ def lib():
         L.clh_edit_plan_timing.argtypes = [C.c_void_p, C.c_void_p]
         L.clh_edit_distance_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.clh_edit_distance_batch.restype = C.c_int
+        L.clh_edit_align_plan_create.restype = C.c_void_p
+        L.clh_edit_align_plan_create.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(EditAlignOpts)]
+        L.clh_edit_align_plan_destroy.restype = None
+        L.clh_edit_align_plan_destroy.argtypes = [C.c_void_p]
+        L.clh_edit_align_plan_run.argtypes = [C.c_void_p, C.c_void_p]
+        L.clh_edit_align_plan_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_int64,
+                                                C.POINTER(C.c_int64)]
+        L.clh_edit_align_plan_timing.argtypes = [C.c_void_p, C.c_void_p]
+        L.clh_edit_align_plan_caps.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.clh_edit_align_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(EditAlignOpts),
+                                           C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
         L.clh_poa_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]
         L.clh_ccs_results_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -360,6 +383,19 @@ class Context(object):
     def edit_plan(self, xs, ys):
         return EditPlan(self, xs, ys)
 
+    def edit_align_batch(self, queries, targets, mode='NW', task='distance', k=-1, equalities=(), workspace_bytes=0):
+        """edlib.align of the pairs (queries[k], targets[k]) (str or bytes) through K4m / K4t -> (rows EDIT_ALIGN_DTYPE,
+        locs int32[.., 2] of (start, end), cigar uint32 BAM ops).  equalities: pairs of letters that also match."""
+        plan = EditAlignPlan(self, queries, targets, mode, task, k, equalities, workspace_bytes)
+        try:
+            plan.run()
+            return plan.fetch()
+        finally:
+            plan.close()
+
+    def edit_align_plan(self, queries, targets, mode='NW', task='distance', k=-1, equalities=(), workspace_bytes=0):
+        return EditAlignPlan(self, queries, targets, mode, task, k, equalities, workspace_bytes)
+
     def ccs_file(self, in_path, is_fastq, ccs_fa_path, raw_fa_path, batch_reads=0, first_record=0, max_records=-1, byte_offset=0):
         """Stage 1 from file to file in native code -> (total_reads, reads_with_consensus, reads_too_long); with
         first_record / max_records for one rank's contiguous shard of the records, counted from `byte_offset` (the first byte of a
@@ -432,6 +468,74 @@ class EditPlan(object):
         if self._h:
             if getattr(self.ctx, '_h', None):
                 lib().clh_edit_plan_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _letter(c):
+    if isinstance(c, int):
+        return c
+    b = c.encode('latin-1') if isinstance(c, str) else bytes(c)
+    if len(b) != 1:
+        raise ValueError('an equality pairs two single letters, got %r' % (c,))
+    return b[0]
+
+
+class EditAlignPlan(object):
+    """Pairs resident on the GPU for edlib.align's modes: run() any number of times, fetch() (rows, locs, cigar)."""
+
+    def __init__(self, ctx, queries, targets, mode='NW', task='distance', k=-1, equalities=(), workspace_bytes=0):
+        if len(queries) != len(targets):
+            raise ValueError('EditAlignPlan: the two lists differ in length')
+        if mode not in EA_MODES:
+            raise ValueError('mode must be one of NW, SHW, HW, got %r' % (mode,))
+        if task not in EA_TASKS:
+            raise ValueError('task must be one of distance, locations, path, got %r' % (task,))
+        self.ctx, self.n, self._h = ctx, len(queries), None
+        q, q_off = _pack_bytes(queries)
+        t, t_off = _pack_bytes(targets)
+        eq = np.array([[_letter(a), _letter(b)] for a, b in (equalities or ())], dtype=np.uint8).reshape(-1)
+        self._eq = np.ascontiguousarray(np.concatenate([eq, np.zeros(2, dtype=np.uint8)]))
+        opts = EditAlignOpts(EA_MODES[mode], EA_TASKS[task], int(k), len(eq) // 2, self._eq.ctypes.data, int(workspace_bytes))
+        self._h = lib().clh_edit_align_plan_create(ctx._h, self.n, q.ctypes.data, q_off.ctypes.data, t.ctypes.data, t_off.ctypes.data,
+                                                   C.byref(opts))
+        if not self._h:
+            raise ClhError('clh_edit_align_plan_create failed: %s' % last_error())
+        lc, cc = C.c_int64(0), C.c_int64(0)
+        lib().clh_edit_align_plan_caps(self._h, C.byref(lc), C.byref(cc))
+        self._caps = (int(lc.value), int(cc.value))
+
+    def run(self, stream=0):
+        rc = lib().clh_edit_align_plan_run(self._h, C.c_void_p(stream))
+        if rc != 0:
+            raise ClhError('clh_edit_align_plan_run failed (%d): %s' % (rc, last_error()))
+
+    def fetch(self):
+        rows = np.zeros(self.n, dtype=EDIT_ALIGN_DTYPE)
+        locs = np.zeros((max(self._caps[0], 1), 2), dtype=np.int32)
+        cig = np.zeros(max(self._caps[1], 1), dtype=np.uint32)
+        lu, cu = C.c_int64(0), C.c_int64(0)
+        rc = lib().clh_edit_align_plan_fetch(self._h, rows.ctypes.data, locs.ctypes.data, self._caps[0], C.byref(lu), cig.ctypes.data,
+                                             self._caps[1], C.byref(cu))
+        if rc != 0:
+            raise ClhError('clh_edit_align_plan_fetch failed (%d): %s' % (rc, last_error()))
+        return rows, locs[:lu.value].copy(), cig[:cu.value].copy()
+
+    def timing(self):
+        ms = C.c_float(0)
+        if lib().clh_edit_align_plan_timing(self._h, C.byref(ms)) != 0:
+            raise ClhError('clh_edit_align_plan_timing: %s' % last_error())
+        return float(ms.value)
+
+    def close(self):
+        if self._h:
+            if getattr(self.ctx, '_h', None):
+                lib().clh_edit_align_plan_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -278,6 +278,42 @@ int clh_edit_plan_run(clh_edit_plan* plan, void* stream);
 int clh_edit_plan_fetch(clh_edit_plan* plan, int32_t* out);
 int clh_edit_plan_timing(clh_edit_plan* plan, float* ms);       /* HIP-event duration of the last run */
 
+/* ---- edlib.align: modes, end / start locations, CIGARs ----------------------------------------------------------------
+ * Unit-cost alignment of the whole query (pattern) q[q_off[k]..q_off[k+1]) against the target t[t_off[k]..t_off[k+1]),
+ * bytes compared for equality (any byte value).  mode: CLH_EA_NW (whole target), CLH_EA_SHW (a prefix of the target),
+ * CLH_EA_HW (any substring).  task: CLH_EA_DISTANCE (distance and end locations), CLH_EA_LOCATIONS (+ starts),
+ * CLH_EA_PATH (+ the CIGAR of the first location).  k >= 0: a best above k gives distance -1, no location, no CIGAR
+ * (status CLH_EA_ST_ABOVE_K).  eq: n_eq pairs of letters (2 n_eq bytes) that also count as equal (symmetric, not
+ * transitive).  workspace_bytes: the path pass's storage per chunk of the batch (0: 1 GiB); a pair that alone needs more
+ * fails with CLH_E_CAPACITY.
+ * Row k: distance, nlocs locations at locs[2 loc_off ..] as (start, end) int32 pairs, both inclusive, 0-based; end -1 =
+ * before the first target letter; start -1 = not computed (task distance).  The CIGAR (task path) is cigar_len BAM-style
+ * uint32 ops (len << 4 | op; = 7, X 8, I 1 query letter, D 2 target letter) at cigar[cigar_off ..].  alphabet_len: the
+ * number of distinct bytes in query and target.  locs_cap is counted in locations, cigar_cap in ops. */
+#define CLH_EA_NW  0
+#define CLH_EA_SHW 1
+#define CLH_EA_HW  2
+#define CLH_EA_DISTANCE  0
+#define CLH_EA_LOCATIONS 1
+#define CLH_EA_PATH      2
+#define CLH_EA_ST_ABOVE_K 1
+typedef struct { int32_t mode, task, k, n_eq; const uint8_t* eq; int64_t workspace_bytes; } clh_edit_align_opts;
+typedef struct { int32_t distance, nlocs; int64_t loc_off, cigar_off; int32_t cigar_len, status, alphabet_len, reserved; } clh_edit_align_row;
+int clh_edit_align_batch(clh_ctx* ctx, int32_t n, const uint8_t* q, const int64_t* q_off, const uint8_t* t, const int64_t* t_off,
+                         const clh_edit_align_opts* opts, clh_edit_align_row* rows, int32_t* locs, int64_t locs_cap, int64_t* locs_used,
+                         uint32_t* cigar, int64_t cigar_cap, int64_t* cigar_used);
+/* the same in three steps (strings uploaded once, any number of runs; a timed run excludes the upload) */
+typedef struct clh_edit_align_plan clh_edit_align_plan;
+clh_edit_align_plan* clh_edit_align_plan_create(clh_ctx* ctx, int32_t n, const uint8_t* q, const int64_t* q_off, const uint8_t* t,
+                                                const int64_t* t_off, const clh_edit_align_opts* opts);
+void clh_edit_align_plan_destroy(clh_edit_align_plan* plan);
+int clh_edit_align_plan_run(clh_edit_align_plan* plan, void* stream);
+int clh_edit_align_plan_fetch(clh_edit_align_plan* plan, clh_edit_align_row* rows, int32_t* locs, int64_t locs_cap, int64_t* locs_used,
+                              uint32_t* cigar, int64_t cigar_cap, int64_t* cigar_used);
+int clh_edit_align_plan_timing(clh_edit_align_plan* plan, float* ms);   /* HIP-event duration of the last run */
+/* capacities fetch needs for this plan: locations and CIGAR ops */
+int clh_edit_align_plan_caps(clh_edit_align_plan* plan, int64_t* locs_cap, int64_t* cigar_cap);
+
 /* ASCII -> codes exactly as ssw_wrap.py:234-252 (A/a C/c G/g T/t N/n, anything else 4), on the host. */
 void clh_encode_dna(const char* seq, int64_t len, int8_t* out);
 
