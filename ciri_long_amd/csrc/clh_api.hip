@@ -173,6 +173,7 @@ struct clh_plan {
     int64_t refs_bytes = -1;                 // size of the caller's refs buffer if stated (clh_plan_set_refs_bytes), else -1
     std::vector<hipEvent_t> chain_ev;   // between the parts of a split K1w class
     std::vector<hipEvent_t> ev;     // per segment: K1 start, K1 stop; then K1b small-window start/stop, large-window start/stop
+    std::vector<int32_t> w32_prefix;   // tasks in launch order: how many before k could need the int32 traceback (clh::launch_traceback_w32)
     bool alpha = false;             // matrix edge 6..32: every alignment in the K1a classes (ssw_alpha.hip)
     void* d_alpha_mat = nullptr;    // their n x n matrix
 };
@@ -429,6 +430,14 @@ static clh_plan* ssw_plan_build(clh_ctx* ctx, int32_t n, const int64_t* read_off
     }
     pl->tasks.swap(sorted);
     pl->n_rows = n_all;
+    // the 16-bit traceback forms hand an alignment to the int32 one only if its score can reach 32767, its read + reference exceed
+    // their LDS (12 352 bases) or its read their band ring (4 097 rows): classes without such a task skip that launch
+    pl->w32_prefix.assign((size_t)n_all + 1, 0);
+    for (int k = 0; k < n_all; ++k) {
+        const clh::SswTask& t = pl->tasks[k];
+        const bool maybe = t.out_index < n && ((int64_t)mx * t.read_len >= 32767 || (int64_t)t.read_len + t.ref_len > 12352 || t.read_len > 4097);
+        pl->w32_prefix[k + 1] = pl->w32_prefix[k] + (maybe ? 1 : 0);
+    }
     for (auto& sg : pl->segs) {
         if (sg.rv != clh::kRvScanWide && sg.rv != clh::kRvScanTr) continue;
         int lmax = 1;
@@ -809,6 +818,8 @@ extern "C" int clh_ssw_run(clh_plan* pl, const void* d_reads, const void* d_refs
             HIPCHK(clh::launch_traceback_rows_wide(PG, first, count, pl->n_all, seg, pool, head, pl->pool_bytes, ls));
         } else HIPCHK(clh::launch_traceback_pool(0, PG, first, count, pl->n_all, seg, pool, head, pl->pool_bytes, ls));
         HIPCHK(clh::launch_traceback_pool(rvbig, PG, first, count, pl->n_all, seg, pool, head, pl->pool_bytes, ls));
+        // what those 16-bit forms cannot hold (a score saturated at 32767, a sequence span or band past their LDS): int32 state
+        if (pl->w32_prefix[first + count] > pl->w32_prefix[first]) HIPCHK(clh::launch_traceback_w32(PG, first, count, pool, head, pl->pool_bytes, ls));
         return 0;
     };
     // the first stage of the prefilter, with its own pair of events in profiling runs (clh_plan_prefilter_timing)
@@ -921,6 +932,7 @@ extern "C" int clh_ssw_run(clh_plan* pl, const void* d_reads, const void* d_refs
         HIPCHK(hipEventRecord(pl->ev[eb + 2], st));
         if (tb_rows_on()) HIPCHK(clh::launch_traceback_rows_wide(PG, 0, pl->n_all, pl->n_all, 0, pool, head, pl->pool_bytes, st));
         HIPCHK(clh::launch_traceback_pool(rvmax, PG, 0, pl->n_all, pl->n_all, 0, pool, head, pl->pool_bytes, st));
+        HIPCHK(clh::launch_traceback_w32(PG, 0, pl->n_all, pool, head, pl->pool_bytes, st));
         HIPCHK(hipEventRecord(pl->ev[eb + 3], st));
     }
     if (!pl->done_ev) HIPCHK(hipEventCreateWithFlags(&pl->done_ev, hipEventDisableTiming));

@@ -13,7 +13,8 @@ enum {
     CLH_STATUS_NO_CIGAR = 8,    // CIGAR not requested / filtered by flag (ssw.c:850)
     CLH_STATUS_CIGAR_TRUNC = 16, // CIGAR buffer share / traceback pool exhausted
     CLH_STATUS_NEED_BIG = 32,    // internal: traceback must be redone with the large LDS window
-    CLH_STATUS_BAD_CODE = 64     // K1a: a read or reference code outside [0, n) (clh_ssw_fetch turns it into CLH_E_ARG)
+    CLH_STATUS_BAD_CODE = 64,    // K1a: a read or reference code outside [0, n) (clh_ssw_fetch turns it into CLH_E_ARG)
+    CLH_STATUS_NEED_W32 = 128    // internal: CIGAR for the int32 traceback (a score saturated at 32767, or beyond the 16-bit forms' capacity)
 };
 
 // One alignment = one workgroup of one wavefront.  Offsets are into the packed batch arrays.
@@ -328,5 +329,9 @@ hipError_t launch_traceback_rows_wide(const SswParams& p, int task_base, int nta
 // second list); rv > 0: the class's second list, window sized for rows <= 128 * rv
 hipError_t launch_traceback_pool(int rv, const SswParams& p, int task_base, int ntasks, int n_total, int seg, uint8_t* pool_base, unsigned long long* pool_head,
                                  unsigned long long pool_size, hipStream_t stream);
+// the DNA alignments of tasks [task_base, task_base + ntasks) that the 16-bit forms marked CLH_STATUS_NEED_W32: K1a's int32 traceback
+// (ssw_alpha.hip) with the plan's matrix, sequences read from HBM where they do not fit LDS
+hipError_t launch_traceback_w32(const SswParams& p, int task_base, int ntasks, uint8_t* pool_base, unsigned long long* pool_head,
+                                unsigned long long pool_size, hipStream_t stream);
 
 }  // namespace clh

@@ -317,8 +317,10 @@ __device__ __forceinline__ int ad_stride(int w, int readLen, int refLen)
     return s > refLen ? refLen : s;
 }
 
-__device__ void alpha_traceback(const SswParams& p, const int8_t* smat, const AlPool& pool, const int ws, const int wsp, const int big,
-                                const int seq_cap, const int task_index)
+// need: the status bit that lists an alignment for a big != 0 launch (CLH_STATUS_NEED_BIG; CLH_STATUS_NEED_W32 for the DNA alignments
+// the 16-bit forms hand over, whose genome windows may be reverse-complemented)
+__device__ __forceinline__ void alpha_traceback(const SswParams& p, const int8_t* smat, const AlPool& pool, const int ws, const int wsp, const int big,
+                                const int seq_cap, const int task_index, const int need = CLH_STATUS_NEED_BIG)
 {
     // int32 state: past the 16-bit pass's ceiling (score1 = 32767) the reference's int DP keeps counting
     extern __shared__ __attribute__((aligned(16))) int tb_lds[];
@@ -341,8 +343,9 @@ __device__ void alpha_traceback(const SswParams& p, const int8_t* smat, const Al
     uint32_t* cig = p.cigars + task.cigar_off;
     int* cig_len = p.cigar_len + task.out_index;
     if (big) {
-        if (!(res.status & CLH_STATUS_NEED_BIG)) return;
-        res.status &= ~CLH_STATUS_NEED_BIG;
+        if (!(res.status & need)) return;
+        res.status &= ~need;
+        __syncthreads();        // every wave has read the row (and found the bit) before it is cleared in memory
         if (lane == 0) p.results[task.out_index].status = res.status;
     }
     const bool no_cigar = (res.status & (CLH_STATUS_OVERFLOW8 | CLH_STATUS_BAD_CODE)) || (7 & p.flag) == 0 ||
@@ -356,7 +359,11 @@ __device__ void alpha_traceback(const SswParams& p, const int8_t* smat, const Al
         if (lane == 0) { cig[0] = (1u << 4); *cig_len = 1; }
         return;
     }
-    const int8_t* ref = p.refs + task.ref_off + res.ref_begin1;
+    // DNA (need == CLH_STATUS_NEED_W32): reference bytes through ref_code, as the 16-bit forms read them (genome windows: case and N
+    // flags, reverse complement); K1a's references are packed codes, forward
+    const bool dna = need == CLH_STATUS_NEED_W32;
+    const int rdir = task.ref_rc ? -1 : 1, rc = task.ref_rc;
+    const int8_t* ref = p.refs + task.ref_off + (int64_t)res.ref_begin1 * rdir;
     const int8_t* read = p.reads + task.read_off + res.read_begin1;
     const int refLen = res.ref_end1 - res.ref_begin1 + 1, readLen = res.read_end1 - res.read_begin1 + 1;
     const int score = res.score1, gO = p.gapO, gE = p.gapE, n = p.n;
@@ -371,11 +378,12 @@ __device__ void alpha_traceback(const SswParams& p, const int8_t* smat, const Al
     }
     if (staged) {
         for (int k = lane; k < readLen; k += nt) sseq[k] = read[k];
-        for (int k = lane; k < refLen; k += nt) sseq[readLen + k] = ref[k];
+        for (int k = lane; k < refLen; k += nt) sseq[readLen + k] = dna ? (int8_t)ref_code((int)ref[(int64_t)k * rdir], rc) : ref[k];
     }
     __syncthreads();
     const int8_t* const sread = staged ? sseq : read;
     const int8_t* const sref = staged ? sseq + readLen : ref;
+    auto ref_at = [&](int j) -> int { return (staged || !dna) ? (int)sref[j] : ref_code((int)ref[(int64_t)j * rdir], rc); };
     int w = refLen > readLen ? refLen - readLen : readLen - refLen;
     w += 1;
     const int nAD = readLen + refLen - 1;
@@ -437,7 +445,7 @@ __device__ void alpha_traceback(const SswParams& p, const int8_t* smat, const Al
                     const int df = t1 > t2 ? 5 : 4;
                     const int e1v = e > 0 ? e : 0, f1v = f > 0 ? f : 0;
                     t1 = e1v > f1v ? e1v : f1v;
-                    t2 = hd + smat[(int)sref[j] * n + (int)sread[i]];
+                    t2 = hd + smat[ref_at(j) * n + (int)sread[i]];
                     const int h = t1 > t2 ? t1 : t2;
                     const int dh = t1 <= t2 ? 1 : (e1v > f1v ? de : df);
                     itmax = h > itmax ? h : itmax;
@@ -566,7 +574,50 @@ __global__ void __launch_bounds__(1024) ssw_alpha_traceback_kernel(const SswPara
     }
 }
 
+// The DNA alignments the 16-bit traceback forms marked CLH_STATUS_NEED_W32 among tasks [task_base, task_base + ntasks): the workgroups
+// split the range, each scans its part a block at a time (the marked ones are few) and runs the int32 traceback on what it finds.
+__global__ void __launch_bounds__(1024) ssw_w32_traceback_kernel(const SswParams p, AlPool pool, int ws, int wsp, int seq_cap, int ntasks)
+{
+    __shared__ int8_t smat[1024];
+    __shared__ int s_n, s_list[1024];
+    if ((int)threadIdx.x < p.n * p.n) smat[threadIdx.x] = p.mat[threadIdx.x];
+    const int per = (ntasks + (int)gridDim.x - 1) / (int)gridDim.x;
+    const int k0 = (int)blockIdx.x * per, k1 = min(ntasks, k0 + per);
+    for (int b = k0; b < k1; b += (int)blockDim.x) {
+        if (threadIdx.x == 0) s_n = 0;
+        __syncthreads();
+        const int k = b + (int)threadIdx.x;
+        if (k < k1) {
+            const SswTask& t = p.tasks[pool.task_base + k];
+            if (t.out_index < p.n_real && (p.results[t.out_index].status & CLH_STATUS_NEED_W32)) s_list[atomicAdd(&s_n, 1)] = pool.task_base + k;
+        }
+        __syncthreads();
+        const int nf = __builtin_amdgcn_readfirstlane(s_n);
+        for (int q = 0; q < nf; ++q) {
+            alpha_traceback(p, smat, pool, ws, wsp, 1, seq_cap, __builtin_amdgcn_readfirstlane(s_list[q]), CLH_STATUS_NEED_W32);
+            __syncthreads();
+        }
+    }
+}
+
 }  // namespace
+
+hipError_t launch_traceback_w32(const SswParams& p, int task_base, int ntasks, uint8_t* pool_base, unsigned long long* pool_head,
+                                unsigned long long pool_size, hipStream_t stream)
+{
+    if (ntasks <= 0) return hipSuccess;
+    AlPool pool; pool.base = pool_base; pool.head = pool_head; pool.size = pool_size; pool.task_base = task_base;
+    pool.n_big = nullptr; pool.list_big = nullptr;           // (a big = 1 pass lists nothing)
+    const int ws = 5122;                                      // H/E/F (int32) of 5120 rows, the rest of 146 KiB for the sequences
+    int wsp = 1;
+    while (wsp * 2 <= ws) wsp *= 2;
+    const int seq_cap = 149504 - 7 * ws * (int)sizeof(int);  // (4 KiB less than K1a's large launch: the kernel's list of marked tasks)
+    const size_t lds = (size_t)7 * ws * sizeof(int) + (size_t)seq_cap;
+    // a few workgroups (each holds a CU's LDS): the marked alignments are rare, and most launches only scan
+    const int grid = std::min((ntasks + 255) / 256, 64);
+    hipLaunchKernelGGL(ssw_w32_traceback_kernel, dim3(grid), dim3(1024), lds, stream, p, pool, ws, wsp, seq_cap, ntasks);
+    return hipGetLastError();
+}
 
 size_t alpha_lds_bytes(int lcap) { return (size_t)3 * (size_t)((lcap + 15) & ~15) * sizeof(short) + (size_t)lcap + 16; }
 

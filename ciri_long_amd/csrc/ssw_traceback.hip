@@ -101,6 +101,7 @@ __device__ void tb_antidiagonal(const SswParams& p, const TbPool& pool, const in
     if (big) {
         if (!(res.status & CLH_STATUS_NEED_BIG)) return;
         res.status &= ~CLH_STATUS_NEED_BIG;
+        __syncthreads();        // every wave has read the row (and found the bit) before it is cleared in memory
         if (lane == 0) p.results[task.out_index].status = res.status;
     }
 
@@ -115,6 +116,10 @@ __device__ void tb_antidiagonal(const SswParams& p, const TbPool& pool, const in
         if (lane == 0) { cig[0] = (1u << 4); *cig_len = 1; }
         return;
     }
+    if (res.score1 >= 32767) {   // saturated by the 16-bit pass: the reference's int DP counts past what this kernel's state holds
+        if (lane == 0) { *cig_len = 0; p.results[task.out_index].status = res.status | CLH_STATUS_NEED_W32; }
+        return;
+    }
     const int rdir = task.ref_rc ? -1 : 1;
     const int8_t* ref = p.refs + task.ref_off + (int64_t)res.ref_begin1 * rdir;
     const int8_t* read = p.reads + task.read_off + res.read_begin1;
@@ -125,7 +130,7 @@ __device__ void tb_antidiagonal(const SswParams& p, const TbPool& pool, const in
     // anti-diagonal); with LDS-only reads the stores are fire-and-forget.
     if (readLen + refLen > seq_cap) {   // does not fit this launch's LDS: retry in the large configuration, or report the capacity limit
         if (lane == 0) {
-            *cig_len = 0; p.results[task.out_index].status = res.status | (big == 1 ? CLH_STATUS_CIGAR_TRUNC : CLH_STATUS_NEED_BIG);
+            *cig_len = 0; p.results[task.out_index].status = res.status | (big == 1 ? CLH_STATUS_NEED_W32 : CLH_STATUS_NEED_BIG);
             if (big != 1) pool.list_big[atomicAdd(pool.n_big, 1)] = task_index;
         }
         return;
@@ -156,7 +161,7 @@ __device__ void tb_antidiagonal(const SswParams& p, const TbPool& pool, const in
             continue;
         }
         const bool ring = w + 3 <= wsp;   // the active rows of an anti-diagonal span <= w+1 rows
-        if (!ring && readLen + 1 > ws) { status = big == 1 ? CLH_STATUS_CIGAR_TRUNC : CLH_STATUS_NEED_BIG; break; }
+        if (!ring && readLen + 1 > ws) { status = big == 1 ? CLH_STATUS_NEED_W32 : CLH_STATUS_NEED_BIG; break; }
         const int imask = ring ? wsp - 1 : -1;
         unsigned long long need = ((unsigned long long)nAD * (unsigned long long)stride_w + 63ull) & ~63ull;
         unsigned long long at = 0;

@@ -376,6 +376,10 @@ __device__ __forceinline__ bool tb_rows_setup(const SswParams& p, const uint2* s
         if (writer) { jb.cig[0] = (1u << 4); *jb.cig_len = 1; }
         return false;
     }
+    if (res.score1 >= 32767) {   // saturated by the 16-bit pass: the reference's int DP counts past the 16-bit frame -> the int32 traceback
+        if (writer) { *jb.cig_len = 0; p.results[task.out_index].status = res.status | CLH_STATUS_NEED_W32; }
+        return false;
+    }
     TbIn& in = jb.in;
     in.rdir = task.ref_rc ? -1 : 1; in.rc = task.ref_rc;
     in.ref = p.refs + task.ref_off + (int64_t)res.ref_begin1 * in.rdir;
