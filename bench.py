@@ -21,9 +21,12 @@ Headline workload (BASELINE.json `configs[2]`, the configuration the metric is q
                 alternately, so a batch's traceback tail runs under the next batch's score kernel.
   c4            the per-GPU share of configs[3]: 125 000 reads of 500-4000 bases through the c3 step.
 
-At N = 1 the default run also reports, under `extra`, one line each for c2, c4, the production shape of the clip
+A plain run does only what the headline figure needs: it sets up, warms up, times the steps, writes what the last step
+computed if --dump-outputs is given, and prints the line.  Everything else is behind --full: the CPU baseline and the oracle
+spot check it makes possible, the per-kernel launches and roofline objects (runs of their own after the timed loop), the
+prefilter's self-check of --prod-windows, and at N = 1 under `extra` one line each for c2, c4, the production shape of the clip
 re-alignment (20-300 nt clips vs +-200 kb windows of a resident genome), the C5-shaped collapse kernels (K4 edit
-distances, K1+K1b junction alignments) and the file-to-file stage 1 (`clh_ccs_file`), each with its own roofline object.
+distances, K1+K1b junction alignments) and the file-to-file stages, each with its own roofline object.
 
 One process per GPU, reads sharded by rank, no data-path collective (weak scaling); with N > 1 the seven counters of
 `call` (main.py:81-100) are all-reduced on RCCL after the timed loop, as the reference merges them.  Inputs are packed
@@ -433,8 +436,13 @@ class FullStep(object):
         return out, valu
 
 
-def run_full(torch, dist, hip, synth, ctx, wl, nreads, rank, world, steps, warmup, expect, use_dist=False, prod_windows=False, outputs=False):
+def run_full(torch, dist, hip, synth, ctx, wl, nreads, rank, world, steps, warmup, expect, use_dist=False, prod_windows=False, outputs=False,
+             full=True, prime=False):
+    """full=False: the timed loop and what it computed only (no per-kernel launches, no self-check); prime: one untimed step before
+    the warm-up when no spot check runs one"""
     fs = FullStep(torch, hip, synth, ctx, wl, nreads, rank, expect, prod_windows)
+    if prime:
+        fs.step()
     for _ in range(warmup):
         fs.step()
     fs.t_k5 = fs.t_k6 = fs.t_fetch = 0.0
@@ -462,8 +470,16 @@ def run_full(torch, dist, hip, synth, ctx, wl, nreads, rank, world, steps, warmu
         res_exchange = 'int64[7] all_reduce(sum) on RCCL over %d rank(s): total %d' % (world, int(counters[0]))
     else:
         res_exchange = None
-    launches, valu = fs.launches(steps)
     sig = fs.last['sig']
+    res = {'value': world * nreads * steps / el, 'ms_per_step': el / steps * 1e3, 'reads_with_consensus': int(len(fs.has)),
+           'counters': dict(zip(['total', 'consensus', 'raw_unmapped', 'ccs_mapped', 'bsj', 'signal', 'partial'], [int(x) for x in counters])),
+           'splice_handed_back': int((sig[:, 0] != 0).sum()), 'counter_exchange': res_exchange}
+    if outputs:
+        res['outputs'] = dumped
+    if not full:
+        fs.genome.close()
+        return res
+    launches, valu = fs.launches(steps)
     pf_stats = fs.ssw_plan.prefilter_stats()
     pf_check = None
     if prod_windows:
@@ -487,10 +503,7 @@ def run_full(torch, dist, hip, synth, ctx, wl, nreads, rank, world, steps, warmu
         same = all((r1[f] == r2[f]).all() for f in ('score1', 'ref_begin1', 'ref_end1', 'read_begin1', 'read_end1'))
         assert same, 'prefilter changed an answer'
         pf_check = '%d clips re-run without the prefilter (static window slices): rows identical' % m
-    res = {'value': world * nreads * steps / el, 'ms_per_step': el / steps * 1e3, 'launches': launches, **split_prefilter(valu), 'valu_roofline_k3': fs.k3_valu,
-           'roofline': roofline_of(launches), 'reads_with_consensus': int(len(fs.has)),
-           'counters': dict(zip(['total', 'consensus', 'raw_unmapped', 'ccs_mapped', 'bsj', 'signal', 'partial'], [int(x) for x in counters])),
-           'splice_handed_back': int((sig[:, 0] != 0).sum()), 'counter_exchange': res_exchange}
+    res.update({'launches': launches, **split_prefilter(valu), 'valu_roofline_k3': fs.k3_valu, 'roofline': roofline_of(launches)})
     if prod_windows and res['roofline']['kernel'].startswith('ssw_prefilter_kernel'):      # (its own counters: profiles/r04c_c3prod_pmc_summary.csv)
         try:
             res['roofline']['traffic'] = json.load(open(os.path.join(ROOT, 'profiles', 'hbm_traffic.json'))).get('c3_production_windows: ' + res['roofline']['kernel'])
@@ -500,13 +513,11 @@ def run_full(torch, dist, hip, synth, ctx, wl, nreads, rank, world, steps, warmu
         res['prefilter'] = pf_stats
     if pf_check:
         res['prefilter_check'] = pf_check
-    if outputs:
-        res['outputs'] = dumped
     fs.genome.close()
     return res
 
 
-def run_c2(torch, dist, hip, synth, ctx, nreads, rank, world, steps, warmup, expect, use_dist=False, outputs=False):
+def run_c2(torch, dist, hip, synth, ctx, nreads, rank, world, steps, warmup, expect, use_dist=False, outputs=False, full=True):
     reads, wins = make_batch(synth, 'c2', nreads, rank)
     rd, ro = hip.pack(reads)
     fd, fo = hip.pack(wins)
@@ -548,11 +559,12 @@ def run_c2(torch, dist, hip, synth, ctx, nreads, rank, world, steps, warmup, exp
             got = lanes[s_ & 1][0].fetch()          # rows and CIGARs on the host inside the timed region
         return got
 
-    # both lanes warm (events created, first launches done) whatever --warmup is, and the second plan's answers checked against the first's
-    # (the oracle spot check above saw only ssw_plan; plan_b produces half of the timed fetches)
+    # both lanes warm (events created, first launches done) whatever --warmup is, and with full the second plan's answers checked against
+    # the first's (the oracle spot check above saw only ssw_plan; plan_b produces half of the timed fetches)
     plan_b.run(d_reads.data_ptr(), d_wins.data_ptr(), lanes[1][1])
     brow, bcig = plan_b.fetch()
-    assert all((brow[f] == srow[f]).all() for f in srow.dtype.names) and (bcig == scig).all(), 'the two C2 plans disagree'
+    if full:
+        assert all((brow[f] == srow[f]).all() for f in srow.dtype.names) and (bcig == scig).all(), 'the two C2 plans disagree'
     run_steps(warmup)
     if use_dist:
         dist.barrier()
@@ -567,9 +579,10 @@ def run_c2(torch, dist, hip, synth, ctx, nreads, rank, world, steps, warmup, exp
         t = torch.tensor([el], dtype=torch.float64, device='cuda')
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
-    launches, valu = k1_launches(ssw_plan, lambda: ssw_plan.run(d_reads.data_ptr(), d_wins.data_ptr(), stream), ro, np.diff(fo), c2=True)
-    res = {'value': world * nreads * steps / el, 'ms_per_step': el / steps * 1e3, 'launches': launches, 'valu_roofline': valu,
-           'roofline': roofline_of(launches)}
+    res = {'value': world * nreads * steps / el, 'ms_per_step': el / steps * 1e3}
+    if full:
+        launches, valu = k1_launches(ssw_plan, lambda: ssw_plan.run(d_reads.data_ptr(), d_wins.data_ptr(), stream), ro, np.diff(fo), c2=True)
+        res.update(launches=launches, valu_roofline=valu, roofline=roofline_of(launches))
     if outputs:         # the complete s_align of every read: every field of its row, and the CIGARs (len << 4 | op: exact in float32)
         rows, cig = last
         assert not len(cig) or int(cig.max()) < 1 << 24
@@ -1104,18 +1117,21 @@ def main():
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--workload', choices=('c3', 'c2', 'c4'), default='c3')
     ap.add_argument('--reads', type=int, default=0, help='reads per GPU (default: 100000 for c3, 10000 for c2, 125000 for c4)')
-    ap.add_argument('--cpu-seconds', type=float, default=12.0)
-    ap.add_argument('--no-cpu', action='store_true')
+    ap.add_argument('--full', action='store_true', help='also run and report everything beyond the headline figure: the CPU baseline and the oracle '
+                    'spot check before timing, per-kernel launches and roofline objects, the prefilter self-check of --prod-windows, and at N = 1 '
+                    'with c3 the extra lines; without it a run sets up, warms up, times the steps, dumps outputs if asked and prints the line')
+    ap.add_argument('--cpu-seconds', type=float, default=12.0, help='with --full: how long the CPU baseline runs')
+    ap.add_argument('--no-cpu', action='store_true', help='with --full: skip the CPU baseline (and with it the spot check)')
     ap.add_argument('--prod-windows', action='store_true', help='c3 / c4 with the reference\'s own clip window (hit +- 200 kb, find_bsj.py:196-197) instead of 2 kb: the extra line c3_production_windows as the main workload (for profiling)')
     ap.add_argument('--detail', default=None, help='where the full record goes (default: bench_detail.json beside bench.py); stdout carries one short line')
-    ap.add_argument('--no-extra', action='store_true', help='skip the extra lines (c2, c4, production shape, collapse, stage 1)')
+    ap.add_argument('--no-extra', action='store_true', help='with --full: skip the extra lines (c2, c4, production shape, collapse, file stages)')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the last timed step computed as DIR/<name>.npy (float32/float64, '
                     'rank 0\'s shard), so that two builds can be compared output for output on the same seeded inputs')
     args = ap.parse_args()
     if args.steps < 1:
         ap.error('--steps must be at least 1')
     wl = args.workload
-    full = wl != 'c2'            # c3 / c4: the whole device part of `call`; c2: Smith-Waterman only
+    chain = wl != 'c2'            # c3 / c4: the whole device part of `call`; c2: Smith-Waterman only
     nreads = args.reads or {'c3': 100000, 'c2': 10000, 'c4': 125000}[wl]
 
     # under rocprofv3 the preloaded tool library has initialised the GPU before Python started: this process must then neither
@@ -1135,16 +1151,17 @@ def main():
         raise SystemExit('bench.py: --gpus %d but WORLD_SIZE=%d' % (args.gpus, world))
     # under a launcher the process group exists even for one rank, so the RCCL exchange of `call` runs wherever a launcher does
     use_dist = 'WORLD_SIZE' in os.environ
-    # The CPU leg spawns one process per host core.  It runs BEFORE this process touches the GPU (a child of a process
+    # With --full the CPU leg spawns one process per host core.  It runs BEFORE this process touches the GPU (a child of a process
     # that has initialised the GPU must not exec), and not at all under rocprofv3, whose preloaded library initialises
     # the GPU before Python starts (and again in every child).
+    cpu_leg = rank == 0 and world == 1 and not profiled
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu and not profiled:
+    if args.full and cpu_leg and not args.no_cpu:
         cpu = cpu_baseline(args.cpu_seconds, wl)
 
     # the worker processes of the mapper-pool line: forked now, before this process touches the GPU (a spawned CPU leg is behind us)
     pool_prep = None
-    if rank == 0 and world == 1 and not args.no_extra and not profiled and wl == 'c3':
+    if args.full and rank == 0 and world == 1 and not args.no_extra and not profiled and wl == 'c3':
         try:
             pool_prep = prepare_stage2_pool()
         except Exception as ex:          # an extra line must not cost the headline
@@ -1166,11 +1183,13 @@ def main():
     expect = cpu.pop('_expect') if cpu else None     # None: no CPU leg in this run (multi-GPU, --no-cpu, profiler): no spot check
     ctx = hip.Context(local_rank)
     dump = args.dump_outputs is not None and rank == 0
-    if full:
+    if chain:
+        # the spot check of a --full run takes one untimed step before the warm-up; a plain run takes that step where the CPU leg would have
+        # run, so that its timed loop starts from the same state
         res = run_full(torch, dist, hip, synth, ctx, wl, nreads, rank, world, args.steps, args.warmup, None if args.prod_windows else expect, use_dist,
-                       prod_windows=args.prod_windows, outputs=dump)
+                       prod_windows=args.prod_windows, outputs=dump, full=args.full, prime=cpu_leg and not args.full and not args.prod_windows)
     else:
-        res = run_c2(torch, dist, hip, synth, ctx, nreads, rank, world, args.steps, args.warmup, expect, use_dist, outputs=dump)
+        res = run_c2(torch, dist, hip, synth, ctx, nreads, rank, world, args.steps, args.warmup, expect, use_dist, outputs=dump, full=args.full)
     if dump:
         dump_outputs(res.pop('outputs'), args.dump_outputs)
 
@@ -1186,14 +1205,14 @@ def main():
         'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'int16', 'data': 'synthetic',
         'config': {
             'workload': (('C4 (per-GPU share of 1 M reads, lengths 500-4000): ' if wl == 'c4' else 'C3: ') +
-                         '%d NanoSim-shaped reads per GPU (~1 kb for C3) %s' % (nreads, step_text)) if full else
+                         '%d NanoSim-shaped reads per GPU (~1 kb for C3) %s' % (nreads, step_text)) if chain else
                         ('C2: %d NanoSim-shaped ~1 kb reads per GPU, SSW step only, complete s_align (second best, begin/end, '
                          'CIGAR) vs own 2 kb window, rows and CIGARs to the host in every step; two batches in flight on two '
                          'streams (a step queues the next batch before it waits for its own results)' % nreads),
             'reads_per_gpu': nreads, 'window': 'hit +- 200 kb' if args.prod_windows else WINDOW, 'scoring': '1/1/1/1',
             'parallelism': 'reads sharded x%d, no data-path collective%s' % (world, '; int64[7] counter all-reduce on RCCL after the timed loop' if world > 1 else ''),
-            'consensus_parity': 'unpinned (pyccs/spoa absent from the reference tree; clh-poa v3 restates the published spoa algorithm, no departures, oracle/poa_oracle.c)' if full else None},
-        'roofline': res['roofline'], 'valu_roofline': res.get('valu_roofline'),
+            'consensus_parity': 'unpinned (pyccs/spoa absent from the reference tree; clh-poa v3 restates the published spoa algorithm, no departures, oracle/poa_oracle.c)' if chain else None},
+        'roofline': res.get('roofline'), 'valu_roofline': res.get('valu_roofline'),
     }
     if 'valu_roofline_k3' in res:
         out['valu_roofline_k3'] = res['valu_roofline_k3']      # the kernel that is most of the step
@@ -1205,8 +1224,8 @@ def main():
         out['counters'] = res['counters']
         out['splice_handed_back'] = res['splice_handed_back']
         out['counter_exchange'] = res['counter_exchange']
-    out['cpu_baseline'] = cpu      # rank 0 at N=1 only; None under a profiler or with --no-cpu
-    if world == 1 and not args.no_extra and not profiled and wl == 'c3':
+    out['cpu_baseline'] = cpu      # --full, rank 0 at N=1 only; None without --full, under a profiler or with --no-cpu
+    if args.full and world == 1 and not args.no_extra and not profiled and wl == 'c3':
         extra = {}
         try:
             s = run_c2(torch, dist, hip, synth, ctx, 10000, 0, 1, 10, 2, None)
@@ -1230,7 +1249,8 @@ def main():
         except Exception as ex:                      # an extra line must not cost the headline
             extra['error'] = repr(ex)
         out['extra'] = extra
-    out['launches'] = res['launches']
+    if 'launches' in res:
+        out['launches'] = res['launches']
     out['summary'] = summary_of(out)
     if rank == 0:
         emit(out, args.detail)
