@@ -17,7 +17,8 @@
 #include "clh_device.h"
 
 static thread_local std::string g_err;
-static int fail(int code, const std::string& m) { g_err = m; return code; }
+static thread_local int g_code = CLH_E_ARG;            // the code of the last failure: what a batch call returns when its plan was refused
+static int fail(int code, const std::string& m) { g_err = m; g_code = code; return code; }
 #define HIPCHK(expr)                                                                         \
     do {                                                                                     \
         hipError_t e_ = (expr);                                                              \
@@ -129,13 +130,84 @@ extern "C" void clh_destroy(clh_ctx* c)
 
 extern "C" int clh_device_of(const clh_ctx* c) { return c ? c->device : -1; }
 
+// What every plan kind and the resident genome share: the device blocks they take from the context's allocator and the
+// events they create are recorded as they are handed out, and deleting the object gives all of them back.
+struct clh_owned {
+    clh_ctx* ctx = nullptr;
+    bool ran = false;
+    hipStream_t last_stream = nullptr;
+    std::vector<void*> blocks;
+    std::vector<hipEvent_t> events;
+
+    explicit clh_owned(clh_ctx* c) : ctx(c) {}
+    clh_owned(const clh_owned&) = delete;
+    clh_owned& operator=(const clh_owned&) = delete;
+    virtual ~clh_owned()
+    {
+        (void)hipSetDevice(ctx->device);
+        if (ran) (void)hipStreamSynchronize(last_stream);
+        for (void* b : blocks) ctx->release(b);
+        for (hipEvent_t e : events) (void)hipEventDestroy(e);
+    }
+    void* alloc(size_t bytes)
+    {
+        void* p = ctx->alloc(bytes);
+        if (p) blocks.push_back(p);
+        return p;
+    }
+    // alloc + copy; null on failure (the block, if any, stays owned)
+    void* upload(const void* host, size_t bytes)
+    {
+        void* p = alloc(bytes);
+        return p && (bytes == 0 || hipMemcpy(p, host, bytes, hipMemcpyHostToDevice) == hipSuccess) ? p : nullptr;
+    }
+    // gives one block back before the object goes
+    void free_block(void* p)
+    {
+        auto it = std::find(blocks.begin(), blocks.end(), p);
+        if (it == blocks.end()) return;
+        blocks.erase(it);
+        ctx->release(p);
+    }
+    hipError_t event(hipEvent_t* e, unsigned flags = hipEventDefault)
+    {
+        const hipError_t r = hipEventCreateWithFlags(e, flags);
+        if (r == hipSuccess) events.push_back(*e);
+        return r;
+    }
+};
+
 // ------------------------------------------------------------------------------------------------------------
 // plan
 // ------------------------------------------------------------------------------------------------------------
-struct clh_plan {
-    clh_ctx* ctx = nullptr;
+// The A/B switches of the Smith-Waterman classes, read once when a plan is built: the plan keeps them
+struct SswSwitches {
+    bool no_scan, no_scanw, no_slices, no_prefilter, no_lanes, no_pf2, no_tb_rows, no_guess, pf2_always;
+    int pf2_share;
+};
+
+static SswSwitches ssw_switches()
+{
+    SswSwitches sw;
+    sw.no_scan = getenv("CLH_NO_SCAN") != nullptr;
+    sw.no_scanw = getenv("CLH_NO_SCANW") != nullptr;
+    sw.no_slices = getenv("CLH_NO_SLICES") != nullptr;
+    sw.no_prefilter = getenv("CLH_NO_PREFILTER") != nullptr;
+    sw.no_lanes = getenv("CLH_NO_LANES") != nullptr;
+    sw.no_pf2 = getenv("CLH_NO_PF2") != nullptr;
+    sw.no_tb_rows = getenv("CLH_NO_TB_ROWS") != nullptr;
+    sw.no_guess = getenv("CLH_NO_GUESS") != nullptr;
+    sw.pf2_always = getenv("CLH_PF2_ALWAYS") != nullptr;
+    const char* share = getenv("CLH_PF2_SHARE");
+    sw.pf2_share = share ? std::max(1, atoi(share)) : 8;
+    return sw;
+}
+
+struct clh_plan : clh_owned {
+    using clh_owned::clh_owned;
     int n = 0;
     clh_ssw_opts opts;
+    SswSwitches sw;
     clh::SswParams params;          // device pointers filled at run time
     bool quirk = false, do_cigar = false;
     std::vector<clh::SswTask> tasks;    // launch order
@@ -162,38 +234,30 @@ struct clh_plan {
     int n_all = 0;                           // tasks incl. those slices (their result rows sit behind the n real ones)
     std::vector<Seg> segs;
     void *d_tasks = nullptr, *d_results = nullptr, *d_colmax = nullptr, *d_cigars = nullptr, *d_cigar_len = nullptr,
-         *d_pool = nullptr, *d_pool_head = nullptr, *d_reads = nullptr, *d_refs = nullptr;
+         *d_pool = nullptr, *d_pool_head = nullptr;
     size_t colmax_elems = 0, cigar_elems = 0, strip_bytes = 0;
     unsigned long long pool_bytes = 0;
     void* d_strips = nullptr;
-    hipStream_t last_stream = nullptr;
     hipEvent_t done_ev = nullptr;           // recorded behind the run's last launch: fetch waits for the RUN, not for what the caller queued later
-    bool ran = false;
     bool profiling = false;
     int64_t refs_bytes = -1;                 // size of the caller's refs buffer if stated (clh_plan_set_refs_bytes), else -1
-    std::vector<hipEvent_t> chain_ev;   // between the parts of a split K1w class
     std::vector<hipEvent_t> ev;     // per segment: K1 start, K1 stop; then K1b small-window start/stop, large-window start/stop
     std::vector<int32_t> w32_prefix;   // tasks in launch order: how many before k could need the int32 traceback (clh::launch_traceback_w32)
     bool alpha = false;             // matrix edge 6..32: every alignment in the K1a classes (ssw_alpha.hip)
     void* d_alpha_mat = nullptr;    // their n x n matrix
+
+    // the workspaces of a class's persistent workgroups in the strip buffer: wgs slots of `bytes` rounded up to 256; returns their offset
+    int64_t reserve_ws(size_t bytes, int wgs, int* slot)
+    {
+        *slot = (int)((bytes + 255) & ~(size_t)255);
+        strip_bytes = (strip_bytes + 255) & ~(size_t)255;
+        const int64_t off = (int64_t)strip_bytes;
+        strip_bytes += (size_t)*slot * (size_t)wgs;
+        return off;
+    }
 };
 
-extern "C" void clh_plan_destroy(clh_plan* pl)
-{
-    if (!pl) return;
-    clh_ctx* c = pl->ctx;
-    (void)hipSetDevice(c->device);
-    if (pl->ran) (void)hipStreamSynchronize(pl->last_stream);
-    void* bufs[] = {pl->d_tasks, pl->d_results, pl->d_colmax, pl->d_cigars, pl->d_cigar_len, pl->d_pool, pl->d_pool_head,
-                    pl->d_reads, pl->d_refs, pl->d_strips, pl->d_slices, pl->d_parts, pl->d_slice_base, pl->d_seg_ctr, pl->d_alpha_mat};
-    for (void* b : bufs) c->release(b);
-    for (auto& f : pl->pf) { void* pb[] = {f.d_win, f.d_pieces, f.d_work, f.d_dmin, f.d_queue, f.d_out, f.d_ctl, f.d_bound, f.d_parts, f.d_q2}; for (void* b : pb) c->release(b); }
-    for (hipEvent_t e : pl->ev) (void)hipEventDestroy(e);
-    for (auto& f : pl->pf) for (hipEvent_t e : f.ev) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : pl->chain_ev) (void)hipEventDestroy(e);
-    if (pl->done_ev) (void)hipEventDestroy(pl->done_ev);
-    delete pl;
-}
+extern "C" void clh_plan_destroy(clh_plan* pl) { delete pl; }
 
 // K1a (ssw_alpha.hip): the read-length bucket of an alignment over a matrix of edge 6..32
 static int alpha_class_for(int64_t L)
@@ -203,8 +267,9 @@ static int alpha_class_for(int64_t L)
     return clh::kRvAlpha - (clh::kNumAlphaBuckets - 1);
 }
 
-static int rv_class_for(int rows)
+static int rv_class_for(int64_t L)
 {
+    const int64_t rows = (L + 15) / 16 * 16;
     for (int i = 0; i < clh::kNumRvClasses; ++i)
         if (128 * clh::kRvClasses[i] >= rows) return clh::kRvClasses[i];
     return clh::kRvStrips;      // longer than 4096 rows: RV = 32 kernel with row strips
@@ -213,55 +278,54 @@ static int rv_class_for(int rows)
 // K1s (ssw_scan.hip) takes the alignments whose scores provably fit the reference's 8-bit pass (ssw.c:804-806 chooses it and
 // it cannot overflow), with the read short enough for its (score, row) keys and the gap extension for its 16-bit frames.
 // CLH_NO_SCAN=1 in the environment sends everything to the anti-diagonal kernels (A/B measurements).
-// CLH_NO_TB_ROWS=1: CIGARs from the anti-diagonal traceback kernel only (A/B measurements)
-static bool tb_rows_on() { static const bool off = getenv("CLH_NO_TB_ROWS") != nullptr; return !off; }
-
-static bool scan_class_ok(int64_t L, const clh_ssw_opts* o, int max_match, int bias)
+static bool scan_class_ok(int64_t L, const clh_ssw_opts* o, int max_match, int bias, const SswSwitches& sw)
 {
-    static const bool off = getenv("CLH_NO_SCAN") != nullptr;
-    return !off && L <= 254 && o->score_size != 1 && (int64_t)max_match * L + bias < 255 && o->gap_extend >= 0 && o->gap_extend <= 16 && o->gap_open <= 255;
+    return !sw.no_scan && L <= 254 && o->score_size != 1 && (int64_t)max_match * L + bias < 255 && o->gap_extend >= 0 && o->gap_extend <= 16 && o->gap_open <= 255;
 }
 
 // K1w (ssw_scan_wide.hip): the same walk for what K1s leaves -- reads up to 4096 bases, any score below the 16-bit ceiling -- on
 // windows that are not cut into slices.  CLH_NO_SCANW=1 switches it off (A/B measurements): the anti-diagonal classes take over.
-static bool scanw_class_ok(int64_t L, int64_t R, const clh_ssw_opts* o, int max_match)
+static bool scanw_class_ok(int64_t L, int64_t R, const clh_ssw_opts* o, int max_match, const SswSwitches& sw)
 {
-    const bool off = getenv("CLH_NO_SCAN") != nullptr || getenv("CLH_NO_SCANW") != nullptr;      // (read per plan: the tests switch it)
-    return !off && L <= 4096 && R < 32768 && (int64_t)max_match * L < 32000 && o->gap_extend >= 0 && o->gap_extend <= 16 && o->gap_open <= 255;
+    return !sw.no_scan && !sw.no_scanw && L <= 4096 && R < 32768 && (int64_t)max_match * L < 32000 && o->gap_extend >= 0 && o->gap_extend <= 16 && o->gap_open <= 255;
 }
 
 // K1s on long windows: the forward pass runs as slices of >= 8192 owned columns (at most 64 per alignment), each started
 // `overlap` columns early (ssw_scan.hip: ssw_scan_slice_kernel).  Needs a positive gap extension (else a local alignment has
 // no bounded span).  CLH_NO_SLICES=1 switches it off (A/B measurements).
 static const int kSliceMinWindow = 32768, kSliceMinCols = 8192;
-static bool scan_sliced(int64_t R, const clh_ssw_opts* o)
+static bool scan_sliced(int64_t R, const clh_ssw_opts* o, const SswSwitches& sw)
 {
-    static const bool off = getenv("CLH_NO_SLICES") != nullptr;
-    // (experiment: CLH_PF_MIN_WINDOW lowers the window length from which K1s goes behind the prefilter -- call-path options only)
-    static const int pf_min = getenv("CLH_PF_MIN_WINDOW") ? atoi(getenv("CLH_PF_MIN_WINDOW")) : kSliceMinWindow;
-    if (!o->want_score2 && R >= pf_min && o->gap_extend >= 1 && !off && getenv("CLH_NO_PREFILTER") == nullptr) return true;
-    return !off && R >= kSliceMinWindow && o->gap_extend >= 1;
+    return !sw.no_slices && R >= kSliceMinWindow && o->gap_extend >= 1;
+}
+
+// The window slices of a long alignment: each owns `own` columns and starts `overlap` columns early -- a local alignment spans at
+// most L (1 + max_match / gap_extend) columns (+ wildcard rows + slack).  At most 64 slices of >= 8192 owned columns, and with
+// own_overlaps > 0 at least that many overlaps.
+struct SliceGeom { int64_t overlap, own; };
+static SliceGeom slice_geom(int64_t L, int64_t R, int max_match, int gap_extend, int own_overlaps)
+{
+    const int64_t overlap = L + (L * max_match + gap_extend - 1) / gap_extend + 32;
+    return {overlap, std::max<int64_t>(std::max<int64_t>(kSliceMinCols, own_overlaps * overlap), (R + 63) / 64)};
 }
 
 // The sliced class behind the exact prefilter (ssw_prefilter.hip): needs the bound's constant c = min(max_match, gap_extend) >= 1
 // and no second-best score (the column maxima of the columns it skips would be missing).  CLH_NO_PREFILTER=1 switches it off
 // (A/B measurements, and the parity tests run both ways).
-static bool prefilter_ok(const clh_ssw_opts* o, int max_match)
+static bool prefilter_ok(const clh_ssw_opts* o, int max_match, const SswSwitches& sw)
 {
-    return getenv("CLH_NO_PREFILTER") == nullptr && !o->want_score2 && max_match >= 1 && o->gap_extend >= 1;
+    return !sw.no_prefilter && !o->want_score2 && max_match >= 1 && o->gap_extend >= 1;
 }
 
 // K1w on long windows (ssw_scan_wide.hip, class kRvScanWideSliced): what K1s's 8-bit class does not take, on windows of 32 kb and
 // more with call-path options -- the prefilter in pieces of the read, a seed, candidate regions as K1w tasks.  Windows up to 1.5 Mb
 // (a static slice + its overlap must stay inside K1w's 32 767 columns).  Without the prefilter (CLH_NO_PREFILTER) these alignments
 // run as window-slice tasks of the anti-diagonal classes, as in rounds 2-3.
-static bool scanw_sliced_ok(int64_t L, int64_t R, const clh_ssw_opts* o, int max_match)
+static bool scanw_sliced_ok(int64_t L, int64_t R, const clh_ssw_opts* o, int max_match, const SswSwitches& sw)
 {
-    const bool off = getenv("CLH_NO_SCAN") != nullptr || getenv("CLH_NO_SCANW") != nullptr || getenv("CLH_NO_SLICES") != nullptr;
-    if (off || !prefilter_ok(o, max_match)) return false;
-    const int64_t overlap = L + (L * max_match + o->gap_extend - 1) / o->gap_extend + 32;
-    const int64_t own = std::max<int64_t>(std::max<int64_t>(8192, 2 * overlap), (R + 63) / 64);
-    return L <= 4096 && R >= kSliceMinWindow && R <= 1500000 && own + overlap < 32768 && (int64_t)max_match * L < 32000 && o->gap_extend <= 16 && o->gap_open <= 255;
+    if (sw.no_scan || sw.no_scanw || sw.no_slices || !prefilter_ok(o, max_match, sw)) return false;
+    const SliceGeom g = slice_geom(L, R, max_match, o->gap_extend, 2);
+    return L <= 4096 && R >= kSliceMinWindow && R <= 1500000 && g.own + g.overlap < 32768 && (int64_t)max_match * L < 32000 && o->gap_extend <= 16 && o->gap_open <= 255;
 }
 
 // K1l (ssw_lanes.hip): one alignment per lane for references of at most 64 columns -- the collapse stage's junction alignments
@@ -270,17 +334,30 @@ static bool scanw_sliced_ok(int64_t L, int64_t R, const clh_ssw_opts* o, int max
 // pass with gap_open == gap_extend truncates F at stripe boundaries, rowmajor_spec.c), code 4 scoring 0.  A lane walks its alignment alone: a long
 // read against a short reference goes there only when the plan holds enough of them to fill the GPU's lanes (`many`), else to the
 // wave-per-alignment classes.  CLH_NO_LANES=1 switches the class off (A/B measurements, and the parity tests run both ways).
-static int lanes_class_for(int64_t L, int64_t R, const clh_ssw_opts* o, int max_match, int bias, int null_code, bool many)
+static int lanes_class_for(int64_t L, int64_t R, const clh_ssw_opts* o, int max_match, int bias, int null_code, bool many, const SswSwitches& sw)
 {
-    if (getenv("CLH_NO_LANES") != nullptr) return 0;
+    if (sw.no_lanes) return 0;
     if (o->want_score2 || R < 1 || R > 64 || L < 1 || L > 65535) return 0;
     if (!(o->n_mat <= 4 || null_code == 4)) return 0;
     if (o->gap_open > 255 || o->gap_extend < 0) return 0;
     if (o->gap_open <= o->gap_extend && !((int64_t)max_match * std::min(L, R) + bias < 255 && o->score_size != 1)) return 0;
     // a lane is alone with its alignment: ~25 ns per cell and pass.  Up to 2048 cells that is nothing; more only when the plan fills the GPU's lanes
     // (and then not beyond 262144 cells: a 6 ms chain)
-    if ((!many && L * R > 2048) || L * R > 262144) return (L <= 32767 && !getenv("CLH_NO_SCANW") && !getenv("CLH_NO_SCAN")) ? clh::kRvScanTr : 0;      // a wave per alignment, transposed (ssw_scan_wide.hip)
+    if ((!many && L * R > 2048) || L * R > 262144) return (L <= 32767 && !sw.no_scanw && !sw.no_scan) ? clh::kRvScanTr : 0;      // a wave per alignment, transposed (ssw_scan_wide.hip)
     return R <= 20 ? clh::kRvLanes20 : (R <= 32 ? clh::kRvLanes32 : (R <= 52 ? clh::kRvLanes52 : clh::kRvLanes64));
+}
+
+// the class of one alignment: K1a for the wide alphabets; else K1l / K1w-T, K1s (sliced on long windows), K1w, K1w behind the
+// prefilter, the anti-diagonal classes by read length
+static int ssw_class_for(int64_t L, int64_t R, const clh_ssw_opts* o, int max_match, int bias, int null_code, bool alpha, bool many,
+                         const SswSwitches& sw)
+{
+    if (alpha) return alpha_class_for(L);
+    if (int rv = lanes_class_for(L, R, o, max_match, bias, null_code, many, sw)) return rv;
+    if (scan_class_ok(L, o, max_match, bias, sw)) return scan_sliced(R, o, sw) ? clh::kRvScanSliced : clh::kRvScan;
+    if (scanw_class_ok(L, R, o, max_match, sw)) return clh::kRvScanWide;
+    if (scanw_sliced_ok(L, R, o, max_match, sw)) return clh::kRvScanWideSliced;
+    return rv_class_for(L);
 }
 
 // ref_off != nullptr: packed references, alignment a against [ref_off[a], ref_off[a+1]).  Otherwise windows of a resident
@@ -300,8 +377,9 @@ static clh_plan* ssw_plan_build(clh_ctx* ctx, int32_t n, const int64_t* read_off
     const bool alpha = o->n_mat > 5;
     if (alpha && !ref_off) { fail(CLH_E_UNSUPPORTED, "windows of a resident genome take substitution matrices of edge 1..5 only"); return nullptr; }
     if (hipSetDevice(ctx->device) != hipSuccess) { fail(CLH_E_HIP, "hipSetDevice failed"); return nullptr; }
-    clh_plan* pl = new clh_plan();
-    pl->ctx = ctx; pl->n = n; pl->opts = *o;
+    clh_plan* pl = new clh_plan(ctx);
+    pl->n = n; pl->opts = *o;
+    const SswSwitches& sw = pl->sw = ssw_switches();
     clh::SswParams& P = pl->params;
     memset(&P, 0, sizeof(P));
     int mn = 0, mx = -128;
@@ -327,22 +405,21 @@ static clh_plan* ssw_plan_build(clh_ctx* ctx, int32_t n, const int64_t* read_off
     pl->tasks.resize(n);
     size_t colmax = 0, cig = 0;
     unsigned long long pool = 0;
+    auto class_of = [&](int a, bool many) {
+        const int64_t L = read_off[a + 1] - read_off[a], R = ref_off ? ref_off[a + 1] - ref_off[a] : (int64_t)win_len[a];
+        return ssw_class_for(L, R, o, mx, -mn, P.null_code, alpha, many, sw);
+    };
     int n_short_ref = 0;                     // alignments K1l could take: enough of them fill the GPU's lanes whatever their read length
     for (int a = 0; a < n; ++a) {
-        const int64_t L = read_off[a + 1] - read_off[a], R = ref_off ? ref_off[a + 1] - ref_off[a] : (int64_t)win_len[a];
-        n_short_ref += !alpha && lanes_class_for(L, R, o, mx, -mn, P.null_code, true) != 0;
+        const int rv = class_of(a, true);
+        n_short_ref += clh::rv_is_lanes(rv) || rv == clh::kRvScanTr;
     }
     const bool many_short_ref = n_short_ref >= 32768;
     for (int a = 0; a < n; ++a) {
         const int64_t L = read_off[a + 1] - read_off[a], R = ref_off ? ref_off[a + 1] - ref_off[a] : (int64_t)win_len[a];
         if (L < 1 || R < 0 || L > 0x7fffffff || R > 0x7fffffff) { fail(CLH_E_ARG, "empty read or negative length in batch"); delete pl; return nullptr; }
         const int rc = (!ref_off && win_rc && win_rc[a]) ? 1 : 0;
-        const int rows = (int)((L + 15) / 16) * 16;
-        const int lanes_rv = alpha ? 0 : lanes_class_for(L, R, o, mx, -mn, P.null_code, many_short_ref);
-        const int rv = alpha ? alpha_class_for(L)
-                     : lanes_rv ? lanes_rv : scan_class_ok(L, o, mx, -mn) ? (scan_sliced(R, o) ? clh::kRvScanSliced : clh::kRvScan)
-                                                    : (scanw_class_ok(L, R, o, mx) ? clh::kRvScanWide
-                                                       : (scanw_sliced_ok(L, R, o, mx) ? clh::kRvScanWideSliced : rv_class_for(rows)));
+        const int rv = class_of(a, many_short_ref);
         cls[a] = rv;
         clh::SswTask& t = pl->tasks[a];
         t.read_off = read_off[a]; t.ref_off = ref_off ? ref_off[a] : (rc ? win_off[a] + R - 1 : win_off[a]);
@@ -375,13 +452,12 @@ static clh_plan* ssw_plan_build(clh_ctx* ctx, int32_t n, const int64_t* read_off
     // (started that far before its owned columns) computes the whole-window H there; a later slice that sees the same cell
     // in its overlap can only underestimate, and loses the tie.  The reverse pass of the owning slice runs inside the slice.
     int n_all = n;
-    if (!alpha && !o->want_score2 && o->gap_extend >= 1 && !getenv("CLH_NO_SLICES")) {
+    if (!alpha && !o->want_score2 && o->gap_extend >= 1 && !sw.no_slices) {
         for (int a = 0; a < n; ++a) {
             if (cls[a] < 1 || cls[a] == clh::kRvStrips || pl->tasks[a].ref_len < kSliceMinWindow) continue;
             const clh::SswTask par = pl->tasks[a];
-            const int64_t R = par.ref_len, L = par.read_len;
-            const int64_t overlap = L + (L * mx + o->gap_extend - 1) / o->gap_extend + 32;
-            const int64_t own = std::max<int64_t>(std::max<int64_t>(kSliceMinCols, 2 * overlap), (R + 63) / 64);
+            const int64_t R = par.ref_len;
+            const auto [overlap, own] = slice_geom(par.read_len, R, mx, o->gap_extend, 2);
             const int rdir = par.ref_rc ? -1 : 1;
             pl->tasks[a].dir_off = (int64_t)pl->slice_base.size();       // first scratch row of this alignment (relative to n)
             int ns = 0;
@@ -415,17 +491,11 @@ static clh_plan* ssw_plan_build(clh_ctx* ctx, int32_t n, const int64_t* read_off
     });
     std::vector<clh::SswTask> sorted(n_all);
     for (int k = 0; k < n_all; ++k) sorted[k] = pl->tasks[order[k]];
-    for (int k = 0; k < n_all;) {
+    for (int k = 0; k < n_all;) {       // one segment per class
         int e = k;
         while (e < n_all && cls[order[e]] == cls[order[k]]) ++e;
-        // a large K1w class with CIGARs goes as up to four launches: the traceback of one runs under the score kernel of the next
-        // (clh_ssw_run) instead of all of it behind the one score kernel
-        const int parts = (cls[order[k]] == clh::kRvScanWide && pl->do_cigar && e - k >= 4096 && getenv("CLH_SCANW_PARTS")) ? std::max(1, std::min(8, atoi(getenv("CLH_SCANW_PARTS")))) : 1;   // (measured on C2, 10 000 alignments: 4 parts of 2 500 are each less than one round of the GPU's wave slots -- 28 -> 35 ms; kept for batches far above that, off by default)
-        for (int q = 0; q < parts; ++q) {
-            const int b = k + (int)((int64_t)(e - k) * q / parts), b2 = k + (int)((int64_t)(e - k) * (q + 1) / parts);
-            clh_plan::Seg sg; sg.rv = cls[order[k]]; sg.begin = b; sg.count = b2 - b;
-            pl->segs.push_back(sg);
-        }
+        clh_plan::Seg sg; sg.rv = cls[order[k]]; sg.begin = k; sg.count = e - k;
+        pl->segs.push_back(sg);
         k = e;
     }
     pl->tasks.swap(sorted);
@@ -442,34 +512,23 @@ static clh_plan* ssw_plan_build(clh_ctx* ctx, int32_t n, const int64_t* read_off
         if (sg.rv != clh::kRvScanWide && sg.rv != clh::kRvScanTr) continue;
         int lmax = 1;
         for (int k = 0; k < sg.count; ++k) lmax = std::max(lmax, sg.rv == clh::kRvScanTr ? 64 : (int)pl->tasks[sg.begin + k].read_len);
-        sg.ws_slot = (int)((clh::scanw_task_bytes(lmax) + 255) & ~(size_t)255);
         sg.ws_wgs = std::min(sg.count, ctx->n_cu * 12);
-        pl->strip_bytes = (pl->strip_bytes + 255) & ~(size_t)255;
-        sg.ws_off = (int64_t)pl->strip_bytes;
-        pl->strip_bytes += (size_t)sg.ws_slot * (size_t)sg.ws_wgs;
+        sg.ws_off = pl->reserve_ws(clh::scanw_task_bytes(lmax), sg.ws_wgs, &sg.ws_slot);
     }
     for (auto& sg : pl->segs) {
         if (!clh::rv_is_alpha(sg.rv)) continue;
         for (int k = 0; k < sg.count; ++k) sg.lmax = std::max(sg.lmax, (int)pl->tasks[sg.begin + k].read_len);
         if (sg.lmax <= clh::kAlphaLdsRows) continue;
         // the global form: pass state of the longest read per persistent workgroup
-        sg.ws_slot = (int)((clh::alpha_lds_bytes(sg.lmax) + 255) & ~(size_t)255);
         sg.ws_wgs = std::min(sg.count, ctx->n_cu * 8);
-        pl->strip_bytes = (pl->strip_bytes + 255) & ~(size_t)255;
-        sg.ws_off = (int64_t)pl->strip_bytes;
-        pl->strip_bytes += (size_t)sg.ws_slot * (size_t)sg.ws_wgs;
+        sg.ws_off = pl->reserve_ws(clh::alpha_lds_bytes(sg.lmax), sg.ws_wgs, &sg.ws_slot);
     }
-    if (alpha) {
-        pl->d_alpha_mat = ctx->alloc((size_t)o->n_mat * (size_t)o->n_mat);
-        if (!pl->d_alpha_mat || hipMemcpy(pl->d_alpha_mat, o->mat, (size_t)o->n_mat * (size_t)o->n_mat, hipMemcpyHostToDevice) != hipSuccess) {
-            fail(CLH_E_HIP, "out of device memory while building the plan");
-            clh_plan_destroy(pl); return nullptr;
-        }
-    }
-    pl->d_seg_ctr = ctx->alloc(sizeof(int) * std::max<size_t>(pl->segs.size(), 1));
+    auto oom = [&] { fail(CLH_E_HIP, "out of device memory while building the plan"); delete pl; return nullptr; };
+    if (alpha && !(pl->d_alpha_mat = pl->upload(o->mat, (size_t)o->n_mat * (size_t)o->n_mat))) return oom();
+    if (!(pl->d_seg_ctr = pl->alloc(sizeof(int) * std::max<size_t>(pl->segs.size(), 1)))) return oom();
     for (const auto& sg : pl->segs) {
         const int ci = sg.rv == clh::kRvScanSliced ? 0 : (sg.rv == clh::kRvScanWideSliced ? 1 : -1);
-        if (ci < 0 || !prefilter_ok(o, mx)) continue;
+        if (ci < 0 || !prefilter_ok(o, mx, sw)) continue;
         // per alignment: the 256-byte blocks of the refs buffer its window touches, in processing order (minus-strand windows run
         // down the addresses); per piece of its read (<= 254 rows) one run of block minima; a lane of the prefilter owns bpl blocks
         clh_plan::PfClass& f = pl->pf[ci];
@@ -500,8 +559,7 @@ static clh_plan* ssw_plan_build(clh_ctx* ctx, int32_t n, const int64_t* read_off
             lmax = std::max(lmax, L);
             if (total > 0x7fffffffll || cap > 0x3fffffffll) { fail(CLH_E_CAPACITY, "batch too large for the prefilter's 32-bit block offsets; split it"); delete pl; return nullptr; }
         }
-        int bpl = (int)std::min<int64_t>(16, std::max<int64_t>(4, total / (64 * 12288)));
-        if (const char* e = getenv("CLH_PF_BPL")) bpl = std::max(1, atoi(e));
+        const int bpl = (int)std::min<int64_t>(16, std::max<int64_t>(4, total / (64 * 12288)));
         for (int q = 0; q < (int)pieces.size(); ++q) {
             clh::PfWin& w = wins[pieces[q].task];
             if (q == w.piece_first) w.work_first = (int32_t)work.size();
@@ -509,50 +567,37 @@ static clh_plan* ssw_plan_build(clh_ctx* ctx, int32_t n, const int64_t* read_off
             w.work_count = (int32_t)work.size() - w.work_first;
         }
         f.on = true; f.ntasks = sg.count; f.bpl = bpl; f.cap = (int)cap; f.nwork = (int)work.size();
-        f.d_win = ctx->alloc(sizeof(clh::PfWin) * wins.size());
-        f.d_pieces = ctx->alloc(sizeof(clh::PfTask) * pieces.size());
-        f.d_work = ctx->alloc(sizeof(clh::PfWork) * std::max<size_t>(work.size(), 1));
-        f.d_dmin = ctx->alloc((size_t)total + 64);
-        f.d_out = ctx->alloc(sizeof(clh::PfOut) * wins.size());
-        f.d_ctl = ctx->alloc(sizeof(clh::PfCtl));
-        bool ok = f.d_win && f.d_pieces && f.d_work && f.d_dmin && f.d_out && f.d_ctl;
+        f.d_win = pl->upload(wins.data(), sizeof(clh::PfWin) * wins.size());
+        f.d_pieces = pl->upload(pieces.data(), sizeof(clh::PfTask) * pieces.size());
+        f.d_work = work.empty() ? pl->alloc(sizeof(clh::PfWork)) : pl->upload(work.data(), sizeof(clh::PfWork) * work.size());
+        f.d_dmin = pl->alloc((size_t)total + 64);
+        f.d_out = pl->alloc(sizeof(clh::PfOut) * wins.size());
+        f.d_ctl = pl->alloc(sizeof(clh::PfCtl));
+        if (!f.d_win || !f.d_pieces || !f.d_work || !f.d_dmin || !f.d_out || !f.d_ctl || hipMemset(f.d_ctl, 0, sizeof(clh::PfCtl)) != hipSuccess) return oom();
         if (ci == 0) {
-            f.d_queue = ctx->alloc(sizeof(clh::ScanSlice) * (size_t)cap);
-            f.d_parts = ctx->alloc(sizeof(clh::ScanPart) * (size_t)cap);
-            ok = ok && f.d_queue && f.d_parts;
-            if (!getenv("CLH_NO_PF2")) {       // the second stage's queue: at most every entry of the work list (A/B: one stage only)
-                f.d_q2 = ctx->alloc(sizeof(int32_t) * std::max<size_t>(work.size(), 1));
-                ok = ok && f.d_q2;
-            }
+            f.d_queue = pl->alloc(sizeof(clh::ScanSlice) * (size_t)cap);
+            f.d_parts = pl->alloc(sizeof(clh::ScanPart) * (size_t)cap);
+            if (!f.d_queue || !f.d_parts) return oom();
+            // the second stage's queue: at most every entry of the work list (A/B: one stage only)
+            if (!sw.no_pf2 && !(f.d_q2 = pl->alloc(sizeof(int32_t) * std::max<size_t>(work.size(), 1)))) return oom();
         } else {
             // 2 seed tasks per alignment in fixed places, then the candidate queue; 130 scratch result rows per alignment behind every other
             // row; the K1w workspaces belong to the persistent workgroups, not to the tasks
-            f.d_queue = ctx->alloc(sizeof(clh::WsTask) * ((size_t)2 * sg.count + (size_t)cap));
-            f.d_bound = ctx->alloc(sizeof(uint16_t) * (size_t)(dtot + 64));
-            ok = ok && f.d_queue && f.d_bound;
+            f.d_queue = pl->alloc(sizeof(clh::WsTask) * ((size_t)2 * sg.count + (size_t)cap));
+            f.d_bound = pl->alloc(sizeof(uint16_t) * (size_t)(dtot + 64));
+            if (!f.d_queue || !f.d_bound) return oom();
             f.ws_row0 = pl->n_rows;
             pl->n_rows += clh::kWsRows * sg.count;
-            f.ws_slot = (int)((clh::scanw_task_bytes(lmax) + 255) & ~(size_t)255);
             f.ws_wgs = (int)std::min<int64_t>((int64_t)2 * sg.count + cap, (int64_t)ctx->n_cu * 12);
-            pl->strip_bytes = (pl->strip_bytes + 255) & ~(size_t)255;
-            f.ws_dirs_off = (int64_t)pl->strip_bytes;
-            pl->strip_bytes += (size_t)f.ws_slot * (size_t)f.ws_wgs;
-        }
-        if (!ok || hipMemcpy(f.d_win, wins.data(), sizeof(clh::PfWin) * wins.size(), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(f.d_pieces, pieces.data(), sizeof(clh::PfTask) * pieces.size(), hipMemcpyHostToDevice) != hipSuccess ||
-            (!work.empty() && hipMemcpy(f.d_work, work.data(), sizeof(clh::PfWork) * work.size(), hipMemcpyHostToDevice) != hipSuccess) ||
-            hipMemset(f.d_ctl, 0, sizeof(clh::PfCtl)) != hipSuccess) {
-            fail(CLH_E_HIP, "out of device memory while building the plan");
-            clh_plan_destroy(pl); return nullptr;
+            f.ws_dirs_off = pl->reserve_ws(clh::scanw_task_bytes(lmax), f.ws_wgs, &f.ws_slot);
         }
     }
     for (const auto& sg : pl->segs) {
         if (sg.rv != clh::kRvScanSliced || pl->pf[0].on) continue;
         for (int k = 0; k < sg.count; ++k) {
             clh::SswTask& t = pl->tasks[sg.begin + k];
-            const int64_t R = t.ref_len, L = t.read_len;
-            const int64_t overlap = L + (L * mx + o->gap_extend - 1) / o->gap_extend + 32;    // span of a local alignment + wildcard rows + slack
-            const int64_t own = std::max<int64_t>(kSliceMinCols, (R + 63) / 64);
+            const int64_t R = t.ref_len;
+            const auto [overlap, own] = slice_geom(t.read_len, R, mx, o->gap_extend, 0);
             t.dir_off = (int64_t)pl->slices.size();
             int ns = 0;
             for (int64_t b = 0; b < R; b += own, ++ns) {
@@ -566,39 +611,23 @@ static clh_plan* ssw_plan_build(clh_ctx* ctx, int32_t n, const int64_t* read_off
         }
     }
 
-    pl->d_tasks = ctx->alloc(sizeof(clh::SswTask) * (size_t)std::max(n_all, 1));
-    pl->d_results = ctx->alloc(sizeof(clh::SswResult) * (size_t)std::max(pl->n_rows, 1));
-    pl->d_cigar_len = ctx->alloc(sizeof(int32_t) * (size_t)std::max(n_all, 1));
-    if (!pl->slice_base.empty()) {
-        pl->d_slice_base = ctx->alloc(sizeof(int32_t) * pl->slice_base.size());
-        if (!pl->d_slice_base || hipMemcpy(pl->d_slice_base, pl->slice_base.data(), sizeof(int32_t) * pl->slice_base.size(), hipMemcpyHostToDevice) != hipSuccess) {
-            fail(CLH_E_HIP, "out of device memory while building the plan");
-            clh_plan_destroy(pl); return nullptr;
-        }
-    }
-    if (o->want_score2) pl->d_colmax = ctx->alloc(sizeof(uint16_t) * std::max<size_t>(colmax, 1));
+    pl->d_tasks = n_all > 0 ? pl->upload(pl->tasks.data(), sizeof(clh::SswTask) * (size_t)n_all) : pl->alloc(sizeof(clh::SswTask));
+    pl->d_results = pl->alloc(sizeof(clh::SswResult) * (size_t)std::max(pl->n_rows, 1));
+    pl->d_cigar_len = pl->alloc(sizeof(int32_t) * (size_t)std::max(n_all, 1));
+    if (!pl->d_tasks || !pl->d_results || !pl->d_cigar_len) return oom();
+    if (!pl->slice_base.empty() && !(pl->d_slice_base = pl->upload(pl->slice_base.data(), sizeof(int32_t) * pl->slice_base.size()))) return oom();
+    if (o->want_score2 && !(pl->d_colmax = pl->alloc(sizeof(uint16_t) * std::max<size_t>(colmax, 1)))) return oom();
     if (pl->do_cigar) {
-        pl->d_cigars = ctx->alloc(sizeof(uint32_t) * std::max<size_t>(cig, 1));
-        pl->d_pool = ctx->alloc((size_t)pl->pool_bytes);
-        pl->d_pool_head = ctx->alloc(clh::tb_head_bytes(n_all));
+        pl->d_cigars = pl->alloc(sizeof(uint32_t) * std::max<size_t>(cig, 1));
+        pl->d_pool = pl->alloc((size_t)pl->pool_bytes);
+        pl->d_pool_head = pl->alloc(clh::tb_head_bytes(n_all));
+        if (!pl->d_cigars || !pl->d_pool || !pl->d_pool_head) return oom();
     }
-    if (pl->strip_bytes) pl->d_strips = ctx->alloc(pl->strip_bytes);
+    if (pl->strip_bytes && !(pl->d_strips = pl->alloc(pl->strip_bytes))) return oom();
     if (!pl->slices.empty()) {
-        pl->d_slices = ctx->alloc(sizeof(clh::ScanSlice) * pl->slices.size());
-        pl->d_parts = ctx->alloc(sizeof(clh::ScanPart) * pl->slices.size());
-        if (!pl->d_slices || !pl->d_parts || hipMemcpy(pl->d_slices, pl->slices.data(), sizeof(clh::ScanSlice) * pl->slices.size(), hipMemcpyHostToDevice) != hipSuccess) {
-            fail(CLH_E_HIP, "out of device memory while building the plan");
-            clh_plan_destroy(pl); return nullptr;
-        }
-    }
-    if (!pl->d_tasks || !pl->d_results || !pl->d_cigar_len || !pl->d_seg_ctr || (pl->strip_bytes && !pl->d_strips) || (o->want_score2 && !pl->d_colmax) ||
-        (pl->do_cigar && (!pl->d_cigars || !pl->d_pool || !pl->d_pool_head))) {
-        fail(CLH_E_HIP, "out of device memory while building the plan");
-        clh_plan_destroy(pl); return nullptr;
-    }
-    if (n_all > 0 && hipMemcpy(pl->d_tasks, pl->tasks.data(), sizeof(clh::SswTask) * (size_t)n_all, hipMemcpyHostToDevice) != hipSuccess) {
-        fail(CLH_E_HIP, "task upload failed");
-        clh_plan_destroy(pl); return nullptr;
+        pl->d_slices = pl->upload(pl->slices.data(), sizeof(clh::ScanSlice) * pl->slices.size());
+        pl->d_parts = pl->alloc(sizeof(clh::ScanPart) * pl->slices.size());
+        if (!pl->d_slices || !pl->d_parts) return oom();
     }
     return pl;
 }
@@ -620,8 +649,8 @@ extern "C" clh_plan* clh_ssw_plan_windows(clh_ctx* ctx, int32_t n, const int64_t
 // ---------------------------------------------------------------------------------------------------------------
 // K5: resident genome
 // ---------------------------------------------------------------------------------------------------------------
-struct clh_genome {
-    clh_ctx* ctx = nullptr;
+struct clh_genome : clh_owned {
+    using clh_owned::clh_owned;
     int64_t len = 0;
     void *d_codes = nullptr, *d_pre = nullptr;
     void* d_ascii = nullptr;                    // the characters themselves (K6 compares flanks as the reference's strings do)
@@ -629,24 +658,18 @@ struct clh_genome {
     int64_t n_sites[4] = {0, 0, 0, 0};
 };
 
-extern "C" void clh_genome_destroy(clh_genome* g)
-{
-    if (!g) return;
-    (void)hipSetDevice(g->ctx->device);
-    g->ctx->release(g->d_codes); g->ctx->release(g->d_pre); g->ctx->release(g->d_sites); g->ctx->release(g->d_ascii);
-    delete g;
-}
+extern "C" void clh_genome_destroy(clh_genome* g) { delete g; }
 
 extern "C" clh_genome* clh_genome_create(clh_ctx* ctx, const char* ascii, int64_t len)
 {
     if (!ctx || len < 0 || (len > 0 && !ascii)) { fail(CLH_E_ARG, "clh_genome_create: null argument"); return nullptr; }
     if (hipSetDevice(ctx->device) != hipSuccess) { fail(CLH_E_HIP, "hipSetDevice failed"); return nullptr; }
-    clh_genome* g = new clh_genome();
-    g->ctx = ctx; g->len = len;
+    clh_genome* g = new clh_genome(ctx);
+    g->len = len;
     const size_t nblk = (size_t)(len / clh::kGenomeBlock) + 2;
-    g->d_codes = ctx->alloc((size_t)len + 64);
-    g->d_pre = ctx->alloc(sizeof(unsigned int) * nblk);
-    g->d_ascii = ctx->alloc((size_t)len + 64);
+    g->d_codes = g->alloc((size_t)len + 64);
+    g->d_pre = g->alloc(sizeof(unsigned int) * nblk);
+    g->d_ascii = g->alloc((size_t)len + 64);
     void* d_ascii = g->d_ascii;
     bool ok = g->d_codes && g->d_pre && d_ascii;
     if (!ok) fail(CLH_E_HIP, "out of device memory for the genome");
@@ -666,7 +689,7 @@ extern "C" clh_genome* clh_genome_create(clh_ctx* ctx, const char* ascii, int64_
              hipStreamSynchronize(ctx->stream) == hipSuccess;
         if (!ok) fail(CLH_E_HIP, "genome prefix upload failed");
     }
-    if (!ok) { clh_genome_destroy(g); return nullptr; }
+    if (!ok) { delete g; return nullptr; }
     return g;
 }
 
@@ -712,14 +735,14 @@ extern "C" int clh_genome_set_splice_sites(clh_genome* g, const int64_t* pos, co
     }
     clh_ctx* ctx = g->ctx;
     HIPCHK(hipSetDevice(ctx->device));
-    ctx->release(g->d_sites); g->d_sites = nullptr;
+    g->free_block(g->d_sites); g->d_sites = nullptr;
     for (int k = 0; k < 4; ++k) g->n_sites[k] = 0;
     if (tot == 0) return 0;
-    g->d_sites = ctx->alloc(sizeof(int64_t) * (size_t)tot);
+    g->d_sites = g->alloc(sizeof(int64_t) * (size_t)tot);
     if (!g->d_sites) return fail(CLH_E_HIP, "out of device memory");
     if (hipMemcpyAsync(g->d_sites, pos, sizeof(int64_t) * (size_t)tot, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
         hipStreamSynchronize(ctx->stream) != hipSuccess) {
-        ctx->release(g->d_sites); g->d_sites = nullptr;
+        g->free_block(g->d_sites); g->d_sites = nullptr;
         return fail(CLH_E_HIP, "splice-site upload failed");
     }
     for (int k = 0; k < 4; ++k) g->n_sites[k] = count4[k];
@@ -774,10 +797,10 @@ extern "C" int clh_ssw_run(clh_plan* pl, const void* d_reads, const void* d_refs
     P.results = (clh::SswResult*)pl->d_results;
     P.colmax = (uint16_t*)pl->d_colmax;
     P.cigars = (uint32_t*)pl->d_cigars; P.cigar_len = (int32_t*)pl->d_cigar_len; P.dirs = (uint8_t*)pl->d_strips;
-    P.no_guess = getenv("CLH_NO_GUESS") != nullptr;
+    P.no_guess = pl->sw.no_guess;
     if (pl->profiling && pl->ev.empty()) {
         pl->ev.resize(pl->segs.size() * 2 + 4);
-        for (auto& e : pl->ev) HIPCHK(hipEventCreate(&e));
+        for (auto& e : pl->ev) HIPCHK(pl->event(&e));
     }
     // One launch per read-length class for K1, followed on the same stream by that class's small-window traceback.
     // Classes are independent, so outside profiling runs they go round-robin to the caller's stream and three side
@@ -809,11 +832,11 @@ extern "C" int clh_ssw_run(clh_plan* pl, const void* d_reads, const void* d_refs
     // CIGARs of one class, all on one stream: the row kernel, its wide form for what it hands over, the anti-diagonal
     // kernel for what is left (sized for the class; workgroups share the short lists).  Per class, so that the seconds-long
     // tail of a few wide-band alignments of one class runs under the score kernels of the others.
-    auto traceback = [&](int first, int count, int seg, int rv, hipStream_t ls) -> int {
+    auto traceback = [&](int first, int count, int seg, hipStream_t ls) -> int {
         // the anti-diagonal fallback stages both aligned sequences in LDS: always the largest configuration (12 kB of sequence,
         // 4098 rows) -- a short read can align against thousands of reference bases; its few workgroups share the list
-        const int rvbig = 32; (void)rv;
-        if (tb_rows_on()) {
+        const int rvbig = 32;
+        if (!pl->sw.no_tb_rows) {
             HIPCHK(clh::launch_traceback_rows(PG, first, count, pl->n_all, seg, pool, head, pl->pool_bytes, ls));
             HIPCHK(clh::launch_traceback_rows_wide(PG, first, count, pl->n_all, seg, pool, head, pl->pool_bytes, ls));
         } else HIPCHK(clh::launch_traceback_pool(0, PG, first, count, pl->n_all, seg, pool, head, pl->pool_bytes, ls));
@@ -827,7 +850,7 @@ extern "C" int clh_ssw_run(clh_plan* pl, const void* d_reads, const void* d_refs
         f.timed = false;
         if (!P.pf_dmin) return 0;
         if (pl->profiling) {
-            for (auto& e : f.ev) if (!e) HIPCHK(hipEventCreate(&e));
+            for (auto& e : f.ev) if (!e) HIPCHK(pl->event(&e));
             HIPCHK(hipEventRecord(f.ev[0], ls));
         }
         HIPCHK(clh::launch_ssw_prefilter(P, f.nwork, ls));
@@ -835,19 +858,11 @@ extern "C" int clh_ssw_run(clh_plan* pl, const void* d_reads, const void* d_refs
         return 0;
     };
     P.slice_base = (const int32_t*)pl->d_slice_base; PG.slice_base = P.slice_base;
-    int rv_all = 4;                                              // longest read class of the plan (the combined alignments have any length)
-    for (const auto& s : pl->segs) rv_all = std::max(rv_all, s.rv == clh::kRvStrips ? 32 : s.rv);
-    int n_wide = 0, i_wide = 0;
-    for (const auto& s : pl->segs) n_wide += s.rv == clh::kRvScanWide;
     for (size_t q = 0; q < ord.size(); ++q) {
         const size_t k = ord[q];
         const auto& s = pl->segs[k];
         if (s.rv == clh::kRvCombine) continue;                   // after the join below: it reads the other classes' rows
-        hipStream_t ls = (fan && (q & 3)) ? c->side[(q & 3) - 1] : st;
-        // the parts of a K1w class: score kernels one after the other on the main stream, the traceback of each part on a side
-        // stream behind an event (the last part's stays on the main stream)
-        const bool chained = fan && tb && s.rv == clh::kRvScanWide && n_wide > 1;
-        if (chained) ls = st;
+        const hipStream_t ls = (fan && (q & 3)) ? c->side[(q & 3) - 1] : st;
         P.tasks = (const clh::SswTask*)pl->d_tasks + s.begin;
         if (pl->profiling) HIPCHK(hipEventRecord(pl->ev[2 * k + 0], ls));
         if ((s.rv == clh::kRvScanSliced && pl->pf[0].on) || s.rv == clh::kRvScanWideSliced) {
@@ -861,7 +876,7 @@ extern "C" int clh_ssw_run(clh_plan* pl, const void* d_reads, const void* d_refs
             P.pf_dmin = ((uintptr_t)d_refs & 255) == 0 && (pl->refs_bytes < 0 || f.extent <= pl->refs_bytes) ? (uint8_t*)f.d_dmin : nullptr;
             HIPCHK(hipMemsetAsync(f.d_ctl, 0, sizeof(clh::PfCtl), ls));
             if (s.rv == clh::kRvScanSliced) {
-                P.pf_slices = (clh::ScanSlice*)f.d_queue; P.parts = (clh::ScanPart*)f.d_parts; P.pf_q2 = (int32_t*)f.d_q2; P.pf2_always = getenv("CLH_PF2_ALWAYS") != nullptr; P.pf2_share = getenv("CLH_PF2_SHARE") ? std::max(1, atoi(getenv("CLH_PF2_SHARE"))) : 8;
+                P.pf_slices = (clh::ScanSlice*)f.d_queue; P.parts = (clh::ScanPart*)f.d_parts; P.pf_q2 = (int32_t*)f.d_q2; P.pf2_always = pl->sw.pf2_always; P.pf2_share = pl->sw.pf2_share;
                 if (int rc = prefilter(f, ls)) return rc;
                 HIPCHK(clh::launch_ssw_scan_filtered(pl->quirk, P, s.count, std::min(f.cap, c->n_cu * 12), std::min(f.nwork, c->n_cu * 16), ls));
             } else {
@@ -888,17 +903,11 @@ extern "C" int clh_ssw_run(clh_plan* pl, const void* d_reads, const void* d_refs
         }
         else HIPCHK(clh::launch_ssw(s.rv, pl->quirk, P, s.count, ls));
         if (pl->profiling) HIPCHK(hipEventRecord(pl->ev[2 * k + 1], ls));
-        if (chained && ++i_wide < n_wide) {
-            if (pl->chain_ev.size() < (size_t)i_wide) { hipEvent_t e; HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); pl->chain_ev.push_back(e); }
-            HIPCHK(hipEventRecord(pl->chain_ev[i_wide - 1], st));
-            ls = c->side[(i_wide - 1) % 3];
-            HIPCHK(hipStreamWaitEvent(ls, pl->chain_ev[i_wide - 1], 0));
-        }
         if (tb && !pl->profiling) {
             if (clh::rv_is_alpha(s.rv))
                 HIPCHK(clh::launch_ssw_alpha_traceback(PG, (const int8_t*)pl->d_alpha_mat, s.begin, s.count, pl->n_all, (int)(k % clh::kTbMaxSeg), s.lmax,
                                                        pool, head, pl->pool_bytes, ls));
-            else if (int rc = traceback(s.begin, s.count, (int)(k % clh::kTbMaxSeg), s.rv, ls)) return rc;
+            else if (int rc = traceback(s.begin, s.count, (int)(k % clh::kTbMaxSeg), ls)) return rc;
         }
     }
     if (fan)
@@ -913,7 +922,7 @@ extern "C" int clh_ssw_run(clh_plan* pl, const void* d_reads, const void* d_refs
         if (pl->profiling) HIPCHK(hipEventRecord(pl->ev[2 * k + 0], st));
         HIPCHK(clh::launch_ssw_combine(P, s.count, st));
         if (pl->profiling) HIPCHK(hipEventRecord(pl->ev[2 * k + 1], st));
-        if (tb && !pl->profiling) { if (int rc = traceback(s.begin, s.count, (int)(k % clh::kTbMaxSeg), rv_all, st)) return rc; }
+        if (tb && !pl->profiling) { if (int rc = traceback(s.begin, s.count, (int)(k % clh::kTbMaxSeg), st)) return rc; }
     }
     if (tb && pl->profiling && pl->alpha) {   // profiling runs of the K1a classes: their tracebacks after the score kernels, as one span
         HIPCHK(hipEventRecord(pl->ev[eb + 0], st));
@@ -926,16 +935,16 @@ extern "C" int clh_ssw_run(clh_plan* pl, const void* d_reads, const void* d_refs
     } else if (tb && pl->profiling) {   // profiling runs: the traceback of all classes as serial launches after the score kernels
         const int rvmax = 32;
         HIPCHK(hipEventRecord(pl->ev[eb + 0], st));
-        if (tb_rows_on()) HIPCHK(clh::launch_traceback_rows(PG, 0, pl->n_all, pl->n_all, 0, pool, head, pl->pool_bytes, st));
+        if (!pl->sw.no_tb_rows) HIPCHK(clh::launch_traceback_rows(PG, 0, pl->n_all, pl->n_all, 0, pool, head, pl->pool_bytes, st));
         else HIPCHK(clh::launch_traceback_pool(0, PG, 0, pl->n_all, pl->n_all, 0, pool, head, pl->pool_bytes, st));
         HIPCHK(hipEventRecord(pl->ev[eb + 1], st));
         HIPCHK(hipEventRecord(pl->ev[eb + 2], st));
-        if (tb_rows_on()) HIPCHK(clh::launch_traceback_rows_wide(PG, 0, pl->n_all, pl->n_all, 0, pool, head, pl->pool_bytes, st));
+        if (!pl->sw.no_tb_rows) HIPCHK(clh::launch_traceback_rows_wide(PG, 0, pl->n_all, pl->n_all, 0, pool, head, pl->pool_bytes, st));
         HIPCHK(clh::launch_traceback_pool(rvmax, PG, 0, pl->n_all, pl->n_all, 0, pool, head, pl->pool_bytes, st));
         HIPCHK(clh::launch_traceback_w32(PG, 0, pl->n_all, pool, head, pl->pool_bytes, st));
         HIPCHK(hipEventRecord(pl->ev[eb + 3], st));
     }
-    if (!pl->done_ev) HIPCHK(hipEventCreateWithFlags(&pl->done_ev, hipEventDisableTiming));
+    if (!pl->done_ev) HIPCHK(pl->event(&pl->done_ev, hipEventDisableTiming));
     HIPCHK(hipEventRecord(pl->done_ev, st));
     pl->last_stream = st;
     pl->ran = true;
@@ -1123,22 +1132,13 @@ extern "C" int clh_ssw_fetch(clh_plan* pl, clh_align_t* out, uint32_t* cigar_buf
     return 0;
 }
 
-// the return code of a batch call whose plan was refused: what the plan builder reported as unsupported stays so
-static int plan_fail_code()
-{
-    if (g_err.empty()) return CLH_E_ARG;
-    const bool unsupported = g_err.find("not implemented") != std::string::npos || g_err.find("matrix edge must be") != std::string::npos ||
-                             g_err.find("resident genome take") != std::string::npos;
-    return unsupported ? CLH_E_UNSUPPORTED : CLH_E_ARG;
-}
-
 extern "C" int clh_ssw_batch(clh_ctx* ctx, int32_t n, const int8_t* reads, const int64_t* read_off, const int8_t* refs,
                              const int64_t* ref_off, const int32_t* mask_len, const clh_ssw_opts* opts, clh_align_t* out,
                              uint32_t* cigar_buf, int64_t cigar_cap, int64_t* cigar_used)
 {
     if (!ctx || !reads || !refs || !read_off || !ref_off) return fail(CLH_E_ARG, "clh_ssw_batch: null argument");
     clh_plan* pl = clh_ssw_plan(ctx, n, read_off, ref_off, mask_len, opts);
-    if (!pl) return plan_fail_code();
+    if (!pl) return g_code;
     int rc = 0;
     if (pl->alpha) {       // codes outside the matrix: named here, before anything runs (the kernel checks them too)
         const int nm = pl->opts.n_mat;
@@ -1148,17 +1148,17 @@ extern "C" int clh_ssw_batch(clh_ctx* ctx, int32_t n, const int8_t* reads, const
             for (int64_t k = ref_off[a]; k < ref_off[a + 1] && !bad; ++k) bad = refs[k] < 0 || refs[k] >= nm;
             if (bad) rc = fail(CLH_E_ARG, "alignment " + std::to_string(a) + ": a read or reference code outside [0, " + std::to_string(nm) + ")");
         }
-        if (rc) { clh_plan_destroy(pl); return rc; }
+        if (rc) { delete pl; return rc; }
     }
     const size_t rb = (size_t)read_off[n], fb = (size_t)ref_off[n];
-    pl->d_reads = ctx->alloc(rb + 64);
-    pl->d_refs = ctx->alloc(fb + 64);
-    if (!pl->d_reads || !pl->d_refs) { rc = fail(CLH_E_HIP, "out of device memory for the batch"); }
-    if (!rc && hipMemcpyAsync(pl->d_reads, reads, rb, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = fail(CLH_E_HIP, "H2D reads failed");
-    if (!rc && hipMemcpyAsync(pl->d_refs, refs, fb, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = fail(CLH_E_HIP, "H2D refs failed");
-    if (!rc) rc = clh_ssw_run(pl, pl->d_reads, pl->d_refs, nullptr);
+    void* d_reads = pl->alloc(rb + 64);
+    void* d_refs = pl->alloc(fb + 64);
+    if (!d_reads || !d_refs) { rc = fail(CLH_E_HIP, "out of device memory for the batch"); }
+    if (!rc && hipMemcpyAsync(d_reads, reads, rb, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = fail(CLH_E_HIP, "H2D reads failed");
+    if (!rc && hipMemcpyAsync(d_refs, refs, fb, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = fail(CLH_E_HIP, "H2D refs failed");
+    if (!rc) rc = clh_ssw_run(pl, d_reads, d_refs, nullptr);
     if (!rc) rc = clh_ssw_fetch(pl, out, cigar_buf, cigar_cap, cigar_used);
-    clh_plan_destroy(pl);
+    delete pl;
     return rc;
 }
 
@@ -1172,43 +1172,33 @@ extern "C" int clh_ssw_windows_batch(clh_genome* genome, int32_t n, const int8_t
         if (win_off[i] < 0 || win_len[i] < 0 || win_off[i] + win_len[i] > genome->len) return fail(CLH_E_ARG, "clh_ssw_windows_batch: window outside the genome");
     clh_ctx* ctx = genome->ctx;
     clh_plan* pl = clh_ssw_plan_windows(ctx, n, read_off, win_off, win_len, win_rc, mask_len, opts);
-    if (!pl) return plan_fail_code();
+    if (!pl) return g_code;
     int rc = 0;
     const size_t rb = (size_t)read_off[n];
-    pl->d_reads = ctx->alloc(rb + 64);
-    if (!pl->d_reads) { rc = fail(CLH_E_HIP, "out of device memory for the batch"); }
-    if (!rc && hipMemcpyAsync(pl->d_reads, reads, rb, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = fail(CLH_E_HIP, "H2D reads failed");
-    if (!rc) rc = clh_ssw_run(pl, pl->d_reads, genome->d_codes, nullptr);
+    void* d_reads = pl->alloc(rb + 64);
+    if (!d_reads) { rc = fail(CLH_E_HIP, "out of device memory for the batch"); }
+    if (!rc && hipMemcpyAsync(d_reads, reads, rb, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = fail(CLH_E_HIP, "H2D reads failed");
+    if (!rc) rc = clh_ssw_run(pl, d_reads, genome->d_codes, nullptr);
     if (!rc) rc = clh_ssw_fetch(pl, out, cigar_buf, cigar_cap, cigar_used);
-    clh_plan_destroy(pl);
+    delete pl;
     return rc;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 // K4: unit-cost edit distance of n pairs of byte strings (utils.py:153-159 `distance`)
 // ---------------------------------------------------------------------------------------------------------------
-struct clh_edit_plan {
-    clh_ctx* ctx = nullptr;
+struct clh_edit_plan : clh_owned {
+    using clh_owned::clh_owned;
     int n = 0, planes = 3;
     std::vector<clh::EdTask> tasks;          // launch order (by lane-group class, longest text first)
     std::vector<int32_t> trivial;            // out[k] for pairs with an empty side, -1 otherwise
     void *d_sym = nullptr, *d_tasks = nullptr, *d_out = nullptr, *d_carry = nullptr;
-    hipStream_t last_stream = nullptr;
-    bool ran = false;
     hipEvent_t ev[2] = {nullptr, nullptr};
 };
 
 static int ed_group(const clh::EdTask& t) { int B = (t.pat_len + 63) >> 6, G = 1; while (G < B && G < 64) G <<= 1; return G; }   // above 64 blocks: passes
 
-extern "C" void clh_edit_plan_destroy(clh_edit_plan* pl)
-{
-    if (!pl) return;
-    (void)hipSetDevice(pl->ctx->device);
-    if (pl->ran) (void)hipStreamSynchronize(pl->last_stream);
-    pl->ctx->release(pl->d_sym); pl->ctx->release(pl->d_tasks); pl->ctx->release(pl->d_out); pl->ctx->release(pl->d_carry);
-    for (hipEvent_t e : pl->ev) if (e) (void)hipEventDestroy(e);
-    delete pl;
-}
+extern "C" void clh_edit_plan_destroy(clh_edit_plan* pl) { delete pl; }
 
 // uploads the strings (as dense symbol codes) and the task table; the plan then runs any number of times
 extern "C" clh_edit_plan* clh_edit_plan_create(clh_ctx* ctx, int32_t n, const uint8_t* a, const int64_t* a_off, const uint8_t* b, const int64_t* b_off)
@@ -1217,8 +1207,8 @@ extern "C" clh_edit_plan* clh_edit_plan_create(clh_ctx* ctx, int32_t n, const ui
     if (hipSetDevice(ctx->device) != hipSuccess) { fail(CLH_E_HIP, "hipSetDevice failed"); return nullptr; }
     const int64_t ta = n ? a_off[n] - a_off[0] : 0, tb = n ? b_off[n] - b_off[0] : 0;
     if (ta < 0 || tb < 0) { fail(CLH_E_ARG, "clh_edit_plan_create: offsets must ascend"); return nullptr; }
-    clh_edit_plan* pl = new clh_edit_plan();
-    pl->ctx = ctx; pl->n = n;
+    clh_edit_plan* pl = new clh_edit_plan(ctx);
+    pl->n = n;
     // the batch's alphabet -> dense codes; the kernel builds match vectors from 3 bit planes (<= 8 symbols: DNA) or 8
     int code[256];
     for (int& c : code) c = -1;
@@ -1254,15 +1244,13 @@ extern "C" clh_edit_plan* clh_edit_plan_create(clh_ctx* ctx, int32_t n, const ui
         return x.txt_len > y.txt_len;                 // similar step counts share a wave
     });
     const size_t nt = pl->tasks.size();
-    pl->d_sym = ctx->alloc(sym.size());
-    pl->d_tasks = ctx->alloc(sizeof(clh::EdTask) * std::max<size_t>(nt, 1));
-    pl->d_out = ctx->alloc(sizeof(int32_t) * (size_t)std::max(n, 1));
-    if (carry_bytes) pl->d_carry = ctx->alloc(carry_bytes + 64);
-    if (!pl->d_sym || !pl->d_tasks || !pl->d_out || (carry_bytes && !pl->d_carry) ||
-        hipMemcpy(pl->d_sym, sym.data(), sym.size(), hipMemcpyHostToDevice) != hipSuccess ||
-        (nt && hipMemcpy(pl->d_tasks, pl->tasks.data(), sizeof(clh::EdTask) * nt, hipMemcpyHostToDevice) != hipSuccess)) {
+    pl->d_sym = pl->upload(sym.data(), sym.size());
+    pl->d_tasks = nt ? pl->upload(pl->tasks.data(), sizeof(clh::EdTask) * nt) : pl->alloc(sizeof(clh::EdTask));
+    pl->d_out = pl->alloc(sizeof(int32_t) * (size_t)std::max(n, 1));
+    if (carry_bytes) pl->d_carry = pl->alloc(carry_bytes + 64);
+    if (!pl->d_sym || !pl->d_tasks || !pl->d_out || (carry_bytes && !pl->d_carry)) {
         fail(CLH_E_HIP, "out of device memory or upload failed while building the edit-distance plan");
-        clh_edit_plan_destroy(pl); return nullptr;
+        delete pl; return nullptr;
     }
     return pl;
 }
@@ -1272,7 +1260,7 @@ extern "C" int clh_edit_plan_run(clh_edit_plan* pl, void* stream_)
     if (!pl) return fail(CLH_E_ARG, "clh_edit_plan_run: null argument");
     HIPCHK(hipSetDevice(pl->ctx->device));
     hipStream_t st = stream_ ? (hipStream_t)stream_ : pl->ctx->stream;
-    if (!pl->ev[0]) for (auto& e : pl->ev) HIPCHK(hipEventCreate(&e));
+    if (!pl->ev[0]) for (auto& e : pl->ev) HIPCHK(pl->event(&e));
     HIPCHK(hipEventRecord(pl->ev[0], st));
     const int nt = (int)pl->tasks.size();
     for (int i = 0; i < nt;) {
@@ -1313,18 +1301,18 @@ extern "C" int clh_edit_distance_batch(clh_ctx* ctx, int32_t n, const uint8_t* a
     if (!out) return fail(CLH_E_ARG, "clh_edit_distance_batch: null argument");
     if (n == 0) return 0;
     clh_edit_plan* pl = clh_edit_plan_create(ctx, n, a, a_off, b, b_off);
-    if (!pl) return CLH_E_ARG;
+    if (!pl) return g_code;
     int rc = clh_edit_plan_run(pl, nullptr);
     if (!rc) rc = clh_edit_plan_fetch(pl, out);
-    clh_edit_plan_destroy(pl);
+    delete pl;
     return rc;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 // K4m / K4t: edlib.align -- modes NW / SHW / HW, end and start locations, CIGARs (edit_align.hip)
 // ---------------------------------------------------------------------------------------------------------------
-struct clh_edit_align_plan {
-    clh_ctx* ctx = nullptr;
+struct clh_edit_align_plan : clh_owned {
+    using clh_owned::clh_owned;
     int n = 0, nk = 0, planes = 3, mode = 0, task = 0, k = -1;
     bool eq = false, starts = false;
     std::vector<int32_t> qlen, tlen, alpha, kidx;     // per pair; kidx: index among the pairs that reach the kernels, -1 trivial
@@ -1342,26 +1330,13 @@ struct clh_edit_align_plan {
          *d_slot_pair = nullptr, *d_rev_tasks = nullptr, *d_paths = nullptr, *d_path_tasks = nullptr, *d_ws = nullptr, *d_cig = nullptr,
          *d_cig_len = nullptr, *d_carry_score = nullptr, *d_carry_rev = nullptr, *d_carry_path = nullptr, *d_eq_off = nullptr,
          *d_eq_list = nullptr, *d_eqm = nullptr;
-    hipStream_t last_stream = nullptr;
-    bool ran = false;
     hipEvent_t ev[2] = {nullptr, nullptr};
 };
 
 static int ea_group(int m) { int B = (m + 63) >> 6, G = 1; while (G < B && G < 64) G <<= 1; return G; }
 static int64_t ea_pad(int64_t n) { return ((n + 63) & ~(int64_t)63) + 64; }   // one between-pass delta buffer (as K4)
 
-extern "C" void clh_edit_align_plan_destroy(clh_edit_align_plan* pl)
-{
-    if (!pl) return;
-    (void)hipSetDevice(pl->ctx->device);
-    if (pl->ran) (void)hipStreamSynchronize(pl->last_stream);
-    for (void* p : {pl->d_sym, pl->d_tasks, pl->d_pairs, pl->d_best, pl->d_cnt, pl->d_ends, pl->d_rev_out, pl->d_slot_pair, pl->d_rev_tasks,
-                    pl->d_paths, pl->d_path_tasks, pl->d_ws, pl->d_cig, pl->d_cig_len, pl->d_carry_score, pl->d_carry_rev, pl->d_carry_path,
-                    pl->d_eq_off, pl->d_eq_list, pl->d_eqm})
-        pl->ctx->release(p);
-    for (hipEvent_t e : pl->ev) if (e) (void)hipEventDestroy(e);
-    delete pl;
-}
+extern "C" void clh_edit_align_plan_destroy(clh_edit_align_plan* pl) { delete pl; }
 
 extern "C" clh_edit_align_plan* clh_edit_align_plan_create(clh_ctx* ctx, int32_t n, const uint8_t* q, const int64_t* q_off, const uint8_t* t,
                                                            const int64_t* t_off, const clh_edit_align_opts* opts)
@@ -1377,8 +1352,8 @@ extern "C" clh_edit_align_plan* clh_edit_align_plan_create(clh_ctx* ctx, int32_t
         if (q_off[k + 1] < q_off[k] || t_off[k + 1] < t_off[k] || q_off[k + 1] - q_off[k] > INT32_MAX / 4 || t_off[k + 1] - t_off[k] > INT32_MAX / 4) {
             fail(CLH_E_ARG, "clh_edit_align_plan_create: offsets must ascend, strings below 2^29 bytes"); return nullptr;
         }
-    clh_edit_align_plan* pl = new clh_edit_align_plan();
-    pl->ctx = ctx; pl->n = n; pl->mode = opts->mode; pl->task = opts->task; pl->k = opts->k;
+    clh_edit_align_plan* pl = new clh_edit_align_plan(ctx);
+    pl->n = n; pl->mode = opts->mode; pl->task = opts->task; pl->k = opts->k;
     pl->starts = opts->mode == CLH_EA_HW && opts->task >= CLH_EA_LOCATIONS;
     const int64_t ws_limit = opts->workspace_bytes > 0 ? opts->workspace_bytes : ((int64_t)1 << 30);
     // the batch's alphabet -> dense codes (bit planes: 3 for <= 8 letters, else 8), as K4
@@ -1531,36 +1506,31 @@ extern "C" clh_edit_align_plan* clh_edit_align_plan_create(clh_ctx* ctx, int32_t
         }
     }
     const size_t nk = (size_t)std::max(pl->nk, 1);
-    pl->d_sym = ctx->alloc(sym.size());
-    pl->d_tasks = ctx->alloc(sizeof(clh::EaTask) * std::max<size_t>(pl->tasks.size(), 1));
-    pl->d_pairs = ctx->alloc(sizeof(clh::EaPair) * nk);
-    pl->d_best = ctx->alloc(4 * nk); pl->d_cnt = ctx->alloc(4 * nk); pl->d_cig_len = ctx->alloc(4 * nk);
-    pl->d_ends = ctx->alloc(4 * (size_t)std::max<int64_t>(pl->ends_total, 1));
-    pl->d_rev_out = ctx->alloc(4 * (size_t)(pl->starts ? std::max<int64_t>(pl->ends_total, 1) : 1));
-    pl->d_slot_pair = ctx->alloc(4 * (size_t)std::max<int64_t>(pl->nslots, 1));
-    pl->d_rev_tasks = ctx->alloc(sizeof(clh::EaTask) * (size_t)std::max<int64_t>(pl->nslots, 1));
-    pl->d_paths = ctx->alloc(sizeof(clh::EaPath) * std::max<size_t>(pl->paths.size(), 1));
-    pl->d_path_tasks = ctx->alloc(sizeof(clh::EaTask) * std::max<size_t>(pl->paths.size(), 1));
-    pl->d_ws = ctx->alloc((size_t)std::max<int64_t>(pl->ws_bytes, 256));
-    pl->d_cig = ctx->alloc(4 * (size_t)std::max<int64_t>(pl->cig_total, 1));
-    pl->d_carry_score = ctx->alloc((size_t)pl->carry_score + 64);
-    pl->d_carry_rev = ctx->alloc((size_t)pl->carry_rev + 64);
-    pl->d_carry_path = ctx->alloc((size_t)pl->carry_path + 64);
-    pl->d_eq_off = ctx->alloc(4 * eq_off.size()); pl->d_eq_list = ctx->alloc(eq_list.size()); pl->d_eqm = ctx->alloc(4 * eqm.size());
-    bool ok = pl->d_sym && pl->d_tasks && pl->d_pairs && pl->d_best && pl->d_cnt && pl->d_cig_len && pl->d_ends && pl->d_rev_out && pl->d_slot_pair &&
-              pl->d_rev_tasks && pl->d_paths && pl->d_path_tasks && pl->d_ws && pl->d_cig && pl->d_carry_score && pl->d_carry_rev && pl->d_carry_path &&
-              pl->d_eq_off && pl->d_eq_list && pl->d_eqm;
-    ok = ok && hipMemcpy(pl->d_sym, sym.data(), sym.size(), hipMemcpyHostToDevice) == hipSuccess;
-    ok = ok && (pl->tasks.empty() || hipMemcpy(pl->d_tasks, pl->tasks.data(), sizeof(clh::EaTask) * pl->tasks.size(), hipMemcpyHostToDevice) == hipSuccess);
-    ok = ok && (pl->kp.empty() || hipMemcpy(pl->d_pairs, pl->kp.data(), sizeof(clh::EaPair) * pl->kp.size(), hipMemcpyHostToDevice) == hipSuccess);
-    ok = ok && (slot_pair.empty() || hipMemcpy(pl->d_slot_pair, slot_pair.data(), 4 * slot_pair.size(), hipMemcpyHostToDevice) == hipSuccess);
-    ok = ok && (pl->paths.empty() || hipMemcpy(pl->d_paths, pl->paths.data(), sizeof(clh::EaPath) * pl->paths.size(), hipMemcpyHostToDevice) == hipSuccess);
-    ok = ok && hipMemcpy(pl->d_eq_off, eq_off.data(), 4 * eq_off.size(), hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(pl->d_eq_list, eq_list.data(), eq_list.size(), hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(pl->d_eqm, eqm.data(), 4 * eqm.size(), hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) {
+    // a block for every buffer, even an empty one (the kernels take the pointers as they are)
+    auto put = [&](const void* host, size_t bytes, size_t min_bytes) { return bytes ? pl->upload(host, bytes) : pl->alloc(min_bytes); };
+    pl->d_sym = pl->upload(sym.data(), sym.size());
+    pl->d_tasks = put(pl->tasks.data(), sizeof(clh::EaTask) * pl->tasks.size(), sizeof(clh::EaTask));
+    pl->d_pairs = put(pl->kp.data(), sizeof(clh::EaPair) * pl->kp.size(), sizeof(clh::EaPair));
+    pl->d_best = pl->alloc(4 * nk); pl->d_cnt = pl->alloc(4 * nk); pl->d_cig_len = pl->alloc(4 * nk);
+    pl->d_ends = pl->alloc(4 * (size_t)std::max<int64_t>(pl->ends_total, 1));
+    pl->d_rev_out = pl->alloc(4 * (size_t)(pl->starts ? std::max<int64_t>(pl->ends_total, 1) : 1));
+    pl->d_slot_pair = put(slot_pair.data(), 4 * slot_pair.size(), 4);
+    pl->d_rev_tasks = pl->alloc(sizeof(clh::EaTask) * (size_t)std::max<int64_t>(pl->nslots, 1));
+    pl->d_paths = put(pl->paths.data(), sizeof(clh::EaPath) * pl->paths.size(), sizeof(clh::EaPath));
+    pl->d_path_tasks = pl->alloc(sizeof(clh::EaTask) * std::max<size_t>(pl->paths.size(), 1));
+    pl->d_ws = pl->alloc((size_t)std::max<int64_t>(pl->ws_bytes, 256));
+    pl->d_cig = pl->alloc(4 * (size_t)std::max<int64_t>(pl->cig_total, 1));
+    pl->d_carry_score = pl->alloc((size_t)pl->carry_score + 64);
+    pl->d_carry_rev = pl->alloc((size_t)pl->carry_rev + 64);
+    pl->d_carry_path = pl->alloc((size_t)pl->carry_path + 64);
+    pl->d_eq_off = pl->upload(eq_off.data(), 4 * eq_off.size());
+    pl->d_eq_list = pl->upload(eq_list.data(), eq_list.size());
+    pl->d_eqm = pl->upload(eqm.data(), 4 * eqm.size());
+    if (!pl->d_sym || !pl->d_tasks || !pl->d_pairs || !pl->d_best || !pl->d_cnt || !pl->d_cig_len || !pl->d_ends || !pl->d_rev_out || !pl->d_slot_pair ||
+        !pl->d_rev_tasks || !pl->d_paths || !pl->d_path_tasks || !pl->d_ws || !pl->d_cig || !pl->d_carry_score || !pl->d_carry_rev || !pl->d_carry_path ||
+        !pl->d_eq_off || !pl->d_eq_list || !pl->d_eqm) {
         fail(CLH_E_HIP, "out of device memory or upload failed while building the edit-align plan");
-        clh_edit_align_plan_destroy(pl); return nullptr;
+        delete pl; return nullptr;
     }
     return pl;
 }
@@ -1583,7 +1553,7 @@ extern "C" int clh_edit_align_plan_run(clh_edit_align_plan* pl, void* stream_)
     if (!pl) return fail(CLH_E_ARG, "clh_edit_align_plan_run: null argument");
     HIPCHK(hipSetDevice(pl->ctx->device));
     hipStream_t st = stream_ ? (hipStream_t)stream_ : pl->ctx->stream;
-    if (!pl->ev[0]) for (auto& e : pl->ev) HIPCHK(hipEventCreate(&e));
+    if (!pl->ev[0]) for (auto& e : pl->ev) HIPCHK(pl->event(&e));
     HIPCHK(hipEventRecord(pl->ev[0], st));
     const size_t nk = (size_t)std::max(pl->nk, 1);
     HIPCHK(hipMemsetAsync(pl->d_cnt, 0xff, 4 * nk, st));       // -1: no result (a kernel that left a pair out is caught by fetch)
@@ -1727,10 +1697,10 @@ extern "C" int clh_edit_align_batch(clh_ctx* ctx, int32_t n, const uint8_t* q, c
 {
     if (!rows || !locs_used || !cigar_used) return fail(CLH_E_ARG, "clh_edit_align_batch: null argument");
     clh_edit_align_plan* pl = clh_edit_align_plan_create(ctx, n, q, q_off, t, t_off, opts);
-    if (!pl) return g_err.find("workspace") != std::string::npos ? CLH_E_CAPACITY : CLH_E_ARG;
+    if (!pl) return g_code;
     int rc = clh_edit_align_plan_run(pl, nullptr);
     if (!rc) rc = clh_edit_align_plan_fetch(pl, rows, locs, locs_cap, locs_used, cigar, cigar_cap, cigar_used);
-    clh_edit_align_plan_destroy(pl);
+    delete pl;
     return rc;
 }
 
@@ -1842,8 +1812,8 @@ struct clh_ccs_plan;
 static clh_ccs_plan* ccs_plan_create(clh_ctx* ctx, int32_t n, const int64_t* read_off, int mcap_hint, bool wide_hint = false);
 extern "C" clh_ccs_plan* clh_ccs_plan_create(clh_ctx* ctx, int32_t n, const int64_t* read_off) { return ccs_plan_create(ctx, n, read_off, 0); }
 
-struct clh_ccs_plan {
-    clh_ctx* ctx = nullptr;
+struct clh_ccs_plan : clh_owned {
+    using clh_owned::clh_owned;
     int n = 0, lcap = 0, lmax = 0, n_long = 0, nslots = 0, nslots_big = 0;
     void *d_long = nullptr, *d_k2ws = nullptr, *d_busy = nullptr;
     struct K2Class { int begin, count, lcap; };
@@ -1851,22 +1821,11 @@ struct clh_ccs_plan {
     int64_t total = 0;
     size_t slot_bytes = 0, slot_bytes_big = 0;      // second tier: a few slots sized for the worst case of the batch
     void *d_off = nullptr, *d_scan = nullptr, *d_res = nullptr, *d_segs = nullptr, *d_ccs = nullptr, *d_ws = nullptr, *d_ws_big = nullptr,
-         *d_counter = nullptr, *d_order = nullptr, *d_order3 = nullptr, *d_reads = nullptr, *d_score = nullptr, *d_wide = nullptr;
-    hipStream_t last_stream = nullptr;
-    bool ran = false;
+         *d_counter = nullptr, *d_order = nullptr, *d_wide = nullptr;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};   // K2 start, K2 stop = K3 start, K3 stop
 };
 
-extern "C" void clh_ccs_plan_destroy(clh_ccs_plan* pl)
-{
-    if (!pl) return;
-    (void)hipSetDevice(pl->ctx->device);
-    if (pl->ran) (void)hipStreamSynchronize(pl->last_stream);
-    void* bufs[] = {pl->d_off, pl->d_scan, pl->d_res, pl->d_segs, pl->d_ccs, pl->d_ws, pl->d_ws_big, pl->d_counter, pl->d_order, pl->d_order3, pl->d_reads, pl->d_long, pl->d_k2ws, pl->d_busy, pl->d_score, pl->d_wide};
-    for (void* b : bufs) pl->ctx->release(b);
-    for (hipEvent_t e : pl->ev) if (e) (void)hipEventDestroy(e);
-    delete pl;
-}
+extern "C" void clh_ccs_plan_destroy(clh_ccs_plan* pl) { delete pl; }
 
 // scores of the consensus step of find_consensus: local alignment with the numbers of the reference's call
 // (tests/test_poa.py:30), consensus over the nodes crossed by at least half of the copies (oracle/ccs_oracle.c)
@@ -1876,8 +1835,8 @@ static clh_ccs_plan* ccs_plan_create(clh_ctx* ctx, int32_t n, const int64_t* rea
 {
     if (!ctx || n < 0 || !read_off) { fail(CLH_E_ARG, "clh_ccs_plan_create: null argument"); return nullptr; }
     if (hipSetDevice(ctx->device) != hipSuccess) { fail(CLH_E_HIP, "hipSetDevice failed"); return nullptr; }
-    clh_ccs_plan* pl = new clh_ccs_plan();
-    pl->ctx = ctx; pl->n = n; pl->total = read_off[n];
+    clh_ccs_plan* pl = new clh_ccs_plan(ctx);
+    pl->n = n; pl->total = read_off[n];
     int lmax = 1;
     std::vector<int32_t> order(n), long_idx;
     for (int i = 0; i < n; ++i) {
@@ -1932,48 +1891,37 @@ static clh_ccs_plan* ccs_plan_create(clh_ctx* ctx, int32_t n, const int64_t* rea
         pl->nslots_big = std::min(pl->nslots_big, std::max(n, 1));
         if (const char* e = getenv("CLH_POA_BIG_SLOTS")) pl->nslots_big = std::max(1, std::min(pl->nslots_big, atoi(e)));       // tests: make the large slots scarce
     }
-    pl->d_off = ctx->alloc(sizeof(int64_t) * (size_t)(n + 1));
-    pl->d_scan = ctx->alloc(sizeof(clh::CcsScan) * (size_t)std::max(n, 1));
-    pl->d_res = ctx->alloc(sizeof(clh::CcsResult) * (size_t)std::max(n, 1));
-    pl->d_segs = ctx->alloc(sizeof(int32_t) * 2 * clh::CCS_SEG_CAP * (size_t)std::max(n, 1));
-    pl->d_ccs = ctx->alloc((size_t)std::max<int64_t>(pl->total, 1) + 64);
-    pl->d_ws = ctx->alloc(pl->slot_bytes * (size_t)pl->nslots);
+    auto oom = [&] { fail(CLH_E_HIP, "out of device memory while building the consensus plan"); delete pl; return nullptr; };
+    pl->d_off = pl->upload(read_off, sizeof(int64_t) * (size_t)(n + 1));
+    pl->d_scan = pl->alloc(sizeof(clh::CcsScan) * (size_t)std::max(n, 1));
+    pl->d_res = pl->alloc(sizeof(clh::CcsResult) * (size_t)std::max(n, 1));
+    pl->d_segs = pl->alloc(sizeof(int32_t) * 2 * clh::CCS_SEG_CAP * (size_t)std::max(n, 1));
+    pl->d_ccs = pl->alloc((size_t)std::max<int64_t>(pl->total, 1) + 64);
+    pl->d_ws = pl->alloc(pl->slot_bytes * (size_t)pl->nslots);
+    pl->d_counter = pl->alloc(256);
+    pl->d_order = n > 0 ? pl->upload(order.data(), sizeof(int32_t) * (size_t)n) : pl->alloc(sizeof(int32_t));
+    pl->d_wide = pl->alloc(sizeof(int32_t) * (size_t)std::max(n, 1));       // reads for the wide form of K3's pass
+    if (!pl->d_off || !pl->d_scan || !pl->d_res || !pl->d_segs || !pl->d_ccs || !pl->d_ws || !pl->d_counter || !pl->d_order || !pl->d_wide) return oom();
     if (pl->nslots_big) {
-        pl->d_ws_big = ctx->alloc(pl->slot_bytes_big * (size_t)pl->nslots_big);
-        pl->d_busy = ctx->alloc(sizeof(int) * (size_t)pl->nslots_big);
-        if (pl->d_busy && hipMemset(pl->d_busy, 0, sizeof(int) * (size_t)pl->nslots_big) != hipSuccess) { ctx->release(pl->d_busy); pl->d_busy = nullptr; }
+        pl->d_ws_big = pl->alloc(pl->slot_bytes_big * (size_t)pl->nslots_big);
+        pl->d_busy = pl->alloc(sizeof(int) * (size_t)pl->nslots_big);
+        if (!pl->d_ws_big || !pl->d_busy || hipMemset(pl->d_busy, 0, sizeof(int) * (size_t)pl->nslots_big) != hipSuccess) return oom();
     }
     if (pl->n_long) {
-        pl->d_long = ctx->alloc(sizeof(int32_t) * (size_t)pl->n_long);
-        pl->d_k2ws = ctx->alloc(clh::k2_long_slot_bytes(lmax) * (size_t)pl->n_long);
-        if (!pl->d_long || !pl->d_k2ws || hipMemcpy(pl->d_long, long_idx.data(), sizeof(int32_t) * (size_t)pl->n_long, hipMemcpyHostToDevice) != hipSuccess) {
-            fail(CLH_E_HIP, "out of device memory for the long-read scan workspace");
-            clh_ccs_plan_destroy(pl); return nullptr;
-        }
-    }
-    pl->d_counter = ctx->alloc(256);
-    pl->d_order = ctx->alloc(sizeof(int32_t) * (size_t)std::max(n, 1));
-    pl->d_order3 = ctx->alloc(sizeof(int32_t) * (size_t)std::max(n, 1));     // K3's work list by cost (clh_ccs_run)
-    pl->d_wide = ctx->alloc(sizeof(int32_t) * (size_t)std::max(n, 1));       // reads for the wide form of K3's pass
-    if (!pl->d_off || !pl->d_scan || !pl->d_res || !pl->d_segs || !pl->d_ccs || !pl->d_ws || (pl->nslots_big && (!pl->d_ws_big || !pl->d_busy)) || !pl->d_counter || !pl->d_order || !pl->d_order3 || !pl->d_wide) {
-        fail(CLH_E_HIP, "out of device memory while building the consensus plan");
-        clh_ccs_plan_destroy(pl); return nullptr;
+        pl->d_long = pl->upload(long_idx.data(), sizeof(int32_t) * (size_t)pl->n_long);
+        pl->d_k2ws = pl->alloc(clh::k2_long_slot_bytes(lmax) * (size_t)pl->n_long);
+        if (!pl->d_long || !pl->d_k2ws) return oom();
     }
     (void)hipMemset(pl->d_segs, 0, sizeof(int32_t) * 2 * clh::CCS_SEG_CAP * (size_t)std::max(n, 1));   // entries beyond nseg read as 0
-    if (hipMemcpy(pl->d_off, read_off, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyHostToDevice) != hipSuccess ||
-        (n > 0 && hipMemcpy(pl->d_order, order.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice) != hipSuccess)) {
-        fail(CLH_E_HIP, "plan upload failed");
-        clh_ccs_plan_destroy(pl); return nullptr;
-    }
     return pl;
 }
 
 // the K3 launches of a plan: first tier over every read, second tier over what found no slot large enough
-static int launch_poa_tiers(clh_ccs_plan* pl, clh::CcsParams& P, hipStream_t st, bool by_cost = false)
+static int launch_poa_tiers(clh_ccs_plan* pl, clh::CcsParams& P, hipStream_t st)
 {
     P.poa_ws = (uint8_t*)pl->d_ws; P.work_counter = (int*)pl->d_counter; P.stats = (int*)pl->d_counter + 2;
     P.wide_list = (int32_t*)pl->d_wide; P.wide_count = (int*)pl->d_counter + 32;
-    P.work_order = (const int32_t*)(by_cost ? pl->d_order3 : pl->d_order);
+    P.work_order = (const int32_t*)pl->d_order;
     P.slot_bytes = pl->slot_bytes; P.n = pl->n; P.lcap = pl->lcap; P.tier = 0;
     if (pl->nslots_big) { P.big_ws = (uint8_t*)pl->d_ws_big; P.big_slot_bytes = pl->slot_bytes_big; P.big_busy = (int*)pl->d_busy; P.n_big = pl->nslots_big; }
     HIPCHK(clh::launch_poa(P, pl->nslots, st));
@@ -2008,8 +1956,7 @@ extern "C" int clh_ccs_run(clh_ccs_plan* pl, const void* d_reads, void* stream_)
     P.n_long = pl->n_long; P.k2_lmax = pl->lmax; P.k2_lds_max = clh::kK2LdsMax;
     P.sc = ccs_scores();
     if (getenv("CLH_POA_FORCE_WIDE")) P.sc.algorithm |= 0x200;      // tests: every read through the wide (32-bit) form of the pass
-    P.aln_score = (int32_t*)pl->d_score;
-    if (!pl->ev[0]) for (auto& e : pl->ev) HIPCHK(hipEventCreate(&e));
+    if (!pl->ev[0]) for (auto& e : pl->ev) HIPCHK(pl->event(&e));
     HIPCHK(hipMemsetAsync(pl->d_counter, 0, 256, st));        // the two work counters and every statistic of the run
     const bool trace = getenv("CLH_TRACE") != nullptr;
     HIPCHK(hipEventRecord(pl->ev[0], st));
@@ -2021,12 +1968,8 @@ extern "C" int clh_ccs_run(clh_ccs_plan* pl, const void* d_reads, void* stream_)
     P.lcap = pl->lcap;
     if (trace) { fprintf(stderr, "[clh] K2 launched (n=%d lcap=%d)\n", pl->n, pl->lcap); HIPCHK(hipStreamSynchronize(st)); fprintf(stderr, "[clh] K2 done\n"); }
     HIPCHK(hipEventRecord(pl->ev[1], st));
-    // K3's work list: by read length (the plan's order).  By estimated cost after K2, heaviest first (CLH_POA_ORDER_BY_COST=1), measured
-    // SLOWER: 19.3 -> 20.8 ms on C3, 76.5 -> 85.3 on C4 -- with the heavy reads all at the start every wave of a SIMD is in its pass
-    // at once and nothing is left to fill the latency of the others' walks; the mixed order overlaps better than the balanced one
-    static const bool by_len = getenv("CLH_POA_ORDER_BY_COST") == nullptr;
-    if (!by_len) HIPCHK(clh::launch_ccs_work_order((const clh::CcsScan*)pl->d_scan, pl->n, (int32_t*)pl->d_order3, st));
-    if (int rc = launch_poa_tiers(pl, P, st, !by_len)) return rc;
+    // K3's work list: by read length (the plan's order; by estimated cost after K2, heaviest first, was measured slower -- LABNOTES)
+    if (int rc = launch_poa_tiers(pl, P, st)) return rc;
     if (trace) { fprintf(stderr, "[clh] K3 launched (slots %d x %zu, big %d x %zu)\n", pl->nslots, pl->slot_bytes, pl->nslots_big, pl->slot_bytes_big); HIPCHK(hipStreamSynchronize(st)); fprintf(stderr, "[clh] K3 done\n"); }
     HIPCHK(hipEventRecord(pl->ev[2], st));
     pl->last_stream = st; pl->ran = true;
@@ -2113,19 +2056,19 @@ extern "C" int clh_ccs_batch(clh_ctx* ctx, int32_t n, const int8_t* reads, const
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t0 = trace ? now() : 0;
     clh_ccs_plan* pl = clh_ccs_plan_create(ctx, n, read_off);
-    if (!pl) return CLH_E_ARG;
+    if (!pl) return g_code;
     const double t1 = trace ? now() : 0;
     int rc = 0;
-    pl->d_reads = ctx->alloc((size_t)read_off[n] + 64);
-    if (!pl->d_reads) rc = fail(CLH_E_HIP, "out of device memory for the batch");
-    if (!rc && read_off[n] > 0 && hipMemcpyAsync(pl->d_reads, reads, (size_t)read_off[n], hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+    void* d_reads = pl->alloc((size_t)read_off[n] + 64);
+    if (!d_reads) rc = fail(CLH_E_HIP, "out of device memory for the batch");
+    if (!rc && read_off[n] > 0 && hipMemcpyAsync(d_reads, reads, (size_t)read_off[n], hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
         rc = fail(CLH_E_HIP, "H2D reads failed");
-    if (!rc) rc = clh_ccs_run(pl, pl->d_reads, nullptr);
+    if (!rc) rc = clh_ccs_run(pl, d_reads, nullptr);
     double t2 = 0, t3 = 0;
     if (trace) { t2 = now(); (void)hipStreamSynchronize(ctx->stream); t3 = now(); }
     if (!rc) rc = clh_ccs_fetch(pl, out, segs, ccs);
     const double t4 = trace ? now() : 0;
-    clh_ccs_plan_destroy(pl);
+    delete pl;
     if (trace) fprintf(stderr, "[clh] ccs batch of %d reads: plan %.2f ms, H2D + launches %.2f, kernels (wait) %.2f, fetch %.2f, destroy %.2f\n", n,
                        (t1 - t0) * 1e3, (t2 - t1) * 1e3, (t3 - t2) * 1e3, (t4 - t3) * 1e3, (now() - t4) * 1e3);
     return rc;
@@ -2190,28 +2133,28 @@ extern "C" int clh_poa_batch(clh_ctx* ctx, int32_t ngroups, const int8_t* seqs, 
     // (global and overlap alignments can sink below the 16-bit cells with any scores: their large slots are sized for the wide form, so that
     // a group the packed kernel hands over finds room there)
     clh_ccs_plan* pl = ccs_plan_create(ctx, ngroups, roff.data(), mcap, (sc.algorithm & 0x200) != 0 || (sc.algorithm & 0xff) != 0);
-    if (!pl) return CLH_E_ARG;
+    if (!pl) return g_code;
     int rc = 0;
     const size_t total = (size_t)roff[ngroups];
-    pl->d_reads = ctx->alloc(total + 64);
-    void* d_xcuts = ctx->alloc(sizeof(int32_t) * (xcuts.size() + 1));
-    void* d_xoff = ctx->alloc(sizeof(int64_t) * (size_t)(ngroups + 1));
-    void* d_col = msa_col ? ctx->alloc(sizeof(int32_t) * (total + 1)) : nullptr;
-    void* d_ncols = msa_col ? ctx->alloc(sizeof(int32_t) * (size_t)ngroups) : nullptr;
-    if (aln_score) pl->d_score = ctx->alloc(sizeof(int32_t) * clh::CCS_SEG_CAP * (size_t)ngroups);
+    void* d_reads = pl->alloc(total + 64);
+    void* d_xcuts = pl->alloc(sizeof(int32_t) * (xcuts.size() + 1));
+    void* d_xoff = pl->alloc(sizeof(int64_t) * (size_t)(ngroups + 1));
+    void* d_col = msa_col ? pl->alloc(sizeof(int32_t) * (total + 1)) : nullptr;
+    void* d_ncols = msa_col ? pl->alloc(sizeof(int32_t) * (size_t)ngroups) : nullptr;
+    void* d_score = aln_score ? pl->alloc(sizeof(int32_t) * clh::CCS_SEG_CAP * (size_t)ngroups) : nullptr;
     hipStream_t st = ctx->stream;
-    if (!pl->d_reads || !d_xcuts || !d_xoff || (msa_col && (!d_col || !d_ncols)) || (aln_score && !pl->d_score)) rc = fail(CLH_E_HIP, "out of device memory");
-    if (!rc && hipMemcpyAsync(pl->d_reads, seqs, total, hipMemcpyHostToDevice, st) != hipSuccess) rc = fail(CLH_E_HIP, "H2D failed");
+    if (!d_reads || !d_xcuts || !d_xoff || (msa_col && (!d_col || !d_ncols)) || (aln_score && !d_score)) rc = fail(CLH_E_HIP, "out of device memory");
+    if (!rc && hipMemcpyAsync(d_reads, seqs, total, hipMemcpyHostToDevice, st) != hipSuccess) rc = fail(CLH_E_HIP, "H2D failed");
     if (!rc && !xcuts.empty() && hipMemcpyAsync(d_xcuts, xcuts.data(), sizeof(int32_t) * xcuts.size(), hipMemcpyHostToDevice, st) != hipSuccess) rc = fail(CLH_E_HIP, "H2D failed");
     if (!rc && hipMemcpyAsync(d_xoff, xoff.data(), sizeof(int64_t) * (size_t)(ngroups + 1), hipMemcpyHostToDevice, st) != hipSuccess) rc = fail(CLH_E_HIP, "H2D failed");
-    if (!rc && aln_score && hipMemsetAsync(pl->d_score, 0, sizeof(int32_t) * clh::CCS_SEG_CAP * (size_t)ngroups, st) != hipSuccess) rc = fail(CLH_E_HIP, "memset failed");
+    if (!rc && aln_score && hipMemsetAsync(d_score, 0, sizeof(int32_t) * clh::CCS_SEG_CAP * (size_t)ngroups, st) != hipSuccess) rc = fail(CLH_E_HIP, "memset failed");
     if (!rc) {
         clh::CcsParams P;
         memset(&P, 0, sizeof(P));
-        P.reads = (const int8_t*)pl->d_reads; P.read_off = (const int64_t*)pl->d_off; P.scan = (clh::CcsScan*)pl->d_scan;
+        P.reads = (const int8_t*)d_reads; P.read_off = (const int64_t*)pl->d_off; P.scan = (clh::CcsScan*)pl->d_scan;
         P.results = (clh::CcsResult*)pl->d_res; P.segs = (int32_t*)pl->d_segs; P.ccs = (int8_t*)pl->d_ccs;
         P.sc = sc; P.xcuts = (const int32_t*)d_xcuts; P.xcut_off = (const int64_t*)d_xoff;
-        P.msa_col = (int32_t*)d_col; P.msa_ncols = (int32_t*)d_ncols; P.aln_score = (int32_t*)pl->d_score;
+        P.msa_col = (int32_t*)d_col; P.msa_ncols = (int32_t*)d_ncols; P.aln_score = (int32_t*)d_score;
         if (hipMemsetAsync(pl->d_counter, 0, 256, st) != hipSuccess) rc = fail(CLH_E_HIP, "memset failed");
         if (!rc) rc = launch_poa_tiers(pl, P, st);
         pl->ran = true; pl->last_stream = st;
@@ -2223,11 +2166,10 @@ extern "C" int clh_poa_batch(clh_ctx* ctx, int32_t ngroups, const int8_t* seqs, 
         if (!rc && msa_col && (hipMemcpy(msa_col, d_col, sizeof(int32_t) * total, hipMemcpyDeviceToHost) != hipSuccess ||
                                (msa_ncols && hipMemcpy(msa_ncols, d_ncols, sizeof(int32_t) * (size_t)ngroups, hipMemcpyDeviceToHost) != hipSuccess)))
             rc = fail(CLH_E_HIP, "D2H failed");
-        if (!rc && aln_score && hipMemcpy(aln_score, pl->d_score, sizeof(int32_t) * clh::CCS_SEG_CAP * (size_t)ngroups, hipMemcpyDeviceToHost) != hipSuccess)
+        if (!rc && aln_score && hipMemcpy(aln_score, d_score, sizeof(int32_t) * clh::CCS_SEG_CAP * (size_t)ngroups, hipMemcpyDeviceToHost) != hipSuccess)
             rc = fail(CLH_E_HIP, "D2H failed");
     } else (void)hipStreamSynchronize(st);
     if (!rc) (void)clh_ccs_plan_stats(pl, ctx->last_poa_stats);
-    ctx->release(d_xcuts); ctx->release(d_xoff); ctx->release(d_col); ctx->release(d_ncols);
-    clh_ccs_plan_destroy(pl);
+    delete pl;
     return rc;
 }

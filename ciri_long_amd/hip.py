@@ -176,6 +176,32 @@ def last_error():
     return lib().clh_last_error().decode()
 
 
+def _check(rc, what):
+    """raise ClhError('<what> failed (<rc>): <last error>') for a non-zero return code of libclh"""
+    if rc != 0:
+        raise ClhError('%s failed (%d): %s' % (what, rc, last_error()))
+
+
+class _Handle(object):
+    """A libclh object that belongs to a Context (a plan, a resident genome).  close() destroys it once, and not after the context
+    has closed: clh_destroy has given back everything the context's objects held."""
+    _destroy = None         # name of the libclh function that destroys the handle
+
+    def __init__(self, ctx):
+        self.ctx, self._h = ctx, None
+
+    def close(self):
+        h, self._h = getattr(self, '_h', None), None
+        if h and getattr(self.ctx, '_h', None):
+            getattr(lib(), self._destroy)(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 _LUT = np.full(256, 4, dtype=np.int8)
 for _c, _v in zip('ACGTN', range(5)):
     _LUT[ord(_c)] = _v
@@ -287,11 +313,9 @@ class Context(object):
         ml = None
         if mask_len is not None:
             ml = np.ascontiguousarray(mask_len, dtype=np.int32)
-        rc = L.clh_ssw_batch(self._h, n, reads.ctypes.data, read_off.ctypes.data, refs.ctypes.data, ref_off.ctypes.data,
-                             ml.ctypes.data if ml is not None else None, C.byref(o), out.ctypes.data,
-                             cig.ctypes.data if want_cigar else None, cap, C.byref(used))
-        if rc != 0:
-            raise ClhError('clh_ssw_batch failed (%d): %s' % (rc, last_error()))
+        _check(L.clh_ssw_batch(self._h, n, reads.ctypes.data, read_off.ctypes.data, refs.ctypes.data, ref_off.ctypes.data,
+                               ml.ctypes.data if ml is not None else None, C.byref(o), out.ctypes.data,
+                               cig.ctypes.data if want_cigar else None, cap, C.byref(used)), 'clh_ssw_batch')
         return out, cig[:used.value]
 
     def ccs_batch(self, reads, read_off):
@@ -302,9 +326,7 @@ class Context(object):
         out = np.zeros(n, dtype=CCS_DTYPE)
         segs = np.zeros((n, CCS_SEG_CAP, 2), dtype=np.int32)
         ccs = np.zeros(max(1, len(reads)), dtype=np.int8)
-        rc = lib().clh_ccs_batch(self._h, n, reads.ctypes.data, read_off.ctypes.data, out.ctypes.data, segs.ctypes.data, ccs.ctypes.data)
-        if rc != 0:
-            raise ClhError('clh_ccs_batch failed (%d): %s' % (rc, last_error()))
+        _check(lib().clh_ccs_batch(self._h, n, reads.ctypes.data, read_off.ctypes.data, out.ctypes.data, segs.ctypes.data, ccs.ctypes.data), 'clh_ccs_batch')
         return out, segs, ccs
 
     def poa_batch(self, seqs, seq_off, group_off, algorithm=0, scores=(10, -4, -8, -2, -24, -1), min_coverage=0, genmsa=False,
@@ -324,11 +346,9 @@ class Context(object):
         col = np.zeros(max(1, len(seqs)), dtype=np.int32) if genmsa else None
         ncols = np.zeros(max(1, ng), dtype=np.int32) if genmsa else None
         asc = np.zeros((max(1, ng), CCS_SEG_CAP), dtype=np.int32) if with_scores else None
-        rc = lib().clh_poa_batch(self._h, ng, seqs.ctypes.data, seq_off.ctypes.data, group_off.ctypes.data, opts.ctypes.data,
-                                 lens.ctypes.data, out.ctypes.data, col.ctypes.data if genmsa else None,
-                                 ncols.ctypes.data if genmsa else None, asc.ctypes.data if with_scores else None)
-        if rc != 0:
-            raise ClhError('clh_poa_batch failed (%d): %s' % (rc, last_error()))
+        _check(lib().clh_poa_batch(self._h, ng, seqs.ctypes.data, seq_off.ctypes.data, group_off.ctypes.data, opts.ctypes.data,
+                                   lens.ctypes.data, out.ctypes.data, col.ctypes.data if genmsa else None,
+                                   ncols.ctypes.data if genmsa else None, asc.ctypes.data if with_scores else None), 'clh_poa_batch')
         bases = np.frombuffer(b'ACGTN', dtype=np.uint8)
         res = []
         for k in range(ng):
@@ -358,8 +378,7 @@ class Context(object):
     def poa_last_stats(self):
         """statistics of the last poa_batch (see CcsPlan.stats)"""
         out = np.zeros(16, dtype=np.int64)
-        if lib().clh_poa_last_stats(self._h, out.ctypes.data) != 0:
-            raise ClhError('clh_poa_last_stats: %s' % last_error())
+        _check(lib().clh_poa_last_stats(self._h, out.ctypes.data), 'clh_poa_last_stats')
         return {'dp_cells': int(out[0]), 'dp_row_steps': int(out[1]), 'band_misses': int(out[2]), 'dropped': {k: int(out[2 + k]) for k in range(1, 8) if out[2 + k]}}
 
     def edit_distance_batch(self, xs, ys):
@@ -375,9 +394,7 @@ class Context(object):
         a = np.frombuffer(b''.join(ba) + b'\0', dtype=np.uint8)
         b = np.frombuffer(b''.join(bb) + b'\0', dtype=np.uint8)
         out = np.zeros(n, dtype=np.int32)
-        rc = lib().clh_edit_distance_batch(self._h, n, a.ctypes.data, a_off.ctypes.data, b.ctypes.data, b_off.ctypes.data, out.ctypes.data)
-        if rc != 0:
-            raise ClhError('clh_edit_distance_batch failed (%d): %s' % (rc, last_error()))
+        _check(lib().clh_edit_distance_batch(self._h, n, a.ctypes.data, a_off.ctypes.data, b.ctypes.data, b_off.ctypes.data, out.ctypes.data), 'clh_edit_distance_batch')
         return out
 
     def edit_plan(self, xs, ys):
@@ -404,10 +421,8 @@ class Context(object):
         st = (C.c_int64 * 4)()
         L = lib()
         L.clh_ccs_file_at.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_char_p, C.c_char_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]
-        rc = L.clh_ccs_file_at(self._h, os.fsencode(in_path), int(bool(is_fastq)), os.fsencode(ccs_fa_path), os.fsencode(raw_fa_path),
-                               int(batch_reads), int(byte_offset), int(first_record), int(max_records), C.byref(st))
-        if rc != 0:
-            raise ClhError('clh_ccs_file failed (%d): %s' % (rc, last_error()))
+        _check(L.clh_ccs_file_at(self._h, os.fsencode(in_path), int(bool(is_fastq)), os.fsencode(ccs_fa_path), os.fsencode(raw_fa_path),
+                                 int(batch_reads), int(byte_offset), int(first_record), int(max_records), C.byref(st)), 'clh_ccs_file')
         self.capacity_dropped = getattr(self, 'capacity_dropped', 0) + int(st[3])
         self.last_capacity_dropped = int(st[3])
         return int(st[0]), int(st[1]), int(st[2])
@@ -433,10 +448,12 @@ def _pack_bytes(items):
     return np.frombuffer(b''.join(bs) + b'\0', dtype=np.uint8), off
 
 
-class EditPlan(object):
+class EditPlan(_Handle):
     """Pairs of strings resident on the GPU: run() the edit distances any number of times, fetch() the int32 array."""
+    _destroy = 'clh_edit_plan_destroy'
 
     def __init__(self, ctx, xs, ys):
+        _Handle.__init__(self, ctx)
         if len(xs) != len(ys):
             raise ValueError('EditPlan: the two lists differ in length')
         self.n = len(xs)
@@ -447,34 +464,17 @@ class EditPlan(object):
             raise ClhError('clh_edit_plan_create failed: %s' % last_error())
 
     def run(self, stream=0):
-        rc = lib().clh_edit_plan_run(self._h, C.c_void_p(stream))
-        if rc != 0:
-            raise ClhError('clh_edit_plan_run failed (%d): %s' % (rc, last_error()))
+        _check(lib().clh_edit_plan_run(self._h, C.c_void_p(stream)), 'clh_edit_plan_run')
 
     def fetch(self):
         out = np.zeros(self.n, dtype=np.int32)
-        rc = lib().clh_edit_plan_fetch(self._h, out.ctypes.data)
-        if rc != 0:
-            raise ClhError('clh_edit_plan_fetch failed (%d): %s' % (rc, last_error()))
+        _check(lib().clh_edit_plan_fetch(self._h, out.ctypes.data), 'clh_edit_plan_fetch')
         return out
 
     def timing(self):
         ms = C.c_float(0)
-        if lib().clh_edit_plan_timing(self._h, C.byref(ms)) != 0:
-            raise ClhError('clh_edit_plan_timing: %s' % last_error())
+        _check(lib().clh_edit_plan_timing(self._h, C.byref(ms)), 'clh_edit_plan_timing')
         return float(ms.value)
-
-    def close(self):
-        if self._h:
-            if getattr(self.ctx, '_h', None):
-                lib().clh_edit_plan_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _letter(c):
@@ -486,17 +486,19 @@ def _letter(c):
     return b[0]
 
 
-class EditAlignPlan(object):
+class EditAlignPlan(_Handle):
     """Pairs resident on the GPU for edlib.align's modes: run() any number of times, fetch() (rows, locs, cigar)."""
+    _destroy = 'clh_edit_align_plan_destroy'
 
     def __init__(self, ctx, queries, targets, mode='NW', task='distance', k=-1, equalities=(), workspace_bytes=0):
+        _Handle.__init__(self, ctx)
         if len(queries) != len(targets):
             raise ValueError('EditAlignPlan: the two lists differ in length')
         if mode not in EA_MODES:
             raise ValueError('mode must be one of NW, SHW, HW, got %r' % (mode,))
         if task not in EA_TASKS:
             raise ValueError('task must be one of distance, locations, path, got %r' % (task,))
-        self.ctx, self.n, self._h = ctx, len(queries), None
+        self.n = len(queries)
         q, q_off = _pack_bytes(queries)
         t, t_off = _pack_bytes(targets)
         eq = np.array([[_letter(a), _letter(b)] for a, b in (equalities or ())], dtype=np.uint8).reshape(-1)
@@ -511,38 +513,21 @@ class EditAlignPlan(object):
         self._caps = (int(lc.value), int(cc.value))
 
     def run(self, stream=0):
-        rc = lib().clh_edit_align_plan_run(self._h, C.c_void_p(stream))
-        if rc != 0:
-            raise ClhError('clh_edit_align_plan_run failed (%d): %s' % (rc, last_error()))
+        _check(lib().clh_edit_align_plan_run(self._h, C.c_void_p(stream)), 'clh_edit_align_plan_run')
 
     def fetch(self):
         rows = np.zeros(self.n, dtype=EDIT_ALIGN_DTYPE)
         locs = np.zeros((max(self._caps[0], 1), 2), dtype=np.int32)
         cig = np.zeros(max(self._caps[1], 1), dtype=np.uint32)
         lu, cu = C.c_int64(0), C.c_int64(0)
-        rc = lib().clh_edit_align_plan_fetch(self._h, rows.ctypes.data, locs.ctypes.data, self._caps[0], C.byref(lu), cig.ctypes.data,
-                                             self._caps[1], C.byref(cu))
-        if rc != 0:
-            raise ClhError('clh_edit_align_plan_fetch failed (%d): %s' % (rc, last_error()))
+        _check(lib().clh_edit_align_plan_fetch(self._h, rows.ctypes.data, locs.ctypes.data, self._caps[0], C.byref(lu), cig.ctypes.data,
+                                               self._caps[1], C.byref(cu)), 'clh_edit_align_plan_fetch')
         return rows, locs[:lu.value].copy(), cig[:cu.value].copy()
 
     def timing(self):
         ms = C.c_float(0)
-        if lib().clh_edit_align_plan_timing(self._h, C.byref(ms)) != 0:
-            raise ClhError('clh_edit_align_plan_timing: %s' % last_error())
+        _check(lib().clh_edit_align_plan_timing(self._h, C.byref(ms)), 'clh_edit_align_plan_timing')
         return float(ms.value)
-
-    def close(self):
-        if self._h:
-            if getattr(self.ctx, '_h', None):
-                lib().clh_edit_align_plan_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def flatten_splice_sites(ss_index, offset, length):
@@ -572,14 +557,15 @@ def flatten_splice_sites(ss_index, offset, length):
     return flat, cnt
 
 
-class Genome(object):
+class Genome(_Handle):
     """Contigs resident in HBM as base codes (K5).  A Smith-Waterman reference is then a window (contig, start, end,
     minus-strand flag) read in place: no window string, no reverse complement, no per-base encode on the host."""
+    _destroy = 'clh_genome_destroy'
 
     def __init__(self, ctx, contigs):
         """contigs: {name: str} (or an iterable of (name, str)); they are concatenated in iteration order"""
+        _Handle.__init__(self, ctx)
         items = list(contigs.items()) if hasattr(contigs, 'items') else list(contigs)
-        self.ctx = ctx
         self.offset, self.length = {}, {}
         pos = 0
         for name, seq in items:
@@ -589,18 +575,6 @@ class Genome(object):
         self._h = lib().clh_genome_create(ctx._h, blob, len(blob))
         if not self._h:
             raise ClhError('clh_genome_create failed: %s' % last_error())
-
-    def close(self):
-        if self._h:
-            if getattr(self.ctx, '_h', None):        # a context closed first has already given everything back
-                lib().clh_genome_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @property
     def codes_ptr(self):
@@ -622,18 +596,14 @@ class Genome(object):
         out = np.zeros(n, dtype=np.int64)
         if n == 0:
             return out
-        rc = lib().clh_genome_count_n(self._h, n, off.ctypes.data, ln.ctypes.data, out.ctypes.data)
-        if rc != 0:
-            raise ClhError('clh_genome_count_n failed (%d): %s' % (rc, last_error()))
+        _check(lib().clh_genome_count_n(self._h, n, off.ctypes.data, ln.ctypes.data, out.ctypes.data), 'clh_genome_count_n')
         return out
 
     def set_splice_sites(self, ss_index):
         """Annotated splice sites for splice_signals(): ss_index = {contig: {pos: {strand: {'start'|'end': 1}}}} (the
         reference's splice_site_index, align.py:235-252) or None.  Contigs that are not resident are ignored."""
         flat, cnt = flatten_splice_sites(ss_index, self.offset, self.length)
-        rc = lib().clh_genome_set_splice_sites(self._h, flat.ctypes.data, cnt.ctypes.data)
-        if rc != 0:
-            raise ClhError('clh_genome_set_splice_sites failed (%d): %s' % (rc, last_error()))
+        _check(lib().clh_genome_set_splice_sites(self._h, flat.ctypes.data, cnt.ctypes.data), 'clh_genome_set_splice_sites')
         self._sites_of = ss_index
 
     def splice_signals(self, cands, search_extra=10, shift_threshold=3, is_canonical=True, index_slices=False):
@@ -655,10 +625,8 @@ class Genome(object):
         out = np.zeros((n, 8), dtype=np.int32)
         if n == 0:
             return out
-        rc = lib().clh_splice_signal_batch(self._h, n, off.ctypes.data, ln.ctypes.data, st.ctypes.data, en.ctypes.data, cb.ctypes.data,
-                                           hm.ctypes.data, search_extra, shift_threshold, (1 if is_canonical else 0) | (2 if index_slices else 0), out.ctypes.data)
-        if rc != 0:
-            raise ClhError('clh_splice_signal_batch failed (%d): %s' % (rc, last_error()))
+        _check(lib().clh_splice_signal_batch(self._h, n, off.ctypes.data, ln.ctypes.data, st.ctypes.data, en.ctypes.data, cb.ctypes.data,
+                                             hm.ctypes.data, search_extra, shift_threshold, (1 if is_canonical else 0) | (2 if index_slices else 0), out.ctypes.data), 'clh_splice_signal_batch')
         return out
 
     def plan_windows(self, read_off, win_off, win_len, minus, mat, gap_open, gap_extend, flag=1, score_size=2, want_score2=True,
@@ -685,21 +653,20 @@ class Genome(object):
         cig = np.empty(cap, dtype=np.uint32)     # worst-case capacity; only the used prefix is written
         used = C.c_int64(0)
         ml = np.ascontiguousarray(mask_len, dtype=np.int32) if mask_len is not None else None
-        rc = lib().clh_ssw_windows_batch(self._h, n, reads.ctypes.data, read_off.ctypes.data, off.ctypes.data, ln32.ctypes.data, rcf.ctypes.data,
-                                         ml.ctypes.data if ml is not None else None, C.byref(o), out.ctypes.data,
-                                         cig.ctypes.data if want_cigar else None, cap, C.byref(used))
-        if rc != 0:
-            raise ClhError('clh_ssw_windows_batch failed (%d): %s' % (rc, last_error()))
+        _check(lib().clh_ssw_windows_batch(self._h, n, reads.ctypes.data, read_off.ctypes.data, off.ctypes.data, ln32.ctypes.data, rcf.ctypes.data,
+                                           ml.ctypes.data if ml is not None else None, C.byref(o), out.ctypes.data,
+                                           cig.ctypes.data if want_cigar else None, cap, C.byref(used)), 'clh_ssw_windows_batch')
         return out, cig[:used.value]
 
 
-class Plan(object):
+class Plan(_Handle):
     """A batch shape resident on the GPU: run() it on device pointers any number of times."""
+    _destroy = 'clh_plan_destroy'
 
     def __init__(self, ctx, read_off, ref_off, mat, gap_open, gap_extend, flag, score_size, want_score2, want_cigar, mask_len,
                  windows=None):
+        _Handle.__init__(self, ctx)
         L = lib()
-        self.ctx = ctx
         self.read_off = np.ascontiguousarray(read_off, dtype=np.int64)
         self.n = len(self.read_off) - 1
         self.want_cigar = bool(want_cigar)
@@ -719,18 +686,14 @@ class Plan(object):
     def run(self, d_reads_ptr, d_refs_ptr, stream=0):
         """stream: a hipStream_t handle (e.g. torch.cuda.Stream().cuda_stream).  0 selects libclh's own private stream, which
         is NOT ordered with torch's default stream: pass the stream your inputs are produced on."""
-        rc = lib().clh_ssw_run(self._h, C.c_void_p(d_reads_ptr), C.c_void_p(d_refs_ptr), C.c_void_p(stream))
-        if rc != 0:
-            raise ClhError('clh_ssw_run failed (%d): %s' % (rc, last_error()))
+        _check(lib().clh_ssw_run(self._h, C.c_void_p(d_reads_ptr), C.c_void_p(d_refs_ptr), C.c_void_p(stream)), 'clh_ssw_run')
 
     def fetch(self):
         out = np.zeros(self.n, dtype=ALIGN_DTYPE)
         cap = int(2 * (self.read_off[-1] if self.n else 0) + 2 * self.n + 8) if self.want_cigar else 1
         cig = np.empty(cap, dtype=np.uint32)     # worst-case capacity; only the used prefix is ever written or touched
         used = C.c_int64(0)
-        rc = lib().clh_ssw_fetch(self._h, out.ctypes.data, cig.ctypes.data if self.want_cigar else None, cap, C.byref(used))
-        if rc != 0:
-            raise ClhError('clh_ssw_fetch failed (%d): %s' % (rc, last_error()))
+        _check(lib().clh_ssw_fetch(self._h, out.ctypes.data, cig.ctypes.data if self.want_cigar else None, cap, C.byref(used)), 'clh_ssw_fetch')
         return out, cig[:used.value]
 
     def set_refs_bytes(self, nbytes):
@@ -750,8 +713,7 @@ class Plan(object):
     def traceback_counts(self):
         """(alignments handed to the wide row traceback, alignments handed on to the anti-diagonal traceback) of the last run"""
         c = np.zeros(2, dtype=np.int32)
-        if lib().clh_plan_traceback_counts(self._h, c.ctypes.data) != 0:
-            raise ClhError('clh_plan_traceback_counts: %s' % last_error())
+        _check(lib().clh_plan_traceback_counts(self._h, c.ctypes.data), 'clh_plan_traceback_counts')
         return int(c[0]), int(c[1])
 
     def prefilter_stats(self):
@@ -759,16 +721,14 @@ class Plan(object):
         them with candidate slices, slices run, window columns computed, window columns of the class, alignments that also went
         through the second stage (indel-distance bound)"""
         c = np.zeros(6, dtype=np.int64)
-        if lib().clh_plan_prefilter_stats(self._h, c.ctypes.data) != 0:
-            raise ClhError('clh_plan_prefilter_stats: %s' % last_error())
+        _check(lib().clh_plan_prefilter_stats(self._h, c.ctypes.data), 'clh_plan_prefilter_stats')
         return dict(zip(('alignments', 'pruned', 'slices', 'cols_computed', 'cols_window', 'second_stage'), (int(x) for x in c)))
 
     def prefilter_timing(self):
         """ssw_prefilter_kernel alone in the last profiling run, per long-window class (reads up to 254 bases, longer reads):
         [(ms, window columns x W words, the same x (11 W + 8) instructions per column and lane), ...]"""
         ms = np.zeros(2, dtype=np.float32); w = np.zeros(4, dtype=np.int64)
-        if lib().clh_plan_prefilter_timing(self._h, ms.ctypes.data, w.ctypes.data) != 0:
-            raise ClhError('clh_plan_prefilter_timing: %s' % last_error())
+        _check(lib().clh_plan_prefilter_timing(self._h, ms.ctypes.data, w.ctypes.data), 'clh_plan_prefilter_timing')
         return [(float(ms[k]), int(w[2 * k]), int(w[2 * k + 1])) for k in range(2)]
 
     def timing(self):
@@ -776,30 +736,19 @@ class Plan(object):
         a = np.zeros(32, dtype=np.float32); b = np.zeros(2, dtype=np.float32)
         ns = lib().clh_plan_timing(self._h, 32, a.ctypes.data, b.ctypes.data)
         if ns < 0:
-            raise ClhError('clh_plan_timing: %s' % last_error())
+            _check(ns, 'clh_plan_timing')
         return [float(a[k]) for k in range(ns)], (float(b[0]), float(b[1]))
 
     def results_dev_ptr(self):
         return lib().clh_ssw_results_dev(self._h)
 
-    def close(self):
-        if getattr(self, '_h', None):
-            if getattr(self.ctx, '_h', None):
-                lib().clh_plan_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class CcsPlan(object):
+class CcsPlan(_Handle):
     """Consensus step for a batch shape resident on the GPU (K2 + K3)."""
+    _destroy = 'clh_ccs_plan_destroy'
 
     def __init__(self, ctx, read_off):
-        self.ctx = ctx
+        _Handle.__init__(self, ctx)
         self.read_off = np.ascontiguousarray(read_off, dtype=np.int64)
         self.n = len(self.read_off) - 1
         self._h = lib().clh_ccs_plan_create(ctx._h, self.n, self.read_off.ctypes.data)
@@ -808,22 +757,18 @@ class CcsPlan(object):
 
     def run(self, d_reads_ptr, stream=0):
         """stream: see Plan.run"""
-        rc = lib().clh_ccs_run(self._h, C.c_void_p(d_reads_ptr), C.c_void_p(stream))
-        if rc != 0:
-            raise ClhError('clh_ccs_run failed (%d): %s' % (rc, last_error()))
+        _check(lib().clh_ccs_run(self._h, C.c_void_p(d_reads_ptr), C.c_void_p(stream)), 'clh_ccs_run')
 
     def timing(self):
         """(K2 ms, K3 ms) of the last run"""
         ms = np.zeros(2, dtype=np.float32)
-        if lib().clh_ccs_plan_timing(self._h, ms.ctypes.data) != 0:
-            raise ClhError('clh_ccs_plan_timing: %s' % last_error())
+        _check(lib().clh_ccs_plan_timing(self._h, ms.ctypes.data), 'clh_ccs_plan_timing')
         return float(ms[0]), float(ms[1])
 
     def info(self):
         """dict(slots, slot_bytes, big_slots, big_slot_bytes, ran_in_claimed_big_slot, ran_in_second_launch) of the last run"""
         out = np.zeros(6, dtype=np.int64)
-        if lib().clh_ccs_plan_info(self._h, out.ctypes.data) != 0:
-            raise ClhError('clh_ccs_plan_info: %s' % last_error())
+        _check(lib().clh_ccs_plan_info(self._h, out.ctypes.data), 'clh_ccs_plan_info')
         return dict(zip(('slots', 'slot_bytes', 'big_slots', 'big_slot_bytes', 'ran_in_claimed_big_slot', 'ran_in_second_launch'), (int(x) for x in out)))
 
     def stats(self):
@@ -831,37 +776,21 @@ class CcsPlan(object):
         without a consensus (status 1 workspace, 2 graph limits, 3 output, 4 (unused since round 4), 5 back-track guard, 6 16-bit
         range, 7 alignment without a base)"""
         out = np.zeros(16, dtype=np.int64)
-        if lib().clh_ccs_plan_stats(self._h, out.ctypes.data) != 0:
-            raise ClhError('clh_ccs_plan_stats: %s' % last_error())
+        _check(lib().clh_ccs_plan_stats(self._h, out.ctypes.data), 'clh_ccs_plan_stats')
         return {'dp_cells': int(out[0]), 'dp_row_steps': int(out[1]), 'band_misses': int(out[2]), 'dropped': {k: int(out[2 + k]) for k in range(1, 8) if out[2 + k]}}
 
     def results_dev(self):
         """device pointers (rows, segs, ccs) of the last run's outputs; ccs is packed at the read offsets"""
         a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        if lib().clh_ccs_results_dev(self._h, C.byref(a), C.byref(b), C.byref(c)) != 0:
-            raise ClhError('clh_ccs_results_dev: %s' % last_error())
+        _check(lib().clh_ccs_results_dev(self._h, C.byref(a), C.byref(b), C.byref(c)), 'clh_ccs_results_dev')
         return a.value, b.value, c.value
 
     def fetch(self):
         out = np.zeros(self.n, dtype=CCS_DTYPE)
         segs = np.zeros((self.n, CCS_SEG_CAP, 2), dtype=np.int32)
         ccs = np.zeros(max(1, int(self.read_off[-1])), dtype=np.int8)
-        rc = lib().clh_ccs_fetch(self._h, out.ctypes.data, segs.ctypes.data, ccs.ctypes.data)
-        if rc != 0:
-            raise ClhError('clh_ccs_fetch failed (%d): %s' % (rc, last_error()))
+        _check(lib().clh_ccs_fetch(self._h, out.ctypes.data, segs.ctypes.data, ccs.ctypes.data), 'clh_ccs_fetch')
         return out, segs, ccs
-
-    def close(self):
-        if getattr(self, '_h', None):
-            if getattr(self.ctx, '_h', None):
-                lib().clh_ccs_plan_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 _default_ctx = {}

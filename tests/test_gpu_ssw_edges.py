@@ -9,8 +9,6 @@ import ctypes as C
 import gzip
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -89,7 +87,7 @@ def run_and_check(refs, qs, scheme, mat=None, score_size=2, flag=1, want_score2=
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
 # the golden sets: the 16-bit ceiling, gap extensions above 16, general matrices, score_size / flag -- through the default routing and
-# with K1l / K1w switched off; the anti-diagonal traceback (CLH_NO_TB_ROWS, read once per process) in a child process
+# with K1l / K1w switched off, and with every CIGAR from the anti-diagonal traceback (CLH_NO_TB_ROWS)
 # ---------------------------------------------------------------------------------------------------------------------------------------
 def _golden_groups(key):
     """the cases of a golden set, grouped into batches of one option set"""
@@ -127,13 +125,11 @@ def test_golden_edges(key, switch, monkeypatch):
         assert n_sat > 0 and n_k1 >= n_sat, (key, n_k1, n_sat)           # the saturated alignments ran in the anti-diagonal classes
 
 
-def test_golden_edges_anti_diagonal_traceback():
-    """every golden set again with every CIGAR from the anti-diagonal traceback kernel (CLH_NO_TB_ROWS=1), in a fresh process"""
-    env = dict(os.environ, CLH_NO_TB_ROWS='1')
-    code = 'import sys; sys.path[:0] = [%r, %r]\nimport test_gpu_ssw_edges as t\nfor k in t.ssw_edges.all_cases(): t.check_golden_set(k)\nprint("ok")' % (
-        HERE, os.path.dirname(HERE))
-    r = subprocess.run([sys.executable, '-c', code], env=env, capture_output=True, text=True, timeout=240)
-    assert r.returncode == 0 and r.stdout.strip().endswith('ok'), (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+def test_golden_edges_anti_diagonal_traceback(monkeypatch):
+    """every golden set again with every CIGAR from the anti-diagonal traceback kernel (CLH_NO_TB_ROWS=1)"""
+    monkeypatch.setenv('CLH_NO_TB_ROWS', '1')
+    for k in ssw_edges.all_cases():
+        check_golden_set(k)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
