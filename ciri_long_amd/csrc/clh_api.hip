@@ -245,6 +245,7 @@ struct clh_plan : clh_owned {
     std::vector<int32_t> w32_prefix;   // tasks in launch order: how many before k could need the int32 traceback (clh::launch_traceback_w32)
     bool alpha = false;             // matrix edge 6..32: every alignment in the K1a classes (ssw_alpha.hip)
     void* d_alpha_mat = nullptr;    // their n x n matrix
+    const void *run_reads = nullptr, *run_refs = nullptr;     // the last run's sequences (K1a's further traceback rounds in clh_ssw_fetch)
 
     // the workspaces of a class's persistent workgroups in the strip buffer: wgs slots of `bytes` rounded up to 256; returns their offset
     int64_t reserve_ws(size_t bytes, int wgs, int* slot)
@@ -798,6 +799,7 @@ extern "C" int clh_ssw_run(clh_plan* pl, const void* d_reads, const void* d_refs
     P.colmax = (uint16_t*)pl->d_colmax;
     P.cigars = (uint32_t*)pl->d_cigars; P.cigar_len = (int32_t*)pl->d_cigar_len; P.dirs = (uint8_t*)pl->d_strips;
     P.no_guess = pl->sw.no_guess;
+    pl->run_reads = d_reads; pl->run_refs = d_refs;
     if (pl->profiling && pl->ev.empty()) {
         pl->ev.resize(pl->segs.size() * 2 + 4);
         for (auto& e : pl->ev) HIPCHK(pl->event(&e));
@@ -1061,6 +1063,60 @@ __global__ void cigar_gather_kernel(const uint32_t* __restrict__ src, const int3
     for (int k = threadIdx.x; k < L; k += blockDim.x) d[k] = s[k];
 }
 
+// K1a's traceback keeps one byte per band cell of every band iteration in the pool, far more than the plan's share for an alignment
+// whose band is wide: what did not fit in the run (CLH_STATUS_NEED_POOL) runs again here, over the emptied pool, in as many rounds as it
+// takes (the scores are final).  A round in which none fits (several at once can fill the pool between them) is repeated one alignment
+// after the other; there the first runs alone on the empty pool, and if it does not fit it is reported as CLH_ST_CIGAR_TRUNC.
+static int alpha_pool_rounds(clh_plan* pl, std::vector<clh::SswResult>& res)
+{
+    const int n = pl->n;
+    std::vector<int32_t> list(1, 0);
+    for (int k = 0; k < pl->n_all; ++k) {
+        const int a = pl->tasks[k].out_index;
+        if (a < n && (res[a].status & clh::CLH_STATUS_NEED_POOL)) list.push_back(k);
+    }
+    if (list.size() == 1) return 0;
+    clh_ctx* c = pl->ctx;
+    hipStream_t st = c->stream;
+    clh::SswParams PG = pl->params;
+    PG.reads = (const int8_t*)pl->run_reads; PG.refs = (const int8_t*)pl->run_refs;
+    PG.results = (clh::SswResult*)pl->d_results; PG.colmax = (uint16_t*)pl->d_colmax;
+    PG.cigars = (uint32_t*)pl->d_cigars; PG.cigar_len = (int32_t*)pl->d_cigar_len; PG.dirs = (uint8_t*)pl->d_strips;
+    PG.no_guess = pl->sw.no_guess;
+    PG.tasks = (const clh::SswTask*)pl->d_tasks;
+    void* d_list = c->alloc(sizeof(int32_t) * list.size());
+    if (!d_list) return fail(CLH_E_HIP, "out of device memory for the traceback rounds");
+    int rc = 0;
+    bool one_by_one = false;
+    while (list.size() > 1) {
+        const int left = (int)list.size() - 1;
+        list[0] = left;
+        if (hipMemcpy(d_list, list.data(), sizeof(int32_t) * list.size(), hipMemcpyHostToDevice) != hipSuccess ||
+            clh::launch_ssw_alpha_traceback_retry(PG, (const int8_t*)pl->d_alpha_mat, (int*)d_list, left, one_by_one, (uint8_t*)pl->d_pool,
+                                                  (unsigned long long*)pl->d_pool_head, pl->pool_bytes, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess ||
+            hipMemcpy(res.data(), pl->d_results, sizeof(clh::SswResult) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) {
+            rc = fail(CLH_E_HIP, "traceback round failed");
+            break;
+        }
+        std::vector<int32_t> next(1, 0);
+        for (int q = 1; q <= left; ++q)
+            if (res[pl->tasks[list[q]].out_index].status & clh::CLH_STATUS_NEED_POOL) next.push_back(list[q]);
+        if ((int)next.size() - 1 == left) {      // not one of them fit
+            if (!one_by_one) { one_by_one = true; continue; }
+            // one by one, the first ran alone on the empty pool: it does not fit at all
+            clh::SswResult& r = res[pl->tasks[list[1]].out_index];
+            r.status = (r.status & ~clh::CLH_STATUS_NEED_POOL) | clh::CLH_STATUS_CIGAR_TRUNC;
+            next.erase(next.begin() + 1);
+            if (hipMemcpy(&((clh::SswResult*)pl->d_results)[pl->tasks[list[1]].out_index].status, &r.status, sizeof(r.status),
+                          hipMemcpyHostToDevice) != hipSuccess) { rc = fail(CLH_E_HIP, "traceback round failed"); break; }
+        }
+        list.swap(next);
+    }
+    c->release(d_list);
+    return rc;
+}
+
 extern "C" int clh_ssw_fetch(clh_plan* pl, clh_align_t* out, uint32_t* cigar_buf, int64_t cigar_cap, int64_t* cigar_used)
 {
     if (!pl || !out) return fail(CLH_E_ARG, "clh_ssw_fetch: null argument");
@@ -1075,6 +1131,8 @@ extern "C" int clh_ssw_fetch(clh_plan* pl, clh_align_t* out, uint32_t* cigar_buf
         for (int a = 0; a < n; ++a)
             if (res[a].status & clh::CLH_STATUS_BAD_CODE)
                 return fail(CLH_E_ARG, "alignment " + std::to_string(a) + ": a read or reference code outside [0, " + std::to_string(pl->opts.n_mat) + ")");
+    if (pl->alpha && pl->do_cigar && n > 0)
+        if (int rc = alpha_pool_rounds(pl, res)) return rc;
     if (pl->do_cigar && n > 0) HIPCHK(hipMemcpy(clen.data(), pl->d_cigar_len, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
     std::vector<int32_t> share_off((size_t)std::max(n, 1), 0), glen((size_t)std::max(n, 1), 0);
     std::vector<int64_t> dst_off((size_t)std::max(n, 1), 0);

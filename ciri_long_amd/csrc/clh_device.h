@@ -14,7 +14,8 @@ enum {
     CLH_STATUS_CIGAR_TRUNC = 16, // CIGAR buffer share / traceback pool exhausted
     CLH_STATUS_NEED_BIG = 32,    // internal: traceback must be redone with the large LDS window
     CLH_STATUS_BAD_CODE = 64,    // K1a: a read or reference code outside [0, n) (clh_ssw_fetch turns it into CLH_E_ARG)
-    CLH_STATUS_NEED_W32 = 128    // internal: CIGAR for the int32 traceback (a score saturated at 32767, or beyond the 16-bit forms' capacity)
+    CLH_STATUS_NEED_W32 = 128,   // internal: CIGAR for the int32 traceback (a score saturated at 32767, or beyond the 16-bit forms' capacity)
+    CLH_STATUS_NEED_POOL = 256   // internal, K1a: the traceback pool ran out; clh_ssw_fetch runs it again over the emptied pool
 };
 
 // One alignment = one workgroup of one wavefront.  Offsets are into the packed batch arrays.
@@ -301,6 +302,10 @@ hipError_t launch_ssw_alpha(const SswParams& p, const int8_t* d_mat, int ntasks,
                             hipStream_t stream);
 hipError_t launch_ssw_alpha_traceback(const SswParams& p, const int8_t* d_mat, int task_base, int ntasks, int n_total, int seg, int lmax,
                                       uint8_t* pool_base, unsigned long long* pool_head, unsigned long long pool_size, hipStream_t stream);
+// the K1a tracebacks marked CLH_STATUS_NEED_POOL again, over the pool emptied first: d_list = {count, task indices...} (nlist entries);
+// one_by_one: one after the other in list order, the first of them alone on the empty pool
+hipError_t launch_ssw_alpha_traceback_retry(const SswParams& p, const int8_t* d_mat, int* d_list, int nlist, bool one_by_one, uint8_t* pool_base,
+                                            unsigned long long* pool_head, unsigned long long pool_size, hipStream_t stream);
 // K1b launches.  All take the plan's WHOLE task table in p.tasks and work on the tasks [task_base, task_base + ntasks) of launch
 // class `seg` (every class has its own hand-over counters and list regions, so the classes' launch chains run on different
 // streams at once).  Words behind the pool's bump pointer: [4 + seg] alignments the row kernel handed to its wide form,

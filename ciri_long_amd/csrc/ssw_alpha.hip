@@ -411,7 +411,8 @@ __device__ __forceinline__ void alpha_traceback(const SswParams& p, const int8_t
         if (lane == 0) s_at = atomicAdd(pool.head, need);
         __syncthreads();
         at = (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(s_at & 0xffffffffull)) | ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(s_at >> 32)) << 32);
-        if (at + need > pool.size) { status = CLH_STATUS_CIGAR_TRUNC; break; }
+        // the pool ran out: K1a's alignments go round again over the emptied pool (clh_ssw_fetch), the DNA ones report it
+        if (at + need > pool.size) { status = dna ? CLH_STATUS_CIGAR_TRUNC : CLH_STATUS_NEED_POOL; break; }
         dir = pool.base + at;
         last_at = at;
         if (lane == 0 && niter < 24) { hist_at[niter] = at; hist_w[niter] = w; }
@@ -561,15 +562,17 @@ __device__ __forceinline__ void alpha_traceback(const SswParams& p, const int8_t
     if (lane == 0) *cig_len = nops;
 }
 
+// big != 0: the alignments listed in pool.list_big that carry the status bit `need` (CLH_STATUS_NEED_BIG, or CLH_STATUS_NEED_POOL for a
+// round over the emptied pool)
 __global__ void __launch_bounds__(1024) ssw_alpha_traceback_kernel(const SswParams p, const int8_t* __restrict__ mat, AlPool pool, int ws, int wsp,
-                                                                   int big, int seq_cap)
+                                                                   int big, int seq_cap, int need)
 {
     __shared__ int8_t smat[1024];
     stage_matrix(mat, p.n, smat);
     if (big == 0) { alpha_traceback(p, smat, pool, ws, wsp, big, seq_cap, pool.task_base + (int)blockIdx.x); return; }
     const int nb = __builtin_amdgcn_readfirstlane(*pool.n_big);
     for (int k = (int)blockIdx.x; k < nb; k += (int)gridDim.x) {
-        alpha_traceback(p, smat, pool, ws, wsp, big, seq_cap, __builtin_amdgcn_readfirstlane(pool.list_big[k]));
+        alpha_traceback(p, smat, pool, ws, wsp, big, seq_cap, __builtin_amdgcn_readfirstlane(pool.list_big[k]), need);
         __syncthreads();
     }
 }
@@ -649,11 +652,30 @@ hipError_t launch_ssw_alpha_traceback(const SswParams& p, const int8_t* d_mat, i
         const int seq_cap = big ? 153600 - 7 * ws * (int)sizeof(int) : 6144;
         const size_t lds = (size_t)7 * ws * sizeof(int) + (size_t)seq_cap;
         const int grid = big == 0 ? ntasks : std::min(ntasks, 512);
-        hipLaunchKernelGGL(ssw_alpha_traceback_kernel, dim3(grid), dim3(big ? 1024 : 128), lds, stream, p, d_mat, pool, ws, wsp, big, seq_cap);
+        hipLaunchKernelGGL(ssw_alpha_traceback_kernel, dim3(grid), dim3(big ? 1024 : 128), lds, stream, p, d_mat, pool, ws, wsp, big, seq_cap,
+                           (int)CLH_STATUS_NEED_BIG);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+// the large configuration whatever the class (a window sized for 5 120 rows gives every alignment the CIGAR its class's own would);
+// one_by_one: a single workgroup, which takes the listed alignments in list order
+hipError_t launch_ssw_alpha_traceback_retry(const SswParams& p, const int8_t* d_mat, int* d_list, int nlist, bool one_by_one, uint8_t* pool_base,
+                                            unsigned long long* pool_head, unsigned long long pool_size, hipStream_t stream)
+{
+    if (nlist <= 0) return hipSuccess;
+    AlPool pool; pool.base = pool_base; pool.head = pool_head; pool.size = pool_size; pool.task_base = 0;
+    pool.n_big = d_list; pool.list_big = d_list + 1;
+    const int ws = 5122, wsp = 4096;
+    const int seq_cap = 153600 - 7 * ws * (int)sizeof(int);
+    const size_t lds = (size_t)7 * ws * sizeof(int) + (size_t)seq_cap;
+    hipError_t e = hipMemsetAsync(pool_head, 0, sizeof(unsigned long long), stream);      // the bump pointer only
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(ssw_alpha_traceback_kernel, dim3(one_by_one ? 1 : std::min(nlist, 512)), dim3(1024), lds, stream, p, d_mat, pool, ws, wsp, 1, seq_cap,
+                       (int)CLH_STATUS_NEED_POOL);
+    return hipGetLastError();
 }
 
 }  // namespace clh

@@ -685,7 +685,9 @@ class Plan(_Handle):
 
     def run(self, d_reads_ptr, d_refs_ptr, stream=0):
         """stream: a hipStream_t handle (e.g. torch.cuda.Stream().cuda_stream).  0 selects libclh's own private stream, which
-        is NOT ordered with torch's default stream: pass the stream your inputs are produced on."""
+        is NOT ordered with torch's default stream: pass the stream your inputs are produced on.  With a matrix of edge 6..32 and
+        CIGARs wanted, the two buffers must stay allocated and unmodified until fetch() returns: fetch() may run tracebacks again
+        on libclh's own stream, and they read them (include/ciri_long_hip.h: clh_ssw_fetch)."""
         _check(lib().clh_ssw_run(self._h, C.c_void_p(d_reads_ptr), C.c_void_p(d_refs_ptr), C.c_void_p(stream)), 'clh_ssw_run')
 
     def fetch(self):

@@ -36,9 +36,12 @@ extern "C" {
 #define CLH_ST_NULL        2    /* the reference would have returned NULL (ssw.c:810-813: score_size 0 overflow) */
 #define CLH_ST_TRACE_ERR   4    /* the reference's "Trace back error" (ssw.c:674-682) */
 #define CLH_ST_NO_CIGAR    8    /* CIGAR not produced because of flag/filters (ssw.c:834,850) */
-#define CLH_ST_CIGAR_TRUNC 16   /* no CIGAR for a capacity reason, scores and coordinates are valid: the traceback workspace ran out
-                                 * (retry with a smaller batch), or the band is wider than 2048 cells on an aligned reference of more than
-                                 * 2048 bases AND read + reference of the aligned part exceed 12 kB (or the read 4096 rows) */
+#define CLH_ST_CIGAR_TRUNC 16   /* no CIGAR for a capacity reason, scores and coordinates are valid.  DNA (matrix edge 1..5): the
+                                 * traceback workspace ran out (retry with a smaller batch), or the band is wider than 2048 cells on an
+                                 * aligned reference of more than 2048 bases AND read + reference of the aligned part exceed 12 kB (or the
+                                 * read 4096 rows).  Matrix edge 6..32: the final band is wider than 4093 cells on an aligned read of more
+                                 * than 5121 letters, or the alignment alone needs more than the whole, empty workspace -- tracebacks the
+                                 * shared workspace could not hold during the run are run again in clh_ssw_fetch (see there) */
 
 /* One result row: the fields of s_align (ssw.h:42-52) with the cigar pointer replaced by a slice of the
  * caller's cigar buffer. */
@@ -109,7 +112,9 @@ int clh_plan_prefilter_timing(clh_plan* pl, float* ms, int64_t* work);
  * a caller has queued on the default stream (or on any other stream) is then unordered with these kernels.  A caller
  * who produces inputs or consumes clh_ssw_results_dev() on a stream of its own passes THAT stream; hipStreamLegacy /
  * hipStreamPerThread are passed through like any other handle.  Results stay in HBM until clh_ssw_fetch, which waits
- * for the stream of the last run.  The same holds for every `stream` argument of this header. */
+ * for the stream of the last run.  The same holds for every `stream` argument of this header.
+ * Matrix edge 6..32 with CIGARs wanted: d_reads and d_refs must stay allocated and unmodified until clh_ssw_fetch returns --
+ * fetch may run tracebacks again (CLH_ST_CIGAR_TRUNC below) on the context's own stream, and they read both buffers. */
 int clh_ssw_run(clh_plan* plan, const void* d_reads, const void* d_refs, void* stream);
 
 /* Padding contract of d_refs.  For windows of 32 kb and more the column prefilter reads the window text in whole, address-aligned
@@ -122,11 +127,14 @@ int clh_plan_set_refs_bytes(clh_plan* plan, int64_t nbytes);
 
 /* Wait for the last run and copy results out.  cigar_buf may be NULL.  *cigar_used receives the u32 count (the CIGARs come back
  * as one dense array).  It waits for the completion of the plan's last clh_ssw_run (an event recorded behind its last launch),
- * not for work the caller queued on the stream afterwards. */
+ * not for work the caller queued on the stream afterwards.  Matrix edge 6..32 with CIGARs wanted: the tracebacks the run's shared
+ * workspace could not hold are run here, on the context's own stream, over the emptied workspace (they read the run's d_reads and
+ * d_refs, which must still hold the run's sequences), before the rows are read. */
 int clh_ssw_fetch(clh_plan* plan, clh_align_t* out, uint32_t* cigar_buf, int64_t cigar_cap, int64_t* cigar_used);
 
 /* Device pointer of the raw result table of the last run (8 x int32 per alignment: score1 score2 ref_begin1 ref_end1
- * read_begin1 read_end1 ref_end2 status), for callers that keep post-processing on the GPU. */
+ * read_begin1 read_end1 ref_end2 status), for callers that keep post-processing on the GPU.  Matrix edge 6..32: the CIGAR part of
+ * `status` is final only after clh_ssw_fetch (before it, a row may carry an internal bit, 256, for a traceback still to run). */
 const void* clh_ssw_results_dev(const clh_plan* plan);
 
 /* Measurement hooks (bench.py): per launch-segment (one read-length class each) HIP-event durations of the score
