@@ -300,6 +300,7 @@ inline bool rv_is_alpha(int rv) { return rv <= kRvAlpha && rv > kRvAlpha - kNumA
 size_t alpha_lds_bytes(int lcap);
 hipError_t launch_ssw_alpha(const SswParams& p, const int8_t* d_mat, int ntasks, int lcap, int nworkgroups, long long ws_off, int ws_slot,
                             hipStream_t stream);
+// K1a's CIGARs: the anti-diagonal form of ssw_traceback.hip with int32 state and the n x n matrix
 hipError_t launch_ssw_alpha_traceback(const SswParams& p, const int8_t* d_mat, int task_base, int ntasks, int n_total, int seg, int lmax,
                                       uint8_t* pool_base, unsigned long long* pool_head, unsigned long long pool_size, hipStream_t stream);
 // the K1a tracebacks marked CLH_STATUS_NEED_POOL again, over the pool emptied first: d_list = {count, task indices...} (nlist entries);
@@ -333,8 +334,8 @@ hipError_t launch_traceback_rows_wide(const SswParams& p, int task_base, int nta
 // second list); rv > 0: the class's second list, window sized for rows <= 128 * rv
 hipError_t launch_traceback_pool(int rv, const SswParams& p, int task_base, int ntasks, int n_total, int seg, uint8_t* pool_base, unsigned long long* pool_head,
                                  unsigned long long pool_size, hipStream_t stream);
-// the DNA alignments of tasks [task_base, task_base + ntasks) that the 16-bit forms marked CLH_STATUS_NEED_W32: K1a's int32 traceback
-// (ssw_alpha.hip) with the plan's matrix, sequences read from HBM where they do not fit LDS
+// the DNA alignments of tasks [task_base, task_base + ntasks) that the 16-bit forms marked CLH_STATUS_NEED_W32: the anti-diagonal form with
+// int32 state (ssw_traceback.hip) and the plan's matrix, sequences read from HBM where they do not fit LDS
 hipError_t launch_traceback_w32(const SswParams& p, int task_base, int ntasks, uint8_t* pool_base, unsigned long long* pool_head,
                                 unsigned long long pool_size, hipStream_t stream);
 

@@ -1,5 +1,7 @@
-// clh_device_ops.h -- the packed-16 arithmetic and the cross-lane moves the row-form kernels share (ssw_scan.hip, ssw_scan_wide.hip,
-// ssw_traceback_rows.hip, ccs_poa.hip).  Device code only; every function is one or a few gfx950 instructions.
+// clh_device_ops.h -- the packed-16 arithmetic and the cross-lane moves the row-form kernels share (ssw_wavefront.hip, ssw_scan.hip,
+// ssw_scan_wide.hip, ssw_traceback_rows.hip, ccs_poa.hip), and the few helpers every Smith-Waterman kernel file would otherwise repeat
+// (the LDS-only barrier, the staged substitution matrix, the masked second best).  Device code only; all but the last are one or a few
+// gfx950 instructions.
 //
 // Two DP cells per 32-bit lane register: the 16-bit halves are independent chains (v_pk_add_i16 clamp, v_pk_max_i16, v_pk_sub_u16 clamp --
 // the saturating arithmetic of the reference's SSE2 passes, libs/striped_smith_waterman/ssw.c:123-345, 371-546).  A lane's low half sits
@@ -103,6 +105,43 @@ __device__ __forceinline__ int wave_min(int v) {
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_xor(v, d); v = o < v ? o : v; }
     return v;
+}
+
+// workgroup barrier that orders LDS traffic only: the LDS words written before it have landed, outstanding global stores (a step's
+// direction bytes on their way to HBM) keep flying.  A __syncthreads() waits for those as well, an HBM round trip (~700 clocks) per step.
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// the n x n substitution matrix into LDS, by the whole workgroup
+template <typename M>
+__device__ __forceinline__ void stage_matrix(const int8_t* mat, int n, M* smat)
+{
+    for (int k = threadIdx.x; k < n * n; k += blockDim.x) smat[k] = mat[k];
+    __syncthreads();
+}
+
+// masked second-best column maximum, ssw.c:325-340 (8 bit, resumes at edge + 1) / 528-541 (16 bit: `word`, at edge); wave-parallel.
+// The position of a lane that found nothing never reaches the output: it loses every tie against a lane with bv > 0, and bv == 0 gives 0.
+__device__ inline void second_best(const uint16_t* colmax, int refLen, int end_ref, int maskLen, int word, int& score2, int& ref_end2)
+{
+    const int lane = threadIdx.x & 63;
+    int e1 = end_ref - maskLen; if (e1 < 0) e1 = 0;
+    int e2 = end_ref + maskLen; if (e2 > refLen) e2 = refLen;
+    e2 += word ? 0 : 1;
+    int bv = 0, bp = 0x7fffffff;
+    for (int i = lane; i < refLen; i += 64) {
+        if (i < e1 || i >= e2) {
+            const int v = colmax[i];
+            if (v > bv) { bv = v; bp = i; }
+        }
+    }
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int v2 = __shfl_xor(bv, d), p2 = __shfl_xor(bp, d);
+        const bool take = v2 > bv || (v2 == bv && p2 < bp);
+        bv = take ? v2 : bv; bp = take ? p2 : bp;
+    }
+    score2 = bv;
+    ref_end2 = bv > 0 ? bp : 0;
 }
 
 }  // namespace

@@ -227,30 +227,6 @@ __device__ ScanOut scan_pass(const ScanIn& in, const ScanLds& lds, const int gap
     return o;
 }
 
-// masked second-best column maximum, ssw.c:325-340 (8-bit pass); wave-parallel
-__device__ void second_best8(const uint16_t* colmax, int refLen, int end_ref, int maskLen, int& score2, int& ref_end2)
-{
-    const int lane = threadIdx.x & 63;
-    int e1 = end_ref - maskLen; if (e1 < 0) e1 = 0;
-    int e2 = end_ref + maskLen; if (e2 > refLen) e2 = refLen;
-    e2 += 1;
-    int bv = 0, bp = 0x7fffffff;
-    for (int i = lane; i < refLen; i += 64) {
-        if (i < e1 || i >= e2) {
-            const int v = colmax[i];
-            if (v > bv) { bv = v; bp = i; }
-        }
-    }
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int v2 = __shfl_xor(bv, d), p2 = __shfl_xor(bp, d);
-        const bool take = v2 > bv || (v2 == bv && p2 < bp);
-        bv = take ? v2 : bv; bp = take ? p2 : bp;
-    }
-    score2 = bv;
-    ref_end2 = bv > 0 ? bp : 0;
-}
-
 // everything after the forward pass: second best, reverse pass (begin coordinates), the result row
 template <bool GEQ>
 __device__ void scan_finish(const SswParams& p, const SswTask& task, const ScanOut& fw, const ScanLds& lds)
@@ -266,7 +242,7 @@ __device__ void scan_finish(const SswParams& p, const SswTask& task, const ScanO
     res.score1 = fw.max;
     if (fw.max == 0) { res.ref_end1 = -1; res.read_end1 = 0; }
     else { res.ref_end1 = fw.col; res.read_end1 = fw.row; }
-    if (task.mask_len >= 15 && colmax) { __syncthreads(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); second_best8(colmax, refLen, res.ref_end1, task.mask_len, res.score2, res.ref_end2); }
+    if (task.mask_len >= 15 && colmax) { __syncthreads(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); second_best(colmax, refLen, res.ref_end1, task.mask_len, 0, res.score2, res.ref_end2); }
     else { res.score2 = 0; res.ref_end2 = task.mask_len >= 15 ? 0 : -1; }
 
     // ---- reverse: begin coordinates (ssw.c:834-849) ---------------------------------------------------------------

@@ -382,30 +382,6 @@ __device__ bool scanw_align_tr(const SswParams& p, const int8_t* read, const int
     return true;
 }
 
-// masked second-best column maximum, ssw.c:325-340 (8 bit) / 528-541 (16 bit); wave-parallel
-__device__ void second_best_w(const uint16_t* colmax, int refLen, int end_ref, int maskLen, int word, int& score2, int& ref_end2)
-{
-    const int lane = threadIdx.x & 63;
-    int e1 = end_ref - maskLen; if (e1 < 0) e1 = 0;
-    int e2 = end_ref + maskLen; if (e2 > refLen) e2 = refLen;
-    e2 += word ? 0 : 1;
-    int bv = 0, bp = W_INF;
-    for (int i = lane; i < refLen; i += 64) {
-        if (i < e1 || i >= e2) {
-            const int v = colmax[i];
-            if (v > bv) { bv = v; bp = i; }
-        }
-    }
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int v2 = __shfl_xor(bv, d), p2 = __shfl_xor(bp, d);
-        const bool take = v2 > bv || (v2 == bv && p2 < bp);
-        bv = take ? v2 : bv; bp = take ? p2 : bp;
-    }
-    score2 = bv;
-    ref_end2 = bv > 0 ? bp : 0;
-}
-
 }  // namespace
 
 // bytes of HBM workspace of one K1w task (SswTask.dir_off into SswParams.dirs): boundary rows of a chunk + the two hand-over arrays
@@ -500,7 +476,7 @@ __device__ bool scanw_align(const SswParams& p, const int8_t* read, const int8_t
     res.score1 = fw.max;
     if (fw.max == 0) { res.ref_end1 = regime ? 0 : -1; res.read_end1 = 0; }
     else { res.ref_end1 = fw.col; res.read_end1 = fw.row; }
-    if (mask_len >= 15 && colmax) { __syncthreads(); __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent"); second_best_w(colmax, refLen, res.ref_end1, mask_len, regime, res.score2, res.ref_end2); }
+    if (mask_len >= 15 && colmax) { __syncthreads(); __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent"); second_best(colmax, refLen, res.ref_end1, mask_len, regime, res.score2, res.ref_end2); }
     else { res.score2 = 0; res.ref_end2 = mask_len >= 15 ? 0 : -1; }
 
     // ---- reverse: begin coordinates (ssw.c:834-849) ---------------------------------------------------------------

@@ -20,17 +20,46 @@
 //     is not reset (ssw.c:560,631-632).
 // One direction byte per cell: bits 0-2 = H code (1..5), bit 3 = E opened (code 3), bit 4 = F opened (code 5),
 // stored anti-diagonal-major so that a wave's stores are contiguous.
+//
+// One function (tb_antidiagonal) serves three kernels: ssw_traceback_kernel (DNA, int16 state), ssw_alpha_traceback_kernel (K1a's
+// matrices of 6..32 letters, int32 state) and ssw_w32_traceback_kernel (the DNA alignments the 16-bit forms hand over, int32 state).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <algorithm>
 #include "clh_device.h"
+#include "clh_device_ops.h"
 
 namespace clh {
 
-// DP state lives in dynamic LDS as int16 (scores <= 32767; E and F never drop below -gapO-gapE): 7 arrays of `ws`
-// rows, ws = row capacity of the launch's read-length class + 2.  While the band is narrow the arrays are a ring
-// indexed by row & (wsp-1); once the band is wider than the ring they are indexed by the row itself.
+// DP state lives in dynamic LDS: 7 arrays of `ws` rows, ws = row capacity of the launch's read-length class + 2.  While the
+// band is narrow the arrays are a ring indexed by row & (wsp-1); once the band is wider than the ring they are indexed by
+// the row itself.
+//
+// One function, three instantiations; what differs between them is known when a kernel is compiled:
+struct TbDna {       // ssw_traceback_kernel: DNA below the 16-bit passes' ceiling
+    typedef short state_t;      // H/E/F as int16 (scores <= 32767; E and F never drop below -gapO-gapE)
+    typedef int mat_t;          // the 5 x 5 matrix, widened
+    static constexpr bool kDna = true;          // reference bytes through ref_code: genome windows (case and N flags, reverse complement)
+    static constexpr bool kHandOver = true;     // what this state or this launch's LDS cannot hold goes on to TbDna32 (CLH_STATUS_NEED_W32)
+    static constexpr int kSelect = CLH_STATUS_NEED_BIG;      // the status bit that marks an alignment for a big launch
+};
+struct TbAlpha {     // ssw_alpha_traceback_kernel: K1a, matrices of 6..32 letters
+    typedef int state_t;        // int32: past the 16-bit pass's ceiling (score1 = 32767) the reference's int DP keeps counting
+    typedef int8_t mat_t;       // n x n
+    static constexpr bool kDna = false;         // references are packed codes, forward; a full pool means another round (CLH_STATUS_NEED_POOL)
+    static constexpr bool kHandOver = false;    // nothing behind it: the large launch reads sequences that do not fit LDS from global
+                                                // memory, and reports what exceeds it as CLH_STATUS_CIGAR_TRUNC
+    static constexpr int kSelect = CLH_STATUS_NEED_BIG | CLH_STATUS_NEED_POOL;      // (NEED_POOL: a round over the emptied pool; an
+                                                // alignment carries one of the two, the one its list was made from)
+};
+struct TbDna32 {     // ssw_w32_traceback_kernel: the DNA alignments TbDna handed over
+    typedef int state_t;
+    typedef int8_t mat_t;
+    static constexpr bool kDna = true;
+    static constexpr bool kHandOver = false;
+    static constexpr int kSelect = CLH_STATUS_NEED_W32;
+};
 
 struct TbPool {
     uint8_t* base;
@@ -40,16 +69,6 @@ struct TbPool {
     int* list_small; int* list_big;   // its list regions (task indices into the plan's task table)
     int task_base;              // first task of the class
 };
-
-__device__ __forceinline__ int wave_max(int v)
-{
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { int o = __shfl_xor(v, d); v = o > v ? o : v; }
-    return v;
-}
-
-// workgroup barrier that orders LDS traffic only (outstanding global stores keep flying)
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // first row of anti-diagonal a inside the band: ceil((a - w) / 2), not clamped
 __device__ __forceinline__ int ad_first_row(int a, int w) { int t = a - w; return t >= 0 ? (t + 1) >> 1 : -((-t) >> 1); }
@@ -70,24 +89,27 @@ __device__ __forceinline__ int ad_stride(int w, int readLen, int refLen)
 }
 
 // big = 0: every alignment of the class, with a small LDS window (high occupancy); alignments whose band outgrows it are
-// marked CLH_STATUS_NEED_BIG and listed.  big = 1: the listed ones, with a window sized for the read-length class.
-__device__ void tb_antidiagonal(const SswParams& p, const TbPool& pool, const int ws, const int wsp, const int big, const int seq_cap, const int task_index)
+// marked CLH_STATUS_NEED_BIG and listed.  big = 1: the marked ones (T::kSelect), with a window sized for the read-length class.
+// smat: the substitution matrix in LDS (stage_matrix).
+template <typename T>
+__device__ void tb_antidiagonal(const SswParams& p, const typename T::mat_t* smat, const TbPool& pool, const int ws, const int wsp, const int big,
+                                const int seq_cap, const int task_index)
 {
-    extern __shared__ __attribute__((aligned(16))) short tb_lds[];
-    short* const H0 = tb_lds;                 // H[3][ws]
-    short* const E0 = tb_lds + 3 * ws;        // E[2][ws]
-    short* const F0 = tb_lds + 5 * ws;        // F[2][ws]
-    int8_t* const sseq = (int8_t*)(tb_lds + 7 * ws);   // read then reference codes of the aligned region, if they fit
+    typedef typename T::state_t state_t;
+    // where the large launch cannot go on either: the int32 form takes over, or the CIGAR is reported as not made
+    constexpr int kOver = T::kHandOver ? CLH_STATUS_NEED_W32 : CLH_STATUS_CIGAR_TRUNC;
+    extern __shared__ __attribute__((aligned(16))) uint8_t tb_lds[];
+    state_t* const H0 = (state_t*)tb_lds;     // H[3][ws]
+    state_t* const E0 = H0 + 3 * ws;          // E[2][ws]
+    state_t* const F0 = H0 + 5 * ws;          // F[2][ws]
+    int8_t* const sseq = (int8_t*)(H0 + 7 * ws);       // read then reference codes of the aligned region, if they fit
     __shared__ uint8_t stage[64 * 66];
-    __shared__ int smat[32];
     __shared__ unsigned long long hist_at[24];   // every band iteration keeps its direction bytes (see hist_lookup)
     __shared__ int hist_w[24];
     __shared__ unsigned long long s_at;
     __shared__ int s_max[16];
     const int lane = threadIdx.x;            // "lane" = thread of the workgroup; thread 0 does the scalar stores
     const int nt = blockDim.x;
-    if (lane < 25) smat[lane] = p.mat[lane];
-    __syncthreads();
     const SswTask task = p.tasks[task_index];
     if (task.out_index >= p.n_real) return;            // a window slice of an anti-diagonal class: scratch row, no CIGAR
     SswResult res = p.results[task.out_index];
@@ -99,13 +121,14 @@ __device__ void tb_antidiagonal(const SswParams& p, const TbPool& pool, const in
     uint32_t* cig = p.cigars + task.cigar_off;
     int* cig_len = p.cigar_len + task.out_index;
     if (big) {
-        if (!(res.status & CLH_STATUS_NEED_BIG)) return;
-        res.status &= ~CLH_STATUS_NEED_BIG;
+        if (!(res.status & T::kSelect)) return;
+        res.status &= ~T::kSelect;
         __syncthreads();        // every wave has read the row (and found the bit) before it is cleared in memory
         if (lane == 0) p.results[task.out_index].status = res.status;
     }
 
-    const bool no_cigar = (res.status & CLH_STATUS_OVERFLOW8) || (7 & p.flag) == 0 ||
+    // (CLH_STATUS_BAD_CODE: K1a's score kernels set it, no other)
+    const bool no_cigar = (res.status & (CLH_STATUS_OVERFLOW8 | CLH_STATUS_BAD_CODE)) || (7 & p.flag) == 0 ||
                           ((2 & p.flag) != 0 && res.score1 < p.filters) ||
                           ((4 & p.flag) != 0 && (res.ref_end1 - res.ref_begin1 > p.filterd || res.read_end1 - res.read_begin1 > p.filterd));
     if (no_cigar) {
@@ -116,11 +139,11 @@ __device__ void tb_antidiagonal(const SswParams& p, const TbPool& pool, const in
         if (lane == 0) { cig[0] = (1u << 4); *cig_len = 1; }
         return;
     }
-    if (res.score1 >= 32767) {   // saturated by the 16-bit pass: the reference's int DP counts past what this kernel's state holds
-        if (lane == 0) { *cig_len = 0; p.results[task.out_index].status = res.status | CLH_STATUS_NEED_W32; }
+    if (sizeof(state_t) == 2 && res.score1 >= 32767) {   // saturated by the 16-bit pass: the reference's int DP counts past what int16 state holds
+        if (lane == 0) { *cig_len = 0; p.results[task.out_index].status = res.status | kOver; }
         return;
     }
-    const int rdir = task.ref_rc ? -1 : 1;
+    const int rdir = task.ref_rc ? -1 : 1, rc = task.ref_rc;
     const int8_t* ref = p.refs + task.ref_off + (int64_t)res.ref_begin1 * rdir;
     const int8_t* read = p.reads + task.read_off + res.read_begin1;
     const int refLen = res.ref_end1 - res.ref_begin1 + 1, readLen = res.read_end1 - res.read_begin1 + 1;
@@ -128,18 +151,23 @@ __device__ void tb_antidiagonal(const SswParams& p, const TbPool& pool, const in
     // the DP touches read[i] and ref[j] once per cell: both are staged in LDS.  A vector-memory LOAD inside the loop
     // would force s_waitcnt vmcnt(0), which also waits for the previous step's direction store (an HBM round trip per
     // anti-diagonal); with LDS-only reads the stores are fire-and-forget.
-    if (readLen + refLen > seq_cap) {   // does not fit this launch's LDS: retry in the large configuration, or report the capacity limit
+    const bool staged = readLen + refLen <= seq_cap;
+    if (!staged && (big != 1 || T::kHandOver)) {   // does not fit this launch's LDS: retry in the large configuration, or hand over
         if (lane == 0) {
-            *cig_len = 0; p.results[task.out_index].status = res.status | (big == 1 ? CLH_STATUS_NEED_W32 : CLH_STATUS_NEED_BIG);
+            *cig_len = 0; p.results[task.out_index].status = res.status | (big == 1 ? kOver : CLH_STATUS_NEED_BIG);
             if (big != 1) pool.list_big[atomicAdd(pool.n_big, 1)] = task_index;
         }
         return;
     }
-    for (int k = lane; k < readLen; k += nt) sseq[k] = read[k];
-    for (int k = lane; k < refLen; k += nt) sseq[readLen + k] = (int8_t)ref_code((int)ref[(int64_t)k * rdir], task.ref_rc);
+    if (staged) {
+        for (int k = lane; k < readLen; k += nt) sseq[k] = read[k];
+        for (int k = lane; k < refLen; k += nt) sseq[readLen + k] = T::kDna ? (int8_t)ref_code((int)ref[(int64_t)k * rdir], rc) : ref[k];
+    }
     __syncthreads();
-    const int8_t* const sread = sseq;
-    const int8_t* const sref = sseq + readLen;
+    // (!staged: the large launch of a form with nothing behind it, which pays the global reads)
+    const int8_t* const sread = staged ? sseq : read;
+    const int8_t* const sref = staged ? sseq + readLen : ref;
+    auto ref_at = [&](int j) -> int { return (staged || !T::kDna) ? (int)sref[j] : ref_code((int)ref[(int64_t)j * rdir], rc); };
     int w = refLen > readLen ? refLen - readLen : readLen - refLen;
     w += 1;
     const int nAD = readLen + refLen - 1;
@@ -161,7 +189,7 @@ __device__ void tb_antidiagonal(const SswParams& p, const TbPool& pool, const in
             continue;
         }
         const bool ring = w + 3 <= wsp;   // the active rows of an anti-diagonal span <= w+1 rows
-        if (!ring && readLen + 1 > ws) { status = big == 1 ? CLH_STATUS_NEED_W32 : CLH_STATUS_NEED_BIG; break; }
+        if (!ring && readLen + 1 > ws) { status = big == 1 ? kOver : CLH_STATUS_NEED_BIG; break; }
         const int imask = ring ? wsp - 1 : -1;
         unsigned long long need = ((unsigned long long)nAD * (unsigned long long)stride_w + 63ull) & ~63ull;
         unsigned long long at = 0;
@@ -169,7 +197,8 @@ __device__ void tb_antidiagonal(const SswParams& p, const TbPool& pool, const in
         if (lane == 0) s_at = atomicAdd(pool.head, need);
         __syncthreads();
         at = (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(s_at & 0xffffffffull)) | ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(s_at >> 32)) << 32);
-        if (at + need > pool.size) { status = CLH_STATUS_CIGAR_TRUNC; break; }
+        // the pool ran out: K1a's alignments go round again over the emptied pool (clh_ssw_fetch), the DNA ones report it
+        if (at + need > pool.size) { status = T::kDna ? CLH_STATUS_CIGAR_TRUNC : CLH_STATUS_NEED_POOL; break; }
         dir = pool.base + at;
         last_at = at;
         if (lane == 0 && niter < 24) { hist_at[niter] = at; hist_w[niter] = w; }
@@ -203,11 +232,11 @@ __device__ void tb_antidiagonal(const SswParams& p, const TbPool& pool, const in
                     const int df = t1 > t2 ? 5 : 4;
                     const int e1v = e > 0 ? e : 0, f1v = f > 0 ? f : 0;
                     t1 = e1v > f1v ? e1v : f1v;
-                    t2 = hd + smat[(int)sref[j] * n + (int)sread[i]];
+                    t2 = hd + smat[ref_at(j) * n + (int)sread[i]];
                     const int h = t1 > t2 ? t1 : t2;
                     const int dh = t1 <= t2 ? 1 : (e1v > f1v ? de : df);
                     itmax = h > itmax ? h : itmax;
-                    H0[cur * ws + m] = (short)h; E0[e0 * ws + m] = (short)e; F0[e0 * ws + m] = (short)f;
+                    H0[cur * ws + m] = (state_t)h; E0[e0 * ws + m] = (state_t)e; F0[e0 * ws + m] = (state_t)f;
                     dir[(size_t)a * stride_w + (i - ilo)] = (uint8_t)(dh | (de == 3 ? 8 : 0) | (df == 5 ? 16 : 0));
                 }
             }
@@ -231,7 +260,9 @@ __device__ void tb_antidiagonal(const SswParams& p, const TbPool& pool, const in
         return;
     }
     w /= 2;
-    __threadfence_block();
+    // the walk reads direction bytes other waves stored: the stores must have reached L2 and this CU's L1 must not serve old lines
+    // (a workgroup-scope fence does not wait for them: the last anti-diagonals' bytes could still be in flight)
+    __threadfence();
     __syncthreads();
 
     // ---- walk back from the bottom-right corner (ssw.c:636-696); direction bytes staged 64 anti-diagonals at a time.
@@ -326,15 +357,61 @@ __device__ void tb_antidiagonal(const SswParams& p, const TbPool& pool, const in
 
 // big = 0: workgroup k takes task k.  Otherwise the workgroups share the list of handed-over alignments (a few of many
 // thousand: a workgroup per task would spend the launch on workgroups that only find out they have nothing to do).
-__global__ void __launch_bounds__(1024) ssw_traceback_kernel(const SswParams p, TbPool pool, int ws, int wsp, int big, int seq_cap)
+template <typename T>
+__device__ __forceinline__ void tb_class(const SswParams& p, const typename T::mat_t* smat, const TbPool& pool, int ws, int wsp, int big, int seq_cap)
 {
-    if (big == 0) { tb_antidiagonal(p, pool, ws, wsp, big, seq_cap, pool.task_base + (int)blockIdx.x); return; }
+    if (big == 0) { tb_antidiagonal<T>(p, smat, pool, ws, wsp, big, seq_cap, pool.task_base + (int)blockIdx.x); return; }
     const int n = __builtin_amdgcn_readfirstlane(*pool.n_big);
     for (int k = (int)blockIdx.x; k < n; k += (int)gridDim.x) {
-        tb_antidiagonal(p, pool, ws, wsp, big, seq_cap, __builtin_amdgcn_readfirstlane(pool.list_big[k]));
+        tb_antidiagonal<T>(p, smat, pool, ws, wsp, big, seq_cap, __builtin_amdgcn_readfirstlane(pool.list_big[k]));
         __syncthreads();
     }
 }
+
+__global__ void __launch_bounds__(1024) ssw_traceback_kernel(const SswParams p, TbPool pool, int ws, int wsp, int big, int seq_cap)
+{
+    __shared__ int smat[32];
+    stage_matrix(p.mat, p.n, smat);
+    tb_class<TbDna>(p, smat, pool, ws, wsp, big, seq_cap);
+}
+
+// K1a: the matrix is the plan's device copy
+__global__ void __launch_bounds__(1024) ssw_alpha_traceback_kernel(const SswParams p, const int8_t* __restrict__ mat, TbPool pool, int ws, int wsp,
+                                                                   int big, int seq_cap)
+{
+    __shared__ int8_t smat[1024];
+    stage_matrix(mat, p.n, smat);
+    tb_class<TbAlpha>(p, smat, pool, ws, wsp, big, seq_cap);
+}
+
+// The DNA alignments the 16-bit traceback forms marked CLH_STATUS_NEED_W32 among tasks [task_base, task_base + ntasks): the workgroups
+// split the range, each scans its part a block at a time (the marked ones are few) and runs the int32 traceback on what it finds.
+__global__ void __launch_bounds__(1024) ssw_w32_traceback_kernel(const SswParams p, TbPool pool, int ws, int wsp, int seq_cap, int ntasks)
+{
+    __shared__ int8_t smat[1024];
+    __shared__ int s_n, s_list[1024];
+    stage_matrix(p.mat, p.n, smat);
+    const int per = (ntasks + (int)gridDim.x - 1) / (int)gridDim.x;
+    const int k0 = (int)blockIdx.x * per, k1 = min(ntasks, k0 + per);
+    for (int b = k0; b < k1; b += (int)blockDim.x) {
+        if (threadIdx.x == 0) s_n = 0;
+        __syncthreads();
+        const int k = b + (int)threadIdx.x;
+        if (k < k1) {
+            const SswTask& t = p.tasks[pool.task_base + k];
+            if (t.out_index < p.n_real && (p.results[t.out_index].status & CLH_STATUS_NEED_W32)) s_list[atomicAdd(&s_n, 1)] = pool.task_base + k;
+        }
+        __syncthreads();
+        const int nf = __builtin_amdgcn_readfirstlane(s_n);
+        for (int q = 0; q < nf; ++q) {
+            tb_antidiagonal<TbDna32>(p, smat, pool, ws, wsp, 1, seq_cap, __builtin_amdgcn_readfirstlane(s_list[q]));
+            __syncthreads();
+        }
+    }
+}
+
+// ring size of a window: the largest power of two in ws rows
+static int tb_ring(int ws) { int wsp = 1; while (wsp * 2 <= ws) wsp *= 2; return wsp; }
 
 // rv = read-length class of every task in the launch (rows <= 128*rv)
 hipError_t launch_traceback_pool(int rv, const SswParams& p, int task_base, int ntasks, int n_total, int seg, uint8_t* pool_base, unsigned long long* pool_head,
@@ -344,8 +421,6 @@ hipError_t launch_traceback_pool(int rv, const SswParams& p, int task_base, int 
     tb_lists_of(pool_head, n_total, seg, task_base, &pool.n_small, &pool.n_big, &pool.list_small, &pool.list_big);
     // rv == 0: the small-window first attempt (any read length)
     const int ws = rv > 0 ? 128 * rv + 2 : 514;
-    int wsp = 1;
-    while (wsp * 2 <= ws) wsp *= 2;
     const int seq_cap = rv > 0 ? 128 * rv * 3 + 64 : 6144;
     const size_t lds = (size_t)7 * ws * sizeof(short) + (size_t)seq_cap;
     static int nt_small = 0, nt_big = 0;
@@ -355,7 +430,59 @@ hipError_t launch_traceback_pool(int rv, const SswParams& p, int task_base, int 
     }
     const int big = rv > 0 ? 1 : 0;
     const int grid = big == 0 ? ntasks : std::min(ntasks, 512);
-    hipLaunchKernelGGL(ssw_traceback_kernel, dim3(grid), dim3(rv > 0 ? nt_big : nt_small), lds, stream, p, pool, ws, wsp, big, seq_cap);
+    hipLaunchKernelGGL(ssw_traceback_kernel, dim3(grid), dim3(rv > 0 ? nt_big : nt_small), lds, stream, p, pool, ws, tb_ring(ws), big, seq_cap);
+    return hipGetLastError();
+}
+
+hipError_t launch_traceback_w32(const SswParams& p, int task_base, int ntasks, uint8_t* pool_base, unsigned long long* pool_head,
+                                unsigned long long pool_size, hipStream_t stream)
+{
+    if (ntasks <= 0) return hipSuccess;
+    TbPool pool = {}; pool.base = pool_base; pool.head = pool_head; pool.size = pool_size; pool.task_base = task_base;   // (a big = 1 pass lists nothing)
+    const int ws = 5122;                                      // H/E/F (int32) of 5120 rows, the rest of 146 KiB for the sequences
+    const int seq_cap = 149504 - 7 * ws * (int)sizeof(int);  // (4 KiB less than K1a's large launch: the kernel's list of marked tasks)
+    const size_t lds = (size_t)7 * ws * sizeof(int) + (size_t)seq_cap;
+    // a few workgroups (each holds a CU's LDS): the marked alignments are rare, and most launches only scan
+    const int grid = std::min((ntasks + 255) / 256, 64);
+    hipLaunchKernelGGL(ssw_w32_traceback_kernel, dim3(grid), dim3(1024), lds, stream, p, pool, ws, tb_ring(ws), seq_cap, ntasks);
+    return hipGetLastError();
+}
+
+// K1a: the small-window attempt for every alignment of the class, then the listed ones with a window for rows <= lmax
+hipError_t launch_ssw_alpha_traceback(const SswParams& p, const int8_t* d_mat, int task_base, int ntasks, int n_total, int seg, int lmax,
+                                      uint8_t* pool_base, unsigned long long* pool_head, unsigned long long pool_size, hipStream_t stream)
+{
+    if (ntasks <= 0) return hipSuccess;
+    TbPool pool; pool.base = pool_base; pool.head = pool_head; pool.size = pool_size; pool.task_base = task_base;
+    tb_lists_of(pool_head, n_total, seg, task_base, &pool.n_small, &pool.n_big, &pool.list_small, &pool.list_big);
+    for (int big = 0; big < 2; ++big) {
+        // big: H/E/F (int32) of the class's longest read (+2), the rest of 150 KiB for the sequences
+        const int ws = big ? std::min(lmax + 2, 5122) : 514;
+        const int seq_cap = big ? 153600 - 7 * ws * (int)sizeof(int) : 6144;
+        const size_t lds = (size_t)7 * ws * sizeof(int) + (size_t)seq_cap;
+        const int grid = big == 0 ? ntasks : std::min(ntasks, 512);
+        hipLaunchKernelGGL(ssw_alpha_traceback_kernel, dim3(grid), dim3(big ? 1024 : 128), lds, stream, p, d_mat, pool, ws, tb_ring(ws), big, seq_cap);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// K1a's alignments that found the pool full (CLH_STATUS_NEED_POOL), over the emptied pool: the large configuration whatever the class (a
+// window sized for 5 120 rows gives every alignment the CIGAR its class's own would); one_by_one: a single workgroup, which takes the
+// listed alignments in list order
+hipError_t launch_ssw_alpha_traceback_retry(const SswParams& p, const int8_t* d_mat, int* d_list, int nlist, bool one_by_one, uint8_t* pool_base,
+                                            unsigned long long* pool_head, unsigned long long pool_size, hipStream_t stream)
+{
+    if (nlist <= 0) return hipSuccess;
+    TbPool pool = {}; pool.base = pool_base; pool.head = pool_head; pool.size = pool_size;
+    pool.n_big = d_list; pool.list_big = d_list + 1;
+    const int ws = 5122;
+    const int seq_cap = 153600 - 7 * ws * (int)sizeof(int);
+    const size_t lds = (size_t)7 * ws * sizeof(int) + (size_t)seq_cap;
+    hipError_t e = hipMemsetAsync(pool_head, 0, sizeof(unsigned long long), stream);      // the bump pointer only
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(ssw_alpha_traceback_kernel, dim3(one_by_one ? 1 : std::min(nlist, 512)), dim3(1024), lds, stream, p, d_mat, pool, ws, tb_ring(ws), 1, seq_cap);
     return hipGetLastError();
 }
 

@@ -64,9 +64,6 @@ struct TbX {
     int cmd;                // the walk (wave 0) asks every wave for the plane of an earlier iteration
     int lz[8][8];           // the planes of the narrow launch's iterations, one per wave (TbPlane as 8 ints, dir as an offset)
 };
-// the rows' barrier: the LDS words above must have landed; the row's direction bytes on their way to HBM need not (a
-// __syncthreads() waits for them as well, ~700 clocks per row)
-__device__ __forceinline__ void tb_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // One band iteration with band half-width w (2w+1 <= 128*CP*NW).  DIRS: direction nibbles of every cell, row-major:
 // row i = 64*CP bytes at dir + i*64*CP, cell at offset o' = j - i + w + (128*CP - 1 - 2w) in nibble o' of the row.
@@ -180,7 +177,7 @@ __device__ int tb_rows_pass(const TbIn& in, const int w, uint8_t* dir, TbX* xs =
                 int fill = -gE - K;                                           // the cell left of offset 0: H = F = 0
                 if constexpr (NW > 1) {                                       // the waves below: their totals, same frame
                     if (lane == 63) xs->T[par][wave] = inc;
-                    tb_barrier();
+                    lds_barrier();
 #pragma unroll
                     for (int v = 0; v + 1 < NW; ++v) { const int tv = xs->T[par][v]; fill = (v < wave && tv > fill) ? tv : fill; }
                 }
@@ -206,7 +203,7 @@ __device__ int tb_rows_pass(const TbIn& in, const int w, uint8_t* dir, TbX* xs =
                 if constexpr (COLS) { if (lane == 63) xs->he[par][wave] = hn[CP - 1] >> 16; }
                 else if (lane == 0) xs->he[par][wave] = (hn[0] & 0xffffu) | (bfi_keep(inv[0], 0u, e[0]) << 16);
                 if (DIRS && lane == 63) xs->dd[par][wave] = (int)(dd[CP - 1] >> 16);
-                tb_barrier();
+                lds_barrier();
             }
             if (DIRS) {
                 int ddb = -(gO - gE);

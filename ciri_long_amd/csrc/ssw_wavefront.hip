@@ -21,31 +21,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "clh_device.h"
+#include "clh_device_ops.h"
 
 namespace clh {
-
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ uint32_t pk_adds(uint32_t a, uint32_t b) {   // v_pk_add_i16 clamp
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_add_sat(__builtin_bit_cast(s16x2, a), __builtin_bit_cast(s16x2, b)));
-}
-__device__ __forceinline__ uint32_t pk_max(uint32_t a, uint32_t b) {    // v_pk_max_i16
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s16x2, a), __builtin_bit_cast(s16x2, b)));
-}
-__device__ __forceinline__ uint32_t pk_subus(uint32_t a, uint32_t b) {  // v_pk_sub_u16 clamp
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
-}
-__device__ __forceinline__ uint32_t dup16(int v) { return (uint32_t)(v & 0xffff) * 0x10001u; }
-// value of the previous lane (lane 0 receives `lane0`)
-__device__ __forceinline__ uint32_t from_prev_lane(uint32_t v, uint32_t lane0) {
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)lane0, (int)v, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
-}
-// hand a packed (lo,hi) value to the next virtual lane: new lo = previous lane's hi, new hi = own lo
-__device__ __forceinline__ uint32_t hand_down(uint32_t v, uint32_t lane0_lo) {
-    uint32_t x = from_prev_lane(v, lane0_lo << 16);
-    return __builtin_amdgcn_alignbit(v, x, 16);
-}
 
 // the same with 0 entering lane 0's low half: bound_ctrl supplies the zero, no v_mov to seed the destination
 __device__ __forceinline__ uint32_t hand_down0(uint32_t v) {
@@ -382,30 +360,6 @@ __device__ PassOut run_pass(const PassIn& in, uint32_t* __restrict__ lds_prof, c
     }
     if (best.term_col >= 0 && exceeded) { best.max = -1; best.col = -1; best.row = 0; }
     return best;
-}
-
-// masked second-best column maximum, ssw.c:325-340 (8 bit) / 528-541 (16 bit); wave-parallel
-__device__ void second_best(const uint16_t* colmax, int refLen, int end_ref, int maskLen, int word, int& score2, int& ref_end2)
-{
-    const int lane = threadIdx.x & 63;
-    int e1 = end_ref - maskLen; if (e1 < 0) e1 = 0;
-    int e2 = end_ref + maskLen; if (e2 > refLen) e2 = refLen;
-    e2 += word ? 0 : 1;
-    int bv = 0, bp = 0x7fffffff;
-    for (int i = lane; i < refLen; i += 64) {
-        if (i < e1 || i >= e2) {
-            const int v = colmax[i];
-            if (v > bv) { bv = v; bp = i; }
-        }
-    }
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int v2 = __shfl_xor(bv, d), p2 = __shfl_xor(bp, d);
-        const bool take = v2 > bv || (v2 == bv && p2 < bp);
-        bv = take ? v2 : bv; bp = take ? p2 : bp;
-    }
-    score2 = bv;
-    ref_end2 = bv > 0 ? bp : 0;
 }
 
 // half-rate packed ops keep a SIMD busy with two waves; asking for more only causes spills

@@ -20,7 +20,7 @@ LETTERS = 'ABCDEFGHIJKLMNOPQRSTUVWXYZabcdef'
 # the read-length buckets of K1a (csrc/clh_device.h kAlphaRows) and reads around each boundary
 ALPHA_ROWS = (256, 1024, 4096, 8192)
 BUCKET_LENGTHS = (1, 255, 256, 257, 1023, 1024, 1025, 4095, 4096, 4097, 8191, 8192, 8193, 12000, 20000)
-# the traceback's windows (ssw_alpha.hip launch_ssw_alpha_traceback): the small attempt has 514 rows of state, a ring of 512 when
+# the traceback's windows (ssw_traceback.hip launch_ssw_alpha_traceback): the small attempt has 514 rows of state, a ring of 512 when
 # w + 3 <= 512, sequences in LDS up to 6 144 bytes; the big launch for a class whose longest read is >= 5 120 rows has 5 122 rows, a ring
 # of 4 096 and 153 600 - 28 * 5 122 = 10 184 bytes of sequence
 SMALL_WS, SMALL_RING, SMALL_SEQ = 514, 512, 6144
