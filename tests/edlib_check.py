@@ -138,6 +138,94 @@ def align(query, target, mode='NW', task='distance', k=-1, additionalEqualities=
     return {'editDistance': best, 'alphabetLength': alpha, 'locations': locs, 'cigar': cigar}
 
 
+def bounded(res, k):
+    """align()'s k rule applied to a free (k = -1) result: a best above k leaves the empty result"""
+    if k >= 0 and res['editDistance'] > k:
+        return {'editDistance': -1, 'alphabetLength': res['alphabetLength'], 'locations': [], 'cigar': None}
+    return res
+
+
+def suffix_distances(q, t, lo, e, eqm):
+    """NW distance of q against target[s..e] for every s in lo .. e + 1 (at index s - lo), from one programme over the reversed
+    strings.  This is the reverse pass's own idea (hw_start), so check_locations uses it as a cross-check only."""
+    return last_row(q[::-1], t[lo:e + 1][::-1], 'NW', eqm)[::-1]
+
+
+def nw_distance(q, t, eqm, w=None):
+    """forward NW distance of q against t.  With a band w: the distance when it is <= w, else w + 1 -- an alignment of cost
+    <= w never leaves the diagonals |j - i| <= w, and cells outside them count as unreachable (which can only raise a value)"""
+    m, L = len(q), len(t)
+    if w is None or w >= max(m, L):
+        return int(last_row(q, t, 'NW', eqm)[-1])
+    if abs(L - m) > w:
+        return w + 1
+    INF = 1 << 40
+    row = np.full(L + 1, INF, dtype=np.int64)
+    row[:min(L, w) + 1] = np.arange(min(L, w) + 1)
+    for i in range(1, m + 1):
+        lo, hi = max(0, i - w), min(L, i + w)          # the columns of row i inside the band
+        T = row[lo:hi + 1] + 1
+        if lo == 0:
+            T[0] = i
+            if hi >= 1:
+                T[1:] = np.minimum(T[1:], row[0:hi] + ~eqm[q[i - 1]][t[0:hi]])
+        else:
+            T = np.minimum(T, row[lo - 1:hi] + ~eqm[q[i - 1]][t[lo - 1:hi]])
+            row[lo - 1] = INF                          # column lo - 1 has left the band
+        ar = np.arange(hi - lo + 1)
+        row[lo:hi + 1] = np.minimum.accumulate(T - ar) + ar
+    return int(min(row[L], w + 1))
+
+
+def check_locations(res, query, target, mode, additionalEqualities=None, seed=0):
+    """What a location is, stated forwards and without the reverse pass.  For every location (s, e) with a start, the NW distance
+    of the query against target[s..e] -- one forward programme on that slice -- is editDistance.  For HW, no s' < s has that
+    property (s is the smallest start, the longest alignment): one forward programme per candidate s', with two facts that spare
+    programmes and use no reversed string.  A slice of more than m + editDistance letters costs more than editDistance, so the
+    search starts at e + 1 - m - editDistance.  One target letter more or fewer changes an NW distance by at most 1, so a
+    candidate s' whose slice costs editDistance + g rules out every s'' with |s'' - s'| < g, and the search steps down by g; the
+    candidate's programme is banded (nw_distance), which caps g.  Pairs of m * n <= 2**12 are searched at every s' from s - 1
+    down to 0, unbanded, without either fact.  The smallest-start half is applied to every location when m * n <= 2**22, and to
+    the first, the last and two seeded others above that.  Last, as a cross-check only, the one-programme reversed form
+    (suffix_distances) must agree.  -> the number of locations proved in full"""
+    import random
+    q, t = _arr(query), _arr(target)
+    eqm = eq_matrix(additionalEqualities)
+    d, locs = res['editDistance'], [(s, e) for s, e in res['locations'] if s is not None]
+    if d < 0 or not locs:
+        return 0
+    m, n = len(q), len(t)
+    full = set(range(len(locs)))
+    if mode == 'HW' and m * n > 2 ** 22 and len(locs) > 4:
+        full = {0, len(locs) - 1} | set(random.Random(seed).sample(range(1, len(locs) - 1), 2))
+    proved = 0
+    for x, (s, e) in enumerate(locs):
+        assert 0 <= s <= e + 1 <= n, (s, e)
+        assert nw_distance(q, t[s:e + 1], eqm) == d, (s, e, d)
+        if mode != 'HW':
+            assert s == 0
+            proved += 1
+            continue
+        if x not in full:
+            continue
+        if m * n <= 2 ** 12:
+            for s2 in range(s):
+                assert nw_distance(q, t[s2:e + 1], eqm) != d, (s, e, 'a smaller start has the same distance', s2)
+        else:
+            lo, s2, w = max(0, e + 1 - m - d), s - 1, d + 64
+            assert lo <= s, (s, e, 'a slice of more than m + editDistance letters')
+            while s2 >= lo:
+                g = nw_distance(q, t[s2:e + 1], eqm, w) - d
+                assert g != 0, (s, e, 'a smaller start has the same distance', s2)
+                assert g > 0, (s, e, s2, 'a slice below the best distance')
+                s2 -= g
+        lo = max(0, e + 1 - m - d)
+        dist = suffix_distances(q, t, lo, e, eqm)
+        assert dist[s - lo] == d and not (dist[:s - lo] == d).any(), (s, e, 'the reversed programme disagrees')
+        proved += 1
+    return proved
+
+
 def check_invariants(res, query, target, mode, additionalEqualities=None):
     """the CIGAR costs editDistance and consumes exactly the query and target[start..end]; ends are ascending and allowed"""
     q, t = _arr(query), _arr(target)

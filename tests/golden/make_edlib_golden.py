@@ -8,6 +8,9 @@ locations and alphabetLength are uniquely defined and are held to the plain dyna
 HW starts and CIGARs follow tie rules, and their parity with edlib is UNPINNED until this file exists.  What it records:
 for 600 seeded pairs (DNA, DNA+N, 20 letters; queries of 1..300 letters in targets holding a mutated copy, tandem repeats
 or homopolymers; a few empty sides) and every mode x task, edlib.align's dict.  Inputs are stored (they are small).
+Under "edges" it records, call by call, the batches of tests/edlib_edges.py all_cases() (lane-group classes, passes, reverse
+launches, equalities over eight planes, ...; inputs are named by set and index, not stored -- the sets are seeded).  `--no-edges`
+leaves them out; a stub run leaves them out unless `--edges` asks for them (the stand-in would spend minutes on them).
 tests/test_edlib_golden.py compares the file with the checker and, with `-m gpu`, with the kernels.
 
 `--stub DIR` puts DIR in front of sys.path first: a directory holding a stand-in `edlib.py`.  That is how the CPU suite dry-runs
@@ -64,8 +67,22 @@ def cases(seed=2026, count=600):
     return out
 
 
+def edge_calls():
+    """-> (set name, batch index, pair index, query, target, mode, task, k, equalities as edlib takes them) for every pair of every
+    batch of tests/edlib_edges.py all_cases(), the bounded calls of its k set with their k"""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import edlib_edges
+    for name, batches in edlib_edges.all_cases().items():
+        for bi, b in enumerate(batches):
+            eq = [(bytes([x]).decode('latin-1'), bytes([y]).decode('latin-1')) for x, y in b.equalities] if b.equalities else None
+            for pi, (q, t) in enumerate(zip(b.queries, b.targets)):
+                yield name, bi, pi, q, t, b.mode, b.task, b.k, eq
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
+    ap.add_argument('--edges', action='store_true', help='record the edge sets in a stub run too')
+    ap.add_argument('--no-edges', action='store_true', help='leave the edge sets of tests/edlib_edges.py out')
     ap.add_argument('--stub', help='directory with a stand-in edlib.py (dry run; the file is marked as a stub)')
     ap.add_argument('--out', default=OUT)
     ap.add_argument('--count', type=int, default=600)
@@ -87,7 +104,13 @@ def main(argv=None):
                 r['%s/%s' % (mode, task)] = {'editDistance': d['editDistance'], 'alphabetLength': d['alphabetLength'],
                                              'locations': [list(x) for x in d['locations']], 'cigar': d.get('cigar')}
         recs.append(r)
-    doc = {'stub': bool(a.stub), 'edlib_version': getattr(edlib, '__version__', 'unknown'), 'cases': recs}
+    edges = []
+    if a.edges or not (a.stub or a.no_edges):
+        for name, bi, pi, q, t, mode, task, k, eq in edge_calls():
+            d = edlib.align(q, t, mode=mode, task=task, k=k, additionalEqualities=eq)
+            edges.append({'set': name, 'batch': bi, 'pair': pi, 'mode': mode, 'task': task, 'k': k, 'editDistance': d['editDistance'],
+                          'alphabetLength': d['alphabetLength'], 'locations': [list(x) for x in d['locations']], 'cigar': d.get('cigar')})
+    doc = {'stub': bool(a.stub), 'edlib_version': getattr(edlib, '__version__', 'unknown'), 'cases': recs, 'edges': edges}
     with gzip.open(a.out, 'wt') as f:
         json.dump(doc, f)
     print('wrote %d cases to %s' % (len(recs), a.out))
