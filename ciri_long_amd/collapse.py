@@ -3,17 +3,18 @@
 The reference constructs one `Aligner` per alignment and calls python-Levenshtein/edlib per pair
 (CIRI_long/collapse.py:156-173, 210-215, 251-265, 373-387, 458-506, 760-774).  The functions here keep the reference's
 names, arguments and return values, but hand every group of independent alignments / distances to the GPU as ONE batch
-(K1/K1b through `ssw_wrap.align_pairs` / `Aligner.align_batch`, K4 through `utils.distance_batch`, K3 through
-`spoa.poa`).  Scoring of this stage is (10, 4, 8, 2).  Clustering itself (scipy linkage) and everything around these call
+(K1/K1b through `ssw_wrap.align_pairs` / `Aligner.align_batch`, K4 through `utils.distance_batch` and, for the matrices
+of whole lists, `utils.pairwise_distance_groups`, K3 through `spoa.poa`).  Scoring of this stage is (10, 4, 8, 2).  Clustering itself (scipy linkage) and everything around these call
 sites (annotation look-ups, splice signals, max-flow over exons, output tables) is unchanged host code of the reference
 and is not restated here.
 """
 import logging
+import os
 from operator import itemgetter
 
 import numpy as np
 
-from . import env
+from . import env, utils
 from .align import find_alignment_pos
 from .ssw_wrap import Aligner, align_pairs
 from .utils import compress_seq, distance_batch, flatten, get_junc_seq, pairwise, revcomp, transform_seq
@@ -108,32 +109,54 @@ def refine_to_junction(circ_junc_seq, reads):
 # `cluster_steps` answers the requests of ALL coroutines of a round together: one K4 launch for every pair of every request, the
 # linkages on the host, one K3 launch for every cluster with several members.  Per circRNA the sequence of steps -- and so the
 # result -- is the reference's.
+_PAIR_ROUTE = distance_batch      # the K4 pair entry point as imported
+
+
+def _grouped_route():
+    """Whether the distance matrices and the compression go to the GPU as whole lists (utils.pairwise_distance_groups,
+    utils.compress_seq_batch): each string uploaded once, no pair lists built.  CLH_NO_EDIT_MATRIX=1 keeps the pair route
+    (A/B); so does a caller that has put its own function in place of `distance_batch`, which knows pairs only."""
+    return distance_batch is _PAIR_ROUTE and not os.environ.get('CLH_NO_EDIT_MATRIX')
+
+
+def _pair_route_matrices(lists):
+    """[utils.pairwise_distance(l) for l in lists] with one K4 batch: every pair i < j of every list written out as two strings"""
+    xs, ys, spans = [], [], []
+    for seqs in lists:
+        ii, jj = np.triu_indices(len(seqs), 1)
+        spans.append((ii, jj, len(xs)))
+        xs += [seqs[i] for i in ii]
+        ys += [seqs[j] for j in jj]
+    dists = distance_batch(xs, ys) if xs else []
+    out = []
+    for seqs, (ii, jj, at) in zip(lists, spans):
+        dist = np.zeros((len(seqs), len(seqs)))
+        norm = np.array([max(len(seqs[i]), len(seqs[j])) for i, j in zip(ii, jj)], dtype=np.float64)
+        dist[ii, jj] = np.asarray(dists[at:at + len(ii)], dtype=np.float64) / norm
+        out.append(dist + dist.T)
+    return out
+
+
 def cluster_steps(requests):
     """[(hpc_freq, sequence)] -> [clustered hpc_freq], each what collapse.py:458-506 returns for that request: hpc_freq =
     [(homopolymer-compressed sequence, [read ids])], sequence = {read id: sequence}.  All requests share the GPU calls."""
     from scipy.cluster.hierarchy import linkage, leaves_list
     from scipy.spatial.distance import squareform
     out = [None] * len(requests)
-    # 1. every pair of every request with more than one entry: one batch of edit distances (K4)
-    xs, ys, spans = [], [], []
+    # 1. the distance matrix of every request with more than one entry: one call, the strings uploaded once, the pairs built on the GPU (K4)
+    spans = []
     for k, (hpc_freq, _seq) in enumerate(requests):
-        n = len(hpc_freq)
-        if n == 1:
+        if len(hpc_freq) == 1:
             out[k] = hpc_freq
             continue
-        ii, jj = np.triu_indices(n, 1)
-        spans.append((k, n, ii, jj, len(xs)))
-        xs += [hpc_freq[i][0] for i in ii]
-        ys += [hpc_freq[j][0] for j in jj]
-    dists = distance_batch(xs, ys) if xs else []
+        spans.append(k)
+    lists = [[h[0] for h in requests[k][0]] for k in spans]
+    matrices = (utils.pairwise_distance_groups(lists) if _grouped_route() else _pair_route_matrices(lists)) if lists else []
     # 2. per request: the matrix, the leaf order of the ward linkage, neighbours in that order closer than 0.3 share a cluster
     groups, owners = [], []                       # sequences of every cluster with several members; (request, slot in its result)
-    for k, n, ii, jj, at in spans:
+    for k, dist in zip(spans, matrices):
         hpc_freq, sequence = requests[k]
-        dist = np.zeros((n, n))
-        norm = np.array([max(len(hpc_freq[i][0]), len(hpc_freq[j][0])) for i, j in zip(ii, jj)], dtype=np.float64)
-        dist[ii, jj] = np.asarray(dists[at:at + len(ii)], dtype=np.float64) / norm
-        dist = dist + dist.T
+        n = len(hpc_freq)
         order = leaves_list(linkage(squareform(dist), "ward", optimal_ordering=True)) if dist.sum() != 0 else list(range(n))
         clusters = [[order[0]]]
         for a, b in pairwise(order):
@@ -167,11 +190,14 @@ def consensus_of_groups(groups):
     return hip.default_context().poa_batch(data, off, goff, algorithm=2, scores=(10, -4, -8, -2, -24, -1), raw=True)
 
 
-def _cluster_job(circ_id, reads):
+def _cluster_job(circ_id, reads, hpc=None):
     """The steps of collapse.py:419-455 for one circRNA as a coroutine: yields (hpc_freq, sequence) where the reference calls
-    cluster_sequence, receives the clustered list; returns the final list (StopIteration.value)."""
+    cluster_sequence, receives the clustered list; returns the final list (StopIteration.value).  hpc: the reads' homopolymer-
+    compressed sequences when the caller has them already."""
     sequence = {read_id: seq for read_id, seq in reads}
-    hpc_freq = [(compress_seq(seq), [read_id]) for read_id, seq in reads]
+    if hpc is None:
+        hpc = [compress_seq(seq) for _, seq in reads]
+    hpc_freq = [(h, [read_id]) for h, (read_id, _) in zip(hpc, reads)]
 
     def settle(res):
         # until a step leaves the number of clusters as it is, at most 10 steps (collapse.py:428-435, 447-454); the list of the
@@ -197,7 +223,14 @@ def _cluster_job(circ_id, reads):
 def batch_cluster_sequences(jobs):
     """[(circ_id, [(read_id, sequence)])] -> [clusters] (collapse.py:419-436 per circRNA), all circRNAs advanced together so that
     every round is one call of `cluster_steps`."""
-    runs = [_cluster_job(circ_id, reads) for circ_id, reads in jobs]
+    jobs = list(jobs)
+    if _grouped_route():
+        # every job's reads compressed in one device call before the coroutines start
+        hpc = utils.compress_seq_batch([seq for _, reads in jobs for _, seq in reads])
+        at = np.cumsum([0] + [len(reads) for _, reads in jobs])
+        runs = [_cluster_job(circ_id, reads, hpc[at[k]:at[k + 1]]) for k, (circ_id, reads) in enumerate(jobs)]
+    else:
+        runs = [_cluster_job(circ_id, reads) for circ_id, reads in jobs]
     results = [None] * len(runs)
     waiting = {}
     for k, g in enumerate(runs):

@@ -1367,6 +1367,195 @@ extern "C" int clh_edit_distance_batch(clh_ctx* ctx, int32_t n, const uint8_t* a
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// K4 on whole groups: strings uploaded once, compression and the pair tasks built on the device (edit_matrix.hip)
+// ---------------------------------------------------------------------------------------------------------------
+struct clh_edit_matrix_plan : clh_owned {
+    using clh_owned::clh_owned;
+    int nseq = 0, ngroups = 0, planes = 3;
+    bool hpc = false;
+    int64_t npairs = 0, total = 0, carry_cap64 = 0;
+    uint8_t letter[256] = {0};                 // dense code -> the caller's byte
+    std::vector<int64_t> seq_off;              // [nseq + 1], from 0
+    std::vector<int32_t> len;                  // [nseq]: raw lengths, after a run with compression the compressed ones
+    clh::EmCtl ctl;                            // as the last run left it
+    void *d_raw = nullptr, *d_hpc = nullptr, *d_seq_off = nullptr, *d_len = nullptr, *d_group_off = nullptr, *d_pair_base = nullptr;
+    void *d_tasks = nullptr, *d_out = nullptr, *d_ctl = nullptr, *d_carry = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+};
+
+extern "C" void clh_edit_matrix_plan_destroy(clh_edit_matrix_plan* pl) { delete pl; }
+
+extern "C" clh_edit_matrix_plan* clh_edit_matrix_plan_create(clh_ctx* ctx, int32_t nseq, const uint8_t* seqs, const int64_t* seq_off, int32_t ngroups,
+                                                             const int64_t* group_off, int32_t flags)
+{
+    const char* me = "clh_edit_matrix_plan_create: ";
+    if (!ctx || nseq < 0 || ngroups < 0 || !seq_off || (ngroups > 0 && !group_off) || (flags & ~CLH_EM_HPC)) { fail(CLH_E_ARG, std::string(me) + "bad argument"); return nullptr; }
+    for (int s = 0; s < nseq; ++s) {
+        const int64_t l = seq_off[s + 1] - seq_off[s];
+        if (l < 0) { fail(CLH_E_ARG, std::string(me) + "offsets must ascend"); return nullptr; }
+        if (l > INT32_MAX) { fail(CLH_E_ARG, std::string(me) + "a string of 2^31 bytes or more"); return nullptr; }
+    }
+    const int64_t total = seq_off[nseq] - seq_off[0];
+    if (total > 0 && !seqs) { fail(CLH_E_ARG, std::string(me) + "null argument"); return nullptr; }
+    std::vector<int64_t> pair_base((size_t)ngroups + 1, 0);
+    for (int g = 0; g < ngroups; ++g) {
+        const int64_t m = group_off[g + 1] - group_off[g];
+        if (m < 0 || group_off[g] < 0 || group_off[g + 1] > nseq) { fail(CLH_E_ARG, std::string(me) + "group offsets must ascend within 0..nseq"); return nullptr; }
+        if (m > 65536 || pair_base[(size_t)g] + m * (m - 1) / 2 > INT32_MAX) {
+            fail(CLH_E_CAPACITY, std::string(me) + "more than 2^31 - 1 pairs"); return nullptr;
+        }
+        pair_base[(size_t)g + 1] = pair_base[(size_t)g] + m * (m - 1) / 2;
+    }
+    if (hipSetDevice(ctx->device) != hipSuccess) { fail(CLH_E_HIP, "hipSetDevice failed"); return nullptr; }
+    clh_edit_matrix_plan* pl = new clh_edit_matrix_plan(ctx);
+    pl->nseq = nseq; pl->ngroups = ngroups; pl->hpc = (flags & CLH_EM_HPC) != 0;
+    pl->npairs = pair_base[(size_t)ngroups]; pl->total = total;
+    // the batch's alphabet -> dense codes, as clh_edit_plan_create does (compression keeps the set of letters)
+    int code[256];
+    for (int& c : code) c = -1;
+    int nsym = 0;
+    const uint8_t* src = seqs + seq_off[0];
+    std::vector<uint8_t> sym((size_t)total + 32, 0);
+    for (int64_t i = 0; i < total; ++i) {
+        const uint8_t c = src[i];
+        if (code[c] < 0) { pl->letter[nsym] = c; code[c] = nsym++; }
+        sym[(size_t)i] = (uint8_t)code[c];
+    }
+    pl->planes = nsym <= 8 ? 3 : 8;
+    pl->seq_off.resize((size_t)nseq + 1);
+    pl->len.resize((size_t)nseq);
+    for (int s = 0; s <= nseq; ++s) pl->seq_off[(size_t)s] = seq_off[s] - seq_off[0];
+    for (int s = 0; s < nseq; ++s) pl->len[(size_t)s] = (int32_t)(seq_off[s + 1] - seq_off[s]);
+    // between-pass delta space of K4 for patterns above 4096 symbols: sized from the raw lengths, which bound the compressed ones.
+    // Per group, the strings above 4096 in ascending order: the r-th is the text of its r pairs with shorter ones.
+    unsigned long long carry64 = 0;
+    std::vector<int32_t> longs;
+    for (int g = 0; g < ngroups; ++g) {
+        longs.clear();
+        for (int64_t s = group_off[g]; s < group_off[g + 1]; ++s) if (pl->len[(size_t)s] > 4096) longs.push_back(pl->len[(size_t)s]);
+        std::sort(longs.begin(), longs.end());
+        for (size_t r = 1; r < longs.size(); ++r) carry64 += (unsigned long long)r * 2ull * (((unsigned long long)longs[r] + 63) / 64 + 1);
+    }
+    if (const char* e = getenv("CLH_EM_CARRY_BYTES")) carry64 = std::min<unsigned long long>(carry64, strtoull(e, nullptr, 10) / 64);   // tests: too little of it (the run fails)
+    if (carry64 > (unsigned long long)INT32_MAX) { fail(CLH_E_CAPACITY, std::string(me) + "the pairs of strings above 4096 bytes need more than 128 GiB between passes"); delete pl; return nullptr; }
+    pl->carry_cap64 = (int64_t)carry64;
+    const size_t np = (size_t)std::max<int64_t>(pl->npairs, 1);
+    std::vector<int64_t> goff((size_t)ngroups + 1, 0);
+    for (int g = 0; g <= ngroups && ngroups > 0; ++g) goff[(size_t)g] = group_off[g];
+    pl->d_raw = pl->upload(sym.data(), sym.size());
+    pl->d_seq_off = pl->upload(pl->seq_off.data(), sizeof(int64_t) * pl->seq_off.size());
+    pl->d_len = pl->alloc(sizeof(int32_t) * (size_t)std::max(nseq, 1));
+    pl->d_group_off = pl->upload(goff.data(), sizeof(int64_t) * goff.size());
+    pl->d_pair_base = pl->upload(pair_base.data(), sizeof(int64_t) * pair_base.size());
+    pl->d_tasks = pl->alloc(sizeof(clh::EdTask) * np);
+    pl->d_out = pl->alloc(sizeof(int32_t) * np);
+    pl->d_ctl = pl->alloc(sizeof(clh::EmCtl));
+    bool ok = pl->d_raw && pl->d_seq_off && pl->d_len && pl->d_group_off && pl->d_pair_base && pl->d_tasks && pl->d_out && pl->d_ctl;
+    if (ok && pl->hpc) {
+        // K4 reads text 16 bytes at a time past a string's end: the compressed buffer carries the same slack, zeroed once
+        pl->d_hpc = pl->alloc(sym.size());
+        ok = pl->d_hpc && hipMemset(pl->d_hpc, 0, sym.size()) == hipSuccess;
+    }
+    if (ok && !pl->hpc && nseq) ok = hipMemcpy(pl->d_len, pl->len.data(), sizeof(int32_t) * (size_t)nseq, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok && carry64) { pl->d_carry = pl->alloc((size_t)carry64 * 64 + 64); ok = pl->d_carry != nullptr; }
+    if (!ok) {
+        fail(CLH_E_HIP, "out of device memory or upload failed while building the edit-matrix plan");
+        delete pl; return nullptr;
+    }
+    return pl;
+}
+
+extern "C" int clh_edit_matrix_plan_run(clh_edit_matrix_plan* pl, void* stream_)
+{
+    if (!pl) return fail(CLH_E_ARG, "clh_edit_matrix_plan_run: null argument");
+    HIPCHK(hipSetDevice(pl->ctx->device));
+    hipStream_t st = stream_ ? (hipStream_t)stream_ : pl->ctx->stream;
+    if (!pl->ev[0]) for (auto& e : pl->ev) HIPCHK(pl->event(&e));
+    HIPCHK(hipEventRecord(pl->ev[0], st));
+    pl->last_stream = st; pl->ran = true;
+    HIPCHK(hipMemsetAsync(pl->d_ctl, 0, sizeof(clh::EmCtl), st));
+    if (pl->hpc) HIPCHK(clh::launch_hpc_compress((const uint8_t*)pl->d_raw, (const int64_t*)pl->d_seq_off, pl->nseq, (uint8_t*)pl->d_hpc, (int32_t*)pl->d_len, st));
+    clh::EmParams p;
+    p.seq_off = (const int64_t*)pl->d_seq_off; p.len = (const int32_t*)pl->d_len;
+    p.group_off = (const int64_t*)pl->d_group_off; p.pair_base = (const int64_t*)pl->d_pair_base;
+    p.ngroups = pl->ngroups; p.npairs = pl->npairs;
+    p.tasks = (clh::EdTask*)pl->d_tasks; p.out = (int32_t*)pl->d_out; p.ctl = (clh::EmCtl*)pl->d_ctl; p.carry_cap64 = pl->carry_cap64;
+    HIPCHK(clh::launch_edit_matrix_tasks(p, false, st));
+    HIPCHK(clh::launch_edit_matrix_tasks(p, true, st));
+    // the one read-back: how many pairs each class holds (and the lengths, which fetch and sizes report)
+    HIPCHK(hipMemcpyAsync(&pl->ctl, pl->d_ctl, sizeof(clh::EmCtl), hipMemcpyDeviceToHost, st));
+    if (pl->hpc && pl->nseq) HIPCHK(hipMemcpyAsync(pl->len.data(), pl->d_len, sizeof(int32_t) * (size_t)pl->nseq, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (pl->ctl.no_carry) {
+        // such a pair was counted in its class but has no task: the class lists are not complete, so K4 does not run on them
+        HIPCHK(hipEventRecord(pl->ev[1], st));
+        return fail(CLH_E_CAPACITY, "clh_edit_matrix_plan_run: " + std::to_string(pl->ctl.no_carry) + " pairs of strings above 4096 symbols found no room for their between-pass deltas (" +
+                    std::to_string(pl->ctl.carry_used64 * 64) + " bytes asked for, " + std::to_string(pl->carry_cap64 * 64) + " there)");
+    }
+    const uint8_t* sym = (const uint8_t*)(pl->hpc ? pl->d_hpc : pl->d_raw);
+    int64_t at = 0;
+    for (int c = 0; c < 7; ++c) {
+        HIPCHK(clh::launch_edit_distance(sym, (const clh::EdTask*)pl->d_tasks + at, (int)pl->ctl.count[c], 1 << c, pl->planes, (int32_t*)pl->d_out, (int8_t*)pl->d_carry, st));
+        at += pl->ctl.count[c];
+    }
+    HIPCHK(hipEventRecord(pl->ev[1], st));
+    return 0;
+}
+
+extern "C" int clh_edit_matrix_plan_sizes(clh_edit_matrix_plan* pl, int64_t* npairs, int64_t* hpc_bytes)
+{
+    if (!pl || !npairs || !hpc_bytes) return fail(CLH_E_ARG, "clh_edit_matrix_plan_sizes: null argument");
+    if (pl->hpc && !pl->ran) return fail(CLH_E_ARG, "clh_edit_matrix_plan_sizes: the compressed size is known after clh_edit_matrix_plan_run");
+    *npairs = pl->npairs;
+    *hpc_bytes = 0;
+    for (int32_t l : pl->len) *hpc_bytes += l;
+    return 0;
+}
+
+extern "C" int clh_edit_matrix_plan_fetch(clh_edit_matrix_plan* pl, int32_t* dist, int64_t dist_cap, int32_t* len, uint8_t* hpc, int64_t hpc_cap)
+{
+    if (!pl || !len || (!dist && pl->npairs > 0)) return fail(CLH_E_ARG, "clh_edit_matrix_plan_fetch: null argument");
+    if (!pl->ran) return fail(CLH_E_ARG, "clh_edit_matrix_plan_fetch before clh_edit_matrix_plan_run");
+    if (pl->ctl.no_carry) return fail(CLH_E_CAPACITY, "clh_edit_matrix_plan_fetch: the run left " + std::to_string(pl->ctl.no_carry) + " pairs without a distance");
+    if (dist_cap < pl->npairs) return fail(CLH_E_CAPACITY, "clh_edit_matrix_plan_fetch: dist_cap too small");
+    HIPCHK(hipSetDevice(pl->ctx->device));
+    HIPCHK(hipStreamSynchronize(pl->last_stream));
+    if (pl->npairs) HIPCHK(hipMemcpy(dist, pl->d_out, sizeof(int32_t) * (size_t)pl->npairs, hipMemcpyDeviceToHost));
+    int64_t bytes = 0;
+    for (int s = 0; s < pl->nseq; ++s) { len[s] = pl->len[(size_t)s]; bytes += len[s]; }
+    if (hpc) {
+        if (hpc_cap < bytes) return fail(CLH_E_CAPACITY, "clh_edit_matrix_plan_fetch: hpc_cap too small");
+        std::vector<uint8_t> sym((size_t)pl->total + 1);
+        if (pl->total) HIPCHK(hipMemcpy(sym.data(), pl->hpc ? pl->d_hpc : pl->d_raw, (size_t)pl->total, hipMemcpyDeviceToHost));
+        int64_t w = 0;
+        for (int s = 0; s < pl->nseq; ++s) {
+            const uint8_t* from = sym.data() + pl->seq_off[(size_t)s];
+            for (int32_t i = 0; i < len[s]; ++i) hpc[w++] = pl->letter[from[i]];
+        }
+    }
+    return 0;
+}
+
+extern "C" int clh_edit_matrix_plan_timing(clh_edit_matrix_plan* pl, float* ms)
+{
+    if (!pl || !ms || !pl->ran) return fail(CLH_E_ARG, "clh_edit_matrix_plan_timing: no run to time");
+    HIPCHK(hipEventSynchronize(pl->ev[1]));
+    HIPCHK(hipEventElapsedTime(ms, pl->ev[0], pl->ev[1]));
+    return 0;
+}
+
+extern "C" int clh_edit_matrix_batch(clh_ctx* ctx, int32_t nseq, const uint8_t* seqs, const int64_t* seq_off, int32_t ngroups, const int64_t* group_off,
+                                     int32_t flags, int32_t* dist, int64_t dist_cap, int32_t* len, uint8_t* hpc, int64_t hpc_cap)
+{
+    clh_edit_matrix_plan* pl = clh_edit_matrix_plan_create(ctx, nseq, seqs, seq_off, ngroups, group_off, flags);
+    if (!pl) return g_code;
+    int rc = clh_edit_matrix_plan_run(pl, nullptr);
+    if (!rc) rc = clh_edit_matrix_plan_fetch(pl, dist, dist_cap, len, hpc, hpc_cap);
+    delete pl;
+    return rc;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // K4m / K4t: edlib.align -- modes NW / SHW / HW, end and start locations, CIGARs (edit_align.hip)
 // ---------------------------------------------------------------------------------------------------------------
 struct clh_edit_align_plan : clh_owned {

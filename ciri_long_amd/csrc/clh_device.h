@@ -226,6 +226,28 @@ hipError_t launch_genome_count_n(const uint8_t* codes, const unsigned int* pre_n
 static constexpr int kGenomeBlock = 256;     // bases per entry of the N prefix table
 hipError_t launch_edit_distance(const uint8_t* seqs, const EdTask* tasks, int ntasks, int G, int planes, int32_t* out, int8_t* carry_ws, hipStream_t stream);
 
+// edit_matrix.hip: all pairs of groups of strings, in front of K4
+struct EmCtl {                      // zeroed before every run, read back once after the tasks kernel
+    uint32_t count[8];              // pairs per lane-group class G = 1 << c (c = 0..6)
+    uint32_t fill[8];               // the filling pass's cursor per class
+    unsigned long long carry_used64;   // between-pass delta space handed out (asked for, when it ran out), in units of 64 bytes
+    uint32_t no_carry, pad;         // pairs that found no such space: out = -1, the run fails
+};
+struct EmParams {
+    const int64_t* seq_off;         // [nseq + 1] into the symbol buffers
+    const int32_t* len;             // [nseq] the lengths the distances are computed on
+    const int64_t* group_off;       // [ngroups + 1] first sequence of each group
+    const int64_t* pair_base;       // [ngroups + 1] first pair of each group in the output
+    int ngroups;
+    int64_t npairs;
+    EdTask* tasks;                  // [npairs], the classes back to back
+    int32_t* out;                   // [npairs]
+    EmCtl* ctl;
+    int64_t carry_cap64;
+};
+hipError_t launch_hpc_compress(const uint8_t* raw, const int64_t* seq_off, int nseq, uint8_t* hpc, int32_t* len, hipStream_t stream);
+hipError_t launch_edit_matrix_tasks(const EmParams& p, bool fill, hipStream_t stream);
+
 // K4m / K4t (edit_align.hip): edlib.align's modes on K4's block scheme; the query is always the pattern
 struct EaTask {
     int64_t pat_off, txt_off;   // into the packed symbol array

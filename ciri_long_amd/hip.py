@@ -124,6 +124,16 @@ def lib():
         L.clh_edit_plan_timing.argtypes = [C.c_void_p, C.c_void_p]
         L.clh_edit_distance_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.clh_edit_distance_batch.restype = C.c_int
+        L.clh_edit_matrix_plan_create.restype = C.c_void_p
+        L.clh_edit_matrix_plan_create.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
+        L.clh_edit_matrix_plan_destroy.restype = None
+        L.clh_edit_matrix_plan_destroy.argtypes = [C.c_void_p]
+        L.clh_edit_matrix_plan_run.argtypes = [C.c_void_p, C.c_void_p]
+        L.clh_edit_matrix_plan_sizes.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.clh_edit_matrix_plan_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]
+        L.clh_edit_matrix_plan_timing.argtypes = [C.c_void_p, C.c_void_p]
+        L.clh_edit_matrix_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64,
+                                            C.c_void_p, C.c_void_p, C.c_int64]
         L.clh_edit_align_plan_create.restype = C.c_void_p
         L.clh_edit_align_plan_create.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(EditAlignOpts)]
         L.clh_edit_align_plan_destroy.restype = None
@@ -400,6 +410,29 @@ class Context(object):
     def edit_plan(self, xs, ys):
         return EditPlan(self, xs, ys)
 
+    def edit_matrix_batch(self, groups, hpc=False):
+        """Every pair i < j of every group (a list of lists of str or bytes) in one call, the strings uploaded once -> per group
+        (condensed int32 distances in np.triu_indices(n, 1) order, int32 lengths); with hpc=True the strings are homopolymer-
+        compressed on the device first and each group's tuple ends with the compressed strings.  See EditMatrixPlan."""
+        pk = _EditMatrixInput(groups)
+        dist = np.zeros(pk.npairs, dtype=np.int32); lens = np.zeros(pk.nseq, dtype=np.int32)
+        out = np.zeros(pk.data.size, dtype=np.uint8) if hpc else None
+        _check(lib().clh_edit_matrix_batch(self._h, pk.nseq, pk.data.ctypes.data, pk.off.ctypes.data, len(groups), pk.goff.ctypes.data, 1 if hpc else 0,
+                                           dist.ctypes.data, dist.size, lens.ctypes.data, out.ctypes.data if hpc else None, out.size if hpc else 0),
+               'clh_edit_matrix_batch')
+        return pk.split(dist, lens, out)
+
+    def edit_matrix_plan(self, groups, hpc=False):
+        return EditMatrixPlan(self, groups, hpc)
+
+    def hpc_compress_batch(self, seqs):
+        """Homopolymer compression of every string (str or bytes) on the device, no distances: the same call without groups."""
+        pk = _EditMatrixInput([seqs])
+        lens = np.zeros(pk.nseq, dtype=np.int32); out = np.zeros(pk.data.size, dtype=np.uint8)
+        _check(lib().clh_edit_matrix_batch(self._h, pk.nseq, pk.data.ctypes.data, pk.off.ctypes.data, 0, None, 1, None, 0, lens.ctypes.data,
+                                           out.ctypes.data, out.size), 'clh_edit_matrix_batch')
+        return pk.split(np.zeros(0, dtype=np.int32), lens, out)[0][2]
+
     def edit_align_batch(self, queries, targets, mode='NW', task='distance', k=-1, equalities=(), workspace_bytes=0):
         """edlib.align of the pairs (queries[k], targets[k]) (str or bytes) through K4m / K4t -> (rows EDIT_ALIGN_DTYPE,
         locs int32[.., 2] of (start, end), cigar uint32 BAM ops).  equalities: pairs of letters that also match."""
@@ -474,6 +507,76 @@ class EditPlan(_Handle):
     def timing(self):
         ms = C.c_float(0)
         _check(lib().clh_edit_plan_timing(self._h, C.byref(ms)), 'clh_edit_plan_timing')
+        return float(ms.value)
+
+
+class _EditMatrixInput(object):
+    """groups (a list of lists of str or bytes) packed for clh_edit_matrix_*: every string once, groups as runs of strings"""
+
+    def __init__(self, groups):
+        flat = [s for g in groups for s in g]
+        self.is_str = [isinstance(s, str) for s in flat]
+        self.data, self.off = _pack_bytes(flat)
+        self.nseq = len(flat)
+        self.goff = np.zeros(len(groups) + 1, dtype=np.int64)
+        if groups:
+            self.goff[1:] = np.cumsum([len(g) for g in groups])
+        m = np.diff(self.goff)
+        self.pair_off = np.concatenate(([0], np.cumsum(m * (m - 1) // 2))).astype(np.int64)
+        self.npairs = int(self.pair_off[-1])
+
+    def split(self, dist, lens, hpc):
+        """the flat outputs of a fetch -> per group (distances, lengths[, compressed strings])"""
+        res = []
+        if hpc is not None:
+            at = np.concatenate(([0], np.cumsum(lens, dtype=np.int64)))
+            blob = hpc.tobytes()
+        for g in range(len(self.goff) - 1):
+            a, b = int(self.goff[g]), int(self.goff[g + 1])
+            item = (dist[self.pair_off[g]:self.pair_off[g + 1]], lens[a:b])
+            if hpc is not None:
+                strs = [blob[at[s]:at[s + 1]] for s in range(a, b)]
+                item += ([x.decode() if self.is_str[s] else x for s, x in zip(range(a, b), strs)],)
+            res.append(item)
+        return res
+
+
+class EditMatrixPlan(_Handle):
+    """Groups of strings resident on the GPU (each string uploaded once): run() computes every group's condensed edit-distance
+    matrix any number of times -- compression (hpc=True), the pair tasks and K4, all on the device -- fetch() returns per group
+    (int32 distances in np.triu_indices(n, 1) order, int32 lengths the distances were computed on[, the compressed strings])."""
+    _destroy = 'clh_edit_matrix_plan_destroy'
+
+    def __init__(self, ctx, groups, hpc=False):
+        _Handle.__init__(self, ctx)
+        self.hpc = bool(hpc)
+        self._in = pk = _EditMatrixInput(groups)
+        self.ngroups, self.npairs = len(groups), pk.npairs
+        self._h = lib().clh_edit_matrix_plan_create(ctx._h, pk.nseq, pk.data.ctypes.data, pk.off.ctypes.data, self.ngroups, pk.goff.ctypes.data, int(self.hpc))
+        if not self._h:
+            raise ClhError('clh_edit_matrix_plan_create failed: %s' % last_error())
+
+    def run(self, stream=0):
+        _check(lib().clh_edit_matrix_plan_run(self._h, C.c_void_p(stream)), 'clh_edit_matrix_plan_run')
+
+    def sizes(self):
+        """(pairs, bytes of the strings the distances were computed on) of the last run"""
+        n = C.c_int64(0); b = C.c_int64(0)
+        _check(lib().clh_edit_matrix_plan_sizes(self._h, C.byref(n), C.byref(b)), 'clh_edit_matrix_plan_sizes')
+        return int(n.value), int(b.value)
+
+    def fetch(self):
+        pk = self._in
+        dist = np.zeros(pk.npairs, dtype=np.int32); lens = np.zeros(pk.nseq, dtype=np.int32)
+        out = np.zeros(self.sizes()[1], dtype=np.uint8) if self.hpc else None
+        _check(lib().clh_edit_matrix_plan_fetch(self._h, dist.ctypes.data, dist.size, lens.ctypes.data, out.ctypes.data if self.hpc else None,
+                                                out.size if self.hpc else 0), 'clh_edit_matrix_plan_fetch')
+        return pk.split(dist, lens, out)
+
+    def timing(self):
+        """HIP-event milliseconds of the last run: compression + task build + K4"""
+        ms = C.c_float(0)
+        _check(lib().clh_edit_matrix_plan_timing(self._h, C.byref(ms)), 'clh_edit_matrix_plan_timing')
         return float(ms.value)
 
 

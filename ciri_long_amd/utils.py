@@ -79,7 +79,34 @@ def pairwise_distance(seqs):
     return dist + dist.T
 
 
+def pairwise_distance_groups(groups, hpc=False):
+    """[pairwise_distance(g) for g in groups] from ONE device call: every string is uploaded once and the pairs are built on the
+    GPU (hip.Context.edit_matrix_batch).  With hpc=True the strings are homopolymer-compressed on the device first, so the
+    matrices are those of [compress_seq(s) for s in g]."""
+    import numpy as np
+    from . import hip
+    out = []
+    for res in hip.default_context().edit_matrix_batch(groups, hpc=hpc):
+        d, lens = res[0], res[1]
+        n = len(lens)
+        dist = np.zeros((n, n))
+        ii, jj = np.triu_indices(n, 1)
+        if len(ii):
+            dist[ii, jj] = d / np.maximum(lens[ii], lens[jj]).astype(np.float64)
+        out.append(dist + dist.T)
+    return out
+
+
 def compress_seq(seq):
     """Homopolymer compression: every run of equal characters becomes one (utils.py:162-167)."""
     from itertools import groupby
     return ''.join(ch for ch, _ in groupby(seq))
+
+
+def compress_seq_batch(seqs):
+    """[compress_seq(s) for s in seqs] on the GPU: one upload, one wave per string (csrc/edit_matrix.hip)."""
+    from . import hip
+    seqs = list(seqs)
+    if not seqs:
+        return []
+    return hip.default_context().hpc_compress_batch(seqs)

@@ -286,6 +286,32 @@ int clh_edit_plan_run(clh_edit_plan* plan, void* stream);
 int clh_edit_plan_fetch(clh_edit_plan* plan, int32_t* out);
 int clh_edit_plan_timing(clh_edit_plan* plan, float* ms);       /* HIP-event duration of the last run */
 
+/* ---- edit-distance matrices of whole groups ----------------------------------------------------------------------------
+ * The distance matrix cluster_sequence builds (collapse.py:466-473), for many lists at once, without writing the pairs
+ * out: string s is seqs[seq_off[s]..seq_off[s+1]) (nseq strings, uploaded once), group g is the strings group_off[g] ..
+ * group_off[g+1]-1 (ngroups groups; 0 <= group_off[0], ascending, group_off[ngroups] <= nseq).  A group of m strings
+ * yields its m(m-1)/2 distances i < j in the order of the condensed upper triangle (row by row: scipy's pdist order);
+ * dist is the groups' triangles one after the other.  With CLH_EM_HPC every string is homopolymer-compressed on the
+ * device first (utils.py:162-167: each run of equal bytes becomes one) and the distances are those of the compressed
+ * strings.  len[s]: the length string s was compared at; hpc (may be NULL): the compressed strings, dense, in string
+ * order (the strings as given without CLH_EM_HPC).  Strings outside every group are compressed and not compared, so
+ * ngroups = 0 is the compression alone.
+ * create fails with CLH_E_ARG for offsets that do not ascend or a string of 2^31 bytes or more, and with CLH_E_CAPACITY
+ * for more than 2^31 - 1 pairs in all; fetch with CLH_E_CAPACITY when dist_cap (int32 entries) or hpc_cap (bytes) is
+ * too small.  stream NULL = libclh's private stream.  sizes: hpc_bytes is known once the plan has run. */
+#define CLH_EM_HPC 1     /* homopolymer-compress every string on the device first */
+typedef struct clh_edit_matrix_plan clh_edit_matrix_plan;
+clh_edit_matrix_plan* clh_edit_matrix_plan_create(clh_ctx* ctx, int32_t nseq, const uint8_t* seqs, const int64_t* seq_off, int32_t ngroups,
+                                                  const int64_t* group_off, int32_t flags);
+void clh_edit_matrix_plan_destroy(clh_edit_matrix_plan* plan);
+int clh_edit_matrix_plan_run(clh_edit_matrix_plan* plan, void* stream);
+int clh_edit_matrix_plan_sizes(clh_edit_matrix_plan* plan, int64_t* npairs, int64_t* hpc_bytes);
+int clh_edit_matrix_plan_fetch(clh_edit_matrix_plan* plan, int32_t* dist, int64_t dist_cap, int32_t* len, uint8_t* hpc, int64_t hpc_cap);
+int clh_edit_matrix_plan_timing(clh_edit_matrix_plan* plan, float* ms);     /* HIP events around the last run: compression, task build, K4 */
+/* create + run + fetch */
+int clh_edit_matrix_batch(clh_ctx* ctx, int32_t nseq, const uint8_t* seqs, const int64_t* seq_off, int32_t ngroups, const int64_t* group_off,
+                          int32_t flags, int32_t* dist, int64_t dist_cap, int32_t* len, uint8_t* hpc, int64_t hpc_cap);
+
 /* ---- edlib.align: modes, end / start locations, CIGARs ----------------------------------------------------------------
  * Unit-cost alignment of the whole query (pattern) q[q_off[k]..q_off[k+1]) against the target t[t_off[k]..t_off[k+1]),
  * bytes compared for equality (any byte value).  mode: CLH_EA_NW (whole target), CLH_EA_SHW (a prefix of the target),
