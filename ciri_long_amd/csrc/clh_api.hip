@@ -1951,6 +1951,163 @@ extern "C" int clh_edit_align_batch(clh_ctx* ctx, int32_t n, const uint8_t* q, c
     return rc;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// K4s: probes of at most 64 letters against whole texts, HW with locations, one wave per cell (edit_search.hip)
+// ---------------------------------------------------------------------------------------------------------------
+struct clh_edit_search_plan : clh_owned {
+    using clh_owned::clh_owned;
+    int ntext = 0, nprobe = 0, k = -1, n_eq = 0;
+    int64_t ncell = 0, total_chunks = 0, npart = 0;
+    std::vector<int32_t> plen, tlen, list[2], split;   // list[0]: probes of 1..32 letters, list[1]: of 33..64
+    void *d_text = nullptr, *d_text_off = nullptr, *d_probe = nullptr, *d_probe_off = nullptr, *d_list[2] = {nullptr, nullptr}, *d_chunk_base = nullptr,
+         *d_split = nullptr, *d_eq = nullptr, *d_rows = nullptr, *d_part = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+};
+
+extern "C" void clh_edit_search_plan_destroy(clh_edit_search_plan* pl) { delete pl; }
+
+extern "C" clh_edit_search_plan* clh_edit_search_plan_create(clh_ctx* ctx, int32_t ntext, const uint8_t* texts, const int64_t* text_off, int32_t nprobe,
+                                                             const uint8_t* probes, const int64_t* probe_off, const clh_edit_search_opts* opts)
+{
+    const char* me = "clh_edit_search_plan_create: ";
+    if (!ctx || ntext < 0 || nprobe < 0 || !text_off || !probe_off || !opts || opts->n_eq < 0 || (opts->n_eq > 0 && !opts->eq)) {
+        fail(CLH_E_ARG, std::string(me) + "bad argument"); return nullptr;
+    }
+    for (int t = 0; t < ntext; ++t) {
+        const int64_t l = text_off[t + 1] - text_off[t];
+        if (l < 0) { fail(CLH_E_ARG, std::string(me) + "offsets must ascend"); return nullptr; }
+        if (l > ((int64_t)1 << 30)) { fail(CLH_E_ARG, std::string(me) + "a text of more than 2^30 bytes"); return nullptr; }
+    }
+    for (int q = 0; q < nprobe; ++q) {
+        const int64_t l = probe_off[q + 1] - probe_off[q];
+        if (l < 0) { fail(CLH_E_ARG, std::string(me) + "offsets must ascend"); return nullptr; }
+        if (l > 64) { fail(CLH_E_ARG, std::string(me) + "a probe of more than 64 letters (clh_edit_align_batch takes those)"); return nullptr; }
+    }
+    const int64_t tt = text_off[ntext] - text_off[0], tp = probe_off[nprobe] - probe_off[0];
+    if ((tt > 0 && !texts) || (tp > 0 && !probes)) { fail(CLH_E_ARG, std::string(me) + "null argument"); return nullptr; }
+    if (hipSetDevice(ctx->device) != hipSuccess) { fail(CLH_E_HIP, "hipSetDevice failed"); return nullptr; }
+    clh_edit_search_plan* pl = new clh_edit_search_plan(ctx);
+    pl->ntext = ntext; pl->nprobe = nprobe; pl->k = opts->k; pl->n_eq = opts->n_eq;
+    pl->ncell = (int64_t)ntext * nprobe;
+    std::vector<int64_t> toff((size_t)ntext + 1), poff((size_t)nprobe + 1), chunk_base((size_t)ntext + 1, 0);
+    for (int t = 0; t <= ntext; ++t) toff[(size_t)t] = text_off[t] - text_off[0];
+    for (int q = 0; q <= nprobe; ++q) poff[(size_t)q] = probe_off[q] - probe_off[0];
+    pl->tlen.resize((size_t)ntext); pl->plen.resize((size_t)nprobe);
+    for (int t = 0; t < ntext; ++t) {
+        const int64_t l = toff[(size_t)t + 1] - toff[(size_t)t];
+        const int64_t nch = std::max<int64_t>(1, (l + clh::kEsChunk - 1) / clh::kEsChunk);   // an empty text keeps one chunk: its cells are the kernel's too
+        pl->tlen[(size_t)t] = (int32_t)l;
+        chunk_base[(size_t)t + 1] = chunk_base[(size_t)t] + nch;
+        if (nch > 1) pl->split.push_back(t);
+    }
+    pl->total_chunks = chunk_base[(size_t)ntext];
+    for (int q = 0; q < nprobe; ++q) {
+        const int l = (int)(poff[(size_t)q + 1] - poff[(size_t)q]);
+        pl->plen[(size_t)q] = l;
+        if (l > 0) pl->list[l > 32].push_back(q);           // an empty probe is answered by fetch
+    }
+    pl->npart = pl->split.empty() ? 0 : (int64_t)nprobe * pl->total_chunks;
+    pl->d_text = pl->upload(texts ? texts + text_off[0] : nullptr, (size_t)tt);
+    pl->d_probe = pl->upload(probes ? probes + probe_off[0] : nullptr, (size_t)tp);
+    pl->d_text_off = pl->upload(toff.data(), sizeof(int64_t) * toff.size());
+    pl->d_probe_off = pl->upload(poff.data(), sizeof(int64_t) * poff.size());
+    pl->d_chunk_base = pl->upload(chunk_base.data(), sizeof(int64_t) * chunk_base.size());
+    pl->d_split = pl->upload(pl->split.data(), sizeof(int32_t) * pl->split.size());
+    pl->d_eq = pl->upload(opts->eq, 2 * (size_t)opts->n_eq);
+    for (int w = 0; w < 2; ++w) pl->d_list[w] = pl->upload(pl->list[w].data(), sizeof(int32_t) * pl->list[w].size());
+    pl->d_rows = pl->alloc(sizeof(clh_edit_search_row) * (size_t)std::max<int64_t>(pl->ncell, 1));
+    pl->d_part = pl->alloc(16 * (size_t)std::max<int64_t>(pl->npart, 1));
+    if (!pl->d_text || !pl->d_probe || !pl->d_text_off || !pl->d_probe_off || !pl->d_chunk_base || !pl->d_split || !pl->d_eq || !pl->d_list[0] ||
+        !pl->d_list[1] || !pl->d_rows || !pl->d_part) {
+        fail(CLH_E_HIP, "out of device memory or upload failed while building the edit-search plan");
+        delete pl; return nullptr;
+    }
+    return pl;
+}
+
+extern "C" int clh_edit_search_plan_run(clh_edit_search_plan* pl, void* stream_)
+{
+    if (!pl) return fail(CLH_E_ARG, "clh_edit_search_plan_run: null argument");
+    HIPCHK(hipSetDevice(pl->ctx->device));
+    hipStream_t st = stream_ ? (hipStream_t)stream_ : pl->ctx->stream;
+    if (!pl->ev[0]) for (auto& e : pl->ev) HIPCHK(pl->event(&e));
+    HIPCHK(hipEventRecord(pl->ev[0], st));
+    pl->last_stream = st; pl->ran = true;
+    // every cell and every chunk tuple starts as "unwritten": what a kernel did not store is reported by fetch, never returned
+    if (pl->ncell) HIPCHK(hipMemsetAsync(pl->d_rows, 0x80, sizeof(clh_edit_search_row) * (size_t)pl->ncell, st));
+    if (pl->npart) HIPCHK(hipMemsetAsync(pl->d_part, 0x80, 16 * (size_t)pl->npart, st));
+    clh::EsParams p;
+    p.text = (const uint8_t*)pl->d_text; p.text_off = (const int64_t*)pl->d_text_off;
+    p.probe = (const uint8_t*)pl->d_probe; p.probe_off = (const int64_t*)pl->d_probe_off;
+    p.chunk_base = (const int64_t*)pl->d_chunk_base;
+    p.split_list = (const int32_t*)pl->d_split; p.nsplit = (int32_t)pl->split.size();
+    p.eq = (const uint8_t*)pl->d_eq; p.n_eq = pl->n_eq;
+    p.ntext = pl->ntext; p.nprobe = pl->nprobe; p.k = pl->k;
+    p.total_chunks = pl->total_chunks;
+    p.rows = (int32_t*)pl->d_rows; p.ncell = pl->ncell;
+    p.part = (int32_t*)pl->d_part; p.npart = pl->npart;
+    for (int w = 0; w < 2 && pl->ntext > 0; ++w) {
+        p.probe_list = (const int32_t*)pl->d_list[w]; p.nlist = (int32_t)pl->list[w].size();
+        HIPCHK(clh::launch_edit_search(p, w ? 64 : 32, st));
+    }
+    for (int w = 0; w < 2 && p.nsplit > 0; ++w) {
+        p.probe_list = (const int32_t*)pl->d_list[w]; p.nlist = (int32_t)pl->list[w].size();
+        HIPCHK(clh::launch_edit_search_finish(p, w ? 64 : 32, st));
+    }
+    HIPCHK(hipEventRecord(pl->ev[1], st));
+    return 0;
+}
+
+extern "C" int clh_edit_search_plan_fetch(clh_edit_search_plan* pl, clh_edit_search_row* rows, int64_t rows_cap)
+{
+    if (!pl || (!rows && pl->ncell > 0)) return fail(CLH_E_ARG, "clh_edit_search_plan_fetch: null argument");
+    if (!pl->ran) return fail(CLH_E_ARG, "clh_edit_search_plan_fetch before clh_edit_search_plan_run");
+    if (rows_cap < pl->ncell) return fail(CLH_E_CAPACITY, "clh_edit_search_plan_fetch: rows_cap too small");
+    if (!pl->ncell) return 0;
+    HIPCHK(hipSetDevice(pl->ctx->device));
+    HIPCHK(hipStreamSynchronize(pl->last_stream));
+    HIPCHK(hipMemcpy(rows, pl->d_rows, sizeof(clh_edit_search_row) * (size_t)pl->ncell, hipMemcpyDeviceToHost));
+    // the empty probe, stated here as align states it: distance 0 at every column from -1 on, start = end + 1
+    for (int q = 0; q < pl->nprobe; ++q) {
+        if (pl->plen[(size_t)q]) continue;
+        for (int t = 0; t < pl->ntext; ++t) {
+            const int32_t n = pl->tlen[(size_t)t];
+            rows[(int64_t)t * pl->nprobe + q] = clh_edit_search_row{0, 0, -1, n - 1, n + 1};
+        }
+    }
+    int64_t unwritten = 0;
+    for (int64_t c = 0; c < pl->ncell; ++c) unwritten += rows[c].distance == clh::kEsUnwritten || rows[c].nlocs == clh::kEsUnwritten;
+    if (unwritten) return fail(CLH_E_HIP, "clh_edit_search_plan_fetch: the kernels left " + std::to_string(unwritten) + " cells unwritten");
+    return 0;
+}
+
+extern "C" int clh_edit_search_plan_timing(clh_edit_search_plan* pl, float* ms)
+{
+    if (!pl || !ms || !pl->ran) return fail(CLH_E_ARG, "clh_edit_search_plan_timing: no run to time");
+    HIPCHK(hipEventSynchronize(pl->ev[1]));
+    HIPCHK(hipEventElapsedTime(ms, pl->ev[0], pl->ev[1]));
+    return 0;
+}
+
+extern "C" int clh_edit_search_plan_info(clh_edit_search_plan* pl, int64_t* out)
+{
+    if (!pl || !out) return fail(CLH_E_ARG, "clh_edit_search_plan_info: null argument");
+    out[0] = clh::kEsSeg; out[1] = clh::kEsRound; out[2] = clh::kEsChunk; out[3] = pl->ntext;
+    out[4] = pl->total_chunks; out[5] = (int64_t)pl->split.size(); out[6] = (int64_t)pl->list[0].size(); out[7] = (int64_t)pl->list[1].size();
+    return 0;
+}
+
+extern "C" int clh_edit_search_batch(clh_ctx* ctx, int32_t ntext, const uint8_t* texts, const int64_t* text_off, int32_t nprobe, const uint8_t* probes,
+                                     const int64_t* probe_off, const clh_edit_search_opts* opts, clh_edit_search_row* rows, int64_t rows_cap)
+{
+    clh_edit_search_plan* pl = clh_edit_search_plan_create(ctx, ntext, texts, text_off, nprobe, probes, probe_off, opts);
+    if (!pl) return g_code;
+    int rc = clh_edit_search_plan_run(pl, nullptr);
+    if (!rc) rc = clh_edit_search_plan_fetch(pl, rows, rows_cap);
+    delete pl;
+    return rc;
+}
+
 extern "C" void clh_encode_dna(const char* seq, int64_t len, int8_t* out)
 {
     static int8_t lut[256];

@@ -282,7 +282,29 @@ hipError_t launch_edit_align_build_rev(const EaParams& p, const EaPair* pairs, c
 hipError_t launch_edit_align_build_path(const EaParams& p, const EaPair* pairs, const EaPath* paths, int n, EaTask* tasks, hipStream_t stream);
 hipError_t launch_edit_align_traceback(const EaParams& p, const EaPath* paths, const EaTask* tasks, int n, uint32_t* cigar, int32_t* cig_len, hipStream_t stream);
 
-static constexpr int kRvStrips = 1000;   // pseudo class: RV = 32 with row strips (reads longer than 4096 bases)
+// K4s (edit_search.hip): short probes (one Myers word) against whole texts, HW; one wave per (probe, text chunk), its 64 lanes on 64
+// column segments.  tools/edit_search_model.py states the scheme.
+static constexpr int kEsSeg = 16;                       // columns a lane owns per round
+static constexpr int kEsRound = 64 * kEsSeg;            // columns a wave covers per round
+static constexpr int kEsChunkRounds = 8;                // rounds one wave walks; a longer text is split over several waves (chunks)
+static constexpr int kEsChunk = kEsChunkRounds * kEsRound;
+static constexpr int32_t kEsUnwritten = (int32_t)0x80808080;   // what the result buffers are filled with before a run
+struct EsParams {
+    const uint8_t* text; const int64_t* text_off;       // [ntext + 1]
+    const uint8_t* probe; const int64_t* probe_off;     // [nprobe + 1]
+    const int32_t* probe_list; int32_t nlist;           // the probes of this launch (one word width)
+    const int64_t* chunk_base;                          // [ntext + 1]: chunks in front of each text (every text has at least one)
+    const int32_t* split_list; int32_t nsplit;          // texts of more than one chunk (the finish kernel's)
+    const uint8_t* eq; int32_t n_eq;                    // additionalEqualities, pairs of bytes
+    int32_t ntext, nprobe, k;
+    int64_t total_chunks;
+    int32_t* rows; int64_t ncell;                       // 5 x int32 per cell, text-major: distance, start, end, last_end, nlocs
+    int32_t* part; int64_t npart;                       // 4 x int32 per (probe, chunk): best, first, last, count -- split texts only
+};
+hipError_t launch_edit_search(const EsParams& p, int W, hipStream_t stream);          // the segments; finishes the cells of one chunk
+hipError_t launch_edit_search_finish(const EsParams& p, int W, hipStream_t stream);   // joins the chunks of split texts
+
+static constexpr int kRvStrips = 1000;  // pseudo class: RV = 32 with row strips (reads longer than 4096 bases)
 extern const int kRvClasses[];
 extern const int kNumRvClasses;
 hipError_t launch_ssw(int rv, bool quirk, const SswParams& p, int ntasks, hipStream_t stream);

@@ -3,6 +3,7 @@
 
     align(query, target, mode="NW", task="distance", k=-1, additionalEqualities=None) -> dict
     align_batch(queries, targets, ...) -> [dict]          (one batched GPU call)
+    search(probes, texts, k=-1, both_strands=False, ...) -> array   (every probe in every text, HW, one batched GPU call)
     getNiceAlignment(result, query, target, gapSymbol="-") -> dict   (host only)
 
 The result dict has edlib's keys: ``editDistance``, ``alphabetLength``, ``locations`` (a list of (start, end), both
@@ -18,8 +19,11 @@ location, traced back from the end cell preferring I (query letter against nothi
 nothing), then the diagonal.  Distances, end locations and alphabetLength are uniquely defined; HW starts and CIGARs follow
 the tie rules above (parity with edlib itself is unpinned: tests/golden/make_edlib_golden.py records it where edlib runs).
 
-The kernels are K4m / K4t (csrc/edit_align.hip) through clh_edit_align_batch; there is no CPU fallback.
+The kernels are K4m / K4t (csrc/edit_align.hip) through clh_edit_align_batch, and K4s (csrc/edit_search.hip) through
+clh_edit_search_batch for search(); there is no CPU fallback.
 """
+import numpy as np
+
 from . import hip
 
 _OPS = {7: '=', 8: 'X', 1: 'I', 2: 'D'}
@@ -79,6 +83,55 @@ def align_batch(queries, targets, mode='NW', task='distance', k=-1, additionalEq
 def align(query, target, mode='NW', task='distance', k=-1, additionalEqualities=None):
     """edlib.align with edlib's signature and result dict (see the module text)"""
     return align_batch([query], [target], mode, task, k, additionalEqualities)[0]
+
+
+def search(probes, texts, k=-1, both_strands=False, additionalEqualities=None, context=None):
+    """Every probe in every text: the cross product of align(probe, text, mode="HW", task="locations", k=k,
+    additionalEqualities=...) in one batched GPU call, probes and texts uploaded once -> numpy structured array of shape
+    (len(texts), len(probes), 2 if both_strands else 1) with the int32 fields
+
+        distance   r["editDistance"] (-1: above k)
+        start, end r["locations"][0]
+        last_end   the end of r["locations"][-1]
+        nlocs      len(r["locations"])
+
+    of that call's result r; start, end and last_end are -2 when there is no location.  Slot [t, p, 0] is probes[p], slot
+    [t, p, 1] is utils.revcomp(probes[p]) (bytes taken as latin-1).  The tie rules of the module text hold unchanged.
+    additionalEqualities are applied to the letters as given on both strands: they are not complemented.
+    Probes of 1..64 letters run on K4s (csrc/edit_search.hip: one wave per (probe, text) cell, its lanes on 64 column segments
+    of the text).  Longer probes are answered in the same call through the pair route: their cross product goes to
+    Context.edit_align_batch.  Empty probes and empty texts get align's answers."""
+    eq = _check_args('HW', 'locations', additionalEqualities)
+    from . import utils
+    pb = []
+    for p in probes:
+        pb.append(_as_bytes(p))
+        if both_strands:
+            pb.append(utils.revcomp(pb[-1].decode('latin-1')).encode('latin-1'))
+    tb = [_as_bytes(t) for t in texts]
+    ns = 2 if both_strands else 1
+    out = np.zeros((len(tb), len(pb)), dtype=hip.EDIT_SEARCH_DTYPE)
+    if not tb or not pb:
+        return out.reshape(len(tb), len(probes), ns)
+    ctx = context or hip.default_context()
+    short = [i for i, p in enumerate(pb) if len(p) <= 64]
+    wide = [i for i, p in enumerate(pb) if len(p) > 64]
+    if short:
+        out[:, short] = ctx.edit_search_batch([pb[i] for i in short], tb, int(k), eq)
+    if wide:
+        rows, locs, _ = ctx.edit_align_batch([pb[i] for _ in tb for i in wide], [t for t in tb for _ in wide], 'HW', 'locations', int(k), eq)
+        rows = rows.reshape(len(tb), len(wide))
+        n, at = rows['nlocs'].astype(np.int64), rows['loc_off'].astype(np.int64)
+        some = n > 0
+        first, last = np.where(some, at, 0), np.where(some, at + n - 1, 0)
+        sub = np.zeros(rows.shape, dtype=hip.EDIT_SEARCH_DTYPE)
+        sub['distance'], sub['nlocs'] = rows['distance'], rows['nlocs']
+        pad = np.concatenate([locs.reshape(-1, 2), np.full((1, 2), -2, dtype=np.int32)])
+        sub['start'] = np.where(some, pad[first, 0], -2)
+        sub['end'] = np.where(some, pad[first, 1], -2)
+        sub['last_end'] = np.where(some, pad[last, 1], -2)
+        out[:, wide] = sub
+    return out.reshape(len(tb), len(probes), ns)
 
 
 def getNiceAlignment(alignResult, query, target, gapSymbol='-'):

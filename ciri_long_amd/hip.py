@@ -50,6 +50,11 @@ class EditAlignOpts(C.Structure):
                 ('workspace_bytes', C.c_int64)]
 
 
+class EditSearchOpts(C.Structure):
+    _fields_ = [('k', C.c_int32), ('n_eq', C.c_int32), ('eq', C.c_void_p)]
+
+
+EDIT_SEARCH_DTYPE = np.dtype([('distance', '<i4'), ('start', '<i4'), ('end', '<i4'), ('last_end', '<i4'), ('nlocs', '<i4')])
 EDIT_ALIGN_DTYPE = np.dtype([('distance', '<i4'), ('nlocs', '<i4'), ('loc_off', '<i8'), ('cigar_off', '<i8'), ('cigar_len', '<i4'),
                              ('status', '<i4'), ('alphabet_len', '<i4'), ('reserved', '<i4')])
 EA_MODES = {'NW': 0, 'SHW': 1, 'HW': 2}
@@ -145,6 +150,17 @@ def lib():
         L.clh_edit_align_plan_caps.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.clh_edit_align_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(EditAlignOpts),
                                            C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+        L.clh_edit_search_plan_create.restype = C.c_void_p
+        L.clh_edit_search_plan_create.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                                  C.POINTER(EditSearchOpts)]
+        L.clh_edit_search_plan_destroy.restype = None
+        L.clh_edit_search_plan_destroy.argtypes = [C.c_void_p]
+        L.clh_edit_search_plan_run.argtypes = [C.c_void_p, C.c_void_p]
+        L.clh_edit_search_plan_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        L.clh_edit_search_plan_timing.argtypes = [C.c_void_p, C.c_void_p]
+        L.clh_edit_search_plan_info.argtypes = [C.c_void_p, C.c_void_p]
+        L.clh_edit_search_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                            C.POINTER(EditSearchOpts), C.c_void_p, C.c_int64]
         L.clh_poa_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]
         L.clh_ccs_results_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -446,6 +462,19 @@ class Context(object):
     def edit_align_plan(self, queries, targets, mode='NW', task='distance', k=-1, equalities=(), workspace_bytes=0):
         return EditAlignPlan(self, queries, targets, mode, task, k, equalities, workspace_bytes)
 
+    def edit_search_batch(self, probes, texts, k=-1, equalities=()):
+        """Every probe (str or bytes, at most 64 letters) against every text, HW with locations, through K4s -> EDIT_SEARCH_DTYPE
+        array [len(texts), len(probes)].  See EditSearchPlan."""
+        plan = EditSearchPlan(self, probes, texts, k, equalities)
+        try:
+            plan.run()
+            return plan.fetch()
+        finally:
+            plan.close()
+
+    def edit_search_plan(self, probes, texts, k=-1, equalities=()):
+        return EditSearchPlan(self, probes, texts, k, equalities)
+
     def ccs_file(self, in_path, is_fastq, ccs_fa_path, raw_fa_path, batch_reads=0, first_record=0, max_records=-1, byte_offset=0):
         """Stage 1 from file to file in native code -> (total_reads, reads_with_consensus, reads_too_long); with
         first_record / max_records for one rank's contiguous shard of the records, counted from `byte_offset` (the first byte of a
@@ -631,6 +660,47 @@ class EditAlignPlan(_Handle):
         ms = C.c_float(0)
         _check(lib().clh_edit_align_plan_timing(self._h, C.byref(ms)), 'clh_edit_align_plan_timing')
         return float(ms.value)
+
+
+class EditSearchPlan(_Handle):
+    """Probes and texts resident on the GPU (each uploaded once) for the cross product of HW searches: run() any number of times,
+    fetch() the EDIT_SEARCH_DTYPE array [len(texts), len(probes)] -- per cell the distance, (start, end) of the first location,
+    the end of the last one and their number, as edlib.align(probe, text, mode='HW', task='locations') states them."""
+    _destroy = 'clh_edit_search_plan_destroy'
+
+    def __init__(self, ctx, probes, texts, k=-1, equalities=()):
+        _Handle.__init__(self, ctx)
+        self.ntext, self.nprobe = len(texts), len(probes)
+        t, t_off = _pack_bytes(texts)
+        q, q_off = _pack_bytes(probes)
+        eq = np.array([[_letter(a), _letter(b)] for a, b in (equalities or ())], dtype=np.uint8).reshape(-1)
+        self._eq = np.ascontiguousarray(np.concatenate([eq, np.zeros(2, dtype=np.uint8)]))
+        opts = EditSearchOpts(int(k), len(eq) // 2, self._eq.ctypes.data)
+        self._h = lib().clh_edit_search_plan_create(ctx._h, self.ntext, t.ctypes.data, t_off.ctypes.data, self.nprobe, q.ctypes.data,
+                                                    q_off.ctypes.data, C.byref(opts))
+        if not self._h:
+            raise ClhError('clh_edit_search_plan_create failed: %s' % last_error())
+
+    def run(self, stream=0):
+        _check(lib().clh_edit_search_plan_run(self._h, C.c_void_p(stream)), 'clh_edit_search_plan_run')
+
+    def fetch(self):
+        rows = np.zeros((self.ntext, self.nprobe), dtype=EDIT_SEARCH_DTYPE)
+        _check(lib().clh_edit_search_plan_fetch(self._h, rows.ctypes.data, rows.size), 'clh_edit_search_plan_fetch')
+        return rows
+
+    def timing(self):
+        ms = C.c_float(0)
+        _check(lib().clh_edit_search_plan_timing(self._h, C.byref(ms)), 'clh_edit_search_plan_timing')
+        return float(ms.value)
+
+    def info(self):
+        """the geometry of the kernel: columns a lane owns per round (seg), columns of a wave's round, columns one wave walks before a
+        text is split over several waves (chunk); and of this plan: chunks, split texts, probes per word width"""
+        out = (C.c_int64 * 8)()
+        _check(lib().clh_edit_search_plan_info(self._h, out), 'clh_edit_search_plan_info')
+        return {'seg': int(out[0]), 'round': int(out[1]), 'chunk': int(out[2]), 'texts_per_launch': int(out[3]), 'chunks': int(out[4]),
+                'split_texts': int(out[5]), 'probes32': int(out[6]), 'probes64': int(out[7])}
 
 
 def flatten_splice_sites(ss_index, offset, length):

@@ -348,6 +348,36 @@ int clh_edit_align_plan_timing(clh_edit_align_plan* plan, float* ms);   /* HIP-e
 /* capacities fetch needs for this plan: locations and CIGAR ops */
 int clh_edit_align_plan_caps(clh_edit_align_plan* plan, int64_t* locs_cap, int64_t* cigar_cap);
 
+/* ---- edlib.search: short probes against whole sets of texts ---------------------------------------------------------------
+ * The cross product the adapter, primer and junction-probe searches want, without writing it out: every probe
+ * probes[probe_off[p]..probe_off[p+1]) (at most 64 letters) against every text texts[text_off[t]..text_off[t+1]), both
+ * uploaded once.  Cell (t, p) is row t * nprobe + p and holds what clh_edit_align_batch returns for that pair with mode
+ * CLH_EA_HW and task CLH_EA_LOCATIONS: distance, (start, end) of the first location, the end of the last location and the
+ * number of locations (the tie rules of that call: column -1 is a candidate, the start is the longest alignment's).  Without a
+ * location (k >= 0 and a best above k: distance -1, nlocs 0) start, end and last_end are -2.  eq: n_eq pairs of letters (2 n_eq
+ * bytes) that also count as equal, symmetric, not transitive, applied to the letters as given.  Strands are the caller's
+ * business: a search on both strands passes each probe and its reverse complement.
+ * One wave takes one cell and its 64 lanes walk 64 column segments of the text at once (csrc/edit_search.hip); info reports the
+ * geometry: out[8] = {columns a lane owns per round (SEG), columns of a wave's round (64 SEG), columns one wave walks before a
+ * text is split over several waves, texts per launch (all of them: launches are not split), chunks of all texts, texts split
+ * over more than one wave, probes of 1..32 letters (32-bit words), probes of 33..64 letters}.
+ * create fails with CLH_E_ARG for offsets that do not ascend, a probe above 64 letters or a text above 2^30 bytes; fetch with
+ * CLH_E_CAPACITY when rows_cap (records) is below ntext * nprobe, and with CLH_E_HIP if a kernel left a cell unwritten (never a
+ * value).  Life cycle, error codes and `stream` as clh_edit_matrix_plan_*. */
+typedef struct { int32_t k, n_eq; const uint8_t* eq; } clh_edit_search_opts;
+typedef struct { int32_t distance, start, end, last_end, nlocs; } clh_edit_search_row;
+typedef struct clh_edit_search_plan clh_edit_search_plan;
+clh_edit_search_plan* clh_edit_search_plan_create(clh_ctx* ctx, int32_t ntext, const uint8_t* texts, const int64_t* text_off, int32_t nprobe,
+                                                  const uint8_t* probes, const int64_t* probe_off, const clh_edit_search_opts* opts);
+void clh_edit_search_plan_destroy(clh_edit_search_plan* plan);
+int clh_edit_search_plan_run(clh_edit_search_plan* plan, void* stream);
+int clh_edit_search_plan_fetch(clh_edit_search_plan* plan, clh_edit_search_row* rows, int64_t rows_cap);
+int clh_edit_search_plan_timing(clh_edit_search_plan* plan, float* ms);     /* HIP events around the last run */
+int clh_edit_search_plan_info(clh_edit_search_plan* plan, int64_t* out);
+/* create + run + fetch */
+int clh_edit_search_batch(clh_ctx* ctx, int32_t ntext, const uint8_t* texts, const int64_t* text_off, int32_t nprobe, const uint8_t* probes,
+                          const int64_t* probe_off, const clh_edit_search_opts* opts, clh_edit_search_row* rows, int64_t rows_cap);
+
 /* ASCII -> codes exactly as ssw_wrap.py:234-252 (A/a C/c G/g T/t N/n, anything else 4), on the host. */
 void clh_encode_dna(const char* seq, int64_t len, int8_t* out);
 
