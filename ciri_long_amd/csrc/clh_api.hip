@@ -2108,6 +2108,229 @@ extern "C" int clh_edit_search_batch(clh_ctx* ctx, int32_t ntext, const uint8_t*
     return rc;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// K1g: end-anchored affine-gap alignment of pairs -- global, semiglobal, overlap (ssw_ends.hip)
+// ---------------------------------------------------------------------------------------------------------------
+struct clh_ends_plan : clh_owned {
+    using clh_owned::clh_owned;
+    int n = 0, mode = 0, n_mat = 0, go = 0, ge = 0;
+    bool want_cigar = false;
+    std::vector<clh::EnPair> pairs;
+    std::vector<std::pair<int, int>> shares;      // [first, count) of each launch: the batch cut so that a share's decisions fit the workspace
+    int64_t ws_bytes = 0, hand_words = 0, cig_cap = 0, max_pair_ws = 0, nempty = 0;
+    void *d_q = nullptr, *d_r = nullptr, *d_pairs = nullptr, *d_mat = nullptr, *d_hand = nullptr, *d_ws = nullptr, *d_rows = nullptr, *d_cig = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+};
+
+extern "C" void clh_ends_plan_destroy(clh_ends_plan* pl) { delete pl; }
+
+static int64_t en_ws_bytes(int64_t m, int64_t n)
+{
+    const int64_t nch = (n + clh::kEnChunk - 1) / clh::kEnChunk;
+    const int64_t llast = (n - (nch - 1) * clh::kEnChunk + clh::kEnCpl - 1) / clh::kEnCpl;
+    return (4 * m * (64 * (nch - 1) + llast) + 15) & ~(int64_t)15;
+}
+
+extern "C" clh_ends_plan* clh_ends_plan_create(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off,
+                                               const clh_ends_opts* o)
+{
+    const std::string me = "clh_ends_plan_create: ";
+    if (!ctx || n < 0 || !q_off || !r_off || !o || !o->mat) { fail(CLH_E_ARG, me + "bad argument"); return nullptr; }
+    if (o->mode < CLH_ENDS_GLOBAL || o->mode > CLH_ENDS_OVERLAP) { fail(CLH_E_ARG, me + "mode must be CLH_ENDS_GLOBAL, _SEMIGLOBAL or _OVERLAP"); return nullptr; }
+    if (o->n_mat < 1 || o->n_mat > 32) { fail(CLH_E_ARG, me + "n_mat must be 1..32"); return nullptr; }
+    if (o->gap_open < 0 || o->gap_extend < 0 || o->workspace_bytes < 0) { fail(CLH_E_ARG, me + "gap costs and workspace_bytes must not be negative"); return nullptr; }
+    if (o->gap_open < o->gap_extend) {
+        fail(CLH_E_UNSUPPORTED, me + "gap_open < gap_extend: E along a row is a running maximum only when opening a gap costs at least as much as extending one; not implemented");
+        return nullptr;
+    }
+    int64_t smax = std::max<int64_t>(std::max(o->gap_open, o->gap_extend), 1);
+    for (int k = 0; k < o->n_mat * o->n_mat; ++k) smax = std::max<int64_t>(smax, std::abs((int)o->mat[k]));
+    const int64_t workspace = o->workspace_bytes > 0 ? o->workspace_bytes : (int64_t)1 << 30;
+    for (int k = 0; k < n; ++k) {
+        const int64_t m = q_off[k + 1] - q_off[k], nn = r_off[k + 1] - r_off[k];
+        if (m < 0 || nn < 0) { fail(CLH_E_ARG, me + "offsets must ascend"); return nullptr; }
+        if ((m > 0 && !q) || (nn > 0 && !r)) { fail(CLH_E_ARG, me + "null argument"); return nullptr; }
+        if (m + nn >= ((int64_t)1 << 30) || (m + nn) * smax >= ((int64_t)1 << 30)) {
+            fail(CLH_E_ARG, me + "pair " + std::to_string(k) + ": (m + n) * max(|s|, gap_open, gap_extend) = " + std::to_string(m + nn) + " * " +
+                                std::to_string(smax) + " reaches 2^30, the score range of the int32 cells");
+            return nullptr;
+        }
+    }
+    for (int k = 0; k < n; ++k) {
+        for (int side = 0; side < 2; ++side) {
+            const int8_t* s = side ? r : q;
+            const int64_t* off = side ? r_off : q_off;
+            for (int64_t x = off[k]; x < off[k + 1]; ++x)
+                if (s[x] < 0 || s[x] >= o->n_mat) {
+                    fail(CLH_E_ARG, me + "pair " + std::to_string(k) + ": code " + std::to_string((int)s[x]) + " at letter " + std::to_string(x - off[k]) + " of the " +
+                                        (side ? "reference" : "query") + " is outside the matrix (edge " + std::to_string(o->n_mat) + ")");
+                    return nullptr;
+                }
+        }
+    }
+    if (hipSetDevice(ctx->device) != hipSuccess) { fail(CLH_E_HIP, "hipSetDevice failed"); return nullptr; }
+    clh_ends_plan* pl = new clh_ends_plan(ctx);
+    pl->n = n; pl->mode = o->mode; pl->n_mat = o->n_mat; pl->go = o->gap_open; pl->ge = o->gap_extend; pl->want_cigar = o->want_cigar != 0;
+    pl->pairs.resize((size_t)n);
+    int first = 0;
+    int64_t share = 0;
+    for (int k = 0; k < n; ++k) {
+        clh::EnPair& p = pl->pairs[(size_t)k];
+        const int64_t m = q_off[k + 1] - q_off[k], nn = r_off[k + 1] - r_off[k];
+        p.q_off = q_off[k] - q_off[0]; p.r_off = r_off[k] - r_off[0];
+        p.m = (int32_t)m; p.n = (int32_t)nn; p.pad = 0;
+        p.hand_off = -1; p.ws_off = -1; p.cig_off = pl->cig_cap; p.cig_cap = 0;
+        const bool kernel = m > 0 && nn > 0;
+        pl->nempty += !kernel;
+        if (kernel && nn > clh::kEnChunk) { p.hand_off = pl->hand_words; pl->hand_words += 4 * ((m + 63) & ~(int64_t)63); }
+        if (pl->want_cigar) {
+            p.cig_cap = (int32_t)std::min<int64_t>(m + nn, 2 * std::min(m, nn) + 1);      // runs alternate: no CIGAR has more
+            pl->cig_cap += p.cig_cap;
+        }
+        if (pl->want_cigar && kernel) {
+            const int64_t need = en_ws_bytes(m, nn);
+            pl->max_pair_ws = std::max(pl->max_pair_ws, need);
+            if (need > workspace) {
+                fail(CLH_E_CAPACITY, me + "pair " + std::to_string(k) + " alone needs " + std::to_string(need) + " bytes of workspace for the decisions of its " +
+                                     std::to_string(m) + " x " + std::to_string(nn) + " cells, workspace_bytes is " + std::to_string(workspace));
+                delete pl; return nullptr;
+            }
+            if (share + need > workspace) { pl->shares.push_back({first, k - first}); first = k; share = 0; }
+            p.ws_off = share; share += need;
+            pl->ws_bytes = std::max(pl->ws_bytes, share);
+        }
+    }
+    if (n > first) pl->shares.push_back({first, n - first});
+    const int64_t tq = n ? q_off[n] - q_off[0] : 0, tr = n ? r_off[n] - r_off[0] : 0;
+    pl->d_q = pl->upload(q ? q + q_off[0] : nullptr, (size_t)tq);
+    pl->d_r = pl->upload(r ? r + r_off[0] : nullptr, (size_t)tr);
+    pl->d_pairs = pl->upload(pl->pairs.data(), sizeof(clh::EnPair) * pl->pairs.size());
+    pl->d_mat = pl->upload(o->mat, (size_t)o->n_mat * o->n_mat);
+    pl->d_hand = pl->alloc(sizeof(int32_t) * (size_t)std::max<int64_t>(pl->hand_words, 1));
+    pl->d_ws = pl->alloc((size_t)std::max<int64_t>(pl->ws_bytes, 1));
+    pl->d_rows = pl->alloc(32 * (size_t)std::max(n, 1));
+    pl->d_cig = pl->alloc(sizeof(uint32_t) * (size_t)std::max<int64_t>(pl->cig_cap, 1));
+    if (!pl->d_q || !pl->d_r || !pl->d_pairs || !pl->d_mat || !pl->d_hand || !pl->d_ws || !pl->d_rows || !pl->d_cig) {
+        fail(CLH_E_HIP, "out of device memory or upload failed while building the ends plan");
+        delete pl; return nullptr;
+    }
+    return pl;
+}
+
+extern "C" int clh_ends_plan_run(clh_ends_plan* pl, void* stream_)
+{
+    if (!pl) return fail(CLH_E_ARG, "clh_ends_plan_run: null argument");
+    HIPCHK(hipSetDevice(pl->ctx->device));
+    hipStream_t st = stream_ ? (hipStream_t)stream_ : pl->ctx->stream;
+    if (!pl->ev[0]) for (auto& e : pl->ev) HIPCHK(pl->event(&e));
+    HIPCHK(hipEventRecord(pl->ev[0], st));
+    pl->last_stream = st; pl->ran = true;
+    // every row starts as "unwritten": what a kernel did not store is reported by fetch, never returned
+    if (pl->n) HIPCHK(hipMemsetAsync(pl->d_rows, 0x80, 32 * (size_t)pl->n, st));
+    clh::EnParams p;
+    p.qry = (const int8_t*)pl->d_q; p.ref = (const int8_t*)pl->d_r;
+    p.pairs = (const clh::EnPair*)pl->d_pairs; p.npairs = pl->n;
+    p.mat = (const int8_t*)pl->d_mat; p.n_mat = pl->n_mat;
+    p.go = pl->go; p.ge = pl->ge; p.mode = pl->mode;
+    p.hand = (int32_t*)pl->d_hand; p.hand_cap = pl->hand_words;
+    p.ws = (uint8_t*)pl->d_ws; p.ws_cap = pl->ws_bytes;
+    p.rows = (int32_t*)pl->d_rows;
+    p.cigar = (uint32_t*)pl->d_cig; p.cigar_cap = pl->cig_cap;
+    for (const auto& sh : pl->shares) {        // in stream order: a share's walk has read the workspace before the next share fills it
+        HIPCHK(clh::launch_ssw_ends(p, pl->want_cigar, sh.first, sh.second, st));
+        if (pl->want_cigar) HIPCHK(clh::launch_ssw_ends_walk(p, sh.first, sh.second, st));
+    }
+    HIPCHK(hipEventRecord(pl->ev[1], st));
+    return 0;
+}
+
+// what the programme gives when one side has no letter: the boundary itself
+static void en_empty_side(int mode, int m, int n, int go, int ge, clh_ends_row* row, uint32_t* op)
+{
+    *op = 0;
+    row->score = 0; row->ref_begin = 0; row->ref_end = -1; row->query_begin = 0; row->query_end = -1;
+    if (n > 0 && mode == CLH_ENDS_GLOBAL) { row->score = -(go + (n - 1) * ge); row->ref_end = n - 1; *op = ((uint32_t)n << 4) | 2u; }
+    if (m > 0 && mode != CLH_ENDS_OVERLAP) { row->score = -(go + (m - 1) * ge); row->query_end = m - 1; *op = ((uint32_t)m << 4) | 1u; }
+    if (m > 0 && mode == CLH_ENDS_OVERLAP) { row->query_begin = m; row->query_end = m - 1; }
+}
+
+extern "C" int clh_ends_plan_fetch(clh_ends_plan* pl, clh_ends_row* rows, uint32_t* cigar, int64_t cigar_cap, int64_t* cigar_used)
+{
+    const std::string me = "clh_ends_plan_fetch: ";
+    if (!pl || (!rows && pl->n > 0)) return fail(CLH_E_ARG, me + "null argument");
+    if (!pl->ran) return fail(CLH_E_ARG, "clh_ends_plan_fetch before clh_ends_plan_run");
+    if (cigar_used) *cigar_used = 0;
+    if (!pl->n) return 0;
+    HIPCHK(hipSetDevice(pl->ctx->device));
+    HIPCHK(hipStreamSynchronize(pl->last_stream));
+    std::vector<int32_t> raw(8 * (size_t)pl->n);
+    HIPCHK(hipMemcpy(raw.data(), pl->d_rows, 32 * (size_t)pl->n, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> ops;
+    if (pl->want_cigar && pl->cig_cap) {
+        ops.resize((size_t)pl->cig_cap);
+        HIPCHK(hipMemcpy(ops.data(), pl->d_cig, sizeof(uint32_t) * ops.size(), hipMemcpyDeviceToHost));
+    }
+    int64_t used = 0, unwritten = 0, nowalk = 0, first_bad = -1;
+    for (int k = 0; k < pl->n; ++k) {
+        const clh::EnPair& p = pl->pairs[(size_t)k];
+        const int32_t* w = raw.data() + 8 * (size_t)k;
+        clh_ends_row& out = rows[k];
+        uint32_t one = 0;
+        const uint32_t* src = nullptr;
+        int len = 0;
+        if (p.m == 0 || p.n == 0) {
+            en_empty_side(pl->mode, p.m, p.n, pl->go, pl->ge, &out, &one);
+            if (one) { src = &one; len = 1; }
+        } else {
+            bool bad = false;
+            for (int f = 0; f < 8; ++f) bad |= w[f] == clh::kEnUnwritten;
+            if (bad) { ++unwritten; if (first_bad < 0) first_bad = k; continue; }
+            if (w[7] != 0 || w[5] < 0 || w[5] > p.cig_cap) { ++nowalk; if (first_bad < 0) first_bad = k; continue; }
+            out.score = w[0]; out.ref_begin = w[1]; out.ref_end = w[2]; out.query_begin = w[3]; out.query_end = w[4];
+            src = ops.data() + p.cig_off; len = w[5];
+        }
+        out.cigar_len = 0; out.cigar_off = -1;
+        if (pl->want_cigar) {
+            if (cigar && used + len > cigar_cap) return fail(CLH_E_CAPACITY, me + "cigar_cap too small");
+            out.cigar_len = len; out.cigar_off = used;
+            if (cigar && len) memcpy(cigar + used, src, sizeof(uint32_t) * (size_t)len);
+            used += len;
+        }
+    }
+    if (cigar_used) *cigar_used = used;
+    if (unwritten || nowalk)
+        return fail(CLH_E_HIP, me + "the kernels left " + std::to_string(unwritten) + " rows unwritten and " + std::to_string(nowalk) +
+                                   " without their walk (first: pair " + std::to_string(first_bad) + ")");
+    return 0;
+}
+
+extern "C" int clh_ends_plan_timing(clh_ends_plan* pl, float* ms)
+{
+    if (!pl || !ms || !pl->ran) return fail(CLH_E_ARG, "clh_ends_plan_timing: no run to time");
+    HIPCHK(hipEventSynchronize(pl->ev[1]));
+    HIPCHK(hipEventElapsedTime(ms, pl->ev[0], pl->ev[1]));
+    return 0;
+}
+
+extern "C" int clh_ends_plan_info(clh_ends_plan* pl, int64_t* out)
+{
+    if (!pl || !out) return fail(CLH_E_ARG, "clh_ends_plan_info: null argument");
+    out[0] = clh::kEnCpl; out[1] = clh::kEnChunk; out[2] = (int64_t)pl->shares.size(); out[3] = pl->ws_bytes;
+    out[4] = pl->max_pair_ws; out[5] = pl->n - pl->nempty; out[6] = pl->nempty; out[7] = pl->cig_cap;
+    return 0;
+}
+
+extern "C" int clh_ends_batch(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off, const clh_ends_opts* opts,
+                              clh_ends_row* rows, uint32_t* cigar, int64_t cigar_cap, int64_t* cigar_used)
+{
+    clh_ends_plan* pl = clh_ends_plan_create(ctx, n, q, q_off, r, r_off, opts);
+    if (!pl) return g_code;
+    int rc = clh_ends_plan_run(pl, nullptr);
+    if (!rc) rc = clh_ends_plan_fetch(pl, rows, cigar, cigar_cap, cigar_used);
+    delete pl;
+    return rc;
+}
+
 extern "C" void clh_encode_dna(const char* seq, int64_t len, int8_t* out)
 {
     static int8_t lut[256];

@@ -304,6 +304,33 @@ struct EsParams {
 hipError_t launch_edit_search(const EsParams& p, int W, hipStream_t stream);          // the segments; finishes the cells of one chunk
 hipError_t launch_edit_search_finish(const EsParams& p, int W, hipStream_t stream);   // joins the chunks of split texts
 
+// K1g (ssw_ends.hip): end-anchored affine-gap alignment of pairs in int32 cells; one wave per pair, its lanes on kEnCpl reference
+// columns each, chunks of kEnChunk columns handing their last column on.  tools/ends_model.py states the scheme.
+static constexpr int kEnCpl = 8;                        // columns a lane owns
+static constexpr int kEnChunk = 64 * kEnCpl;            // columns of one chunk
+static constexpr int32_t kEnUnwritten = (int32_t)0x80808080;   // what the result rows are filled with before a run
+enum { EN_GLOBAL = 0, EN_SEMIGLOBAL = 1, EN_OVERLAP = 2 };
+enum { EN_ST_NO_WALK = 1 };                             // row status: the decisions were not stored or the walk failed (fetch reports it)
+struct EnPair {
+    int64_t q_off, r_off;                               // first code of the query / the reference
+    int64_t hand_off;                                   // hand-over buffers in `hand` (int32 units, 4 x rows rounded up to 64); -1: one chunk
+    int64_t ws_off;                                     // stored decisions in `ws` (bytes, inside the launch's share); -1: none
+    int64_t cig_off;                                    // first op in `cigar`
+    int32_t m, n, cig_cap, pad;
+};
+struct EnParams {
+    const int8_t* qry; const int8_t* ref;
+    const EnPair* pairs; int32_t npairs;
+    const int8_t* mat; int32_t n_mat;                   // device copy, row = reference code
+    int32_t go, ge, mode;
+    int32_t* hand; int64_t hand_cap;                    // int32 units
+    uint8_t* ws; int64_t ws_cap;                        // bytes
+    int32_t* rows;                                      // 8 x int32 per pair: score, ref_begin, ref_end, query_begin, query_end, cigar ops, 0, status
+    uint32_t* cigar; int64_t cigar_cap;                 // ops
+};
+hipError_t launch_ssw_ends(const EnParams& p, bool store, int first, int count, hipStream_t stream);
+hipError_t launch_ssw_ends_walk(const EnParams& p, int first, int count, hipStream_t stream);     // after the storing form of the same pairs
+
 static constexpr int kRvStrips = 1000;  // pseudo class: RV = 32 with row strips (reads longer than 4096 bases)
 extern const int kRvClasses[];
 extern const int kNumRvClasses;

@@ -54,6 +54,14 @@ class EditSearchOpts(C.Structure):
     _fields_ = [('k', C.c_int32), ('n_eq', C.c_int32), ('eq', C.c_void_p)]
 
 
+class EndsOpts(C.Structure):
+    _fields_ = [('mode', C.c_int32), ('mat', C.c_void_p), ('n_mat', C.c_int32), ('gap_open', C.c_int32), ('gap_extend', C.c_int32),
+                ('want_cigar', C.c_int32), ('workspace_bytes', C.c_int64)]
+
+
+ENDS_DTYPE = np.dtype([('score', '<i4'), ('ref_begin', '<i4'), ('ref_end', '<i4'), ('query_begin', '<i4'), ('query_end', '<i4'),
+                       ('cigar_len', '<i4'), ('cigar_off', '<i8')])
+ENDS_MODES = {'global': 0, 'semiglobal': 1, 'overlap': 2}
 EDIT_SEARCH_DTYPE = np.dtype([('distance', '<i4'), ('start', '<i4'), ('end', '<i4'), ('last_end', '<i4'), ('nlocs', '<i4')])
 EDIT_ALIGN_DTYPE = np.dtype([('distance', '<i4'), ('nlocs', '<i4'), ('loc_off', '<i8'), ('cigar_off', '<i8'), ('cigar_len', '<i4'),
                              ('status', '<i4'), ('alphabet_len', '<i4'), ('reserved', '<i4')])
@@ -161,6 +169,16 @@ def lib():
         L.clh_edit_search_plan_info.argtypes = [C.c_void_p, C.c_void_p]
         L.clh_edit_search_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                             C.POINTER(EditSearchOpts), C.c_void_p, C.c_int64]
+        L.clh_ends_plan_create.restype = C.c_void_p
+        L.clh_ends_plan_create.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(EndsOpts)]
+        L.clh_ends_plan_destroy.restype = None
+        L.clh_ends_plan_destroy.argtypes = [C.c_void_p]
+        L.clh_ends_plan_run.argtypes = [C.c_void_p, C.c_void_p]
+        L.clh_ends_plan_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+        L.clh_ends_plan_timing.argtypes = [C.c_void_p, C.c_void_p]
+        L.clh_ends_plan_info.argtypes = [C.c_void_p, C.c_void_p]
+        L.clh_ends_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(EndsOpts), C.c_void_p,
+                                     C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
         L.clh_poa_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]
         L.clh_ccs_results_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -475,6 +493,19 @@ class Context(object):
     def edit_search_plan(self, probes, texts, k=-1, equalities=()):
         return EditSearchPlan(self, probes, texts, k, equalities)
 
+    def ends_batch(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode='global', want_cigar=True, workspace_bytes=0):
+        """End-anchored affine-gap alignment of the pairs (query k, reference k), packed codes and offsets as ssw_batch takes them,
+        through K1g -> (rows ENDS_DTYPE, cigars uint32 packed ops).  See EndsPlan."""
+        plan = EndsPlan(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode, want_cigar, workspace_bytes)
+        try:
+            plan.run()
+            return plan.fetch()
+        finally:
+            plan.close()
+
+    def ends_plan(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode='global', want_cigar=True, workspace_bytes=0):
+        return EndsPlan(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode, want_cigar, workspace_bytes)
+
     def ccs_file(self, in_path, is_fastq, ccs_fa_path, raw_fa_path, batch_reads=0, first_record=0, max_records=-1, byte_offset=0):
         """Stage 1 from file to file in native code -> (total_reads, reads_with_consensus, reads_too_long); with
         first_record / max_records for one rank's contiguous shard of the records, counted from `byte_offset` (the first byte of a
@@ -701,6 +732,60 @@ class EditSearchPlan(_Handle):
         _check(lib().clh_edit_search_plan_info(self._h, out), 'clh_edit_search_plan_info')
         return {'seg': int(out[0]), 'round': int(out[1]), 'chunk': int(out[2]), 'texts_per_launch': int(out[3]), 'chunks': int(out[4]),
                 'split_texts': int(out[5]), 'probes32': int(out[6]), 'probes64': int(out[7])}
+
+
+class EndsPlan(_Handle):
+    """Pairs resident on the GPU (codes uploaded once) for the end-anchored modes of K1g -- 'global', 'semiglobal' (the whole query in
+    any stretch of the reference), 'overlap' (end gaps free on both sequences): run() any number of times, fetch() (rows ENDS_DTYPE,
+    cigars uint32).  Scores are int32 and may be negative; a span without a letter has end == begin - 1; without want_cigar no walk
+    back is made and a begin the mode does not fix is -1 (include/ciri_long_hip.h)."""
+    _destroy = 'clh_ends_plan_destroy'
+
+    def __init__(self, ctx, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode='global', want_cigar=True, workspace_bytes=0):
+        _Handle.__init__(self, ctx)
+        if mode not in ENDS_MODES:
+            raise ValueError('mode must be one of global, semiglobal, overlap, got %r' % (mode,))
+        q = np.ascontiguousarray(queries, dtype=np.int8); r = np.ascontiguousarray(refs, dtype=np.int8)
+        q_off = np.ascontiguousarray(query_off, dtype=np.int64); r_off = np.ascontiguousarray(ref_off, dtype=np.int64)
+        if len(q_off) != len(r_off) or len(q_off) < 1:
+            raise ValueError('EndsPlan: the two offset tables differ in length')
+        self.n = len(q_off) - 1
+        self.want_cigar = bool(want_cigar)
+        mat = np.ascontiguousarray(mat, dtype=np.int8).reshape(-1)
+        n_mat = int(round(len(mat) ** 0.5))
+        if n_mat * n_mat != len(mat):
+            raise ValueError('EndsPlan: the substitution matrix is not square')
+        opts = EndsOpts(ENDS_MODES[mode], mat.ctypes.data, n_mat, int(gap_open), int(gap_extend), int(self.want_cigar), int(workspace_bytes))
+        self._h = lib().clh_ends_plan_create(ctx._h, self.n, q.ctypes.data, q_off.ctypes.data, r.ctypes.data, r_off.ctypes.data, C.byref(opts))
+        if not self._h:
+            raise ClhError('clh_ends_plan_create failed: %s' % last_error())
+
+    def run(self, stream=0):
+        _check(lib().clh_ends_plan_run(self._h, C.c_void_p(stream)), 'clh_ends_plan_run')
+
+    def fetch(self):
+        rows = np.zeros(self.n, dtype=ENDS_DTYPE)
+        cap = self.info()['cigar_cap'] if self.want_cigar else 0
+        cig = np.empty(max(cap, 1), dtype=np.uint32)     # worst-case capacity; only the used prefix is written
+        used = C.c_int64(0)
+        _check(lib().clh_ends_plan_fetch(self._h, rows.ctypes.data, cig.ctypes.data if self.want_cigar else None, cap, C.byref(used)),
+               'clh_ends_plan_fetch')
+        return rows, cig[:used.value].copy()
+
+    def timing(self):
+        """HIP-event milliseconds of the last run: the score kernel, and with CIGARs the walks, of every share of the batch"""
+        ms = C.c_float(0)
+        _check(lib().clh_ends_plan_timing(self._h, C.byref(ms)), 'clh_ends_plan_timing')
+        return float(ms.value)
+
+    def info(self):
+        """the geometry of the kernel: reference columns a lane owns (cpl) and columns of a chunk (a longer reference is walked chunk
+        after chunk); and of this plan: shares the batch was cut into so that a share's stored decisions fit the workspace, workspace
+        bytes in use, those of the largest pair, pairs the kernels take, pairs with an empty side, CIGAR ops fetch may return"""
+        out = (C.c_int64 * 8)()
+        _check(lib().clh_ends_plan_info(self._h, out), 'clh_ends_plan_info')
+        return {'cpl': int(out[0]), 'chunk': int(out[1]), 'shares': int(out[2]), 'workspace_bytes': int(out[3]), 'max_pair_bytes': int(out[4]),
+                'kernel_pairs': int(out[5]), 'empty_pairs': int(out[6]), 'cigar_cap': int(out[7])}
 
 
 def flatten_splice_sites(ss_index, offset, length):

@@ -13,6 +13,8 @@ Differences, all additive:
     alignments -- what a GPU needs, and what ``find_bsj.align_clip_segments`` / ``collapse`` are restructured around;
   * sequences are encoded with a 256-entry table instead of the reference's per-base Python loop (ssw_wrap.py:234-252);
     the resulting codes are identical (A/a 0, C/c 1, G/g 2, T/t 3, everything else 4);
+  * ``align_pairs_ends`` aligns pairs end to end instead of locally -- ``mode`` 'global', 'semiglobal' (the whole query in any stretch
+    of the reference) or 'overlap' (end gaps free on both sequences) -- under the same affine scores, DNA or matrix (K1g);
   * ``align_pairs_matrix`` aligns over any alphabet of up to 32 letters with its own substitution matrix (``BLOSUM62`` for
     proteins), what the reference's ssw_init / ssw_align take and its Python wrapper does not expose.
 """
@@ -311,4 +313,57 @@ def align_pairs_matrix(ref_seqs, query_seqs, matrix, alphabet, gap_open, gap_ext
         r = rows[k]
         c = cig[r['cigar_off']:r['cigar_off'] + r['cigar_len']] if r['cigar_len'] > 0 else ()
         out.append(_filter(r, c, int(qo[k + 1] - qo[k]), min_score, min_len, report_secondary, report_cigar))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# end-anchored modes beside the local one (K1g, csrc/ssw_ends.hip)
+# ---------------------------------------------------------------------------------------------------------------------------
+def align_pairs_ends(ref_seqs, query_seqs, mode='global', match=2, mismatch=2, gap_open=3, gap_extend=1, report_cigar=False, matrix=None,
+                     alphabet=None, context=None):
+    """n independent (reference, query) alignments anchored at the ends, in one GPU call -> one PyAlignRes per pair.
+
+    mode 'global': both sequences end to end.  'semiglobal': the whole query in any stretch of the reference (a probe, an exon, a
+    junction placed inside a read).  'overlap': end gaps free on both sequences at both ends (dovetails, containment).  Scores are
+    those of ``align_pairs`` -- match / mismatch, or `matrix` (n x n, row = reference letter) over `alphabet` as in
+    ``align_pairs_matrix`` -- with a gap of k letters costing gap_open + (k - 1) gap_extend, gap_open >= gap_extend.
+
+    ``score`` may be negative.  Coordinates are 0-based and inclusive; a span that consumed no letter has end == begin - 1.  Ties: the
+    semiglobal end is the smallest reference column with the best score; the overlap end is sought in the last row first (smallest
+    column), then in the last column (smallest row); the walk back prefers the diagonal, then a reference letter against nothing
+    (D), then a query letter against nothing (I), and leaves a gap as soon as it can.  ``score2`` and ``ref_end2`` are None.
+    ``cigar_string`` (report_cigar) uses M / I / D, with soft clips for the query letters outside query_begin..query_end as
+    ``align_pairs`` writes them.  Parity with other libraries' tie rules is not pinned."""
+    if mode not in hip.ENDS_MODES:
+        raise ValueError("align_pairs_ends: mode must be 'global', 'semiglobal' or 'overlap', got %r" % (mode,))
+    if len(ref_seqs) != len(query_seqs):
+        raise ValueError('align_pairs_ends: %d references vs %d queries' % (len(ref_seqs), len(query_seqs)))
+    if (matrix is None) != (alphabet is None):
+        raise ValueError('align_pairs_ends: matrix and alphabet come together')
+    if matrix is not None:
+        mat = np.ascontiguousarray(matrix, dtype=np.int8).reshape(-1)
+        if mat.size != len(alphabet) ** 2 or not 1 <= len(alphabet) <= 32:
+            raise ValueError('align_pairs_ends: a %d-letter alphabet needs a %d x %d matrix (1..32 letters)' % (len(alphabet), len(alphabet), len(alphabet)))
+        enc = lambda s: encode_alphabet(s, alphabet) if isinstance(s, (str, bytes)) else np.asarray(s, dtype=np.int8)
+    else:
+        mat = hip.score_matrix(match, mismatch)
+        enc = lambda s: hip.encode(s) if isinstance(s, (str, bytes)) else np.asarray(s, dtype=np.int8)
+    if not ref_seqs:
+        return []
+    qd, qo = hip.pack([enc(q) for q in query_seqs])
+    rd, ro = hip.pack([enc(r) for r in ref_seqs])
+    ctx = context or hip.default_context()
+    walk = bool(report_cigar) or mode != 'global'          # the begins come from the walk, unless the mode fixes them
+    rows, cig = ctx.ends_batch(qd, qo, rd, ro, mat, gap_open, gap_extend, mode=mode, want_cigar=walk)
+    out = []
+    for k in range(len(rows)):
+        r = rows[k]
+        ops = cig[int(r['cigar_off']):int(r['cigar_off']) + int(r['cigar_len'])] if walk else ()
+        res = PyAlignRes.__new__(PyAlignRes)
+        res.score = int(r['score'])
+        res.ref_begin, res.ref_end = int(r['ref_begin']), int(r['ref_end'])
+        res.query_begin, res.query_end = int(r['query_begin']), int(r['query_end'])
+        res.score2 = res.ref_end2 = None
+        res.cigar_string = res._cigar_string(ops, int(qo[k + 1] - qo[k])) if report_cigar else None
+        out.append(res)
     return out

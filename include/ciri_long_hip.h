@@ -378,6 +378,48 @@ int clh_edit_search_plan_info(clh_edit_search_plan* plan, int64_t* out);
 int clh_edit_search_batch(clh_ctx* ctx, int32_t ntext, const uint8_t* texts, const int64_t* text_off, int32_t nprobe, const uint8_t* probes,
                           const int64_t* probe_off, const clh_edit_search_opts* opts, clh_edit_search_row* rows, int64_t rows_cap);
 
+/* ---- end-anchored affine-gap alignment of pairs: global, semiglobal, overlap (K1g) ------------------------------------------
+ * What clh_ssw_* does locally, anchored at the ends: query q[q_off[k]..q_off[k+1]) against reference r[r_off[k]..r_off[k+1]), both as
+ * codes in [0, n_mat), under the substitution matrix `mat` (n_mat x n_mat, row = reference code, as in clh_ssw_opts) and a gap of
+ * k letters costing gap_open + (k - 1) gap_extend.  With cells (i, j), i query letters against j reference letters:
+ *     E[i][j] = max(H[i][j-1] - go, E[i][j-1] - ge)   (CIGAR D)      F[i][j] = max(H[i-1][j] - go, F[i-1][j] - ge)   (CIGAR I)
+ *     H[i][j] = max(H[i-1][j-1] + s(q[i-1], r[j-1]), E[i][j], F[i][j]),   H[0][0] = 0
+ * CLH_ENDS_GLOBAL: row 0 and column 0 are one gap, the end cell is (m, n).  CLH_ENDS_SEMIGLOBAL (the whole query in any stretch of
+ * the reference): row 0 is 0, column 0 one gap, the end cell is the greatest H[m][j], smallest j.  CLH_ENDS_OVERLAP (end gaps free on
+ * both sequences at both ends): row 0 and column 0 are 0, the end cell is the greatest H of the last row and the last column,
+ * last-row cells first, smallest j, then smallest i.  The walk back prefers the diagonal, then E, then F, leaves a gap as soon as
+ * E[i][j] == H[i][j-1] - go (F likewise), takes the remaining letters of a boundary that is not free as one gap, and stops at (0, 0)
+ * (global), on row 0 (semiglobal, overlap) or column 0 (overlap).  DESIGN.md section 6 has the rules in full; parity with other
+ * libraries is unpinned.
+ * Row k: score (int32, may be negative); ref / query begin and end, 0-based and inclusive as in clh_align_t, end == begin - 1 for a
+ * span without a letter; with want_cigar the CIGAR as cigar_len packed ops (len << 4 | op; M 0, I 1, D 2 as clh_ssw_fetch returns
+ * them, M for match and mismatch, free end gaps not part of it) at cigar[cigar_off ..].  Without want_cigar no walk is made:
+ * cigar_off is -1 and a begin the mode does not fix (ref_begin outside global, query_begin in overlap) is -1.
+ * create fails with CLH_E_UNSUPPORTED for gap_open < gap_extend; with CLH_E_ARG for a code outside the matrix (the message names
+ * the first such pair) and for a pair with (m + n) max(|s|, gap_open, gap_extend) >= 2^30 (the cells are int32); with
+ * CLH_E_CAPACITY when the stored decisions of one pair (half a byte per cell) exceed workspace_bytes (0: 1 GiB) -- a batch is cut
+ * into shares that fit it.  A pair with an empty side never reaches a kernel; fetch states the programme's answer.  fetch fails
+ * with CLH_E_CAPACITY when cigar_cap (ops) is too small -- info's out[7] always suffices -- and with CLH_E_HIP if a kernel left a row
+ * unwritten (never a value).  info: out[8] = {columns a lane owns, columns of a chunk (a longer reference is walked chunk after
+ * chunk), shares of the batch, workspace bytes in use, those of the largest pair, pairs the kernels take, pairs with an empty side,
+ * CIGAR ops fetch may return}.  Life cycle, error codes and `stream` as clh_edit_align_plan_*. */
+#define CLH_ENDS_GLOBAL     0
+#define CLH_ENDS_SEMIGLOBAL 1
+#define CLH_ENDS_OVERLAP    2
+typedef struct { int32_t mode; const int8_t* mat; int32_t n_mat; int32_t gap_open, gap_extend; int32_t want_cigar; int64_t workspace_bytes; } clh_ends_opts;
+typedef struct { int32_t score, ref_begin, ref_end, query_begin, query_end, cigar_len; int64_t cigar_off; } clh_ends_row;
+typedef struct clh_ends_plan clh_ends_plan;
+clh_ends_plan* clh_ends_plan_create(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off,
+                                    const clh_ends_opts* opts);
+void clh_ends_plan_destroy(clh_ends_plan* plan);
+int clh_ends_plan_run(clh_ends_plan* plan, void* stream);
+int clh_ends_plan_fetch(clh_ends_plan* plan, clh_ends_row* rows, uint32_t* cigar, int64_t cigar_cap, int64_t* cigar_used);
+int clh_ends_plan_timing(clh_ends_plan* plan, float* ms);     /* HIP events around the last run */
+int clh_ends_plan_info(clh_ends_plan* plan, int64_t* out);
+/* create + run + fetch */
+int clh_ends_batch(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off, const clh_ends_opts* opts,
+                   clh_ends_row* rows, uint32_t* cigar, int64_t cigar_cap, int64_t* cigar_used);
+
 /* ASCII -> codes exactly as ssw_wrap.py:234-252 (A/a C/c G/g T/t N/n, anything else 4), on the host. */
 void clh_encode_dna(const char* seq, int64_t len, int8_t* out);
 
