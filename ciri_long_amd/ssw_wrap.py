@@ -288,6 +288,17 @@ def encode_alphabet(seq, alphabet, unknown=None):
     return np.ascontiguousarray(codes, dtype=np.int8)
 
 
+def _int8_matrix(matrix, who):
+    """a substitution matrix as flat int8; an entry the kernels' int8 cannot hold raises and is named, it does not wrap"""
+    mat = np.asarray(matrix)
+    if mat.dtype != np.int8 and mat.size:
+        bad = np.argwhere(~((mat >= -128) & (mat <= 127)))
+        if len(bad):
+            at = tuple(int(x) for x in bad[0])
+            raise ValueError('%s: matrix%s = %s is outside -128..127, the range of a score' % (who, ''.join('[%d]' % x for x in at), mat[at]))
+    return np.ascontiguousarray(mat, dtype=np.int8).reshape(-1)
+
+
 def align_pairs_matrix(ref_seqs, query_seqs, matrix, alphabet, gap_open, gap_extend, report_secondary=False,
                        report_cigar=False, min_score=0, min_len=0, context=None):
     """align_pairs over an alphabet of up to 32 letters: element k is what the reference's ssw_init(query k, matrix) +
@@ -296,7 +307,7 @@ def align_pairs_matrix(ref_seqs, query_seqs, matrix, alphabet, gap_open, gap_ext
     int8 code arrays."""
     if len(ref_seqs) != len(query_seqs):
         raise ValueError('align_pairs_matrix: %d references vs %d queries' % (len(ref_seqs), len(query_seqs)))
-    mat = np.ascontiguousarray(matrix, dtype=np.int8).reshape(-1)
+    mat = _int8_matrix(matrix, 'align_pairs_matrix')
     n = len(alphabet)
     if mat.size != n * n:
         raise ValueError('align_pairs_matrix: a %d-letter alphabet needs a %d x %d matrix' % (n, n, n))
@@ -341,7 +352,7 @@ def align_pairs_ends(ref_seqs, query_seqs, mode='global', match=2, mismatch=2, g
     if (matrix is None) != (alphabet is None):
         raise ValueError('align_pairs_ends: matrix and alphabet come together')
     if matrix is not None:
-        mat = np.ascontiguousarray(matrix, dtype=np.int8).reshape(-1)
+        mat = _int8_matrix(matrix, 'align_pairs_ends')
         if mat.size != len(alphabet) ** 2 or not 1 <= len(alphabet) <= 32:
             raise ValueError('align_pairs_ends: a %d-letter alphabet needs a %d x %d matrix (1..32 letters)' % (len(alphabet), len(alphabet), len(alphabet)))
         enc = lambda s: encode_alphabet(s, alphabet) if isinstance(s, (str, bytes)) else np.asarray(s, dtype=np.int8)

@@ -144,8 +144,9 @@ def plain(q, r, mat, go, ge, mode):
     return _result(H[end[0]][end[1]], end, (i0, j0), ops)
 
 
-def align(q, r, mat, go, ge, mode, path=True):
-    """the same programme row by row in numpy int64; path=False: score and end cell only (begins and cigar None)"""
+def align(q, r, mat, go, ge, mode, path=True, lines=None):
+    """the same programme row by row in numpy int64; path=False: score and end cell only (begins and cigar None); `lines`, a dict,
+    receives what the end cell was chosen from (last_row_and_column)"""
     assert mode in MODES and go >= ge >= 0
     q = np.asarray(q, dtype=np.int64); r = np.asarray(r, dtype=np.int64)
     mat = np.asarray(mat, dtype=np.int64)
@@ -179,12 +180,21 @@ def align(q, r, mat, go, ge, mode, path=True):
             Fp[0] = NEG
         last_col.append(int(Hp[n]))
     end = _end_cell(mode, m, n, [int(x) for x in Hp], last_col)
+    if lines is not None:
+        lines.update(last_row=[int(x) for x in Hp], last_col=list(last_col))
     score = int(Hp[end[1]]) if end[0] == m else last_col[end[0]]
     if not path:
         return {'score': score, 'ref_begin': None, 'ref_end': end[1] - 1, 'query_begin': None, 'query_end': end[0] - 1, 'cigar': None}
     i0, j0, ops = _walk(mode, end, lambda i, j: flags[i, j] & 1, lambda i, j: flags[i, j] & 2, lambda i, j: flags[i, j] & 4,
                         lambda i, j: flags[i, j] & 8, lambda i, j: flags[i, j] & 16)
     return _result(score, end, (i0, j0), ops)
+
+
+def last_row_and_column(q, r, mat, go, ge, mode):
+    """-> (H[m][0..n], H[0..m][n]) of the programme `align` runs"""
+    lines = {}
+    align(q, r, mat, go, ge, mode, path=False, lines=lines)
+    return lines['last_row'], lines['last_col']
 
 
 def rescore(cigar, q, r, ref_begin, query_begin, mat, go, ge):

@@ -30,8 +30,9 @@ def _col0(mode, i, go, ge):
     return 0 if (mode == 'overlap' or i == 0) else -(go + (i - 1) * ge)
 
 
-def run(q, r, mat, go, ge, mode, cpl=8, lanes=64, store=True):
-    """-> the result dict of tests/ends_check.py (begins and cigar None without `store`)"""
+def run(q, r, mat, go, ge, mode, cpl=8, lanes=64, store=True, extreme=None):
+    """-> the result dict of tests/ends_check.py (begins and cigar None without `store`); `extreme`, a list, receives the largest
+    magnitude among the values checked to stay inside int32"""
     assert mode in MODES and go >= ge >= 0
     m, n = len(q), len(r)
     assert m > 0 and n > 0, 'a pair with an empty side never reaches the kernel'
@@ -42,6 +43,7 @@ def run(q, r, mat, go, ge, mode, cpl=8, lanes=64, store=True):
     col_best, col_i = 0, 0                                # of the last column (overlap): H[0][n] = 0
     corner = None
     words = {}
+    peak = 0
     for c in range(nchunks):
         c0 = c * C
         cols = min(C, n - c0)
@@ -87,6 +89,7 @@ def run(q, r, mat, go, ge, mode, cpl=8, lanes=64, store=True):
                     p = l * cpl + k
                     if c0 + 1 + p <= n:
                         _i32(u); _i32(T[l][k])
+                        peak = max(peak, abs(u), abs(T[l][k]))
                     E[l][k] = u - p * ge
                     H[l][k] = max(T[l][k], E[l][k])
                     x = T[l][k] - go + (p + 1) * ge
@@ -116,6 +119,8 @@ def run(q, r, mat, go, ge, mode, cpl=8, lanes=64, store=True):
                     col_best, col_i = hn, i
             Hp, Fp, hleft = H, F, new_left
         hand[c & 1] = out
+    if extreme is not None:
+        extreme.append(peak)
     if mode == 'global':
         score, end = corner, (m, n)
     elif mode == 'semiglobal' or row_best >= col_best:
