@@ -2331,6 +2331,280 @@ extern "C" int clh_ends_batch(clh_ctx* ctx, int32_t n, const int8_t* q, const in
     return rc;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// K1gb: K1g's global and semiglobal programmes over a band of diagonals per pair (ssw_band.hip)
+// ---------------------------------------------------------------------------------------------------------------
+struct clh_band_plan : clh_owned {
+    using clh_owned::clh_owned;
+    int n = 0, mode = 0, n_mat = 0, go = 0, ge = 0;
+    bool want_cigar = false;
+    int64_t splus = 0;                            // max(0, greatest matrix entry): what an M column can add at most
+    std::vector<clh::BdPair> pairs;
+    std::vector<int32_t> order;                   // pair indices filed by share, then by class
+    struct share_t { int first, count; int cfirst[clh::kBdClasses], ccount[clh::kBdClasses]; };
+    std::vector<share_t> shares;                  // pairs [first, first + count): their decisions fit the workspace together
+    int64_t ws_bytes = 0, cig_cap = 0, max_pair_ws = 0, nempty = 0, max_width = 0, nclass[clh::kBdClasses] = {0, 0, 0};
+    void *d_q = nullptr, *d_r = nullptr, *d_pairs = nullptr, *d_order = nullptr, *d_mat = nullptr, *d_ws = nullptr, *d_rows = nullptr, *d_cig = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+};
+
+extern "C" void clh_band_plan_destroy(clh_band_plan* pl) { delete pl; }
+
+extern "C" clh_band_plan* clh_band_plan_create(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off,
+                                               const int32_t* diag, const clh_band_opts* o)
+{
+    const std::string me = "clh_band_plan_create: ";
+    if (!ctx || n < 0 || !q_off || !r_off || !o || !o->mat) { fail(CLH_E_ARG, me + "bad argument"); return nullptr; }
+    if (o->mode == CLH_ENDS_OVERLAP) { fail(CLH_E_UNSUPPORTED, me + "overlap with a band is not built; clh_ends_plan_create takes the mode over the full matrix"); return nullptr; }
+    if (o->mode != CLH_ENDS_GLOBAL && o->mode != CLH_ENDS_SEMIGLOBAL) { fail(CLH_E_ARG, me + "mode must be CLH_ENDS_GLOBAL or CLH_ENDS_SEMIGLOBAL"); return nullptr; }
+    if (o->n_mat < 1 || o->n_mat > 32) { fail(CLH_E_ARG, me + "n_mat must be 1..32"); return nullptr; }
+    if (o->gap_open < 0 || o->gap_extend < 0 || o->workspace_bytes < 0 || o->band < 0) { fail(CLH_E_ARG, me + "gap costs, workspace_bytes and band must not be negative"); return nullptr; }
+    if (o->gap_open < o->gap_extend) {
+        fail(CLH_E_UNSUPPORTED, me + "gap_open < gap_extend: E along a row is a running maximum only when opening a gap costs at least as much as extending one; not implemented");
+        return nullptr;
+    }
+    int64_t smax = std::max<int64_t>(std::max(o->gap_open, o->gap_extend), 1), splus = 0;
+    for (int k = 0; k < o->n_mat * o->n_mat; ++k) { smax = std::max<int64_t>(smax, std::abs((int)o->mat[k])); splus = std::max<int64_t>(splus, o->mat[k]); }
+    const int64_t workspace = o->workspace_bytes > 0 ? o->workspace_bytes : (int64_t)1 << 30;
+    const bool global = o->mode == CLH_ENDS_GLOBAL;
+    std::vector<std::pair<int32_t, int32_t>> bands((size_t)n);
+    for (int k = 0; k < n; ++k) {
+        const int64_t m = q_off[k + 1] - q_off[k], nn = r_off[k + 1] - r_off[k];
+        const std::string pk = me + "pair " + std::to_string(k) + ": ";
+        if (m < 0 || nn < 0) { fail(CLH_E_ARG, me + "offsets must ascend"); return nullptr; }
+        if ((m > 0 && !q) || (nn > 0 && !r)) { fail(CLH_E_ARG, me + "null argument"); return nullptr; }
+        const int64_t span = m + nn + 2 * clh::kBdMaxWidth;
+        if (span >= ((int64_t)1 << 29) || span * smax >= ((int64_t)1 << 29)) {
+            fail(CLH_E_ARG, pk + "(m + n + " + std::to_string(2 * clh::kBdMaxWidth) + ") * max(|s|, gap_open, gap_extend) = " + std::to_string(span) + " * " +
+                                std::to_string(smax) + " reaches 2^29, the score range the banded int32 cells keep apart from minus infinity");
+            return nullptr;
+        }
+        int64_t lo, hi;
+        if (diag) { lo = (int64_t)diag[k] - o->band; hi = (int64_t)diag[k] + o->band; }
+        else { lo = std::min<int64_t>(0, nn - m) - o->band; hi = std::max<int64_t>(0, nn - m) + o->band; }
+        const std::string bt = "the band [" + std::to_string(lo) + ", " + std::to_string(hi) + "] of the " + std::to_string(m) + " x " + std::to_string(nn) + " pair ";
+        if (global && (lo > std::min<int64_t>(0, nn - m) || hi < std::max<int64_t>(0, nn - m))) {
+            fail(CLH_E_ARG, pk + bt + "misses (0, 0) or (m, n): a global band holds the diagonals 0 and n - m = " + std::to_string(nn - m));
+            return nullptr;
+        }
+        if (!global && (hi < 0 || lo > nn - m)) {
+            fail(CLH_E_ARG, pk + bt + "has no start cell on row 0 (hi < 0) or no end cell on row m (lo > n - m = " + std::to_string(nn - m) + ")");
+            return nullptr;
+        }
+        lo = std::max(lo, -m); hi = std::min(hi, nn);
+        if (hi - lo + 1 > clh::kBdMaxWidth) {
+            fail(CLH_E_CAPACITY, pk + "the clipped band [" + std::to_string(lo) + ", " + std::to_string(hi) + "] holds " + std::to_string(hi - lo + 1) +
+                                 " diagonals, more than " + std::to_string(clh::kBdMaxWidth) + "; clh_ends_plan_create takes such pairs over the full matrix");
+            return nullptr;
+        }
+        bands[(size_t)k] = {(int32_t)lo, (int32_t)hi};
+    }
+    for (int k = 0; k < n; ++k) {
+        for (int side = 0; side < 2; ++side) {
+            const int8_t* s = side ? r : q;
+            const int64_t* off = side ? r_off : q_off;
+            for (int64_t x = off[k]; x < off[k + 1]; ++x)
+                if (s[x] < 0 || s[x] >= o->n_mat) {
+                    fail(CLH_E_ARG, me + "pair " + std::to_string(k) + ": code " + std::to_string((int)s[x]) + " at letter " + std::to_string(x - off[k]) + " of the " +
+                                        (side ? "reference" : "query") + " is outside the matrix (edge " + std::to_string(o->n_mat) + ")");
+                    return nullptr;
+                }
+        }
+    }
+    // the shares, before any device call: a pair above the workspace is refused here
+    std::vector<clh::BdPair> pairs((size_t)n);
+    std::vector<clh_band_plan::share_t> shares;
+    int64_t ws_bytes = 0, cig_cap = 0, max_pair_ws = 0, nempty = 0, max_width = 0, nclass[clh::kBdClasses] = {0, 0, 0};
+    int first = 0;
+    int64_t share = 0;
+    for (int k = 0; k < n; ++k) {
+        clh::BdPair& p = pairs[(size_t)k];
+        const int64_t m = q_off[k + 1] - q_off[k], nn = r_off[k + 1] - r_off[k];
+        p.q_off = q_off[k] - q_off[0]; p.r_off = r_off[k] - r_off[0];
+        p.m = (int32_t)m; p.n = (int32_t)nn; p.lo = bands[(size_t)k].first; p.hi = bands[(size_t)k].second;
+        p.ws_off = -1; p.cig_off = cig_cap; p.cig_cap = 0; p.cls = -1;
+        const bool kernel = m > 0 && nn > 0;
+        const int64_t B = (int64_t)p.hi - p.lo + 1;
+        nempty += !kernel;
+        if (kernel) {
+            p.cls = 0;
+            while (B > 64 * clh::kBdCpl[p.cls]) ++p.cls;
+            ++nclass[p.cls];
+            max_width = std::max(max_width, B);
+        }
+        if (o->want_cigar) {
+            p.cig_cap = (int32_t)std::min<int64_t>(m + nn, 2 * std::min(m, nn) + 1);      // runs alternate: no CIGAR has more
+            cig_cap += p.cig_cap;
+        }
+        if (o->want_cigar && kernel) {
+            const int cpl = clh::kBdCpl[p.cls];
+            const int64_t need = (m * ((B + cpl - 1) / cpl) * (cpl / 2) + 15) & ~(int64_t)15;
+            max_pair_ws = std::max(max_pair_ws, need);
+            if (need > workspace) {
+                fail(CLH_E_CAPACITY, me + "pair " + std::to_string(k) + " alone needs " + std::to_string(need) + " bytes of workspace for the decisions of its " +
+                                     std::to_string(m) + " rows of " + std::to_string(B) + " diagonals, workspace_bytes is " + std::to_string(workspace));
+                return nullptr;
+            }
+            if (share + need > workspace) { shares.push_back({first, k - first, {0, 0, 0}, {0, 0, 0}}); first = k; share = 0; }
+            p.ws_off = share; share += need;
+            ws_bytes = std::max(ws_bytes, share);
+        }
+    }
+    if (n > first) shares.push_back({first, n - first, {0, 0, 0}, {0, 0, 0}});
+    std::vector<int32_t> order;
+    for (auto& sh : shares)
+        for (int c = 0; c < clh::kBdClasses; ++c) {
+            sh.cfirst[c] = (int)order.size();
+            for (int k = sh.first; k < sh.first + sh.count; ++k)
+                if (pairs[(size_t)k].cls == c) order.push_back(k);
+            sh.ccount[c] = (int)order.size() - sh.cfirst[c];
+        }
+    if (hipSetDevice(ctx->device) != hipSuccess) { fail(CLH_E_HIP, "hipSetDevice failed"); return nullptr; }
+    clh_band_plan* pl = new clh_band_plan(ctx);
+    pl->n = n; pl->mode = o->mode; pl->n_mat = o->n_mat; pl->go = o->gap_open; pl->ge = o->gap_extend; pl->want_cigar = o->want_cigar != 0;
+    pl->splus = splus;
+    pl->pairs.swap(pairs); pl->order.swap(order); pl->shares.swap(shares);
+    pl->ws_bytes = ws_bytes; pl->cig_cap = cig_cap; pl->max_pair_ws = max_pair_ws; pl->nempty = nempty; pl->max_width = max_width;
+    for (int c = 0; c < clh::kBdClasses; ++c) pl->nclass[c] = nclass[c];
+    const int64_t tq = n ? q_off[n] - q_off[0] : 0, tr = n ? r_off[n] - r_off[0] : 0;
+    pl->d_q = pl->upload(q ? q + q_off[0] : nullptr, (size_t)tq);
+    pl->d_r = pl->upload(r ? r + r_off[0] : nullptr, (size_t)tr);
+    pl->d_pairs = pl->upload(pl->pairs.data(), sizeof(clh::BdPair) * pl->pairs.size());
+    pl->d_order = pl->upload(pl->order.data(), sizeof(int32_t) * pl->order.size());
+    pl->d_mat = pl->upload(o->mat, (size_t)o->n_mat * o->n_mat);
+    pl->d_ws = pl->alloc((size_t)std::max<int64_t>(pl->ws_bytes, 1));
+    pl->d_rows = pl->alloc(32 * (size_t)std::max(n, 1));
+    pl->d_cig = pl->alloc(sizeof(uint32_t) * (size_t)std::max<int64_t>(pl->cig_cap, 1));
+    if (!pl->d_q || !pl->d_r || !pl->d_pairs || !pl->d_order || !pl->d_mat || !pl->d_ws || !pl->d_rows || !pl->d_cig) {
+        fail(CLH_E_HIP, "out of device memory or upload failed while building the band plan");
+        delete pl; return nullptr;
+    }
+    return pl;
+}
+
+extern "C" int clh_band_plan_run(clh_band_plan* pl, void* stream_)
+{
+    if (!pl) return fail(CLH_E_ARG, "clh_band_plan_run: null argument");
+    HIPCHK(hipSetDevice(pl->ctx->device));
+    hipStream_t st = stream_ ? (hipStream_t)stream_ : pl->ctx->stream;
+    if (!pl->ev[0]) for (auto& e : pl->ev) HIPCHK(pl->event(&e));
+    HIPCHK(hipEventRecord(pl->ev[0], st));
+    pl->last_stream = st; pl->ran = true;
+    // every row starts as "unwritten": what a kernel did not store is reported by fetch, never returned
+    if (pl->n) HIPCHK(hipMemsetAsync(pl->d_rows, 0x80, 32 * (size_t)pl->n, st));
+    clh::BdParams p;
+    p.qry = (const int8_t*)pl->d_q; p.ref = (const int8_t*)pl->d_r;
+    p.pairs = (const clh::BdPair*)pl->d_pairs; p.npairs = pl->n;
+    p.order = (const int32_t*)pl->d_order; p.norder = (int32_t)pl->order.size();
+    p.mat = (const int8_t*)pl->d_mat; p.n_mat = pl->n_mat;
+    p.go = pl->go; p.ge = pl->ge; p.mode = pl->mode;
+    p.ws = (uint8_t*)pl->d_ws; p.ws_cap = pl->ws_bytes;
+    p.rows = (int32_t*)pl->d_rows;
+    p.cigar = (uint32_t*)pl->d_cig; p.cigar_cap = pl->cig_cap;
+    for (const auto& sh : pl->shares) {        // in stream order: a share's walk has read the workspace before the next share fills it
+        for (int c = 0; c < clh::kBdClasses; ++c) HIPCHK(clh::launch_ssw_band(p, c, pl->want_cigar, sh.cfirst[c], sh.ccount[c], st));
+        if (pl->want_cigar) HIPCHK(clh::launch_ssw_band_walk(p, sh.first, sh.count, st));
+    }
+    HIPCHK(hipEventRecord(pl->ev[1], st));
+    return 0;
+}
+
+// 1: the unbanded programme provably returns the same row and CIGAR (the argument is in the header and in DESIGN.md section 6)
+static int32_t bd_exact(int mode, int64_t m, int64_t n, int64_t lo, int64_t hi, int64_t score, int64_t splus, int64_t go, int64_t ge)
+{
+    if (lo <= -m && hi >= n) return 1;
+    if (mode != CLH_ENDS_GLOBAL) return 0;
+    bool ok = true;
+    if (hi + 1 <= n) ok = ok && score > splus * std::max<int64_t>(0, n - hi - 1) - 2 * go - (2 * (hi + 1) - (n - m) - 2) * ge;
+    if (lo - 1 >= -m) ok = ok && score > splus * std::max<int64_t>(0, m + lo - 1) - 2 * go - (2 * (1 - lo) + (n - m) - 2) * ge;
+    return ok ? 1 : 0;
+}
+
+extern "C" int clh_band_plan_fetch(clh_band_plan* pl, clh_band_row* rows, uint32_t* cigar, int64_t cigar_cap, int64_t* cigar_used)
+{
+    const std::string me = "clh_band_plan_fetch: ";
+    if (!pl || (!rows && pl->n > 0)) return fail(CLH_E_ARG, me + "null argument");
+    if (!pl->ran) return fail(CLH_E_ARG, "clh_band_plan_fetch before clh_band_plan_run");
+    if (cigar_used) *cigar_used = 0;
+    if (!pl->n) return 0;
+    HIPCHK(hipSetDevice(pl->ctx->device));
+    HIPCHK(hipStreamSynchronize(pl->last_stream));
+    std::vector<int32_t> raw(8 * (size_t)pl->n);
+    HIPCHK(hipMemcpy(raw.data(), pl->d_rows, 32 * (size_t)pl->n, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> ops;
+    if (pl->want_cigar && pl->cig_cap) {
+        ops.resize((size_t)pl->cig_cap);
+        HIPCHK(hipMemcpy(ops.data(), pl->d_cig, sizeof(uint32_t) * ops.size(), hipMemcpyDeviceToHost));
+    }
+    int64_t used = 0, unwritten = 0, nowalk = 0, first_bad = -1;
+    for (int k = 0; k < pl->n; ++k) {
+        const clh::BdPair& p = pl->pairs[(size_t)k];
+        const int32_t* w = raw.data() + 8 * (size_t)k;
+        clh_band_row& out = rows[k];
+        uint32_t one = 0;
+        const uint32_t* src = nullptr;
+        int len = 0;
+        if (p.m == 0 || p.n == 0) {
+            // the boundary cell itself; an admitted band of such a pair is the whole boundary, but for the row 0 of a semiglobal pair
+            // without a query letter, whose first cell in the band is column lo
+            clh_ends_row e;
+            en_empty_side(pl->mode, p.m, p.n, pl->go, pl->ge, &e, &one);
+            out.score = e.score; out.ref_begin = e.ref_begin; out.ref_end = e.ref_end; out.query_begin = e.query_begin; out.query_end = e.query_end;
+            if (pl->mode == CLH_ENDS_SEMIGLOBAL && p.m == 0) { out.ref_begin = p.lo; out.ref_end = p.lo - 1; }
+            if (one) { src = &one; len = 1; }
+        } else {
+            bool bad = false;
+            for (int f = 0; f < 8; ++f) bad |= w[f] == clh::kEnUnwritten;
+            if (bad) { ++unwritten; if (first_bad < 0) first_bad = k; continue; }
+            if (w[7] != 0 || w[5] < 0 || w[5] > p.cig_cap) { ++nowalk; if (first_bad < 0) first_bad = k; continue; }
+            out.score = w[0]; out.ref_begin = w[1]; out.ref_end = w[2]; out.query_begin = w[3]; out.query_end = w[4];
+            src = ops.data() + p.cig_off; len = w[5];
+        }
+        out.band_lo = p.lo; out.band_hi = p.hi; out.reserved = 0;
+        out.exact = bd_exact(pl->mode, p.m, p.n, p.lo, p.hi, out.score, pl->splus, pl->go, pl->ge);
+        out.cigar_len = 0; out.cigar_off = -1;
+        if (pl->want_cigar) {
+            if (cigar && used + len > cigar_cap) return fail(CLH_E_CAPACITY, me + "cigar_cap too small");
+            out.cigar_len = len; out.cigar_off = used;
+            if (cigar && len) memcpy(cigar + used, src, sizeof(uint32_t) * (size_t)len);
+            used += len;
+        }
+    }
+    if (cigar_used) *cigar_used = used;
+    if (unwritten || nowalk)
+        return fail(CLH_E_HIP, me + "the kernels left " + std::to_string(unwritten) + " rows unwritten and " + std::to_string(nowalk) +
+                                   " without their walk (first: pair " + std::to_string(first_bad) + ")");
+    return 0;
+}
+
+extern "C" int clh_band_plan_timing(clh_band_plan* pl, float* ms)
+{
+    if (!pl || !ms || !pl->ran) return fail(CLH_E_ARG, "clh_band_plan_timing: no run to time");
+    HIPCHK(hipEventSynchronize(pl->ev[1]));
+    HIPCHK(hipEventElapsedTime(ms, pl->ev[0], pl->ev[1]));
+    return 0;
+}
+
+extern "C" int clh_band_plan_info(clh_band_plan* pl, int64_t* out)
+{
+    if (!pl || !out) return fail(CLH_E_ARG, "clh_band_plan_info: null argument");
+    for (int c = 0; c < clh::kBdClasses; ++c) { out[c] = clh::kBdCpl[c]; out[7 + c] = pl->nclass[c]; }
+    out[3] = pl->max_width; out[4] = (int64_t)pl->shares.size(); out[5] = pl->ws_bytes; out[6] = pl->max_pair_ws;
+    out[10] = pl->nempty; out[11] = pl->cig_cap;
+    return 0;
+}
+
+extern "C" int clh_band_batch(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off, const int32_t* diag,
+                              const clh_band_opts* opts, clh_band_row* rows, uint32_t* cigar, int64_t cigar_cap, int64_t* cigar_used)
+{
+    clh_band_plan* pl = clh_band_plan_create(ctx, n, q, q_off, r, r_off, diag, opts);
+    if (!pl) return g_code;
+    int rc = clh_band_plan_run(pl, nullptr);
+    if (!rc) rc = clh_band_plan_fetch(pl, rows, cigar, cigar_cap, cigar_used);
+    delete pl;
+    return rc;
+}
+
 extern "C" void clh_encode_dna(const char* seq, int64_t len, int8_t* out)
 {
     static int8_t lut[256];

@@ -331,6 +331,35 @@ struct EnParams {
 hipError_t launch_ssw_ends(const EnParams& p, bool store, int first, int count, hipStream_t stream);
 hipError_t launch_ssw_ends_walk(const EnParams& p, int first, int count, hipStream_t stream);     // after the storing form of the same pairs
 
+// K1gb (ssw_band.hip): K1g's global and semiglobal programmes over a band of diagonals [lo, hi], d = j - i; one wave per pair in the
+// band's frame, a lane on CPL consecutive band positions b = d - lo (classes CPL 2, 4, 8: bands of up to 128, 256, 512 diagonals).
+// tools/band_model.py states the scheme.
+static constexpr int kBdClasses = 3;
+static constexpr int kBdCpl[kBdClasses] = {2, 4, 8};
+static constexpr int kBdMaxWidth = 64 * 8;
+// what stands for minus infinity.  The host admits a pair only if (m + n + 2 kBdMaxWidth) max(|s|, go, ge, 1) < 2^29: every score, and
+// every score moved into the scan's frame (+ at most kBdMaxWidth ge), then stays inside (-2^29, 2^29), and whatever is derived from
+// kBdNeg (a few additions, each below 2^29 in all) stays inside [-2^30 - 2^29, -2^30 + 2^29): below every score, above INT32_MIN.
+static constexpr int32_t kBdNeg = -(1 << 30);
+struct BdPair {
+    int64_t q_off, r_off;                               // first code of the query / the reference
+    int64_t ws_off;                                     // stored decisions in `ws` (bytes, inside the launch's share); -1: none
+    int64_t cig_off;                                    // first op in `cigar`
+    int32_t m, n, cig_cap, lo, hi, cls;                 // the clipped band and its class (index into kBdCpl); -1: an empty side
+};
+struct BdParams {
+    const int8_t* qry; const int8_t* ref;
+    const BdPair* pairs; int32_t npairs;
+    const int32_t* order; int32_t norder;               // pair indices, filed by share and class
+    const int8_t* mat; int32_t n_mat;                   // device copy, row = reference code
+    int32_t go, ge, mode;
+    uint8_t* ws; int64_t ws_cap;                        // bytes
+    int32_t* rows;                                      // as EnParams::rows
+    uint32_t* cigar; int64_t cigar_cap;                 // ops
+};
+hipError_t launch_ssw_band(const BdParams& p, int cls, bool store, int first, int count, hipStream_t stream);   // order[first .. first + count)
+hipError_t launch_ssw_band_walk(const BdParams& p, int first, int count, hipStream_t stream);                   // pairs [first, first + count)
+
 static constexpr int kRvStrips = 1000;  // pseudo class: RV = 32 with row strips (reads longer than 4096 bases)
 extern const int kRvClasses[];
 extern const int kNumRvClasses;

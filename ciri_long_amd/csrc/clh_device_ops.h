@@ -80,6 +80,7 @@ __device__ __forceinline__ uint32_t hand_up(uint32_t v, int top_hi) {
     return __builtin_amdgcn_alignbit(x, v, 16);
 }
 __device__ __forceinline__ int dpp_shr1(int fill, int v) { return __builtin_amdgcn_update_dpp(fill, v, 0x138, 0xf, 0xf, false); }   // wave_shr:1; lane 0 keeps `fill`
+__device__ __forceinline__ int dpp_shl1(int fill, int v) { return __builtin_amdgcn_update_dpp(fill, v, 0x130, 0xf, 0xf, false); }   // wave_shl:1: the next lane's value; lane 63 keeps `fill`
 
 // inclusive prefix maximum over the 64 lanes: row_shr 1,2,4,8 inside each 16-lane row, then row_bcast 15 and 31 carry the row totals.
 // The DPP modifier sits on the max itself (v_max_i32_dpp: dst = max(dpp(src), src)); a lane without a valid DPP source is simply not

@@ -1,0 +1,269 @@
+// ssw_band.hip -- K1gb: K1g's global and semiglobal programmes over a band of diagonals, in the band's own frame (gfx950).
+//
+// The band of a pair is [lo, hi] in d = j - i (i query letters, j reference letters), B = hi - lo + 1 <= 64 CPL diagonals.  One wave
+// takes one pair; lane l owns the CPL consecutive band positions b = d - lo = l CPL + k, the loop runs over the query rows, and
+// position b of row i is the cell (i, i + lo + b).  In this frame
+//     the diagonal source (i-1, j-1) is the lane's own cell of the row before,
+//     F's source (i-1, j) is position b + 1 of the row before: the next register, or the next lane's first (one wave_shl:1 move),
+//     E along the row is K1g's max-plus prefix scan in the frame E[p] + p ge (wave_prefix_max, one exclusive shift, CPL steps),
+// and nothing but the LDS matrix lies outside registers: the band is one chunk, there is no hand-over.  Per row step and lane:
+//     F[k] = max(Hprev[k+1] - go, Fprev[k+1] - ge)
+//     T[k] = max(Hprev[k] + s, F[k])                                  H without E
+//     X[k] = T[k] - go + (p + 1) ge  where the cell exists, else minus infinity;   V = max over k of X[k]
+//     u    = exclusive prefix maximum of V over the lanes, seeded with minus infinity
+//     E[k] = u - p ge,  H[k] = max(T[k], E[k]) where the cell exists, else minus infinity,  u = max(u, X[k])
+// A position is a cell of row i while 0 <= j <= n (and b < B): the cells of column 0 and of column n move through the positions as
+// the rows go, which is one unsigned comparison of the position's column counter per cell and selects, never a branch.  Column 0
+// needs nothing else: its cell has no diagonal source (the position held minus infinity in the row before) and no E, so H = F, the
+// gap from (0, 0), exactly while the band holds the cells above it.  Row 0 is written into the registers before the loop.  The
+// reference letter of a position moves by one per row: the letters slide down the positions with the rows (a register window, one
+// wave_shl:1 move per row), and the letter that enters at the top comes from a register loaded once per 64 rows (v_readlane), as
+// the query letter does.
+// Minus infinity is kBdNeg (clh_device.h has the bound that keeps it apart from every score).  Every cell of an admitted band is
+// reached from a start cell, so H and T of a cell are scores; E and F may be minus infinity, and then they equal no H.
+// STORE: 4 bits per cell as in K1g (H's source 0 diagonal / 1 E / 2 F, "E opened here", "F opened here"), CPL / 2 bytes per lane and
+// row, only the lanes that own a band position: m ceil(B / CPL) CPL / 2 bytes per pair.  ssw_band_walk_kernel walks them back, one
+// lane per pair: a diagonal step keeps b, a D step goes to b - 1, an I step to b + 1.
+// tools/band_model.py is this scheme in Python for any geometry; tests/band_check.py is the definition.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "clh_device.h"
+#include "clh_device_ops.h"
+
+namespace clh {
+
+__device__ __forceinline__ int bd_max(int a, int b) { return a > b ? a : b; }
+
+template <int CPL> struct BdWord;
+template <> struct BdWord<2> { typedef uint8_t type; };
+template <> struct BdWord<4> { typedef uint16_t type; };
+template <> struct BdWord<8> { typedef uint32_t type; };
+
+template <int CPL, int MODE, bool STORE>
+__global__ void __launch_bounds__(64) ssw_band_kernel(const BdParams prm, int first, int count)
+{
+    typedef typename BdWord<CPL>::type word_t;
+    constexpr int W = 64 * CPL;
+    __shared__ int smat[32 * 32];                    // [query code][reference code]
+    const int lane = threadIdx.x & 63;
+    for (int k = lane; k < 32 * 32; k += 64) {
+        const int qc = k >> 5, rc = k & 31;
+        smat[k] = (qc < prm.n_mat && rc < prm.n_mat) ? (int)prm.mat[rc * prm.n_mat + qc] : 0;
+    }
+    __syncthreads();
+    const int x = (int)blockIdx.x;
+    if (x >= count || first + x >= prm.norder) return;
+    const int pi = prm.order[first + x];
+    if (pi < 0 || pi >= prm.npairs) return;
+    const BdPair pr = prm.pairs[pi];
+    const int m = pr.m, n = pr.n, lo = pr.lo;
+    const int B = pr.hi - pr.lo + 1;
+    // a pair the plan would not have filed here leaves its row unwritten, which fetch reports
+    if (m <= 0 || n <= 0 || B < 1 || B > W || lo < -m || pr.hi > n) return;
+    const int go = prm.go, ge = prm.ge;
+    const int8_t* qry = prm.qry + pr.q_off;
+    const int8_t* ref = prm.ref + pr.r_off;
+    const int L = (B + CPL - 1) / CPL;               // lanes with a band position
+    const int64_t rowbytes = (int64_t)L * (CPL / 2);
+    bool ws_ok = true;
+    if (STORE) ws_ok = pr.ws_off >= 0 && (pr.ws_off & 15) == 0 && pr.ws_off + (int64_t)m * rowbytes <= prm.ws_cap;
+    uint8_t* wsp = (STORE && ws_ok) ? prm.ws + pr.ws_off + (size_t)lane * (CPL / 2) : nullptr;
+
+    int rc[CPL], jr[CPL], off[CPL], poff[CPL], Hp[CPL], Fp[CPL];
+#pragma unroll
+    for (int k = 0; k < CPL; ++k) {
+        const int p = lane * CPL + k, j0 = lo + p;             // the position's column in row 0
+        jr[k] = p < B ? j0 + 1 : 0x40000000;                   // its column in the row at hand; a position outside the band never is a cell
+        rc[k] = (j0 >= 0 && j0 < n) ? ((int)ref[j0] & 31) : 0; // the letter of column j0 + 1, whatever B: it slides down to the band
+        poff[k] = (int)((uint32_t)p * (uint32_t)ge);
+        off[k] = (int)((uint32_t)(p + 1) * (uint32_t)ge - (uint32_t)go);
+        const bool cell = p < B && j0 >= 0 && j0 <= n;
+        const int h0 = (MODE == EN_GLOBAL && j0 > 0) ? -(go + (j0 - 1) * ge) : 0;
+        Hp[k] = cell ? h0 : kBdNeg;
+        Fp[k] = kBdNeg;
+    }
+    const int bn = n - m - lo;                                 // the position of (m, n) in row m
+    if (MODE == EN_GLOBAL && (bn < 0 || bn >= B)) return;
+    const int ln = bn / CPL, kn = bn % CPL;
+    int corner = kBdNeg, best_v = (int)0x80000000, best_j = 0x7fffffff;
+
+    for (int i0 = 0; i0 < m; i0 += 64) {
+        const bool mine = i0 + lane < m;
+        const int qv = mine ? ((int)qry[i0 + lane] & 31) : 0;
+        const int64_t ridx = (int64_t)lo + W + i0 + lane;      // what enters at the top position after row i0 + lane + 1
+        const int rv = (ridx >= 0 && ridx < n) ? ((int)ref[ridx] & 31) : 0;
+        const int rows = m - i0 < 64 ? m - i0 : 64;
+        for (int rr = 0; rr < rows; ++rr) {
+            const int i = i0 + rr + 1;
+            const int qc = __builtin_amdgcn_readlane(qv, rr);
+            const int enter = __builtin_amdgcn_readlane(rv, rr);
+            const int hnext = dpp_shl1(kBdNeg, Hp[0]), fnext = dpp_shl1(kBdNeg, Fp[0]);
+            const int* srow = smat + qc * 32;
+            int T[CPL], F[CPL], D[CPL], H[CPL], E[CPL], X[CPL], Hu[CPL];
+            bool ok[CPL];
+            int v = kBdNeg;
+#pragma unroll
+            for (int k = 0; k < CPL; ++k) {
+                Hu[k] = k + 1 < CPL ? Hp[k + 1] : hnext;
+                const int fu = k + 1 < CPL ? Fp[k + 1] : fnext;
+                F[k] = bd_max(Hu[k] - go, fu - ge);
+                D[k] = Hp[k] + srow[rc[k]];
+                ok[k] = (uint32_t)jr[k] <= (uint32_t)n;
+                T[k] = bd_max(D[k], F[k]);
+                X[k] = ok[k] ? T[k] + off[k] : kBdNeg;
+                v = bd_max(v, X[k]);
+            }
+            int u = dpp_shr1(kBdNeg, wave_prefix_max(v));
+#pragma unroll
+            for (int k = 0; k < CPL; ++k) {
+                E[k] = u - poff[k];
+                H[k] = ok[k] ? bd_max(T[k], E[k]) : kBdNeg;
+                u = bd_max(u, X[k]);
+            }
+            if (STORE) {
+                const int nleft = dpp_shr1(kBdNeg, H[CPL - 1]);          // H of position b - 1 of this row
+                uint32_t w = 0;
+#pragma unroll
+                for (int k = 0; k < CPL; ++k) {
+                    const int left = k ? H[k - 1] : nleft;
+                    const uint32_t src = H[k] == D[k] ? 0u : (H[k] == E[k] ? 1u : 2u);
+                    const uint32_t nib = src | (E[k] == left - go ? 4u : 0u) | (F[k] == Hu[k] - go ? 8u : 0u);
+                    w |= nib << (4 * k);
+                }
+                if (wsp && lane < L) *(word_t*)(wsp + (size_t)(i - 1) * rowbytes) = (word_t)w;
+            }
+            if (i == m) {
+                if (MODE == EN_GLOBAL) {
+                    int hn = H[0];
+#pragma unroll
+                    for (int k = 1; k < CPL; ++k) hn = k == kn ? H[k] : hn;
+                    corner = hn;                                         // meaningful in lane ln
+                } else {
+#pragma unroll
+                    for (int k = 0; k < CPL; ++k)
+                        if (ok[k] && H[k] > best_v) { best_v = H[k]; best_j = jr[k]; }
+                }
+            }
+            const int r0 = rc[0];
+#pragma unroll
+            for (int k = 0; k < CPL; ++k) {
+                Hp[k] = H[k]; Fp[k] = F[k];
+                jr[k] += 1;
+                if (k + 1 < CPL) rc[k] = rc[k + 1];
+            }
+            rc[CPL - 1] = dpp_shl1(enter, r0);
+        }
+    }
+    int score, ej;
+    if (MODE == EN_GLOBAL) {
+        score = __shfl(corner, ln); ej = n;
+    } else {
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int v2 = __shfl_xor(best_v, d), j2 = __shfl_xor(best_j, d);
+            const bool take = v2 > best_v || (v2 == best_v && j2 < best_j);
+            best_v = take ? v2 : best_v; best_j = take ? j2 : best_j;
+        }
+        score = best_v; ej = best_j;
+    }
+    if (lane == 0) {
+        int32_t* row = prm.rows + (size_t)pi * 8;
+        row[0] = score;
+        row[1] = MODE == EN_GLOBAL ? 0 : -1;                      // begins: the walk's, unless the mode fixes them
+        row[2] = ej - 1;
+        row[3] = 0;
+        row[4] = m - 1;
+        row[5] = 0;
+        row[6] = 0;
+        row[7] = (STORE && !ws_ok) ? EN_ST_NO_WALK : 0;
+    }
+}
+
+// one lane per pair: walk the stored decisions back from the end cell (K1g's rules: diagonal, then E, then F; a gap is left as soon
+// as "opened here" is set), in the band's frame; BAM ops M 0, I 1, D 2; at most i + j + 2 steps
+__global__ void ssw_band_walk_kernel(const BdParams prm, int first, int count)
+{
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= count || first + x >= prm.npairs) return;
+    const BdPair pr = prm.pairs[first + x];
+    const int m = pr.m, n = pr.n;
+    if (m <= 0 || n <= 0) return;
+    int32_t* row = prm.rows + (size_t)(first + x) * 8;
+    if (row[7] != 0) return;                                     // unwritten, or without stored decisions: fetch reports it
+    const int B = pr.hi - pr.lo + 1;
+    static_assert(kBdCpl[0] == 2 && kBdCpl[1] == 4 && kBdCpl[2] == 8, "the class index is log2(CPL) - 1");
+    if (pr.cls < 0 || pr.cls >= kBdClasses) { row[7] = EN_ST_NO_WALK; return; }
+    const int cpl = 2 << pr.cls;
+    if (B < 1 || B > 64 * cpl) { row[7] = EN_ST_NO_WALK; return; }
+    const int64_t rowbytes = (int64_t)((B + cpl - 1) / cpl) * (cpl / 2);
+    const int64_t nbytes = (int64_t)m * rowbytes;
+    if (pr.ws_off < 0 || pr.ws_off + nbytes > prm.ws_cap || pr.cig_off < 0 || pr.cig_off + pr.cig_cap > prm.cigar_cap) { row[7] = EN_ST_NO_WALK; return; }
+    const uint8_t* ws = prm.ws + pr.ws_off;
+    uint32_t* out = prm.cigar + pr.cig_off;
+    int i = row[4] + 1, j = row[2] + 1;
+    if (i < 0 || i > m || j < 0 || j > n) { row[7] = EN_ST_NO_WALK; return; }
+    const int steps = i + j + 2;
+    int state = 0, nops = 0, cur = -1, run = 0;
+    bool bad = false, done = false;
+    auto emit = [&](int op, int k) {
+        if (k <= 0) return;
+        if (op == cur) { run += k; return; }
+        if (run) { if (nops < pr.cig_cap) out[nops++] = ((uint32_t)run << 4) | (uint32_t)cur; else bad = true; }
+        cur = op; run = k;
+    };
+    for (int step = 0; step < steps && !done; ++step) {
+        if (state == 0 && (i == 0 || j == 0)) {
+            if (prm.mode == EN_GLOBAL) { emit(2, j); emit(1, i); i = 0; j = 0; }
+            else if (j == 0) { emit(1, i); i = 0; }
+            done = true;
+            break;
+        }
+        const int b = j - i - pr.lo;
+        const int64_t bi = (int64_t)(i - 1) * rowbytes + (b >> 1);
+        if (b < 0 || b >= B || i < 1 || bi < 0 || bi >= nbytes) { bad = true; break; }
+        const uint32_t nib = ((uint32_t)ws[bi] >> (4 * (b & 1))) & 15u;
+        if (state == 0) {
+            state = (int)(nib & 3u);                             // a gap state takes its first letter from this same cell
+            if (state == 0) { emit(0, 1); --i; --j; continue; }
+        }
+        if (state == 1) { emit(2, 1); --j; if (nib & 4u) state = 0; }
+        else if (state == 2) { emit(1, 1); --i; if (nib & 8u) state = 0; }
+        else { bad = true; break; }
+    }
+    emit(-2, 1);                                                 // flush the last run
+    if (bad || !done) { row[7] = EN_ST_NO_WALK; return; }
+    for (int a = 0, b = nops - 1; a < b; ++a, --b) { const uint32_t w = out[a]; out[a] = out[b]; out[b] = w; }
+    row[1] = j; row[3] = i; row[5] = nops;
+}
+
+template <int CPL>
+static void bd_launch(const BdParams& p, bool store, int first, int count, hipStream_t st)
+{
+    if (p.mode == EN_GLOBAL) {
+        if (store) hipLaunchKernelGGL((ssw_band_kernel<CPL, EN_GLOBAL, true>), dim3(count), dim3(64), 0, st, p, first, count);
+        else hipLaunchKernelGGL((ssw_band_kernel<CPL, EN_GLOBAL, false>), dim3(count), dim3(64), 0, st, p, first, count);
+    } else {
+        if (store) hipLaunchKernelGGL((ssw_band_kernel<CPL, EN_SEMIGLOBAL, true>), dim3(count), dim3(64), 0, st, p, first, count);
+        else hipLaunchKernelGGL((ssw_band_kernel<CPL, EN_SEMIGLOBAL, false>), dim3(count), dim3(64), 0, st, p, first, count);
+    }
+}
+
+hipError_t launch_ssw_band(const BdParams& p, int cls, bool store, int first, int count, hipStream_t stream)
+{
+    if (count <= 0) return hipSuccess;
+    if (p.mode != EN_GLOBAL && p.mode != EN_SEMIGLOBAL) return hipErrorInvalidValue;
+    if (cls == 0) bd_launch<2>(p, store, first, count, stream);
+    else if (cls == 1) bd_launch<4>(p, store, first, count, stream);
+    else if (cls == 2) bd_launch<8>(p, store, first, count, stream);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+hipError_t launch_ssw_band_walk(const BdParams& p, int first, int count, hipStream_t stream)
+{
+    if (count <= 0) return hipSuccess;
+    hipLaunchKernelGGL(ssw_band_walk_kernel, dim3((count + 63) / 64), dim3(64), 0, stream, p, first, count);
+    return hipGetLastError();
+}
+
+}  // namespace clh

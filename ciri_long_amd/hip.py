@@ -62,6 +62,15 @@ class EndsOpts(C.Structure):
 ENDS_DTYPE = np.dtype([('score', '<i4'), ('ref_begin', '<i4'), ('ref_end', '<i4'), ('query_begin', '<i4'), ('query_end', '<i4'),
                        ('cigar_len', '<i4'), ('cigar_off', '<i8')])
 ENDS_MODES = {'global': 0, 'semiglobal': 1, 'overlap': 2}
+
+
+class BandOpts(C.Structure):
+    _fields_ = [('mode', C.c_int32), ('mat', C.c_void_p), ('n_mat', C.c_int32), ('gap_open', C.c_int32), ('gap_extend', C.c_int32),
+                ('want_cigar', C.c_int32), ('workspace_bytes', C.c_int64), ('band', C.c_int32), ('reserved', C.c_int32)]
+
+
+BAND_DTYPE = np.dtype([('score', '<i4'), ('ref_begin', '<i4'), ('ref_end', '<i4'), ('query_begin', '<i4'), ('query_end', '<i4'),
+                       ('cigar_len', '<i4'), ('cigar_off', '<i8'), ('band_lo', '<i4'), ('band_hi', '<i4'), ('exact', '<i4'), ('reserved', '<i4')])
 EDIT_SEARCH_DTYPE = np.dtype([('distance', '<i4'), ('start', '<i4'), ('end', '<i4'), ('last_end', '<i4'), ('nlocs', '<i4')])
 EDIT_ALIGN_DTYPE = np.dtype([('distance', '<i4'), ('nlocs', '<i4'), ('loc_off', '<i8'), ('cigar_off', '<i8'), ('cigar_len', '<i4'),
                              ('status', '<i4'), ('alphabet_len', '<i4'), ('reserved', '<i4')])
@@ -178,6 +187,16 @@ def lib():
         L.clh_ends_plan_timing.argtypes = [C.c_void_p, C.c_void_p]
         L.clh_ends_plan_info.argtypes = [C.c_void_p, C.c_void_p]
         L.clh_ends_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(EndsOpts), C.c_void_p,
+                                     C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+        L.clh_band_plan_create.restype = C.c_void_p
+        L.clh_band_plan_create.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BandOpts)]
+        L.clh_band_plan_destroy.restype = None
+        L.clh_band_plan_destroy.argtypes = [C.c_void_p]
+        L.clh_band_plan_run.argtypes = [C.c_void_p, C.c_void_p]
+        L.clh_band_plan_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+        L.clh_band_plan_timing.argtypes = [C.c_void_p, C.c_void_p]
+        L.clh_band_plan_info.argtypes = [C.c_void_p, C.c_void_p]
+        L.clh_band_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BandOpts), C.c_void_p,
                                      C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
         L.clh_poa_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]
@@ -506,6 +525,21 @@ class Context(object):
     def ends_plan(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode='global', want_cigar=True, workspace_bytes=0):
         return EndsPlan(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode, want_cigar, workspace_bytes)
 
+    def band_batch(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, band, mode='global', diagonals=None, want_cigar=True,
+                   workspace_bytes=0):
+        """Banded end-anchored alignment of the pairs (query k, reference k) through K1gb: the programme of ends_batch over the
+        diagonals within `band` of the corner diagonals, or of diagonals[k] -> (rows BAND_DTYPE, cigars uint32 packed ops).  See BandPlan."""
+        plan = BandPlan(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, band, mode, diagonals, want_cigar, workspace_bytes)
+        try:
+            plan.run()
+            return plan.fetch()
+        finally:
+            plan.close()
+
+    def band_plan(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, band, mode='global', diagonals=None, want_cigar=True,
+                  workspace_bytes=0):
+        return BandPlan(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, band, mode, diagonals, want_cigar, workspace_bytes)
+
     def ccs_file(self, in_path, is_fastq, ccs_fa_path, raw_fa_path, batch_reads=0, first_record=0, max_records=-1, byte_offset=0):
         """Stage 1 from file to file in native code -> (total_reads, reads_with_consensus, reads_too_long); with
         first_record / max_records for one rank's contiguous shard of the records, counted from `byte_offset` (the first byte of a
@@ -786,6 +820,70 @@ class EndsPlan(_Handle):
         _check(lib().clh_ends_plan_info(self._h, out), 'clh_ends_plan_info')
         return {'cpl': int(out[0]), 'chunk': int(out[1]), 'shares': int(out[2]), 'workspace_bytes': int(out[3]), 'max_pair_bytes': int(out[4]),
                 'kernel_pairs': int(out[5]), 'empty_pairs': int(out[6]), 'cigar_cap': int(out[7])}
+
+
+class BandPlan(_Handle):
+    """Pairs resident on the GPU for K1gb, the global and semiglobal programmes of EndsPlan over a band of diagonals d = j - i per
+    pair: [min(0, n - m) - band, max(0, n - m) + band], or [diagonals[k] - band, diagonals[k] + band] with a hint per pair, clipped
+    to [-m, n] and at most 512 wide.  run() any number of times, fetch() (rows BAND_DTYPE, cigars uint32).  A row carries the
+    clipped band and `exact`: 1 where it is proved that EndsPlan returns the same row and CIGAR (include/ciri_long_hip.h)."""
+    _destroy = 'clh_band_plan_destroy'
+
+    def __init__(self, ctx, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, band, mode='global', diagonals=None, want_cigar=True,
+                 workspace_bytes=0):
+        _Handle.__init__(self, ctx)
+        if mode not in ENDS_MODES:
+            raise ValueError('mode must be one of global, semiglobal, got %r' % (mode,))
+        q = np.ascontiguousarray(queries, dtype=np.int8); r = np.ascontiguousarray(refs, dtype=np.int8)
+        q_off = np.ascontiguousarray(query_off, dtype=np.int64); r_off = np.ascontiguousarray(ref_off, dtype=np.int64)
+        if len(q_off) != len(r_off) or len(q_off) < 1:
+            raise ValueError('BandPlan: the two offset tables differ in length')
+        self.n = len(q_off) - 1
+        self.want_cigar = bool(want_cigar)
+        diag = None
+        if diagonals is not None:
+            diag = np.ascontiguousarray(diagonals, dtype=np.int32)
+            if diag.shape != (self.n,):
+                raise ValueError('BandPlan: %d diagonals for %d pairs' % (diag.size, self.n))
+        mat = np.ascontiguousarray(mat, dtype=np.int8).reshape(-1)
+        n_mat = int(round(len(mat) ** 0.5))
+        if n_mat * n_mat != len(mat):
+            raise ValueError('BandPlan: the substitution matrix is not square')
+        if not 0 <= int(band) < 2 ** 31:
+            raise ValueError('BandPlan: band must be a half-width >= 0, got %r' % (band,))
+        opts = BandOpts(ENDS_MODES[mode], mat.ctypes.data, n_mat, int(gap_open), int(gap_extend), int(self.want_cigar), int(workspace_bytes), int(band), 0)
+        self._h = lib().clh_band_plan_create(ctx._h, self.n, q.ctypes.data, q_off.ctypes.data, r.ctypes.data, r_off.ctypes.data,
+                                             diag.ctypes.data if diag is not None else None, C.byref(opts))
+        if not self._h:
+            raise ClhError('clh_band_plan_create failed: %s' % last_error())
+
+    def run(self, stream=0):
+        _check(lib().clh_band_plan_run(self._h, C.c_void_p(stream)), 'clh_band_plan_run')
+
+    def fetch(self):
+        rows = np.zeros(self.n, dtype=BAND_DTYPE)
+        cap = self.info()['cigar_cap'] if self.want_cigar else 0
+        cig = np.empty(max(cap, 1), dtype=np.uint32)     # worst-case capacity; only the used prefix is written
+        used = C.c_int64(0)
+        _check(lib().clh_band_plan_fetch(self._h, rows.ctypes.data, cig.ctypes.data if self.want_cigar else None, cap, C.byref(used)),
+               'clh_band_plan_fetch')
+        return rows, cig[:used.value].copy()
+
+    def timing(self):
+        """HIP-event milliseconds of the last run: the score kernels of every class, and with CIGARs the walks, of every share"""
+        ms = C.c_float(0)
+        _check(lib().clh_band_plan_timing(self._h, C.byref(ms)), 'clh_band_plan_timing')
+        return float(ms.value)
+
+    def info(self):
+        """the classes of the kernel: band positions a lane owns (cpl; a class holds bands of up to 64 cpl diagonals); and of this plan:
+        the greatest clipped width, shares the batch was cut into so that a share's stored decisions fit the workspace, workspace bytes
+        in use, those of the largest pair, pairs the kernels take per class, pairs with an empty side, CIGAR ops fetch may return"""
+        out = (C.c_int64 * 12)()
+        _check(lib().clh_band_plan_info(self._h, out), 'clh_band_plan_info')
+        return {'cpl': [int(out[c]) for c in range(3)], 'max_width': int(out[3]), 'shares': int(out[4]), 'workspace_bytes': int(out[5]),
+                'max_pair_bytes': int(out[6]), 'class_pairs': [int(out[7 + c]) for c in range(3)], 'empty_pairs': int(out[10]),
+                'cigar_cap': int(out[11])}
 
 
 def flatten_splice_sites(ss_index, offset, length):

@@ -378,3 +378,58 @@ def align_pairs_ends(ref_seqs, query_seqs, mode='global', match=2, mismatch=2, g
         res.cigar_string = res._cigar_string(ops, int(qo[k + 1] - qo[k])) if report_cigar else None
         out.append(res)
     return out
+
+
+def align_pairs_band(ref_seqs, query_seqs, band, mode='global', diagonals=None, match=2, mismatch=2, gap_open=3, gap_extend=1, report_cigar=False,
+                     matrix=None, alphabet=None, context=None):
+    """``align_pairs_ends`` over a band of diagonals, in one GPU call -> one PyAlignRes per pair.
+
+    With i query and j reference letters consumed, only cells with lo <= j - i <= hi exist: lo = min(0, n - m) - band and hi =
+    max(0, n - m) + band (the corner diagonals of the m x n pair widened by `band`), or diagonals[k] - band and diagonals[k] + band
+    where a placement is known (a seed, a minimizer hit, an ``edlib.search`` location: the diagonal is reference position minus
+    query position); both clipped to [-m, n], at most 512 diagonals.  mode is 'global' or 'semiglobal'; scores, coordinates, tie
+    rules and the CIGAR are those of ``align_pairs_ends``, and every result is the best alignment that stays inside the band.  Each
+    result also carries ``band`` = (lo, hi) as clipped, and ``band_exact``: True where it is proved that ``align_pairs_ends`` returns
+    the same result and CIGAR (False: not proved; they may still be equal).  The cost is m x (hi - lo + 1) cells, not m x n, and
+    CIGARs need half a byte per cell of the band.  A band that holds no alignment, 'overlap', and a band above 512 diagonals raise
+    hip.ClhError."""
+    if mode not in ('global', 'semiglobal'):
+        raise ValueError("align_pairs_band: mode must be 'global' or 'semiglobal'%s, got %r"
+                         % (" ('overlap' with a band is not built)" if mode == 'overlap' else '', mode))
+    if len(ref_seqs) != len(query_seqs):
+        raise ValueError('align_pairs_band: %d references vs %d queries' % (len(ref_seqs), len(query_seqs)))
+    if diagonals is not None and len(diagonals) != len(ref_seqs):
+        raise ValueError('align_pairs_band: %d diagonals vs %d pairs' % (len(diagonals), len(ref_seqs)))
+    if int(band) != band or band < 0:
+        raise ValueError('align_pairs_band: band is a half-width in diagonals, an integer >= 0, got %r' % (band,))
+    if (matrix is None) != (alphabet is None):
+        raise ValueError('align_pairs_band: matrix and alphabet come together')
+    if matrix is not None:
+        mat = _int8_matrix(matrix, 'align_pairs_band')
+        if mat.size != len(alphabet) ** 2 or not 1 <= len(alphabet) <= 32:
+            raise ValueError('align_pairs_band: a %d-letter alphabet needs a %d x %d matrix (1..32 letters)' % (len(alphabet), len(alphabet), len(alphabet)))
+        enc = lambda s: encode_alphabet(s, alphabet) if isinstance(s, (str, bytes)) else np.asarray(s, dtype=np.int8)
+    else:
+        mat = hip.score_matrix(match, mismatch)
+        enc = lambda s: hip.encode(s) if isinstance(s, (str, bytes)) else np.asarray(s, dtype=np.int8)
+    if not ref_seqs:
+        return []
+    qd, qo = hip.pack([enc(q) for q in query_seqs])
+    rd, ro = hip.pack([enc(r) for r in ref_seqs])
+    ctx = context or hip.default_context()
+    walk = bool(report_cigar) or mode != 'global'          # the begins come from the walk, unless the mode fixes them
+    rows, cig = ctx.band_batch(qd, qo, rd, ro, mat, gap_open, gap_extend, int(band), mode=mode, diagonals=diagonals, want_cigar=walk)
+    out = []
+    for k in range(len(rows)):
+        r = rows[k]
+        ops = cig[int(r['cigar_off']):int(r['cigar_off']) + int(r['cigar_len'])] if walk else ()
+        res = PyAlignRes.__new__(PyAlignRes)
+        res.score = int(r['score'])
+        res.ref_begin, res.ref_end = int(r['ref_begin']), int(r['ref_end'])
+        res.query_begin, res.query_end = int(r['query_begin']), int(r['query_end'])
+        res.score2 = res.ref_end2 = None
+        res.cigar_string = res._cigar_string(ops, int(qo[k + 1] - qo[k])) if report_cigar else None
+        res.band = (int(r['band_lo']), int(r['band_hi']))
+        res.band_exact = bool(r['exact'])
+        out.append(res)
+    return out

@@ -420,6 +420,54 @@ int clh_ends_plan_info(clh_ends_plan* plan, int64_t* out);
 int clh_ends_batch(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off, const clh_ends_opts* opts,
                    clh_ends_row* rows, uint32_t* cigar, int64_t cigar_cap, int64_t* cigar_used);
 
+/* ---- banded end-anchored alignment of pairs around a diagonal: global, semiglobal (K1gb) ------------------------------------------
+ * The programme of clh_ends_* over a band.  The band of pair k is a closed interval of diagonals [lo, hi], d = j - i: without a hint
+ * (diag == NULL) lo = min(0, n - m) - band, hi = max(0, n - m) + band; with diag[k], lo = diag[k] - band, hi = diag[k] + band; both
+ * are then clipped to [-m, n], and everything below is about the clipped band.  Every cell outside the band is minus infinity in H, E
+ * and F, and row 0 and column 0 come from the same recurrences, started at (0, 0), not from a formula: so every score is the score
+ * of an alignment all of whose cells lie in the band.  CLH_ENDS_GLOBAL: H[0][j] = E[0][j] is the gap of j letters where the band
+ * holds it, column 0 likewise through F, the end cell is (m, n).  CLH_ENDS_SEMIGLOBAL: row 0 is 0 on the band's cells, column 0 is
+ * reached only while (0, 0) and the cells below it are in the band, the end cell is the greatest H[m][j] over the band's cells of
+ * row m, smallest j.  The walk back is that of clh_ends_*; a source outside the band is no source.
+ * create fails -- each message names the first such pair -- with CLH_E_ARG for a global band that misses (0, 0) or (m, n), lo >
+ * min(0, n - m) or hi < max(0, n - m); with CLH_E_ARG for a semiglobal band with hi < 0 (no start cell) or lo > n - m (no end cell).
+ * These conditions guarantee a path inside the band.  Global: the band holds every diagonal between 0 and n - m, so the gap from (0,
+ * 0) to diagonal n - m, then that diagonal to (m, n), lies in it.  Semiglobal: d = min(hi, n - m) is a diagonal of the band, since lo
+ * <= hi and lo <= n - m.  If d >= 0 the cells (0, d) .. (m, m + d) exist (m + d <= n) and are a path.  If d < 0 then d = n - m, as hi
+ * >= 0; the band holds the diagonals d .. 0, and column 0 from (0, 0) down to (-d, 0), then diagonal d to (m, n), is a path.  By the
+ * same steps every cell of such a band is reached from a start cell, which is what lets the kernel tell scores from minus
+ * infinity.  Further refusals: CLH_E_UNSUPPORTED for CLH_ENDS_OVERLAP (a banded overlap is not built) and for gap_open < gap_extend;
+ * CLH_E_CAPACITY for a clipped band of more than 512 diagonals (clh_ends_* takes such pairs over the full matrix) and for one pair
+ * whose stored decisions -- half a byte per cell of the band, m ceil(B / CPL) CPL / 2 bytes -- exceed workspace_bytes (0: 1 GiB);
+ * CLH_E_ARG for a code outside the matrix and for a pair with (m + n + 1024) max(|s|, gap_open, gap_extend, 1) >= 2^29: the cells
+ * are int32 and minus infinity is -2^30, so every score, also moved into the scan's frame (+ at most 512 gap_extend), stays inside
+ * (-2^29, 2^29) while anything derived from minus infinity stays below -2^29 and above INT32_MIN.
+ * Row k: the fields of clh_ends_row, the clipped band, and `exact`: 1 means it is proved that clh_ends_* returns the same row and
+ * the same CIGAR, 0 that it is not proved (they may still be equal).  A global alignment that leaves the band reaches diagonal hi +
+ * 1 or lo - 1 and therefore has two gap runs of known least lengths and a bounded number of M columns; with s+ = max(0, greatest
+ * matrix entry) its score is at most
+ *     ub_top = s+ max(0, n - hi - 1) - 2 go - (2 (hi + 1) - (n - m) - 2) ge      if hi + 1 <= n
+ *     ub_bot = s+ max(0, m + lo - 1) - 2 go - (2 (1 - lo) + (n - m) - 2) ge      if lo - 1 >= -m
+ * and exact = 1 iff the banded score is STRICTLY above both, or neither applies (the band is the whole matrix).  Semiglobal rows get
+ * 1 only when the band is the whole matrix.  Host arithmetic in int64.  A pair with an empty side never reaches a kernel; fetch
+ * states the boundary cell the band holds.  info: out[12] = {band positions a lane owns in class 0, 1, 2 (a pair is filed under the
+ * first class whose 64 lanes hold its band), the greatest clipped width, shares of the batch, workspace bytes in use, those of the
+ * largest pair, pairs the kernels take in class 0, 1, 2, pairs with an empty side, CIGAR ops fetch may return}.  Life cycle, error
+ * codes, fetch's failures and `stream` as clh_ends_plan_*. */
+typedef struct { int32_t mode; const int8_t* mat; int32_t n_mat; int32_t gap_open, gap_extend; int32_t want_cigar; int64_t workspace_bytes; int32_t band; int32_t reserved; } clh_band_opts;
+typedef struct { int32_t score, ref_begin, ref_end, query_begin, query_end, cigar_len; int64_t cigar_off; int32_t band_lo, band_hi, exact, reserved; } clh_band_row;
+typedef struct clh_band_plan clh_band_plan;
+clh_band_plan* clh_band_plan_create(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off,
+                                    const int32_t* diag, const clh_band_opts* opts);
+void clh_band_plan_destroy(clh_band_plan* plan);
+int clh_band_plan_run(clh_band_plan* plan, void* stream);
+int clh_band_plan_fetch(clh_band_plan* plan, clh_band_row* rows, uint32_t* cigar, int64_t cigar_cap, int64_t* cigar_used);
+int clh_band_plan_timing(clh_band_plan* plan, float* ms);     /* HIP events around the last run */
+int clh_band_plan_info(clh_band_plan* plan, int64_t* out);
+/* create + run + fetch */
+int clh_band_batch(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off, const int32_t* diag,
+                   const clh_band_opts* opts, clh_band_row* rows, uint32_t* cigar, int64_t cigar_cap, int64_t* cigar_used);
+
 /* ASCII -> codes exactly as ssw_wrap.py:234-252 (A/a C/c G/g T/t N/n, anything else 4), on the host. */
 void clh_encode_dna(const char* seq, int64_t len, int8_t* out);
 
