@@ -1,6 +1,7 @@
 // clh_api.hip -- host side of libclh.so: contexts, batch plans, launches, and the reference's legacy symbols.
 // Public interface and the reference lines each entry point replaces: include/ciri_long_hip.h, include/ssw_legacy.h.
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -131,11 +132,13 @@ extern "C" void clh_destroy(clh_ctx* c)
 extern "C" int clh_device_of(const clh_ctx* c) { return c ? c->device : -1; }
 
 // What every plan kind and the resident genome share: the device blocks they take from the context's allocator and the
-// events they create are recorded as they are handed out, and deleting the object gives all of them back.
+// events they create are recorded as they are handed out, and deleting the object gives all of them back.  Plans whose run is
+// timed as a whole bracket it with begin_run / end_run, and their *_plan_timing reads elapsed.
 struct clh_owned {
     clh_ctx* ctx = nullptr;
     bool ran = false;
     hipStream_t last_stream = nullptr;
+    hipEvent_t run_ev[2] = {nullptr, nullptr};  // around the last run (created by the first)
     std::vector<void*> blocks;
     std::vector<hipEvent_t> events;
 
@@ -174,6 +177,28 @@ struct clh_owned {
         const hipError_t r = hipEventCreateWithFlags(e, flags);
         if (r == hipSuccess) events.push_back(*e);
         return r;
+    }
+    // the start of a timed run: the device, the stream (the context's own unless one is given), the first event.  From here on
+    // the destructor waits for the stream, whatever becomes of the launches that follow.
+    int begin_run(void* stream_, hipStream_t* st)
+    {
+        HIPCHK(hipSetDevice(ctx->device));
+        *st = stream_ ? (hipStream_t)stream_ : ctx->stream;
+        if (!run_ev[0]) for (auto& e : run_ev) HIPCHK(event(&e));
+        HIPCHK(hipEventRecord(run_ev[0], *st));
+        last_stream = *st; ran = true;
+        return 0;
+    }
+    int end_run()
+    {
+        HIPCHK(hipEventRecord(run_ev[1], last_stream));
+        return 0;
+    }
+    int elapsed(float* ms)
+    {
+        HIPCHK(hipEventSynchronize(run_ev[1]));
+        HIPCHK(hipEventElapsedTime(ms, run_ev[0], run_ev[1]));
+        return 0;
     }
 };
 
@@ -1251,7 +1276,6 @@ struct clh_edit_plan : clh_owned {
     std::vector<clh::EdTask> tasks;          // launch order (by lane-group class, longest text first)
     std::vector<int32_t> trivial;            // out[k] for pairs with an empty side, -1 otherwise
     void *d_sym = nullptr, *d_tasks = nullptr, *d_out = nullptr, *d_carry = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
 };
 
 static int ed_group(const clh::EdTask& t) { int B = (t.pat_len + 63) >> 6, G = 1; while (G < B && G < 64) G <<= 1; return G; }   // above 64 blocks: passes
@@ -1316,10 +1340,8 @@ extern "C" clh_edit_plan* clh_edit_plan_create(clh_ctx* ctx, int32_t n, const ui
 extern "C" int clh_edit_plan_run(clh_edit_plan* pl, void* stream_)
 {
     if (!pl) return fail(CLH_E_ARG, "clh_edit_plan_run: null argument");
-    HIPCHK(hipSetDevice(pl->ctx->device));
-    hipStream_t st = stream_ ? (hipStream_t)stream_ : pl->ctx->stream;
-    if (!pl->ev[0]) for (auto& e : pl->ev) HIPCHK(pl->event(&e));
-    HIPCHK(hipEventRecord(pl->ev[0], st));
+    hipStream_t st;
+    if (int rc = pl->begin_run(stream_, &st)) return rc;
     const int nt = (int)pl->tasks.size();
     for (int i = 0; i < nt;) {
         const int G = ed_group(pl->tasks[(size_t)i]);
@@ -1328,9 +1350,7 @@ extern "C" int clh_edit_plan_run(clh_edit_plan* pl, void* stream_)
         HIPCHK(clh::launch_edit_distance((const uint8_t*)pl->d_sym, (const clh::EdTask*)pl->d_tasks + i, j - i, G, pl->planes, (int32_t*)pl->d_out, (int8_t*)pl->d_carry, st));
         i = j;
     }
-    HIPCHK(hipEventRecord(pl->ev[1], st));
-    pl->last_stream = st; pl->ran = true;
-    return 0;
+    return pl->end_run();
 }
 
 extern "C" int clh_edit_plan_fetch(clh_edit_plan* pl, int32_t* out)
@@ -1348,9 +1368,7 @@ extern "C" int clh_edit_plan_fetch(clh_edit_plan* pl, int32_t* out)
 extern "C" int clh_edit_plan_timing(clh_edit_plan* pl, float* ms)
 {
     if (!pl || !ms || !pl->ran) return fail(CLH_E_ARG, "clh_edit_plan_timing: no run to time");
-    HIPCHK(hipEventSynchronize(pl->ev[1]));
-    HIPCHK(hipEventElapsedTime(ms, pl->ev[0], pl->ev[1]));
-    return 0;
+    return pl->elapsed(ms);
 }
 
 extern "C" int clh_edit_distance_batch(clh_ctx* ctx, int32_t n, const uint8_t* a, const int64_t* a_off, const uint8_t* b, const int64_t* b_off,
@@ -1380,7 +1398,6 @@ struct clh_edit_matrix_plan : clh_owned {
     clh::EmCtl ctl;                            // as the last run left it
     void *d_raw = nullptr, *d_hpc = nullptr, *d_seq_off = nullptr, *d_len = nullptr, *d_group_off = nullptr, *d_pair_base = nullptr;
     void *d_tasks = nullptr, *d_out = nullptr, *d_ctl = nullptr, *d_carry = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
 };
 
 extern "C" void clh_edit_matrix_plan_destroy(clh_edit_matrix_plan* pl) { delete pl; }
@@ -1468,11 +1485,8 @@ extern "C" clh_edit_matrix_plan* clh_edit_matrix_plan_create(clh_ctx* ctx, int32
 extern "C" int clh_edit_matrix_plan_run(clh_edit_matrix_plan* pl, void* stream_)
 {
     if (!pl) return fail(CLH_E_ARG, "clh_edit_matrix_plan_run: null argument");
-    HIPCHK(hipSetDevice(pl->ctx->device));
-    hipStream_t st = stream_ ? (hipStream_t)stream_ : pl->ctx->stream;
-    if (!pl->ev[0]) for (auto& e : pl->ev) HIPCHK(pl->event(&e));
-    HIPCHK(hipEventRecord(pl->ev[0], st));
-    pl->last_stream = st; pl->ran = true;
+    hipStream_t st;
+    if (int rc = pl->begin_run(stream_, &st)) return rc;
     HIPCHK(hipMemsetAsync(pl->d_ctl, 0, sizeof(clh::EmCtl), st));
     if (pl->hpc) HIPCHK(clh::launch_hpc_compress((const uint8_t*)pl->d_raw, (const int64_t*)pl->d_seq_off, pl->nseq, (uint8_t*)pl->d_hpc, (int32_t*)pl->d_len, st));
     clh::EmParams p;
@@ -1488,7 +1502,7 @@ extern "C" int clh_edit_matrix_plan_run(clh_edit_matrix_plan* pl, void* stream_)
     HIPCHK(hipStreamSynchronize(st));
     if (pl->ctl.no_carry) {
         // such a pair was counted in its class but has no task: the class lists are not complete, so K4 does not run on them
-        HIPCHK(hipEventRecord(pl->ev[1], st));
+        if (int rc = pl->end_run()) return rc;
         return fail(CLH_E_CAPACITY, "clh_edit_matrix_plan_run: " + std::to_string(pl->ctl.no_carry) + " pairs of strings above 4096 symbols found no room for their between-pass deltas (" +
                     std::to_string(pl->ctl.carry_used64 * 64) + " bytes asked for, " + std::to_string(pl->carry_cap64 * 64) + " there)");
     }
@@ -1498,8 +1512,7 @@ extern "C" int clh_edit_matrix_plan_run(clh_edit_matrix_plan* pl, void* stream_)
         HIPCHK(clh::launch_edit_distance(sym, (const clh::EdTask*)pl->d_tasks + at, (int)pl->ctl.count[c], 1 << c, pl->planes, (int32_t*)pl->d_out, (int8_t*)pl->d_carry, st));
         at += pl->ctl.count[c];
     }
-    HIPCHK(hipEventRecord(pl->ev[1], st));
-    return 0;
+    return pl->end_run();
 }
 
 extern "C" int clh_edit_matrix_plan_sizes(clh_edit_matrix_plan* pl, int64_t* npairs, int64_t* hpc_bytes)
@@ -1539,9 +1552,7 @@ extern "C" int clh_edit_matrix_plan_fetch(clh_edit_matrix_plan* pl, int32_t* dis
 extern "C" int clh_edit_matrix_plan_timing(clh_edit_matrix_plan* pl, float* ms)
 {
     if (!pl || !ms || !pl->ran) return fail(CLH_E_ARG, "clh_edit_matrix_plan_timing: no run to time");
-    HIPCHK(hipEventSynchronize(pl->ev[1]));
-    HIPCHK(hipEventElapsedTime(ms, pl->ev[0], pl->ev[1]));
-    return 0;
+    return pl->elapsed(ms);
 }
 
 extern "C" int clh_edit_matrix_batch(clh_ctx* ctx, int32_t nseq, const uint8_t* seqs, const int64_t* seq_off, int32_t ngroups, const int64_t* group_off,
@@ -1577,7 +1588,6 @@ struct clh_edit_align_plan : clh_owned {
          *d_slot_pair = nullptr, *d_rev_tasks = nullptr, *d_paths = nullptr, *d_path_tasks = nullptr, *d_ws = nullptr, *d_cig = nullptr,
          *d_cig_len = nullptr, *d_carry_score = nullptr, *d_carry_rev = nullptr, *d_carry_path = nullptr, *d_eq_off = nullptr,
          *d_eq_list = nullptr, *d_eqm = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
 };
 
 static int ea_group(int m) { int B = (m + 63) >> 6, G = 1; while (G < B && G < 64) G <<= 1; return G; }
@@ -1798,10 +1808,8 @@ static clh::EaParams ea_params(const clh_edit_align_plan* pl)
 extern "C" int clh_edit_align_plan_run(clh_edit_align_plan* pl, void* stream_)
 {
     if (!pl) return fail(CLH_E_ARG, "clh_edit_align_plan_run: null argument");
-    HIPCHK(hipSetDevice(pl->ctx->device));
-    hipStream_t st = stream_ ? (hipStream_t)stream_ : pl->ctx->stream;
-    if (!pl->ev[0]) for (auto& e : pl->ev) HIPCHK(pl->event(&e));
-    HIPCHK(hipEventRecord(pl->ev[0], st));
+    hipStream_t st;
+    if (int rc = pl->begin_run(stream_, &st)) return rc;
     const size_t nk = (size_t)std::max(pl->nk, 1);
     HIPCHK(hipMemsetAsync(pl->d_cnt, 0xff, 4 * nk, st));       // -1: no result (a kernel that left a pair out is caught by fetch)
     HIPCHK(hipMemsetAsync(pl->d_cig_len, 0xff, 4 * nk, st));
@@ -1832,9 +1840,7 @@ extern "C" int clh_edit_align_plan_run(clh_edit_align_plan* pl, void* stream_)
             HIPCHK(clh::launch_edit_align(p, clh::EA_STORE, (const clh::EaTask*)pl->d_path_tasks + l.a, (int)(l.b - l.a), l.G, pl->planes, pl->eq, st));
         HIPCHK(clh::launch_edit_align_traceback(p, ph, pt, ch.b - ch.a, (uint32_t*)pl->d_cig, (int32_t*)pl->d_cig_len, st));
     }
-    HIPCHK(hipEventRecord(pl->ev[1], st));
-    pl->last_stream = st; pl->ran = true;
-    return 0;
+    return pl->end_run();
 }
 
 // capacities: a pair has at most n + 1 optimal columns; its CIGAR at most m + n ops
@@ -1933,9 +1939,7 @@ extern "C" int clh_edit_align_plan_fetch(clh_edit_align_plan* pl, clh_edit_align
 extern "C" int clh_edit_align_plan_timing(clh_edit_align_plan* pl, float* ms)
 {
     if (!pl || !ms || !pl->ran) return fail(CLH_E_ARG, "clh_edit_align_plan_timing: no run to time");
-    HIPCHK(hipEventSynchronize(pl->ev[1]));
-    HIPCHK(hipEventElapsedTime(ms, pl->ev[0], pl->ev[1]));
-    return 0;
+    return pl->elapsed(ms);
 }
 
 extern "C" int clh_edit_align_batch(clh_ctx* ctx, int32_t n, const uint8_t* q, const int64_t* q_off, const uint8_t* t, const int64_t* t_off,
@@ -1961,7 +1965,6 @@ struct clh_edit_search_plan : clh_owned {
     std::vector<int32_t> plen, tlen, list[2], split;   // list[0]: probes of 1..32 letters, list[1]: of 33..64
     void *d_text = nullptr, *d_text_off = nullptr, *d_probe = nullptr, *d_probe_off = nullptr, *d_list[2] = {nullptr, nullptr}, *d_chunk_base = nullptr,
          *d_split = nullptr, *d_eq = nullptr, *d_rows = nullptr, *d_part = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
 };
 
 extern "C" void clh_edit_search_plan_destroy(clh_edit_search_plan* pl) { delete pl; }
@@ -2028,11 +2031,8 @@ extern "C" clh_edit_search_plan* clh_edit_search_plan_create(clh_ctx* ctx, int32
 extern "C" int clh_edit_search_plan_run(clh_edit_search_plan* pl, void* stream_)
 {
     if (!pl) return fail(CLH_E_ARG, "clh_edit_search_plan_run: null argument");
-    HIPCHK(hipSetDevice(pl->ctx->device));
-    hipStream_t st = stream_ ? (hipStream_t)stream_ : pl->ctx->stream;
-    if (!pl->ev[0]) for (auto& e : pl->ev) HIPCHK(pl->event(&e));
-    HIPCHK(hipEventRecord(pl->ev[0], st));
-    pl->last_stream = st; pl->ran = true;
+    hipStream_t st;
+    if (int rc = pl->begin_run(stream_, &st)) return rc;
     // every cell and every chunk tuple starts as "unwritten": what a kernel did not store is reported by fetch, never returned
     if (pl->ncell) HIPCHK(hipMemsetAsync(pl->d_rows, 0x80, sizeof(clh_edit_search_row) * (size_t)pl->ncell, st));
     if (pl->npart) HIPCHK(hipMemsetAsync(pl->d_part, 0x80, 16 * (size_t)pl->npart, st));
@@ -2054,8 +2054,7 @@ extern "C" int clh_edit_search_plan_run(clh_edit_search_plan* pl, void* stream_)
         p.probe_list = (const int32_t*)pl->d_list[w]; p.nlist = (int32_t)pl->list[w].size();
         HIPCHK(clh::launch_edit_search_finish(p, w ? 64 : 32, st));
     }
-    HIPCHK(hipEventRecord(pl->ev[1], st));
-    return 0;
+    return pl->end_run();
 }
 
 extern "C" int clh_edit_search_plan_fetch(clh_edit_search_plan* pl, clh_edit_search_row* rows, int64_t rows_cap)
@@ -2084,9 +2083,7 @@ extern "C" int clh_edit_search_plan_fetch(clh_edit_search_plan* pl, clh_edit_sea
 extern "C" int clh_edit_search_plan_timing(clh_edit_search_plan* pl, float* ms)
 {
     if (!pl || !ms || !pl->ran) return fail(CLH_E_ARG, "clh_edit_search_plan_timing: no run to time");
-    HIPCHK(hipEventSynchronize(pl->ev[1]));
-    HIPCHK(hipEventElapsedTime(ms, pl->ev[0], pl->ev[1]));
-    return 0;
+    return pl->elapsed(ms);
 }
 
 extern "C" int clh_edit_search_plan_info(clh_edit_search_plan* pl, int64_t* out)
@@ -2109,143 +2106,142 @@ extern "C" int clh_edit_search_batch(clh_ctx* ctx, int32_t ntext, const uint8_t*
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// K1g: end-anchored affine-gap alignment of pairs -- global, semiglobal, overlap (ssw_ends.hip)
+// K1g and K1gb: what the two pair plans share on the host.  A create checks and plans everything here (pairs, CIGAR room, the
+// shares of the workspace) before its first device call; a run starts and fetch reads the same way for both.
 // ---------------------------------------------------------------------------------------------------------------
-struct clh_ends_plan : clh_owned {
-    using clh_owned::clh_owned;
+// clh_band_opts and clh_band_row begin with the fields of clh_ends_opts and clh_ends_row: one option check and one row writer serve both
+static_assert(offsetof(clh_band_opts, mode) == offsetof(clh_ends_opts, mode) && offsetof(clh_band_opts, mat) == offsetof(clh_ends_opts, mat) &&
+              offsetof(clh_band_opts, n_mat) == offsetof(clh_ends_opts, n_mat) && offsetof(clh_band_opts, gap_open) == offsetof(clh_ends_opts, gap_open) &&
+              offsetof(clh_band_opts, gap_extend) == offsetof(clh_ends_opts, gap_extend) && offsetof(clh_band_opts, want_cigar) == offsetof(clh_ends_opts, want_cigar) &&
+              offsetof(clh_band_opts, workspace_bytes) == offsetof(clh_ends_opts, workspace_bytes) && offsetof(clh_band_opts, band) == sizeof(clh_ends_opts),
+              "clh_band_opts begins with clh_ends_opts");
+static_assert(offsetof(clh_band_row, score) == offsetof(clh_ends_row, score) && offsetof(clh_band_row, ref_begin) == offsetof(clh_ends_row, ref_begin) &&
+              offsetof(clh_band_row, ref_end) == offsetof(clh_ends_row, ref_end) && offsetof(clh_band_row, query_begin) == offsetof(clh_ends_row, query_begin) &&
+              offsetof(clh_band_row, query_end) == offsetof(clh_ends_row, query_end) && offsetof(clh_band_row, cigar_len) == offsetof(clh_ends_row, cigar_len) &&
+              offsetof(clh_band_row, cigar_off) == offsetof(clh_ends_row, cigar_off) && offsetof(clh_band_row, band_lo) == sizeof(clh_ends_row),
+              "clh_band_row begins with clh_ends_row");
+
+// what a create plans on the host
+struct PairsShape {
     int n = 0, mode = 0, n_mat = 0, go = 0, ge = 0;
     bool want_cigar = false;
-    std::vector<clh::EnPair> pairs;
     std::vector<std::pair<int, int>> shares;      // [first, count) of each launch: the batch cut so that a share's decisions fit the workspace
-    int64_t ws_bytes = 0, hand_words = 0, cig_cap = 0, max_pair_ws = 0, nempty = 0;
-    void *d_q = nullptr, *d_r = nullptr, *d_pairs = nullptr, *d_mat = nullptr, *d_hand = nullptr, *d_ws = nullptr, *d_rows = nullptr, *d_cig = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    int64_t ws_bytes = 0, cig_cap = 0, max_pair_ws = 0, nempty = 0;
+};
+struct clh_pairs_plan : clh_owned, PairsShape {
+    using clh_owned::clh_owned;
+    void *d_q = nullptr, *d_r = nullptr, *d_pairs = nullptr, *d_mat = nullptr, *d_ws = nullptr, *d_rows = nullptr, *d_cig = nullptr;
 };
 
-extern "C" void clh_ends_plan_destroy(clh_ends_plan* pl) { delete pl; }
-
-static int64_t en_ws_bytes(int64_t m, int64_t n)
+// the arguments and options both creates take, refused in the order each always refused them; `band`: K1gb's half-width, null for K1g
+static int pairs_check_opts(const std::string& me, const clh_ctx* ctx, int32_t n, const int64_t* q_off, const int64_t* r_off, const clh_ends_opts* o,
+                            const int32_t* band)
 {
-    const int64_t nch = (n + clh::kEnChunk - 1) / clh::kEnChunk;
-    const int64_t llast = (n - (nch - 1) * clh::kEnChunk + clh::kEnCpl - 1) / clh::kEnCpl;
-    return (4 * m * (64 * (nch - 1) + llast) + 15) & ~(int64_t)15;
+    if (!ctx || n < 0 || !q_off || !r_off || !o || !o->mat) return fail(CLH_E_ARG, me + "bad argument");
+    if (band) {
+        if (o->mode == CLH_ENDS_OVERLAP) return fail(CLH_E_UNSUPPORTED, me + "overlap with a band is not built; clh_ends_plan_create takes the mode over the full matrix");
+        if (o->mode != CLH_ENDS_GLOBAL && o->mode != CLH_ENDS_SEMIGLOBAL) return fail(CLH_E_ARG, me + "mode must be CLH_ENDS_GLOBAL or CLH_ENDS_SEMIGLOBAL");
+    } else if (o->mode < CLH_ENDS_GLOBAL || o->mode > CLH_ENDS_OVERLAP) return fail(CLH_E_ARG, me + "mode must be CLH_ENDS_GLOBAL, _SEMIGLOBAL or _OVERLAP");
+    if (o->n_mat < 1 || o->n_mat > 32) return fail(CLH_E_ARG, me + "n_mat must be 1..32");
+    if (o->gap_open < 0 || o->gap_extend < 0 || o->workspace_bytes < 0 || (band && *band < 0))
+        return fail(CLH_E_ARG, me + (band ? "gap costs, workspace_bytes and band must not be negative" : "gap costs and workspace_bytes must not be negative"));
+    if (o->gap_open < o->gap_extend)
+        return fail(CLH_E_UNSUPPORTED, me + "gap_open < gap_extend: E along a row is a running maximum only when opening a gap costs at least as much as extending one; not implemented");
+    return 0;
 }
 
-extern "C" clh_ends_plan* clh_ends_plan_create(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off,
-                                               const clh_ends_opts* o)
+// smax: the greatest of |s|, gap_open, gap_extend, 1, what one step moves a score by at most; *splus: max(0, greatest matrix entry)
+static int64_t pairs_scan_matrix(const clh_ends_opts* o, int64_t* splus)
 {
-    const std::string me = "clh_ends_plan_create: ";
-    if (!ctx || n < 0 || !q_off || !r_off || !o || !o->mat) { fail(CLH_E_ARG, me + "bad argument"); return nullptr; }
-    if (o->mode < CLH_ENDS_GLOBAL || o->mode > CLH_ENDS_OVERLAP) { fail(CLH_E_ARG, me + "mode must be CLH_ENDS_GLOBAL, _SEMIGLOBAL or _OVERLAP"); return nullptr; }
-    if (o->n_mat < 1 || o->n_mat > 32) { fail(CLH_E_ARG, me + "n_mat must be 1..32"); return nullptr; }
-    if (o->gap_open < 0 || o->gap_extend < 0 || o->workspace_bytes < 0) { fail(CLH_E_ARG, me + "gap costs and workspace_bytes must not be negative"); return nullptr; }
-    if (o->gap_open < o->gap_extend) {
-        fail(CLH_E_UNSUPPORTED, me + "gap_open < gap_extend: E along a row is a running maximum only when opening a gap costs at least as much as extending one; not implemented");
-        return nullptr;
-    }
     int64_t smax = std::max<int64_t>(std::max(o->gap_open, o->gap_extend), 1);
-    for (int k = 0; k < o->n_mat * o->n_mat; ++k) smax = std::max<int64_t>(smax, std::abs((int)o->mat[k]));
-    const int64_t workspace = o->workspace_bytes > 0 ? o->workspace_bytes : (int64_t)1 << 30;
-    for (int k = 0; k < n; ++k) {
-        const int64_t m = q_off[k + 1] - q_off[k], nn = r_off[k + 1] - r_off[k];
-        if (m < 0 || nn < 0) { fail(CLH_E_ARG, me + "offsets must ascend"); return nullptr; }
-        if ((m > 0 && !q) || (nn > 0 && !r)) { fail(CLH_E_ARG, me + "null argument"); return nullptr; }
-        if (m + nn >= ((int64_t)1 << 30) || (m + nn) * smax >= ((int64_t)1 << 30)) {
-            fail(CLH_E_ARG, me + "pair " + std::to_string(k) + ": (m + n) * max(|s|, gap_open, gap_extend) = " + std::to_string(m + nn) + " * " +
-                                std::to_string(smax) + " reaches 2^30, the score range of the int32 cells");
-            return nullptr;
-        }
-    }
+    *splus = 0;
+    for (int k = 0; k < o->n_mat * o->n_mat; ++k) { smax = std::max<int64_t>(smax, std::abs((int)o->mat[k])); *splus = std::max<int64_t>(*splus, o->mat[k]); }
+    return smax;
+}
+
+static int pairs_check_codes(const std::string& me, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off, int n_mat)
+{
     for (int k = 0; k < n; ++k) {
         for (int side = 0; side < 2; ++side) {
             const int8_t* s = side ? r : q;
             const int64_t* off = side ? r_off : q_off;
             for (int64_t x = off[k]; x < off[k + 1]; ++x)
-                if (s[x] < 0 || s[x] >= o->n_mat) {
-                    fail(CLH_E_ARG, me + "pair " + std::to_string(k) + ": code " + std::to_string((int)s[x]) + " at letter " + std::to_string(x - off[k]) + " of the " +
-                                        (side ? "reference" : "query") + " is outside the matrix (edge " + std::to_string(o->n_mat) + ")");
-                    return nullptr;
-                }
+                if (s[x] < 0 || s[x] >= n_mat)
+                    return fail(CLH_E_ARG, me + "pair " + std::to_string(k) + ": code " + std::to_string((int)s[x]) + " at letter " + std::to_string(x - off[k]) + " of the " +
+                                               (side ? "reference" : "query") + " is outside the matrix (edge " + std::to_string(n_mat) + ")");
         }
     }
-    if (hipSetDevice(ctx->device) != hipSuccess) { fail(CLH_E_HIP, "hipSetDevice failed"); return nullptr; }
-    clh_ends_plan* pl = new clh_ends_plan(ctx);
-    pl->n = n; pl->mode = o->mode; pl->n_mat = o->n_mat; pl->go = o->gap_open; pl->ge = o->gap_extend; pl->want_cigar = o->want_cigar != 0;
-    pl->pairs.resize((size_t)n);
+    return 0;
+}
+
+// Fills the fields EnPair and BdPair name alike and cuts the batch into shares.  own(k, pair, kernel) fills the pair's other fields
+// and returns the bytes its stored decisions need (read only where CIGARs are wanted and the kernels take the pair); cells(pair)
+// words them for the refusal of a pair that is above the workspace alone.
+template <typename Pair, typename Own, typename Cells>
+static int pairs_cut_shares(const std::string& me, const clh_ends_opts* o, int32_t n, const int64_t* q_off, const int64_t* r_off, PairsShape* sh,
+                            std::vector<Pair>* pairs, Own own, Cells cells)
+{
+    sh->n = n; sh->mode = o->mode; sh->n_mat = o->n_mat; sh->go = o->gap_open; sh->ge = o->gap_extend; sh->want_cigar = o->want_cigar != 0;
+    const int64_t workspace = o->workspace_bytes > 0 ? o->workspace_bytes : (int64_t)1 << 30;
+    pairs->resize((size_t)n);
     int first = 0;
     int64_t share = 0;
     for (int k = 0; k < n; ++k) {
-        clh::EnPair& p = pl->pairs[(size_t)k];
+        Pair& p = (*pairs)[(size_t)k];
         const int64_t m = q_off[k + 1] - q_off[k], nn = r_off[k + 1] - r_off[k];
         p.q_off = q_off[k] - q_off[0]; p.r_off = r_off[k] - r_off[0];
-        p.m = (int32_t)m; p.n = (int32_t)nn; p.pad = 0;
-        p.hand_off = -1; p.ws_off = -1; p.cig_off = pl->cig_cap; p.cig_cap = 0;
+        p.m = (int32_t)m; p.n = (int32_t)nn;
+        p.ws_off = -1; p.cig_off = sh->cig_cap; p.cig_cap = 0;
         const bool kernel = m > 0 && nn > 0;
-        pl->nempty += !kernel;
-        if (kernel && nn > clh::kEnChunk) { p.hand_off = pl->hand_words; pl->hand_words += 4 * ((m + 63) & ~(int64_t)63); }
-        if (pl->want_cigar) {
+        sh->nempty += !kernel;
+        const int64_t need = own(k, p, kernel);
+        if (sh->want_cigar) {
             p.cig_cap = (int32_t)std::min<int64_t>(m + nn, 2 * std::min(m, nn) + 1);      // runs alternate: no CIGAR has more
-            pl->cig_cap += p.cig_cap;
+            sh->cig_cap += p.cig_cap;
         }
-        if (pl->want_cigar && kernel) {
-            const int64_t need = en_ws_bytes(m, nn);
-            pl->max_pair_ws = std::max(pl->max_pair_ws, need);
-            if (need > workspace) {
-                fail(CLH_E_CAPACITY, me + "pair " + std::to_string(k) + " alone needs " + std::to_string(need) + " bytes of workspace for the decisions of its " +
-                                     std::to_string(m) + " x " + std::to_string(nn) + " cells, workspace_bytes is " + std::to_string(workspace));
-                delete pl; return nullptr;
-            }
-            if (share + need > workspace) { pl->shares.push_back({first, k - first}); first = k; share = 0; }
+        if (sh->want_cigar && kernel) {
+            sh->max_pair_ws = std::max(sh->max_pair_ws, need);
+            if (need > workspace)
+                return fail(CLH_E_CAPACITY, me + "pair " + std::to_string(k) + " alone needs " + std::to_string(need) + " bytes of workspace for the decisions of its " +
+                                            cells(p) + ", workspace_bytes is " + std::to_string(workspace));
+            if (share + need > workspace) { sh->shares.push_back({first, k - first}); first = k; share = 0; }
             p.ws_off = share; share += need;
-            pl->ws_bytes = std::max(pl->ws_bytes, share);
+            sh->ws_bytes = std::max(sh->ws_bytes, share);
         }
     }
-    if (n > first) pl->shares.push_back({first, n - first});
+    if (n > first) sh->shares.push_back({first, n - first});
+    return 0;
+}
+
+// the plan takes over what was planned and uploads what both kinds have; false: a block is missing
+template <typename Pair>
+static bool pairs_upload(clh_pairs_plan* pl, PairsShape* sh, const std::vector<Pair>& pairs, const int8_t* q, const int64_t* q_off, const int8_t* r,
+                         const int64_t* r_off, const int8_t* mat)
+{
+    static_cast<PairsShape&>(*pl) = std::move(*sh);
+    const int n = pl->n;
     const int64_t tq = n ? q_off[n] - q_off[0] : 0, tr = n ? r_off[n] - r_off[0] : 0;
     pl->d_q = pl->upload(q ? q + q_off[0] : nullptr, (size_t)tq);
     pl->d_r = pl->upload(r ? r + r_off[0] : nullptr, (size_t)tr);
-    pl->d_pairs = pl->upload(pl->pairs.data(), sizeof(clh::EnPair) * pl->pairs.size());
-    pl->d_mat = pl->upload(o->mat, (size_t)o->n_mat * o->n_mat);
-    pl->d_hand = pl->alloc(sizeof(int32_t) * (size_t)std::max<int64_t>(pl->hand_words, 1));
+    pl->d_pairs = pl->upload(pairs.data(), sizeof(Pair) * pairs.size());
+    pl->d_mat = pl->upload(mat, (size_t)pl->n_mat * pl->n_mat);
     pl->d_ws = pl->alloc((size_t)std::max<int64_t>(pl->ws_bytes, 1));
     pl->d_rows = pl->alloc(32 * (size_t)std::max(n, 1));
     pl->d_cig = pl->alloc(sizeof(uint32_t) * (size_t)std::max<int64_t>(pl->cig_cap, 1));
-    if (!pl->d_q || !pl->d_r || !pl->d_pairs || !pl->d_mat || !pl->d_hand || !pl->d_ws || !pl->d_rows || !pl->d_cig) {
-        fail(CLH_E_HIP, "out of device memory or upload failed while building the ends plan");
-        delete pl; return nullptr;
-    }
-    return pl;
+    return pl->d_q && pl->d_r && pl->d_pairs && pl->d_mat && pl->d_ws && pl->d_rows && pl->d_cig;
 }
 
-extern "C" int clh_ends_plan_run(clh_ends_plan* pl, void* stream_)
+// the start of a run of either kind; every row starts as "unwritten": what a kernel did not store is reported by fetch, never returned
+static int pairs_begin_run(clh_pairs_plan* pl, void* stream_, hipStream_t* st)
 {
-    if (!pl) return fail(CLH_E_ARG, "clh_ends_plan_run: null argument");
-    HIPCHK(hipSetDevice(pl->ctx->device));
-    hipStream_t st = stream_ ? (hipStream_t)stream_ : pl->ctx->stream;
-    if (!pl->ev[0]) for (auto& e : pl->ev) HIPCHK(pl->event(&e));
-    HIPCHK(hipEventRecord(pl->ev[0], st));
-    pl->last_stream = st; pl->ran = true;
-    // every row starts as "unwritten": what a kernel did not store is reported by fetch, never returned
-    if (pl->n) HIPCHK(hipMemsetAsync(pl->d_rows, 0x80, 32 * (size_t)pl->n, st));
-    clh::EnParams p;
-    p.qry = (const int8_t*)pl->d_q; p.ref = (const int8_t*)pl->d_r;
-    p.pairs = (const clh::EnPair*)pl->d_pairs; p.npairs = pl->n;
-    p.mat = (const int8_t*)pl->d_mat; p.n_mat = pl->n_mat;
-    p.go = pl->go; p.ge = pl->ge; p.mode = pl->mode;
-    p.hand = (int32_t*)pl->d_hand; p.hand_cap = pl->hand_words;
-    p.ws = (uint8_t*)pl->d_ws; p.ws_cap = pl->ws_bytes;
-    p.rows = (int32_t*)pl->d_rows;
-    p.cigar = (uint32_t*)pl->d_cig; p.cigar_cap = pl->cig_cap;
-    for (const auto& sh : pl->shares) {        // in stream order: a share's walk has read the workspace before the next share fills it
-        HIPCHK(clh::launch_ssw_ends(p, pl->want_cigar, sh.first, sh.second, st));
-        if (pl->want_cigar) HIPCHK(clh::launch_ssw_ends_walk(p, sh.first, sh.second, st));
-    }
-    HIPCHK(hipEventRecord(pl->ev[1], st));
+    if (int rc = pl->begin_run(stream_, st)) return rc;
+    if (pl->n) HIPCHK(hipMemsetAsync(pl->d_rows, 0x80, 32 * (size_t)pl->n, *st));
     return 0;
 }
 
 // what the programme gives when one side has no letter: the boundary itself
-static void en_empty_side(int mode, int m, int n, int go, int ge, clh_ends_row* row, uint32_t* op)
+template <typename Row>
+static void en_empty_side(int mode, int m, int n, int go, int ge, Row* row, uint32_t* op)
 {
     *op = 0;
     row->score = 0; row->ref_begin = 0; row->ref_end = -1; row->query_begin = 0; row->query_end = -1;
@@ -2254,11 +2250,14 @@ static void en_empty_side(int mode, int m, int n, int go, int ge, clh_ends_row* 
     if (m > 0 && mode == CLH_ENDS_OVERLAP) { row->query_begin = m; row->query_end = m - 1; }
 }
 
-extern "C" int clh_ends_plan_fetch(clh_ends_plan* pl, clh_ends_row* rows, uint32_t* cigar, int64_t cigar_cap, int64_t* cigar_used)
+// fetch of either kind (`kind`: "ends" / "band", for the messages): the rows and CIGARs of the last run, the rows of pairs with an
+// empty side stated here.  more(pair, row) is called once the fields of clh_ends_row but the CIGAR's are in place, for what a kind adds.
+template <typename Plan, typename Row, typename More>
+static int pairs_fetch(const std::string& kind, Plan* pl, Row* rows, uint32_t* cigar, int64_t cigar_cap, int64_t* cigar_used, More more)
 {
-    const std::string me = "clh_ends_plan_fetch: ";
+    const std::string me = "clh_" + kind + "_plan_fetch: ";
     if (!pl || (!rows && pl->n > 0)) return fail(CLH_E_ARG, me + "null argument");
-    if (!pl->ran) return fail(CLH_E_ARG, "clh_ends_plan_fetch before clh_ends_plan_run");
+    if (!pl->ran) return fail(CLH_E_ARG, "clh_" + kind + "_plan_fetch before clh_" + kind + "_plan_run");
     if (cigar_used) *cigar_used = 0;
     if (!pl->n) return 0;
     HIPCHK(hipSetDevice(pl->ctx->device));
@@ -2272,9 +2271,9 @@ extern "C" int clh_ends_plan_fetch(clh_ends_plan* pl, clh_ends_row* rows, uint32
     }
     int64_t used = 0, unwritten = 0, nowalk = 0, first_bad = -1;
     for (int k = 0; k < pl->n; ++k) {
-        const clh::EnPair& p = pl->pairs[(size_t)k];
+        const auto& p = pl->pairs[(size_t)k];
         const int32_t* w = raw.data() + 8 * (size_t)k;
-        clh_ends_row& out = rows[k];
+        Row& out = rows[k];
         uint32_t one = 0;
         const uint32_t* src = nullptr;
         int len = 0;
@@ -2289,6 +2288,7 @@ extern "C" int clh_ends_plan_fetch(clh_ends_plan* pl, clh_ends_row* rows, uint32
             out.score = w[0]; out.ref_begin = w[1]; out.ref_end = w[2]; out.query_begin = w[3]; out.query_end = w[4];
             src = ops.data() + p.cig_off; len = w[5];
         }
+        more(p, out);
         out.cigar_len = 0; out.cigar_off = -1;
         if (pl->want_cigar) {
             if (cigar && used + len > cigar_cap) return fail(CLH_E_CAPACITY, me + "cigar_cap too small");
@@ -2304,12 +2304,97 @@ extern "C" int clh_ends_plan_fetch(clh_ends_plan* pl, clh_ends_row* rows, uint32
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// K1g: end-anchored affine-gap alignment of pairs -- global, semiglobal, overlap (ssw_ends.hip)
+// ---------------------------------------------------------------------------------------------------------------
+struct clh_ends_plan : clh_pairs_plan {
+    using clh_pairs_plan::clh_pairs_plan;
+    std::vector<clh::EnPair> pairs;
+    int64_t hand_words = 0;
+    void* d_hand = nullptr;
+};
+
+extern "C" void clh_ends_plan_destroy(clh_ends_plan* pl) { delete pl; }
+
+static int64_t en_ws_bytes(int64_t m, int64_t n)
+{
+    const int64_t nch = (n + clh::kEnChunk - 1) / clh::kEnChunk;
+    const int64_t llast = (n - (nch - 1) * clh::kEnChunk + clh::kEnCpl - 1) / clh::kEnCpl;
+    return (4 * m * (64 * (nch - 1) + llast) + 15) & ~(int64_t)15;
+}
+
+extern "C" clh_ends_plan* clh_ends_plan_create(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off,
+                                               const clh_ends_opts* o)
+{
+    const std::string me = "clh_ends_plan_create: ";
+    if (pairs_check_opts(me, ctx, n, q_off, r_off, o, nullptr)) return nullptr;
+    int64_t splus;
+    const int64_t smax = pairs_scan_matrix(o, &splus);
+    for (int k = 0; k < n; ++k) {
+        const int64_t m = q_off[k + 1] - q_off[k], nn = r_off[k + 1] - r_off[k];
+        if (m < 0 || nn < 0) { fail(CLH_E_ARG, me + "offsets must ascend"); return nullptr; }
+        if ((m > 0 && !q) || (nn > 0 && !r)) { fail(CLH_E_ARG, me + "null argument"); return nullptr; }
+        if (m + nn >= ((int64_t)1 << 30) || (m + nn) * smax >= ((int64_t)1 << 30)) {
+            fail(CLH_E_ARG, me + "pair " + std::to_string(k) + ": (m + n) * max(|s|, gap_open, gap_extend) = " + std::to_string(m + nn) + " * " +
+                                std::to_string(smax) + " reaches 2^30, the score range of the int32 cells");
+            return nullptr;
+        }
+    }
+    if (pairs_check_codes(me, n, q, q_off, r, r_off, o->n_mat)) return nullptr;
+    PairsShape shape;
+    std::vector<clh::EnPair> pairs;
+    int64_t hand_words = 0;
+    if (pairs_cut_shares(me, o, n, q_off, r_off, &shape, &pairs,
+            [&](int, clh::EnPair& p, bool kernel) {
+                p.pad = 0; p.hand_off = -1;
+                if (kernel && p.n > clh::kEnChunk) { p.hand_off = hand_words; hand_words += 4 * (((int64_t)p.m + 63) & ~(int64_t)63); }
+                return kernel ? en_ws_bytes(p.m, p.n) : 0;
+            },
+            [](const clh::EnPair& p) { return std::to_string(p.m) + " x " + std::to_string(p.n) + " cells"; }))
+        return nullptr;
+    if (hipSetDevice(ctx->device) != hipSuccess) { fail(CLH_E_HIP, "hipSetDevice failed"); return nullptr; }
+    clh_ends_plan* pl = new clh_ends_plan(ctx);
+    pl->hand_words = hand_words;
+    const bool ok = pairs_upload(pl, &shape, pairs, q, q_off, r, r_off, o->mat);
+    pl->pairs.swap(pairs);
+    pl->d_hand = pl->alloc(sizeof(int32_t) * (size_t)std::max<int64_t>(pl->hand_words, 1));
+    if (!ok || !pl->d_hand) {
+        fail(CLH_E_HIP, "out of device memory or upload failed while building the ends plan");
+        delete pl; return nullptr;
+    }
+    return pl;
+}
+
+extern "C" int clh_ends_plan_run(clh_ends_plan* pl, void* stream_)
+{
+    if (!pl) return fail(CLH_E_ARG, "clh_ends_plan_run: null argument");
+    hipStream_t st;
+    if (int rc = pairs_begin_run(pl, stream_, &st)) return rc;
+    clh::EnParams p;
+    p.qry = (const int8_t*)pl->d_q; p.ref = (const int8_t*)pl->d_r;
+    p.pairs = (const clh::EnPair*)pl->d_pairs; p.npairs = pl->n;
+    p.mat = (const int8_t*)pl->d_mat; p.n_mat = pl->n_mat;
+    p.go = pl->go; p.ge = pl->ge; p.mode = pl->mode;
+    p.hand = (int32_t*)pl->d_hand; p.hand_cap = pl->hand_words;
+    p.ws = (uint8_t*)pl->d_ws; p.ws_cap = pl->ws_bytes;
+    p.rows = (int32_t*)pl->d_rows;
+    p.cigar = (uint32_t*)pl->d_cig; p.cigar_cap = pl->cig_cap;
+    for (const auto& sh : pl->shares) {        // in stream order: a share's walk has read the workspace before the next share fills it
+        HIPCHK(clh::launch_ssw_ends(p, pl->want_cigar, sh.first, sh.second, st));
+        if (pl->want_cigar) HIPCHK(clh::launch_ssw_ends_walk(p, sh.first, sh.second, st));
+    }
+    return pl->end_run();
+}
+
+extern "C" int clh_ends_plan_fetch(clh_ends_plan* pl, clh_ends_row* rows, uint32_t* cigar, int64_t cigar_cap, int64_t* cigar_used)
+{
+    return pairs_fetch("ends", pl, rows, cigar, cigar_cap, cigar_used, [](const clh::EnPair&, clh_ends_row&) {});
+}
+
 extern "C" int clh_ends_plan_timing(clh_ends_plan* pl, float* ms)
 {
     if (!pl || !ms || !pl->ran) return fail(CLH_E_ARG, "clh_ends_plan_timing: no run to time");
-    HIPCHK(hipEventSynchronize(pl->ev[1]));
-    HIPCHK(hipEventElapsedTime(ms, pl->ev[0], pl->ev[1]));
-    return 0;
+    return pl->elapsed(ms);
 }
 
 extern "C" int clh_ends_plan_info(clh_ends_plan* pl, int64_t* out)
@@ -2334,38 +2419,29 @@ extern "C" int clh_ends_batch(clh_ctx* ctx, int32_t n, const int8_t* q, const in
 // ---------------------------------------------------------------------------------------------------------------
 // K1gb: K1g's global and semiglobal programmes over a band of diagonals per pair (ssw_band.hip)
 // ---------------------------------------------------------------------------------------------------------------
-struct clh_band_plan : clh_owned {
-    using clh_owned::clh_owned;
-    int n = 0, mode = 0, n_mat = 0, go = 0, ge = 0;
-    bool want_cigar = false;
+struct clh_band_plan : clh_pairs_plan {
+    using clh_pairs_plan::clh_pairs_plan;
     int64_t splus = 0;                            // max(0, greatest matrix entry): what an M column can add at most
     std::vector<clh::BdPair> pairs;
     std::vector<int32_t> order;                   // pair indices filed by share, then by class
-    struct share_t { int first, count; int cfirst[clh::kBdClasses], ccount[clh::kBdClasses]; };
-    std::vector<share_t> shares;                  // pairs [first, first + count): their decisions fit the workspace together
-    int64_t ws_bytes = 0, cig_cap = 0, max_pair_ws = 0, nempty = 0, max_width = 0, nclass[clh::kBdClasses] = {0, 0, 0};
-    void *d_q = nullptr, *d_r = nullptr, *d_pairs = nullptr, *d_order = nullptr, *d_mat = nullptr, *d_ws = nullptr, *d_rows = nullptr, *d_cig = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    struct classes_t { int cfirst[clh::kBdClasses], ccount[clh::kBdClasses]; };
+    std::vector<classes_t> share_classes;         // per share: where the pairs of each class stand in `order`
+    int64_t max_width = 0, nclass[clh::kBdClasses] = {0, 0, 0};
+    void* d_order = nullptr;
 };
 
 extern "C" void clh_band_plan_destroy(clh_band_plan* pl) { delete pl; }
 
 extern "C" clh_band_plan* clh_band_plan_create(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off,
-                                               const int32_t* diag, const clh_band_opts* o)
+                                               const int32_t* diag, const clh_band_opts* bo)
 {
     const std::string me = "clh_band_plan_create: ";
-    if (!ctx || n < 0 || !q_off || !r_off || !o || !o->mat) { fail(CLH_E_ARG, me + "bad argument"); return nullptr; }
-    if (o->mode == CLH_ENDS_OVERLAP) { fail(CLH_E_UNSUPPORTED, me + "overlap with a band is not built; clh_ends_plan_create takes the mode over the full matrix"); return nullptr; }
-    if (o->mode != CLH_ENDS_GLOBAL && o->mode != CLH_ENDS_SEMIGLOBAL) { fail(CLH_E_ARG, me + "mode must be CLH_ENDS_GLOBAL or CLH_ENDS_SEMIGLOBAL"); return nullptr; }
-    if (o->n_mat < 1 || o->n_mat > 32) { fail(CLH_E_ARG, me + "n_mat must be 1..32"); return nullptr; }
-    if (o->gap_open < 0 || o->gap_extend < 0 || o->workspace_bytes < 0 || o->band < 0) { fail(CLH_E_ARG, me + "gap costs, workspace_bytes and band must not be negative"); return nullptr; }
-    if (o->gap_open < o->gap_extend) {
-        fail(CLH_E_UNSUPPORTED, me + "gap_open < gap_extend: E along a row is a running maximum only when opening a gap costs at least as much as extending one; not implemented");
-        return nullptr;
-    }
-    int64_t smax = std::max<int64_t>(std::max(o->gap_open, o->gap_extend), 1), splus = 0;
-    for (int k = 0; k < o->n_mat * o->n_mat; ++k) { smax = std::max<int64_t>(smax, std::abs((int)o->mat[k])); splus = std::max<int64_t>(splus, o->mat[k]); }
-    const int64_t workspace = o->workspace_bytes > 0 ? o->workspace_bytes : (int64_t)1 << 30;
+    clh_ends_opts shared;                                                      // the fields the two share (the static_asserts above)
+    if (bo) memcpy(&shared, bo, sizeof shared);
+    const clh_ends_opts* o = bo ? &shared : nullptr;
+    if (pairs_check_opts(me, ctx, n, q_off, r_off, o, bo ? &bo->band : nullptr)) return nullptr;
+    int64_t splus;
+    const int64_t smax = pairs_scan_matrix(o, &splus);
     const bool global = o->mode == CLH_ENDS_GLOBAL;
     std::vector<std::pair<int32_t, int32_t>> bands((size_t)n);
     for (int k = 0; k < n; ++k) {
@@ -2380,8 +2456,8 @@ extern "C" clh_band_plan* clh_band_plan_create(clh_ctx* ctx, int32_t n, const in
             return nullptr;
         }
         int64_t lo, hi;
-        if (diag) { lo = (int64_t)diag[k] - o->band; hi = (int64_t)diag[k] + o->band; }
-        else { lo = std::min<int64_t>(0, nn - m) - o->band; hi = std::max<int64_t>(0, nn - m) + o->band; }
+        if (diag) { lo = (int64_t)diag[k] - bo->band; hi = (int64_t)diag[k] + bo->band; }
+        else { lo = std::min<int64_t>(0, nn - m) - bo->band; hi = std::max<int64_t>(0, nn - m) + bo->band; }
         const std::string bt = "the band [" + std::to_string(lo) + ", " + std::to_string(hi) + "] of the " + std::to_string(m) + " x " + std::to_string(nn) + " pair ";
         if (global && (lo > std::min<int64_t>(0, nn - m) || hi < std::max<int64_t>(0, nn - m))) {
             fail(CLH_E_ARG, pk + bt + "misses (0, 0) or (m, n): a global band holds the diagonals 0 and n - m = " + std::to_string(nn - m));
@@ -2399,83 +2475,42 @@ extern "C" clh_band_plan* clh_band_plan_create(clh_ctx* ctx, int32_t n, const in
         }
         bands[(size_t)k] = {(int32_t)lo, (int32_t)hi};
     }
-    for (int k = 0; k < n; ++k) {
-        for (int side = 0; side < 2; ++side) {
-            const int8_t* s = side ? r : q;
-            const int64_t* off = side ? r_off : q_off;
-            for (int64_t x = off[k]; x < off[k + 1]; ++x)
-                if (s[x] < 0 || s[x] >= o->n_mat) {
-                    fail(CLH_E_ARG, me + "pair " + std::to_string(k) + ": code " + std::to_string((int)s[x]) + " at letter " + std::to_string(x - off[k]) + " of the " +
-                                        (side ? "reference" : "query") + " is outside the matrix (edge " + std::to_string(o->n_mat) + ")");
-                    return nullptr;
-                }
-        }
-    }
-    // the shares, before any device call: a pair above the workspace is refused here
-    std::vector<clh::BdPair> pairs((size_t)n);
-    std::vector<clh_band_plan::share_t> shares;
-    int64_t ws_bytes = 0, cig_cap = 0, max_pair_ws = 0, nempty = 0, max_width = 0, nclass[clh::kBdClasses] = {0, 0, 0};
-    int first = 0;
-    int64_t share = 0;
-    for (int k = 0; k < n; ++k) {
-        clh::BdPair& p = pairs[(size_t)k];
-        const int64_t m = q_off[k + 1] - q_off[k], nn = r_off[k + 1] - r_off[k];
-        p.q_off = q_off[k] - q_off[0]; p.r_off = r_off[k] - r_off[0];
-        p.m = (int32_t)m; p.n = (int32_t)nn; p.lo = bands[(size_t)k].first; p.hi = bands[(size_t)k].second;
-        p.ws_off = -1; p.cig_off = cig_cap; p.cig_cap = 0; p.cls = -1;
-        const bool kernel = m > 0 && nn > 0;
-        const int64_t B = (int64_t)p.hi - p.lo + 1;
-        nempty += !kernel;
-        if (kernel) {
-            p.cls = 0;
-            while (B > 64 * clh::kBdCpl[p.cls]) ++p.cls;
-            ++nclass[p.cls];
-            max_width = std::max(max_width, B);
-        }
-        if (o->want_cigar) {
-            p.cig_cap = (int32_t)std::min<int64_t>(m + nn, 2 * std::min(m, nn) + 1);      // runs alternate: no CIGAR has more
-            cig_cap += p.cig_cap;
-        }
-        if (o->want_cigar && kernel) {
-            const int cpl = clh::kBdCpl[p.cls];
-            const int64_t need = (m * ((B + cpl - 1) / cpl) * (cpl / 2) + 15) & ~(int64_t)15;
-            max_pair_ws = std::max(max_pair_ws, need);
-            if (need > workspace) {
-                fail(CLH_E_CAPACITY, me + "pair " + std::to_string(k) + " alone needs " + std::to_string(need) + " bytes of workspace for the decisions of its " +
-                                     std::to_string(m) + " rows of " + std::to_string(B) + " diagonals, workspace_bytes is " + std::to_string(workspace));
-                return nullptr;
-            }
-            if (share + need > workspace) { shares.push_back({first, k - first, {0, 0, 0}, {0, 0, 0}}); first = k; share = 0; }
-            p.ws_off = share; share += need;
-            ws_bytes = std::max(ws_bytes, share);
-        }
-    }
-    if (n > first) shares.push_back({first, n - first, {0, 0, 0}, {0, 0, 0}});
+    if (pairs_check_codes(me, n, q, q_off, r, r_off, o->n_mat)) return nullptr;
+    PairsShape shape;
+    std::vector<clh::BdPair> pairs;
+    int64_t max_width = 0, nclass[clh::kBdClasses] = {0, 0, 0};
+    if (pairs_cut_shares(me, o, n, q_off, r_off, &shape, &pairs,
+            [&](int k, clh::BdPair& p, bool kernel) -> int64_t {
+                p.lo = bands[(size_t)k].first; p.hi = bands[(size_t)k].second; p.cls = -1;
+                if (!kernel) return 0;
+                const int64_t B = (int64_t)p.hi - p.lo + 1;
+                p.cls = 0;
+                while (B > 64 * clh::kBdCpl[p.cls]) ++p.cls;
+                ++nclass[p.cls];
+                max_width = std::max(max_width, B);
+                const int cpl = clh::kBdCpl[p.cls];
+                return ((int64_t)p.m * ((B + cpl - 1) / cpl) * (cpl / 2) + 15) & ~(int64_t)15;
+            },
+            [](const clh::BdPair& p) { return std::to_string(p.m) + " rows of " + std::to_string((int64_t)p.hi - p.lo + 1) + " diagonals"; }))
+        return nullptr;
     std::vector<int32_t> order;
-    for (auto& sh : shares)
+    std::vector<clh_band_plan::classes_t> share_classes(shape.shares.size());
+    for (size_t s = 0; s < shape.shares.size(); ++s)
         for (int c = 0; c < clh::kBdClasses; ++c) {
-            sh.cfirst[c] = (int)order.size();
-            for (int k = sh.first; k < sh.first + sh.count; ++k)
+            const auto& sh = shape.shares[s];
+            share_classes[s].cfirst[c] = (int)order.size();
+            for (int k = sh.first; k < sh.first + sh.second; ++k)
                 if (pairs[(size_t)k].cls == c) order.push_back(k);
-            sh.ccount[c] = (int)order.size() - sh.cfirst[c];
+            share_classes[s].ccount[c] = (int)order.size() - share_classes[s].cfirst[c];
         }
     if (hipSetDevice(ctx->device) != hipSuccess) { fail(CLH_E_HIP, "hipSetDevice failed"); return nullptr; }
     clh_band_plan* pl = new clh_band_plan(ctx);
-    pl->n = n; pl->mode = o->mode; pl->n_mat = o->n_mat; pl->go = o->gap_open; pl->ge = o->gap_extend; pl->want_cigar = o->want_cigar != 0;
-    pl->splus = splus;
-    pl->pairs.swap(pairs); pl->order.swap(order); pl->shares.swap(shares);
-    pl->ws_bytes = ws_bytes; pl->cig_cap = cig_cap; pl->max_pair_ws = max_pair_ws; pl->nempty = nempty; pl->max_width = max_width;
+    pl->splus = splus; pl->max_width = max_width;
     for (int c = 0; c < clh::kBdClasses; ++c) pl->nclass[c] = nclass[c];
-    const int64_t tq = n ? q_off[n] - q_off[0] : 0, tr = n ? r_off[n] - r_off[0] : 0;
-    pl->d_q = pl->upload(q ? q + q_off[0] : nullptr, (size_t)tq);
-    pl->d_r = pl->upload(r ? r + r_off[0] : nullptr, (size_t)tr);
-    pl->d_pairs = pl->upload(pl->pairs.data(), sizeof(clh::BdPair) * pl->pairs.size());
+    const bool ok = pairs_upload(pl, &shape, pairs, q, q_off, r, r_off, o->mat);
+    pl->pairs.swap(pairs); pl->order.swap(order); pl->share_classes.swap(share_classes);
     pl->d_order = pl->upload(pl->order.data(), sizeof(int32_t) * pl->order.size());
-    pl->d_mat = pl->upload(o->mat, (size_t)o->n_mat * o->n_mat);
-    pl->d_ws = pl->alloc((size_t)std::max<int64_t>(pl->ws_bytes, 1));
-    pl->d_rows = pl->alloc(32 * (size_t)std::max(n, 1));
-    pl->d_cig = pl->alloc(sizeof(uint32_t) * (size_t)std::max<int64_t>(pl->cig_cap, 1));
-    if (!pl->d_q || !pl->d_r || !pl->d_pairs || !pl->d_order || !pl->d_mat || !pl->d_ws || !pl->d_rows || !pl->d_cig) {
+    if (!ok || !pl->d_order) {
         fail(CLH_E_HIP, "out of device memory or upload failed while building the band plan");
         delete pl; return nullptr;
     }
@@ -2485,13 +2520,8 @@ extern "C" clh_band_plan* clh_band_plan_create(clh_ctx* ctx, int32_t n, const in
 extern "C" int clh_band_plan_run(clh_band_plan* pl, void* stream_)
 {
     if (!pl) return fail(CLH_E_ARG, "clh_band_plan_run: null argument");
-    HIPCHK(hipSetDevice(pl->ctx->device));
-    hipStream_t st = stream_ ? (hipStream_t)stream_ : pl->ctx->stream;
-    if (!pl->ev[0]) for (auto& e : pl->ev) HIPCHK(pl->event(&e));
-    HIPCHK(hipEventRecord(pl->ev[0], st));
-    pl->last_stream = st; pl->ran = true;
-    // every row starts as "unwritten": what a kernel did not store is reported by fetch, never returned
-    if (pl->n) HIPCHK(hipMemsetAsync(pl->d_rows, 0x80, 32 * (size_t)pl->n, st));
+    hipStream_t st;
+    if (int rc = pairs_begin_run(pl, stream_, &st)) return rc;
     clh::BdParams p;
     p.qry = (const int8_t*)pl->d_q; p.ref = (const int8_t*)pl->d_r;
     p.pairs = (const clh::BdPair*)pl->d_pairs; p.npairs = pl->n;
@@ -2501,12 +2531,13 @@ extern "C" int clh_band_plan_run(clh_band_plan* pl, void* stream_)
     p.ws = (uint8_t*)pl->d_ws; p.ws_cap = pl->ws_bytes;
     p.rows = (int32_t*)pl->d_rows;
     p.cigar = (uint32_t*)pl->d_cig; p.cigar_cap = pl->cig_cap;
-    for (const auto& sh : pl->shares) {        // in stream order: a share's walk has read the workspace before the next share fills it
-        for (int c = 0; c < clh::kBdClasses; ++c) HIPCHK(clh::launch_ssw_band(p, c, pl->want_cigar, sh.cfirst[c], sh.ccount[c], st));
-        if (pl->want_cigar) HIPCHK(clh::launch_ssw_band_walk(p, sh.first, sh.count, st));
+    for (size_t s = 0; s < pl->shares.size(); ++s) {        // in stream order: a share's walk has read the workspace before the next share fills it
+        const auto& sh = pl->shares[s];
+        const auto& cl = pl->share_classes[s];
+        for (int c = 0; c < clh::kBdClasses; ++c) HIPCHK(clh::launch_ssw_band(p, c, pl->want_cigar, cl.cfirst[c], cl.ccount[c], st));
+        if (pl->want_cigar) HIPCHK(clh::launch_ssw_band_walk(p, sh.first, sh.second, st));
     }
-    HIPCHK(hipEventRecord(pl->ev[1], st));
-    return 0;
+    return pl->end_run();
 }
 
 // 1: the unbanded programme provably returns the same row and CIGAR (the argument is in the header and in DESIGN.md section 6)
@@ -2522,67 +2553,19 @@ static int32_t bd_exact(int mode, int64_t m, int64_t n, int64_t lo, int64_t hi, 
 
 extern "C" int clh_band_plan_fetch(clh_band_plan* pl, clh_band_row* rows, uint32_t* cigar, int64_t cigar_cap, int64_t* cigar_used)
 {
-    const std::string me = "clh_band_plan_fetch: ";
-    if (!pl || (!rows && pl->n > 0)) return fail(CLH_E_ARG, me + "null argument");
-    if (!pl->ran) return fail(CLH_E_ARG, "clh_band_plan_fetch before clh_band_plan_run");
-    if (cigar_used) *cigar_used = 0;
-    if (!pl->n) return 0;
-    HIPCHK(hipSetDevice(pl->ctx->device));
-    HIPCHK(hipStreamSynchronize(pl->last_stream));
-    std::vector<int32_t> raw(8 * (size_t)pl->n);
-    HIPCHK(hipMemcpy(raw.data(), pl->d_rows, 32 * (size_t)pl->n, hipMemcpyDeviceToHost));
-    std::vector<uint32_t> ops;
-    if (pl->want_cigar && pl->cig_cap) {
-        ops.resize((size_t)pl->cig_cap);
-        HIPCHK(hipMemcpy(ops.data(), pl->d_cig, sizeof(uint32_t) * ops.size(), hipMemcpyDeviceToHost));
-    }
-    int64_t used = 0, unwritten = 0, nowalk = 0, first_bad = -1;
-    for (int k = 0; k < pl->n; ++k) {
-        const clh::BdPair& p = pl->pairs[(size_t)k];
-        const int32_t* w = raw.data() + 8 * (size_t)k;
-        clh_band_row& out = rows[k];
-        uint32_t one = 0;
-        const uint32_t* src = nullptr;
-        int len = 0;
-        if (p.m == 0 || p.n == 0) {
-            // the boundary cell itself; an admitted band of such a pair is the whole boundary, but for the row 0 of a semiglobal pair
-            // without a query letter, whose first cell in the band is column lo
-            clh_ends_row e;
-            en_empty_side(pl->mode, p.m, p.n, pl->go, pl->ge, &e, &one);
-            out.score = e.score; out.ref_begin = e.ref_begin; out.ref_end = e.ref_end; out.query_begin = e.query_begin; out.query_end = e.query_end;
-            if (pl->mode == CLH_ENDS_SEMIGLOBAL && p.m == 0) { out.ref_begin = p.lo; out.ref_end = p.lo - 1; }
-            if (one) { src = &one; len = 1; }
-        } else {
-            bool bad = false;
-            for (int f = 0; f < 8; ++f) bad |= w[f] == clh::kEnUnwritten;
-            if (bad) { ++unwritten; if (first_bad < 0) first_bad = k; continue; }
-            if (w[7] != 0 || w[5] < 0 || w[5] > p.cig_cap) { ++nowalk; if (first_bad < 0) first_bad = k; continue; }
-            out.score = w[0]; out.ref_begin = w[1]; out.ref_end = w[2]; out.query_begin = w[3]; out.query_end = w[4];
-            src = ops.data() + p.cig_off; len = w[5];
-        }
+    return pairs_fetch("band", pl, rows, cigar, cigar_cap, cigar_used, [pl](const clh::BdPair& p, clh_band_row& out) {
+        // an admitted band of a pair with an empty side is the whole boundary, but for the row 0 of a semiglobal pair without a query
+        // letter, whose first cell in the band is column lo
+        if (pl->mode == CLH_ENDS_SEMIGLOBAL && p.m == 0) { out.ref_begin = p.lo; out.ref_end = p.lo - 1; }
         out.band_lo = p.lo; out.band_hi = p.hi; out.reserved = 0;
         out.exact = bd_exact(pl->mode, p.m, p.n, p.lo, p.hi, out.score, pl->splus, pl->go, pl->ge);
-        out.cigar_len = 0; out.cigar_off = -1;
-        if (pl->want_cigar) {
-            if (cigar && used + len > cigar_cap) return fail(CLH_E_CAPACITY, me + "cigar_cap too small");
-            out.cigar_len = len; out.cigar_off = used;
-            if (cigar && len) memcpy(cigar + used, src, sizeof(uint32_t) * (size_t)len);
-            used += len;
-        }
-    }
-    if (cigar_used) *cigar_used = used;
-    if (unwritten || nowalk)
-        return fail(CLH_E_HIP, me + "the kernels left " + std::to_string(unwritten) + " rows unwritten and " + std::to_string(nowalk) +
-                                   " without their walk (first: pair " + std::to_string(first_bad) + ")");
-    return 0;
+    });
 }
 
 extern "C" int clh_band_plan_timing(clh_band_plan* pl, float* ms)
 {
     if (!pl || !ms || !pl->ran) return fail(CLH_E_ARG, "clh_band_plan_timing: no run to time");
-    HIPCHK(hipEventSynchronize(pl->ev[1]));
-    HIPCHK(hipEventElapsedTime(ms, pl->ev[0], pl->ev[1]));
-    return 0;
+    return pl->elapsed(ms);
 }
 
 extern "C" int clh_band_plan_info(clh_band_plan* pl, int64_t* out)

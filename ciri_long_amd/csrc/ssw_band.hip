@@ -23,16 +23,16 @@
 // reached from a start cell, so H and T of a cell are scores; E and F may be minus infinity, and then they equal no H.
 // STORE: 4 bits per cell as in K1g (H's source 0 diagonal / 1 E / 2 F, "E opened here", "F opened here"), CPL / 2 bytes per lane and
 // row, only the lanes that own a band position: m ceil(B / CPL) CPL / 2 bytes per pair.  ssw_band_walk_kernel walks them back, one
-// lane per pair: a diagonal step keeps b, a D step goes to b - 1, an I step to b + 1.
+// lane per pair: a diagonal step keeps b, a D step goes to b - 1, an I step to b + 1.  The walk itself is K1g's, pr_walk in
+// ssw_pairs.h; the kernel here says where the half-byte of a cell lies.
 // tools/band_model.py is this scheme in Python for any geometry; tests/band_check.py is the definition.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "clh_device.h"
 #include "clh_device_ops.h"
+#include "ssw_pairs.h"
 
 namespace clh {
-
-__device__ __forceinline__ int bd_max(int a, int b) { return a > b ? a : b; }
 
 template <int CPL> struct BdWord;
 template <> struct BdWord<2> { typedef uint8_t type; };
@@ -46,11 +46,7 @@ __global__ void __launch_bounds__(64) ssw_band_kernel(const BdParams prm, int fi
     constexpr int W = 64 * CPL;
     __shared__ int smat[32 * 32];                    // [query code][reference code]
     const int lane = threadIdx.x & 63;
-    for (int k = lane; k < 32 * 32; k += 64) {
-        const int qc = k >> 5, rc = k & 31;
-        smat[k] = (qc < prm.n_mat && rc < prm.n_mat) ? (int)prm.mat[rc * prm.n_mat + qc] : 0;
-    }
-    __syncthreads();
+    pr_load_matrix(smat, prm.mat, prm.n_mat, lane);
     const int x = (int)blockIdx.x;
     if (x >= count || first + x >= prm.norder) return;
     const int pi = prm.order[first + x];
@@ -106,19 +102,19 @@ __global__ void __launch_bounds__(64) ssw_band_kernel(const BdParams prm, int fi
             for (int k = 0; k < CPL; ++k) {
                 Hu[k] = k + 1 < CPL ? Hp[k + 1] : hnext;
                 const int fu = k + 1 < CPL ? Fp[k + 1] : fnext;
-                F[k] = bd_max(Hu[k] - go, fu - ge);
+                F[k] = pr_max(Hu[k] - go, fu - ge);
                 D[k] = Hp[k] + srow[rc[k]];
                 ok[k] = (uint32_t)jr[k] <= (uint32_t)n;
-                T[k] = bd_max(D[k], F[k]);
+                T[k] = pr_max(D[k], F[k]);
                 X[k] = ok[k] ? T[k] + off[k] : kBdNeg;
-                v = bd_max(v, X[k]);
+                v = pr_max(v, X[k]);
             }
             int u = dpp_shr1(kBdNeg, wave_prefix_max(v));
 #pragma unroll
             for (int k = 0; k < CPL; ++k) {
                 E[k] = u - poff[k];
-                H[k] = ok[k] ? bd_max(T[k], E[k]) : kBdNeg;
-                u = bd_max(u, X[k]);
+                H[k] = ok[k] ? pr_max(T[k], E[k]) : kBdNeg;
+                u = pr_max(u, X[k]);
             }
             if (STORE) {
                 const int nleft = dpp_shr1(kBdNeg, H[CPL - 1]);          // H of position b - 1 of this row
@@ -179,8 +175,7 @@ __global__ void __launch_bounds__(64) ssw_band_kernel(const BdParams prm, int fi
     }
 }
 
-// one lane per pair: walk the stored decisions back from the end cell (K1g's rules: diagonal, then E, then F; a gap is left as soon
-// as "opened here" is set), in the band's frame; BAM ops M 0, I 1, D 2; at most i + j + 2 steps
+// one lane per pair: pr_walk over the half-bytes the storing form left, row after row, in the band's frame
 __global__ void ssw_band_walk_kernel(const BdParams prm, int first, int count)
 {
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
@@ -199,41 +194,12 @@ __global__ void ssw_band_walk_kernel(const BdParams prm, int first, int count)
     const int64_t nbytes = (int64_t)m * rowbytes;
     if (pr.ws_off < 0 || pr.ws_off + nbytes > prm.ws_cap || pr.cig_off < 0 || pr.cig_off + pr.cig_cap > prm.cigar_cap) { row[7] = EN_ST_NO_WALK; return; }
     const uint8_t* ws = prm.ws + pr.ws_off;
-    uint32_t* out = prm.cigar + pr.cig_off;
-    int i = row[4] + 1, j = row[2] + 1;
-    if (i < 0 || i > m || j < 0 || j > n) { row[7] = EN_ST_NO_WALK; return; }
-    const int steps = i + j + 2;
-    int state = 0, nops = 0, cur = -1, run = 0;
-    bool bad = false, done = false;
-    auto emit = [&](int op, int k) {
-        if (k <= 0) return;
-        if (op == cur) { run += k; return; }
-        if (run) { if (nops < pr.cig_cap) out[nops++] = ((uint32_t)run << 4) | (uint32_t)cur; else bad = true; }
-        cur = op; run = k;
-    };
-    for (int step = 0; step < steps && !done; ++step) {
-        if (state == 0 && (i == 0 || j == 0)) {
-            if (prm.mode == EN_GLOBAL) { emit(2, j); emit(1, i); i = 0; j = 0; }
-            else if (j == 0) { emit(1, i); i = 0; }
-            done = true;
-            break;
-        }
+    pr_walk(row, prm.mode, m, n, prm.cigar + pr.cig_off, pr.cig_cap, [&](int i, int j) -> int {
         const int b = j - i - pr.lo;
         const int64_t bi = (int64_t)(i - 1) * rowbytes + (b >> 1);
-        if (b < 0 || b >= B || i < 1 || bi < 0 || bi >= nbytes) { bad = true; break; }
-        const uint32_t nib = ((uint32_t)ws[bi] >> (4 * (b & 1))) & 15u;
-        if (state == 0) {
-            state = (int)(nib & 3u);                             // a gap state takes its first letter from this same cell
-            if (state == 0) { emit(0, 1); --i; --j; continue; }
-        }
-        if (state == 1) { emit(2, 1); --j; if (nib & 4u) state = 0; }
-        else if (state == 2) { emit(1, 1); --i; if (nib & 8u) state = 0; }
-        else { bad = true; break; }
-    }
-    emit(-2, 1);                                                 // flush the last run
-    if (bad || !done) { row[7] = EN_ST_NO_WALK; return; }
-    for (int a = 0, b = nops - 1; a < b; ++a, --b) { const uint32_t w = out[a]; out[a] = out[b]; out[b] = w; }
-    row[1] = j; row[3] = i; row[5] = nops;
+        if (b < 0 || b >= B || i < 1 || bi < 0 || bi >= nbytes) return -1;
+        return (int)(((uint32_t)ws[bi] >> (4 * (b & 1))) & 15u);
+    });
 }
 
 template <int CPL>

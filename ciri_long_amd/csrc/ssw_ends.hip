@@ -15,12 +15,14 @@
 // The mode is a template parameter: the boundary values, and which end cells are followed (the last row's running maximum keyed
 // by the smallest column, the last column's keyed by the smallest row in the lane that owns column n, the corner).
 // STORE: each cell also leaves 4 bits -- H's source (0 diagonal, 1 E, 2 F; that order is the tie rule), "E opened here", "F opened
-// here" -- one 32-bit word per lane and row, and ssw_ends_walk_kernel walks them back, one lane per pair (as K4t does).
+// here" -- one 32-bit word per lane and row, and ssw_ends_walk_kernel walks them back, one lane per pair (as K4t does): the walk
+// itself is pr_walk in ssw_pairs.h, shared with K1gb, and the kernel here says where the word of a cell lies.
 // tools/ends_model.py is this scheme in Python for any geometry; tests/ends_check.py is the definition.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "clh_device.h"
 #include "clh_device_ops.h"
+#include "ssw_pairs.h"
 
 namespace clh {
 
@@ -37,18 +39,13 @@ __device__ __forceinline__ int en_col0(int i, int go, int ge)
 {
     return (MODE == EN_OVERLAP || i == 0) ? 0 : (int)(0u - (uint32_t)go - (uint32_t)(i - 1) * (uint32_t)ge);
 }
-__device__ __forceinline__ int en_max(int a, int b) { return a > b ? a : b; }
 
 template <int MODE, bool STORE>
 __global__ void __launch_bounds__(64) ssw_ends_kernel(const EnParams prm, int first, int count)
 {
     __shared__ int smat[32 * 32];                    // [query code][reference code]
     const int lane = threadIdx.x & 63;
-    for (int k = lane; k < 32 * 32; k += 64) {
-        const int qc = k >> 5, rc = k & 31;
-        smat[k] = (qc < prm.n_mat && rc < prm.n_mat) ? (int)prm.mat[rc * prm.n_mat + qc] : 0;
-    }
-    __syncthreads();
+    pr_load_matrix(smat, prm.mat, prm.n_mat, lane);
     const int x = (int)blockIdx.x;
     if (x >= count || first + x >= prm.npairs) return;
     const EnPair pr = prm.pairs[first + x];
@@ -108,25 +105,25 @@ __global__ void __launch_bounds__(64) ssw_ends_kernel(const EnParams prm, int fi
                 int hin, ein;                                            // H and E of the column in front of the chunk, this row
                 if (c == 0) { hin = en_col0<MODE>(i, go, ge); ein = hin - go; }
                 else { hin = __builtin_amdgcn_readlane(vH, rr); ein = __builtin_amdgcn_readlane(vE, rr); }
-                const int E0 = en_max(ein - ge, hin - go);
+                const int E0 = pr_max(ein - ge, hin - go);
                 const int* srow = smat + qc * 32;
                 int T[kEnCpl], F[kEnCpl], D[kEnCpl], H[kEnCpl], E[kEnCpl];
                 int v = 0;
 #pragma unroll
                 for (int k = 0; k < kEnCpl; ++k) {
-                    F[k] = en_max(Hp[k] - go, Fp[k] - ge);
+                    F[k] = pr_max(Hp[k] - go, Fp[k] - ge);
                     D[k] = (k ? Hp[k - 1] : hleft) + srow[rcode[k]];
-                    T[k] = en_max(D[k], F[k]);
+                    T[k] = pr_max(D[k], F[k]);
                     const int xk = T[k] + off[k];
-                    v = k ? en_max(v, xk) : xk;
+                    v = k ? pr_max(v, xk) : xk;
                 }
-                v = lane == 0 ? en_max(v, E0) : v;
+                v = lane == 0 ? pr_max(v, E0) : v;
                 int u = dpp_shr1(E0, wave_prefix_max(v));                // lane 0 keeps E0
 #pragma unroll
                 for (int k = 0; k < kEnCpl; ++k) {
                     E[k] = u - poff[k];
-                    H[k] = en_max(T[k], E[k]);
-                    u = en_max(u, T[k] + off[k]);
+                    H[k] = pr_max(T[k], E[k]);
+                    u = pr_max(u, T[k] + off[k]);
                 }
                 const int nleft = dpp_shr1(hin, H[kEnCpl - 1]);          // H[i][first own column - 1]
                 if (STORE) {
@@ -197,8 +194,7 @@ __global__ void __launch_bounds__(64) ssw_ends_kernel(const EnParams prm, int fi
     }
 }
 
-// one lane per pair: walk the stored decisions back from the end cell (tie rules: diagonal, then E, then F; a gap is left as soon as
-// "opened here" is set), BAM ops M 0, I 1, D 2; at most i + j + 1 steps
+// one lane per pair: pr_walk over the words the storing form left, chunk after chunk, per chunk row after row, a word per lane
 __global__ void ssw_ends_walk_kernel(const EnParams prm, int first, int count)
 {
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
@@ -213,42 +209,13 @@ __global__ void ssw_ends_walk_kernel(const EnParams prm, int first, int count)
     const int64_t nwords = (int64_t)m * ((int64_t)64 * (nchunks - 1) + llast);
     if (pr.ws_off < 0 || pr.ws_off + 4 * nwords > prm.ws_cap || pr.cig_off < 0 || pr.cig_off + pr.cig_cap > prm.cigar_cap) { row[7] = EN_ST_NO_WALK; return; }
     const uint32_t* ws = (const uint32_t*)(prm.ws + pr.ws_off);
-    uint32_t* out = prm.cigar + pr.cig_off;
-    int i = row[4] + 1, j = row[2] + 1;
-    if (i < 0 || i > m || j < 0 || j > n) { row[7] = EN_ST_NO_WALK; return; }
-    const int steps = i + j + 2;
-    int state = 0, nops = 0, cur = -1, run = 0;
-    bool bad = false, done = false;
-    auto emit = [&](int op, int k) {
-        if (k <= 0) return;
-        if (op == cur) { run += k; return; }
-        if (run) { if (nops < pr.cig_cap) out[nops++] = ((uint32_t)run << 4) | (uint32_t)cur; else bad = true; }
-        cur = op; run = k;
-    };
-    for (int step = 0; step < steps && !done; ++step) {
-        if (state == 0 && (i == 0 || j == 0)) {
-            if (prm.mode == EN_GLOBAL) { emit(2, j); emit(1, i); i = 0; j = 0; }
-            else if (prm.mode == EN_SEMIGLOBAL && j == 0) { emit(1, i); i = 0; }
-            done = true;
-            break;
-        }
+    pr_walk(row, prm.mode, m, n, prm.cigar + pr.cig_off, pr.cig_cap, [&](int i, int j) -> int {
         const int ch = (j - 1) / kEnChunk, p = (j - 1) % kEnChunk;
         const int L = ch == nchunks - 1 ? llast : 64;
         const int64_t wi = (int64_t)ch * m * 64 + (int64_t)(i - 1) * L + p / kEnCpl;
-        if (wi < 0 || wi >= nwords) { bad = true; break; }
-        const uint32_t nib = (ws[wi] >> (4 * (p % kEnCpl))) & 15u;
-        if (state == 0) {
-            state = (int)(nib & 3u);                             // a gap state takes its first letter from this same cell
-            if (state == 0) { emit(0, 1); --i; --j; continue; }
-        }
-        if (state == 1) { emit(2, 1); --j; if (nib & 4u) state = 0; }
-        else if (state == 2) { emit(1, 1); --i; if (nib & 8u) state = 0; }
-        else { bad = true; break; }
-    }
-    emit(-2, 1);                                                 // flush the last run
-    if (bad || !done) { row[7] = EN_ST_NO_WALK; return; }
-    for (int a = 0, b = nops - 1; a < b; ++a, --b) { const uint32_t w = out[a]; out[a] = out[b]; out[b] = w; }
-    row[1] = j; row[3] = i; row[5] = nops;
+        if (wi < 0 || wi >= nwords) return -1;
+        return (int)((ws[wi] >> (4 * (p % kEnCpl))) & 15u);
+    });
 }
 
 template <int MODE>

@@ -1,0 +1,66 @@
+// ssw_pairs.h -- what K1g (ssw_ends.hip) and K1gb (ssw_band.hip) share on the device: the LDS matrix of their score kernels and the
+// one walk back over the stored decisions.  The two differ in where a cell's decisions lie, which the walk takes as a functor.
+// (The 4 decision bits of a cell and the end cell's argmax over the wave are the same text in both score kernels and stay written
+// out there: as helpers they changed the register allocation of the storing forms -- LABNOTES.md has the tables.)
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "clh_device.h"
+
+namespace clh {
+
+__device__ __forceinline__ int pr_max(int a, int b) { return a > b ? a : b; }
+
+// smat[query code][reference code], 32 x 32 ints in LDS, zero outside the n_mat x n_mat matrix; the whole workgroup (one wave) calls it
+__device__ __forceinline__ void pr_load_matrix(int* smat, const int8_t* mat, int n_mat, int lane)
+{
+    for (int k = lane; k < 32 * 32; k += 64) {
+        const int qc = k >> 5, rc = k & 31;
+        smat[k] = (qc < n_mat && rc < n_mat) ? (int)mat[rc * n_mat + qc] : 0;
+    }
+    __syncthreads();
+}
+
+// One lane walks one pair's stored decisions back from the end cell its score kernel left in `row` (tie rules: diagonal, then E,
+// then F; a gap is left as soon as "opened here" is set), writes the CIGAR (BAM ops M 0, I 1, D 2) and the begins; at most
+// i + j + 2 steps.  cell(i, j) gives the 4 bits of cell (i, j), or -1 where the cell is outside what was stored.  Whatever
+// does not add up sets EN_ST_NO_WALK, which fetch reports.  The caller has checked the pair's own geometry and that `out` holds cig_cap ops.
+template <typename Cell>
+__device__ __forceinline__ void pr_walk(int32_t* row, int mode, int m, int n, uint32_t* out, int cig_cap, Cell cell)
+{
+    int i = row[4] + 1, j = row[2] + 1;
+    if (i < 0 || i > m || j < 0 || j > n) { row[7] = EN_ST_NO_WALK; return; }
+    const int steps = i + j + 2;
+    int state = 0, nops = 0, cur = -1, run = 0;
+    bool bad = false, done = false;
+    auto emit = [&](int op, int k) {
+        if (k <= 0) return;
+        if (op == cur) { run += k; return; }
+        if (run) { if (nops < cig_cap) out[nops++] = ((uint32_t)run << 4) | (uint32_t)cur; else bad = true; }
+        cur = op; run = k;
+    };
+    for (int step = 0; step < steps && !done; ++step) {
+        if (state == 0 && (i == 0 || j == 0)) {
+            if (mode == EN_GLOBAL) { emit(2, j); emit(1, i); i = 0; j = 0; }
+            else if (mode == EN_SEMIGLOBAL && j == 0) { emit(1, i); i = 0; }
+            done = true;
+            break;
+        }
+        const int at = cell(i, j);
+        if (at < 0) { bad = true; break; }
+        const uint32_t nib = (uint32_t)at;
+        if (state == 0) {
+            state = (int)(nib & 3u);                             // a gap state takes its first letter from this same cell
+            if (state == 0) { emit(0, 1); --i; --j; continue; }
+        }
+        if (state == 1) { emit(2, 1); --j; if (nib & 4u) state = 0; }
+        else if (state == 2) { emit(1, 1); --i; if (nib & 8u) state = 0; }
+        else { bad = true; break; }
+    }
+    emit(-2, 1);                                                 // flush the last run
+    if (bad || !done) { row[7] = EN_ST_NO_WALK; return; }
+    for (int a = 0, b = nops - 1; a < b; ++a, --b) { const uint32_t w = out[a]; out[a] = out[b]; out[b] = w; }
+    row[1] = j; row[3] = i; row[5] = nops;
+}
+
+}  // namespace clh

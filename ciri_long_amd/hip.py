@@ -264,6 +264,12 @@ class _Handle(object):
         except Exception:
             pass
 
+    def _timing(self, name):
+        """HIP-event milliseconds of the last run, from the libclh function `name`(handle, float*)"""
+        ms = C.c_float(0)
+        _check(getattr(lib(), name)(self._h, C.byref(ms)), name)
+        return float(ms.value)
+
 
 _LUT = np.full(256, 4, dtype=np.int8)
 for _c, _v in zip('ACGTN', range(5)):
@@ -599,9 +605,7 @@ class EditPlan(_Handle):
         return out
 
     def timing(self):
-        ms = C.c_float(0)
-        _check(lib().clh_edit_plan_timing(self._h, C.byref(ms)), 'clh_edit_plan_timing')
-        return float(ms.value)
+        return self._timing('clh_edit_plan_timing')
 
 
 class _EditMatrixInput(object):
@@ -669,9 +673,7 @@ class EditMatrixPlan(_Handle):
 
     def timing(self):
         """HIP-event milliseconds of the last run: compression + task build + K4"""
-        ms = C.c_float(0)
-        _check(lib().clh_edit_matrix_plan_timing(self._h, C.byref(ms)), 'clh_edit_matrix_plan_timing')
-        return float(ms.value)
+        return self._timing('clh_edit_matrix_plan_timing')
 
 
 def _letter(c):
@@ -722,9 +724,7 @@ class EditAlignPlan(_Handle):
         return rows, locs[:lu.value].copy(), cig[:cu.value].copy()
 
     def timing(self):
-        ms = C.c_float(0)
-        _check(lib().clh_edit_align_plan_timing(self._h, C.byref(ms)), 'clh_edit_align_plan_timing')
-        return float(ms.value)
+        return self._timing('clh_edit_align_plan_timing')
 
 
 class EditSearchPlan(_Handle):
@@ -755,9 +755,7 @@ class EditSearchPlan(_Handle):
         return rows
 
     def timing(self):
-        ms = C.c_float(0)
-        _check(lib().clh_edit_search_plan_timing(self._h, C.byref(ms)), 'clh_edit_search_plan_timing')
-        return float(ms.value)
+        return self._timing('clh_edit_search_plan_timing')
 
     def info(self):
         """the geometry of the kernel: columns a lane owns per round (seg), columns of a wave's round, columns one wave walks before a
@@ -768,49 +766,68 @@ class EditSearchPlan(_Handle):
                 'split_texts': int(out[5]), 'probes32': int(out[6]), 'probes64': int(out[7])}
 
 
-class EndsPlan(_Handle):
+class _PairsPlan(_Handle):
+    """What EndsPlan and BandPlan share: the inputs as libclh takes them, run(), fetch() and timing().  A subclass names its C
+    prefix (`_c`, as in clh_<_c>_plan_run) and the dtype of its rows."""
+    _c = _dtype = None
+
+    def _inputs(self, queries, query_off, refs, ref_off, mat, want_cigar, diagonals=None):
+        """-> (codes and offsets as contiguous arrays, the flat int8 matrix, its edge, the diagonals as int32 or None); sets n and
+        want_cigar"""
+        who = type(self).__name__
+        q = np.ascontiguousarray(queries, dtype=np.int8); r = np.ascontiguousarray(refs, dtype=np.int8)
+        q_off = np.ascontiguousarray(query_off, dtype=np.int64); r_off = np.ascontiguousarray(ref_off, dtype=np.int64)
+        if len(q_off) != len(r_off) or len(q_off) < 1:
+            raise ValueError('%s: the two offset tables differ in length' % who)
+        self.n = len(q_off) - 1
+        self.want_cigar = bool(want_cigar)
+        diag = None
+        if diagonals is not None:
+            diag = np.ascontiguousarray(diagonals, dtype=np.int32)
+            if diag.shape != (self.n,):
+                raise ValueError('%s: %d diagonals for %d pairs' % (who, diag.size, self.n))
+        mat = np.ascontiguousarray(mat, dtype=np.int8).reshape(-1)
+        n_mat = int(round(len(mat) ** 0.5))
+        if n_mat * n_mat != len(mat):
+            raise ValueError('%s: the substitution matrix is not square' % who)
+        return q, q_off, r, r_off, mat, n_mat, diag
+
+    def run(self, stream=0):
+        name = 'clh_%s_plan_run' % self._c
+        _check(getattr(lib(), name)(self._h, C.c_void_p(stream)), name)
+
+    def fetch(self):
+        name = 'clh_%s_plan_fetch' % self._c
+        rows = np.zeros(self.n, dtype=self._dtype)
+        cap = self.info()['cigar_cap'] if self.want_cigar else 0
+        cig = np.empty(max(cap, 1), dtype=np.uint32)     # worst-case capacity; only the used prefix is written
+        used = C.c_int64(0)
+        _check(getattr(lib(), name)(self._h, rows.ctypes.data, cig.ctypes.data if self.want_cigar else None, cap, C.byref(used)), name)
+        return rows, cig[:used.value].copy()
+
+    def timing(self):
+        """HIP-event milliseconds of the last run: the score kernels (of every class, where there are classes), and with CIGARs
+        the walks, of every share of the batch"""
+        return self._timing('clh_%s_plan_timing' % self._c)
+
+
+class EndsPlan(_PairsPlan):
     """Pairs resident on the GPU (codes uploaded once) for the end-anchored modes of K1g -- 'global', 'semiglobal' (the whole query in
     any stretch of the reference), 'overlap' (end gaps free on both sequences): run() any number of times, fetch() (rows ENDS_DTYPE,
     cigars uint32).  Scores are int32 and may be negative; a span without a letter has end == begin - 1; without want_cigar no walk
     back is made and a begin the mode does not fix is -1 (include/ciri_long_hip.h)."""
     _destroy = 'clh_ends_plan_destroy'
+    _c, _dtype = 'ends', ENDS_DTYPE
 
     def __init__(self, ctx, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode='global', want_cigar=True, workspace_bytes=0):
         _Handle.__init__(self, ctx)
         if mode not in ENDS_MODES:
             raise ValueError('mode must be one of global, semiglobal, overlap, got %r' % (mode,))
-        q = np.ascontiguousarray(queries, dtype=np.int8); r = np.ascontiguousarray(refs, dtype=np.int8)
-        q_off = np.ascontiguousarray(query_off, dtype=np.int64); r_off = np.ascontiguousarray(ref_off, dtype=np.int64)
-        if len(q_off) != len(r_off) or len(q_off) < 1:
-            raise ValueError('EndsPlan: the two offset tables differ in length')
-        self.n = len(q_off) - 1
-        self.want_cigar = bool(want_cigar)
-        mat = np.ascontiguousarray(mat, dtype=np.int8).reshape(-1)
-        n_mat = int(round(len(mat) ** 0.5))
-        if n_mat * n_mat != len(mat):
-            raise ValueError('EndsPlan: the substitution matrix is not square')
+        q, q_off, r, r_off, mat, n_mat, _ = self._inputs(queries, query_off, refs, ref_off, mat, want_cigar)
         opts = EndsOpts(ENDS_MODES[mode], mat.ctypes.data, n_mat, int(gap_open), int(gap_extend), int(self.want_cigar), int(workspace_bytes))
         self._h = lib().clh_ends_plan_create(ctx._h, self.n, q.ctypes.data, q_off.ctypes.data, r.ctypes.data, r_off.ctypes.data, C.byref(opts))
         if not self._h:
             raise ClhError('clh_ends_plan_create failed: %s' % last_error())
-
-    def run(self, stream=0):
-        _check(lib().clh_ends_plan_run(self._h, C.c_void_p(stream)), 'clh_ends_plan_run')
-
-    def fetch(self):
-        rows = np.zeros(self.n, dtype=ENDS_DTYPE)
-        cap = self.info()['cigar_cap'] if self.want_cigar else 0
-        cig = np.empty(max(cap, 1), dtype=np.uint32)     # worst-case capacity; only the used prefix is written
-        used = C.c_int64(0)
-        _check(lib().clh_ends_plan_fetch(self._h, rows.ctypes.data, cig.ctypes.data if self.want_cigar else None, cap, C.byref(used)),
-               'clh_ends_plan_fetch')
-        return rows, cig[:used.value].copy()
-
-    def timing(self):
-        """HIP-event milliseconds of the last run: the score kernel, and with CIGARs the walks, of every share of the batch"""
-        ms = C.c_float(0)
-        _check(lib().clh_ends_plan_timing(self._h, C.byref(ms)), 'clh_ends_plan_timing')
-        return float(ms.value)
 
     def info(self):
         """the geometry of the kernel: reference columns a lane owns (cpl) and columns of a chunk (a longer reference is walked chunk
@@ -822,33 +839,20 @@ class EndsPlan(_Handle):
                 'kernel_pairs': int(out[5]), 'empty_pairs': int(out[6]), 'cigar_cap': int(out[7])}
 
 
-class BandPlan(_Handle):
+class BandPlan(_PairsPlan):
     """Pairs resident on the GPU for K1gb, the global and semiglobal programmes of EndsPlan over a band of diagonals d = j - i per
     pair: [min(0, n - m) - band, max(0, n - m) + band], or [diagonals[k] - band, diagonals[k] + band] with a hint per pair, clipped
     to [-m, n] and at most 512 wide.  run() any number of times, fetch() (rows BAND_DTYPE, cigars uint32).  A row carries the
     clipped band and `exact`: 1 where it is proved that EndsPlan returns the same row and CIGAR (include/ciri_long_hip.h)."""
     _destroy = 'clh_band_plan_destroy'
+    _c, _dtype = 'band', BAND_DTYPE
 
     def __init__(self, ctx, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, band, mode='global', diagonals=None, want_cigar=True,
                  workspace_bytes=0):
         _Handle.__init__(self, ctx)
         if mode not in ENDS_MODES:
             raise ValueError('mode must be one of global, semiglobal, got %r' % (mode,))
-        q = np.ascontiguousarray(queries, dtype=np.int8); r = np.ascontiguousarray(refs, dtype=np.int8)
-        q_off = np.ascontiguousarray(query_off, dtype=np.int64); r_off = np.ascontiguousarray(ref_off, dtype=np.int64)
-        if len(q_off) != len(r_off) or len(q_off) < 1:
-            raise ValueError('BandPlan: the two offset tables differ in length')
-        self.n = len(q_off) - 1
-        self.want_cigar = bool(want_cigar)
-        diag = None
-        if diagonals is not None:
-            diag = np.ascontiguousarray(diagonals, dtype=np.int32)
-            if diag.shape != (self.n,):
-                raise ValueError('BandPlan: %d diagonals for %d pairs' % (diag.size, self.n))
-        mat = np.ascontiguousarray(mat, dtype=np.int8).reshape(-1)
-        n_mat = int(round(len(mat) ** 0.5))
-        if n_mat * n_mat != len(mat):
-            raise ValueError('BandPlan: the substitution matrix is not square')
+        q, q_off, r, r_off, mat, n_mat, diag = self._inputs(queries, query_off, refs, ref_off, mat, want_cigar, diagonals)
         if not 0 <= int(band) < 2 ** 31:
             raise ValueError('BandPlan: band must be a half-width >= 0, got %r' % (band,))
         opts = BandOpts(ENDS_MODES[mode], mat.ctypes.data, n_mat, int(gap_open), int(gap_extend), int(self.want_cigar), int(workspace_bytes), int(band), 0)
@@ -856,24 +860,6 @@ class BandPlan(_Handle):
                                              diag.ctypes.data if diag is not None else None, C.byref(opts))
         if not self._h:
             raise ClhError('clh_band_plan_create failed: %s' % last_error())
-
-    def run(self, stream=0):
-        _check(lib().clh_band_plan_run(self._h, C.c_void_p(stream)), 'clh_band_plan_run')
-
-    def fetch(self):
-        rows = np.zeros(self.n, dtype=BAND_DTYPE)
-        cap = self.info()['cigar_cap'] if self.want_cigar else 0
-        cig = np.empty(max(cap, 1), dtype=np.uint32)     # worst-case capacity; only the used prefix is written
-        used = C.c_int64(0)
-        _check(lib().clh_band_plan_fetch(self._h, rows.ctypes.data, cig.ctypes.data if self.want_cigar else None, cap, C.byref(used)),
-               'clh_band_plan_fetch')
-        return rows, cig[:used.value].copy()
-
-    def timing(self):
-        """HIP-event milliseconds of the last run: the score kernels of every class, and with CIGARs the walks, of every share"""
-        ms = C.c_float(0)
-        _check(lib().clh_band_plan_timing(self._h, C.byref(ms)), 'clh_band_plan_timing')
-        return float(ms.value)
 
     def info(self):
         """the classes of the kernel: band positions a lane owns (cpl; a class holds bands of up to 64 cpl diagonals); and of this plan:

@@ -330,6 +330,38 @@ def align_pairs_matrix(ref_seqs, query_seqs, matrix, alphabet, gap_open, gap_ext
 # ---------------------------------------------------------------------------------------------------------------------------
 # end-anchored modes beside the local one (K1g, csrc/ssw_ends.hip)
 # ---------------------------------------------------------------------------------------------------------------------------
+def _pairs_inputs(who, ref_seqs, query_seqs, match, mismatch, matrix, alphabet):
+    """what align_pairs_ends and align_pairs_band send to the device: the flat int8 matrix (match / mismatch, or `matrix` over
+    `alphabet`), and the packed codes (data, offsets) of the queries and of the references"""
+    if (matrix is None) != (alphabet is None):
+        raise ValueError('%s: matrix and alphabet come together' % who)
+    if matrix is not None:
+        mat = _int8_matrix(matrix, who)
+        if mat.size != len(alphabet) ** 2 or not 1 <= len(alphabet) <= 32:
+            raise ValueError('%s: a %d-letter alphabet needs a %d x %d matrix (1..32 letters)' % (who, len(alphabet), len(alphabet), len(alphabet)))
+        enc = lambda s: encode_alphabet(s, alphabet) if isinstance(s, (str, bytes)) else np.asarray(s, dtype=np.int8)
+    else:
+        mat = hip.score_matrix(match, mismatch)
+        enc = lambda s: hip.encode(s) if isinstance(s, (str, bytes)) else np.asarray(s, dtype=np.int8)
+    return mat, hip.pack([enc(q) for q in query_seqs]), hip.pack([enc(r) for r in ref_seqs])
+
+
+def _pairs_results(rows, cig, qo, walk, report_cigar):
+    """rows of ENDS_DTYPE's fields and their CIGAR ops -> one PyAlignRes per pair"""
+    out = []
+    for k in range(len(rows)):
+        r = rows[k]
+        ops = cig[int(r['cigar_off']):int(r['cigar_off']) + int(r['cigar_len'])] if walk else ()
+        res = PyAlignRes.__new__(PyAlignRes)
+        res.score = int(r['score'])
+        res.ref_begin, res.ref_end = int(r['ref_begin']), int(r['ref_end'])
+        res.query_begin, res.query_end = int(r['query_begin']), int(r['query_end'])
+        res.score2 = res.ref_end2 = None
+        res.cigar_string = res._cigar_string(ops, int(qo[k + 1] - qo[k])) if report_cigar else None
+        out.append(res)
+    return out
+
+
 def align_pairs_ends(ref_seqs, query_seqs, mode='global', match=2, mismatch=2, gap_open=3, gap_extend=1, report_cigar=False, matrix=None,
                      alphabet=None, context=None):
     """n independent (reference, query) alignments anchored at the ends, in one GPU call -> one PyAlignRes per pair.
@@ -349,35 +381,13 @@ def align_pairs_ends(ref_seqs, query_seqs, mode='global', match=2, mismatch=2, g
         raise ValueError("align_pairs_ends: mode must be 'global', 'semiglobal' or 'overlap', got %r" % (mode,))
     if len(ref_seqs) != len(query_seqs):
         raise ValueError('align_pairs_ends: %d references vs %d queries' % (len(ref_seqs), len(query_seqs)))
-    if (matrix is None) != (alphabet is None):
-        raise ValueError('align_pairs_ends: matrix and alphabet come together')
-    if matrix is not None:
-        mat = _int8_matrix(matrix, 'align_pairs_ends')
-        if mat.size != len(alphabet) ** 2 or not 1 <= len(alphabet) <= 32:
-            raise ValueError('align_pairs_ends: a %d-letter alphabet needs a %d x %d matrix (1..32 letters)' % (len(alphabet), len(alphabet), len(alphabet)))
-        enc = lambda s: encode_alphabet(s, alphabet) if isinstance(s, (str, bytes)) else np.asarray(s, dtype=np.int8)
-    else:
-        mat = hip.score_matrix(match, mismatch)
-        enc = lambda s: hip.encode(s) if isinstance(s, (str, bytes)) else np.asarray(s, dtype=np.int8)
+    mat, (qd, qo), (rd, ro) = _pairs_inputs('align_pairs_ends', ref_seqs, query_seqs, match, mismatch, matrix, alphabet)
     if not ref_seqs:
         return []
-    qd, qo = hip.pack([enc(q) for q in query_seqs])
-    rd, ro = hip.pack([enc(r) for r in ref_seqs])
     ctx = context or hip.default_context()
     walk = bool(report_cigar) or mode != 'global'          # the begins come from the walk, unless the mode fixes them
     rows, cig = ctx.ends_batch(qd, qo, rd, ro, mat, gap_open, gap_extend, mode=mode, want_cigar=walk)
-    out = []
-    for k in range(len(rows)):
-        r = rows[k]
-        ops = cig[int(r['cigar_off']):int(r['cigar_off']) + int(r['cigar_len'])] if walk else ()
-        res = PyAlignRes.__new__(PyAlignRes)
-        res.score = int(r['score'])
-        res.ref_begin, res.ref_end = int(r['ref_begin']), int(r['ref_end'])
-        res.query_begin, res.query_end = int(r['query_begin']), int(r['query_end'])
-        res.score2 = res.ref_end2 = None
-        res.cigar_string = res._cigar_string(ops, int(qo[k + 1] - qo[k])) if report_cigar else None
-        out.append(res)
-    return out
+    return _pairs_results(rows, cig, qo, walk, report_cigar)
 
 
 def align_pairs_band(ref_seqs, query_seqs, band, mode='global', diagonals=None, match=2, mismatch=2, gap_open=3, gap_extend=1, report_cigar=False,
@@ -402,34 +412,14 @@ def align_pairs_band(ref_seqs, query_seqs, band, mode='global', diagonals=None, 
         raise ValueError('align_pairs_band: %d diagonals vs %d pairs' % (len(diagonals), len(ref_seqs)))
     if int(band) != band or band < 0:
         raise ValueError('align_pairs_band: band is a half-width in diagonals, an integer >= 0, got %r' % (band,))
-    if (matrix is None) != (alphabet is None):
-        raise ValueError('align_pairs_band: matrix and alphabet come together')
-    if matrix is not None:
-        mat = _int8_matrix(matrix, 'align_pairs_band')
-        if mat.size != len(alphabet) ** 2 or not 1 <= len(alphabet) <= 32:
-            raise ValueError('align_pairs_band: a %d-letter alphabet needs a %d x %d matrix (1..32 letters)' % (len(alphabet), len(alphabet), len(alphabet)))
-        enc = lambda s: encode_alphabet(s, alphabet) if isinstance(s, (str, bytes)) else np.asarray(s, dtype=np.int8)
-    else:
-        mat = hip.score_matrix(match, mismatch)
-        enc = lambda s: hip.encode(s) if isinstance(s, (str, bytes)) else np.asarray(s, dtype=np.int8)
+    mat, (qd, qo), (rd, ro) = _pairs_inputs('align_pairs_band', ref_seqs, query_seqs, match, mismatch, matrix, alphabet)
     if not ref_seqs:
         return []
-    qd, qo = hip.pack([enc(q) for q in query_seqs])
-    rd, ro = hip.pack([enc(r) for r in ref_seqs])
     ctx = context or hip.default_context()
     walk = bool(report_cigar) or mode != 'global'          # the begins come from the walk, unless the mode fixes them
     rows, cig = ctx.band_batch(qd, qo, rd, ro, mat, gap_open, gap_extend, int(band), mode=mode, diagonals=diagonals, want_cigar=walk)
-    out = []
-    for k in range(len(rows)):
-        r = rows[k]
-        ops = cig[int(r['cigar_off']):int(r['cigar_off']) + int(r['cigar_len'])] if walk else ()
-        res = PyAlignRes.__new__(PyAlignRes)
-        res.score = int(r['score'])
-        res.ref_begin, res.ref_end = int(r['ref_begin']), int(r['ref_end'])
-        res.query_begin, res.query_end = int(r['query_begin']), int(r['query_end'])
-        res.score2 = res.ref_end2 = None
-        res.cigar_string = res._cigar_string(ops, int(qo[k + 1] - qo[k])) if report_cigar else None
+    out = _pairs_results(rows, cig, qo, walk, report_cigar)
+    for r, res in zip(rows, out):
         res.band = (int(r['band_lo']), int(r['band_hi']))
         res.band_exact = bool(r['exact'])
-        out.append(res)
     return out

@@ -1,4 +1,4 @@
-"""The lifecycle of hip.py's handle wrappers (Plan, EditPlan, EditAlignPlan, CcsPlan, Genome) against a fake libclh that records
+"""The lifecycle of hip.py's handle wrappers (Plan, the edit, ends and band plans, CcsPlan, Genome) against a fake libclh that records
 what is created and destroyed: close() destroys the handle once, and a wrapper whose context has closed destroys nothing (clh_destroy
 has given everything back).  No GPU."""
 import numpy as np
@@ -44,10 +44,15 @@ def _context():
 
 
 MAT = hip.score_matrix(2, 2)
+PAIRS = hip.pack(['ACGT']) + hip.pack(['TACGTA'])       # queries, query_off, refs, ref_off
 WRAPPERS = {
     'Plan': ('clh_plan_destroy', lambda ctx: ctx.plan([0, 4], [0, 8], MAT, 3, 1)),
     'EditPlan': ('clh_edit_plan_destroy', lambda ctx: ctx.edit_plan(['ACGT'], ['ACGA'])),
     'EditAlignPlan': ('clh_edit_align_plan_destroy', lambda ctx: ctx.edit_align_plan(['ACGT'], ['ACGA'], mode='HW', task='path')),
+    'EditMatrixPlan': ('clh_edit_matrix_plan_destroy', lambda ctx: ctx.edit_matrix_plan([['ACGT', 'ACGA', 'AC']], hpc=True)),
+    'EditSearchPlan': ('clh_edit_search_plan_destroy', lambda ctx: ctx.edit_search_plan(['ACG'], ['ACGTACGA'], k=1)),
+    'EndsPlan': ('clh_ends_plan_destroy', lambda ctx: ctx.ends_plan(*PAIRS, MAT, 3, 1, mode='overlap')),
+    'BandPlan': ('clh_band_plan_destroy', lambda ctx: ctx.band_plan(*PAIRS, MAT, 3, 1, 2, mode='semiglobal', diagonals=[1])),
     'CcsPlan': ('clh_ccs_plan_destroy', lambda ctx: ctx.ccs_plan(np.array([0, 100], dtype=np.int64))),
     'Genome': ('clh_genome_destroy', lambda ctx: hip.Genome(ctx, {'chr1': 'ACGTACGT'})),
 }
