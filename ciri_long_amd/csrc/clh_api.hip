@@ -2140,8 +2140,8 @@ static int pairs_check_opts(const std::string& me, const clh_ctx* ctx, int32_t n
     if (!ctx || n < 0 || !q_off || !r_off || !o || !o->mat) return fail(CLH_E_ARG, me + "bad argument");
     if (band) {
         if (o->mode == CLH_ENDS_OVERLAP) return fail(CLH_E_UNSUPPORTED, me + "overlap with a band is not built; clh_ends_plan_create takes the mode over the full matrix");
-        if (o->mode != CLH_ENDS_GLOBAL && o->mode != CLH_ENDS_SEMIGLOBAL) return fail(CLH_E_ARG, me + "mode must be CLH_ENDS_GLOBAL or CLH_ENDS_SEMIGLOBAL");
-    } else if (o->mode < CLH_ENDS_GLOBAL || o->mode > CLH_ENDS_OVERLAP) return fail(CLH_E_ARG, me + "mode must be CLH_ENDS_GLOBAL, _SEMIGLOBAL or _OVERLAP");
+        if (o->mode < CLH_ENDS_GLOBAL || o->mode > CLH_ENDS_EXTEND) return fail(CLH_E_ARG, me + "mode must be CLH_ENDS_GLOBAL, _SEMIGLOBAL, _PREFIX or _EXTEND");
+    } else if (o->mode < CLH_ENDS_GLOBAL || o->mode > CLH_ENDS_EXTEND) return fail(CLH_E_ARG, me + "mode must be CLH_ENDS_GLOBAL, _SEMIGLOBAL, _OVERLAP, _PREFIX or _EXTEND");
     if (o->n_mat < 1 || o->n_mat > 32) return fail(CLH_E_ARG, me + "n_mat must be 1..32");
     if (o->gap_open < 0 || o->gap_extend < 0 || o->workspace_bytes < 0 || (band && *band < 0))
         return fail(CLH_E_ARG, me + (band ? "gap costs, workspace_bytes and band must not be negative" : "gap costs and workspace_bytes must not be negative"));
@@ -2246,6 +2246,7 @@ static void en_empty_side(int mode, int m, int n, int go, int ge, Row* row, uint
     *op = 0;
     row->score = 0; row->ref_begin = 0; row->ref_end = -1; row->query_begin = 0; row->query_end = -1;
     if (n > 0 && mode == CLH_ENDS_GLOBAL) { row->score = -(go + (n - 1) * ge); row->ref_end = n - 1; *op = ((uint32_t)n << 4) | 2u; }
+    if (mode == CLH_ENDS_EXTEND) return;                       // the best cell of a boundary that only loses is (0, 0)
     if (m > 0 && mode != CLH_ENDS_OVERLAP) { row->score = -(go + (m - 1) * ge); row->query_end = m - 1; *op = ((uint32_t)m << 4) | 1u; }
     if (m > 0 && mode == CLH_ENDS_OVERLAP) { row->query_begin = m; row->query_end = m - 1; }
 }
@@ -2305,7 +2306,7 @@ static int pairs_fetch(const std::string& kind, Plan* pl, Row* rows, uint32_t* c
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// K1g: end-anchored affine-gap alignment of pairs -- global, semiglobal, overlap (ssw_ends.hip)
+// K1g: end-anchored affine-gap alignment of pairs -- global, semiglobal, overlap, prefix, extend (ssw_ends.hip)
 // ---------------------------------------------------------------------------------------------------------------
 struct clh_ends_plan : clh_pairs_plan {
     using clh_pairs_plan::clh_pairs_plan;
@@ -2417,7 +2418,7 @@ extern "C" int clh_ends_batch(clh_ctx* ctx, int32_t n, const int8_t* q, const in
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// K1gb: K1g's global and semiglobal programmes over a band of diagonals per pair (ssw_band.hip)
+// K1gb: K1g's global, semiglobal, prefix and extend programmes over a band of diagonals per pair (ssw_band.hip)
 // ---------------------------------------------------------------------------------------------------------------
 struct clh_band_plan : clh_pairs_plan {
     using clh_pairs_plan::clh_pairs_plan;
@@ -2443,6 +2444,7 @@ extern "C" clh_band_plan* clh_band_plan_create(clh_ctx* ctx, int32_t n, const in
     int64_t splus;
     const int64_t smax = pairs_scan_matrix(o, &splus);
     const bool global = o->mode == CLH_ENDS_GLOBAL;
+    const bool anchored = o->mode == CLH_ENDS_PREFIX || o->mode == CLH_ENDS_EXTEND;      // the far end is free: n - m plays no part in the band
     std::vector<std::pair<int32_t, int32_t>> bands((size_t)n);
     for (int k = 0; k < n; ++k) {
         const int64_t m = q_off[k + 1] - q_off[k], nn = r_off[k + 1] - r_off[k];
@@ -2457,13 +2459,22 @@ extern "C" clh_band_plan* clh_band_plan_create(clh_ctx* ctx, int32_t n, const in
         }
         int64_t lo, hi;
         if (diag) { lo = (int64_t)diag[k] - bo->band; hi = (int64_t)diag[k] + bo->band; }
+        else if (anchored) { lo = -(int64_t)bo->band; hi = bo->band; }
         else { lo = std::min<int64_t>(0, nn - m) - bo->band; hi = std::max<int64_t>(0, nn - m) + bo->band; }
         const std::string bt = "the band [" + std::to_string(lo) + ", " + std::to_string(hi) + "] of the " + std::to_string(m) + " x " + std::to_string(nn) + " pair ";
         if (global && (lo > std::min<int64_t>(0, nn - m) || hi < std::max<int64_t>(0, nn - m))) {
             fail(CLH_E_ARG, pk + bt + "misses (0, 0) or (m, n): a global band holds the diagonals 0 and n - m = " + std::to_string(nn - m));
             return nullptr;
         }
-        if (!global && (hi < 0 || lo > nn - m)) {
+        if (anchored && (lo > 0 || hi < 0)) {
+            fail(CLH_E_ARG, pk + bt + "misses (0, 0): a start-anchored band holds the diagonal 0");
+            return nullptr;
+        }
+        if (o->mode == CLH_ENDS_PREFIX && lo > nn - m) {
+            fail(CLH_E_ARG, pk + bt + "has no end cell on row m (lo > n - m = " + std::to_string(nn - m) + ")");
+            return nullptr;
+        }
+        if (!global && !anchored && (hi < 0 || lo > nn - m)) {
             fail(CLH_E_ARG, pk + bt + "has no start cell on row 0 (hi < 0) or no end cell on row m (lo > n - m = " + std::to_string(nn - m) + ")");
             return nullptr;
         }
@@ -2544,6 +2555,13 @@ extern "C" int clh_band_plan_run(clh_band_plan* pl, void* stream_)
 static int32_t bd_exact(int mode, int64_t m, int64_t n, int64_t lo, int64_t hi, int64_t score, int64_t splus, int64_t go, int64_t ge)
 {
     if (lo <= -m && hi >= n) return 1;
+    if (mode == CLH_ENDS_PREFIX || mode == CLH_ENDS_EXTEND) {
+        // the far end is free: an alignment that leaves the band need not come back, so one gap run and the M columns it leaves
+        bool in = true;
+        if (hi + 1 <= n) in = in && score > splus * std::min<int64_t>(m, n - hi - 1) - go - hi * ge;
+        if (lo - 1 >= -m) in = in && score > splus * std::min<int64_t>(n, m + lo - 1) - go - (-lo) * ge;
+        return in ? 1 : 0;
+    }
     if (mode != CLH_ENDS_GLOBAL) return 0;
     bool ok = true;
     if (hi + 1 <= n) ok = ok && score > splus * std::max<int64_t>(0, n - hi - 1) - 2 * go - (2 * (hi + 1) - (n - m) - 2) * ge;

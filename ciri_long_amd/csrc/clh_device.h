@@ -304,12 +304,14 @@ struct EsParams {
 hipError_t launch_edit_search(const EsParams& p, int W, hipStream_t stream);          // the segments; finishes the cells of one chunk
 hipError_t launch_edit_search_finish(const EsParams& p, int W, hipStream_t stream);   // joins the chunks of split texts
 
-// K1g (ssw_ends.hip): end-anchored affine-gap alignment of pairs in int32 cells; one wave per pair, its lanes on kEnCpl reference
+// K1g (ssw_ends.hip): end-anchored and start-anchored affine-gap alignment of pairs in int32 cells; one wave per pair, its lanes on kEnCpl reference
 // columns each, chunks of kEnChunk columns handing their last column on.  tools/ends_model.py states the scheme.
 static constexpr int kEnCpl = 8;                        // columns a lane owns
 static constexpr int kEnChunk = 64 * kEnCpl;            // columns of one chunk
 static constexpr int32_t kEnUnwritten = (int32_t)0x80808080;   // what the result rows are filled with before a run
-enum { EN_GLOBAL = 0, EN_SEMIGLOBAL = 1, EN_OVERLAP = 2 };
+enum { EN_GLOBAL = 0, EN_SEMIGLOBAL = 1, EN_OVERLAP = 2, EN_PREFIX = 3, EN_EXTEND = 4 };
+// start-anchored: pinned at (0, 0) with global's row 0 and column 0; the walk stops at (0, 0); what differs from global is the end cell
+__host__ __device__ constexpr bool en_anchored(int mode) { return mode == EN_GLOBAL || mode == EN_PREFIX || mode == EN_EXTEND; }
 enum { EN_ST_NO_WALK = 1 };                             // row status: the decisions were not stored or the walk failed (fetch reports it)
 struct EnPair {
     int64_t q_off, r_off;                               // first code of the query / the reference
@@ -331,7 +333,7 @@ struct EnParams {
 hipError_t launch_ssw_ends(const EnParams& p, bool store, int first, int count, hipStream_t stream);
 hipError_t launch_ssw_ends_walk(const EnParams& p, int first, int count, hipStream_t stream);     // after the storing form of the same pairs
 
-// K1gb (ssw_band.hip): K1g's global and semiglobal programmes over a band of diagonals [lo, hi], d = j - i; one wave per pair in the
+// K1gb (ssw_band.hip): K1g's global, semiglobal, prefix and extend programmes over a band of diagonals [lo, hi], d = j - i; one wave per pair in the
 // band's frame, a lane on CPL consecutive band positions b = d - lo (classes CPL 2, 4, 8: bands of up to 128, 256, 512 diagonals).
 // tools/band_model.py states the scheme.
 static constexpr int kBdClasses = 3;

@@ -1,4 +1,4 @@
-// ssw_band.hip -- K1gb: K1g's global and semiglobal programmes over a band of diagonals, in the band's own frame (gfx950).
+// ssw_band.hip -- K1gb: K1g's global, semiglobal, prefix and extend programmes over a band of diagonals, in the band's own frame (gfx950).
 //
 // The band of a pair is [lo, hi] in d = j - i (i query letters, j reference letters), B = hi - lo + 1 <= 64 CPL diagonals.  One wave
 // takes one pair; lane l owns the CPL consecutive band positions b = d - lo = l CPL + k, the loop runs over the query rows, and
@@ -21,6 +21,10 @@
 // the query letter does.
 // Minus infinity is kBdNeg (clh_device.h has the bound that keeps it apart from every score).  Every cell of an admitted band is
 // reached from a start cell, so H and T of a cell are scores; E and F may be minus infinity, and then they equal no H.
+// prefix and extend have global's row 0; prefix ends where semiglobal does, over the band's cells of row m.  extend ends at the
+// greatest H over the band's cells, smallest i, then smallest j: a lane keeps the best of its own cells under a bare > (rows ascend,
+// and a lane's columns ascend within a row), seeded with (0, (0, 0)), which cells of column 0 (<= 0) and positions that are no cell
+// (minus infinity) never beat, and the lanes are reduced once by the key after the last row.
 // STORE: 4 bits per cell as in K1g (H's source 0 diagonal / 1 E / 2 F, "E opened here", "F opened here"), CPL / 2 bytes per lane and
 // row, only the lanes that own a band position: m ceil(B / CPL) CPL / 2 bytes per pair.  ssw_band_walk_kernel walks them back, one
 // lane per pair: a diagonal step keeps b, a D step goes to b - 1, an I step to b + 1.  The walk itself is K1g's, pr_walk in
@@ -74,14 +78,14 @@ __global__ void __launch_bounds__(64) ssw_band_kernel(const BdParams prm, int fi
         poff[k] = (int)((uint32_t)p * (uint32_t)ge);
         off[k] = (int)((uint32_t)(p + 1) * (uint32_t)ge - (uint32_t)go);
         const bool cell = p < B && j0 >= 0 && j0 <= n;
-        const int h0 = (MODE == EN_GLOBAL && j0 > 0) ? -(go + (j0 - 1) * ge) : 0;
+        const int h0 = (en_anchored(MODE) && j0 > 0) ? -(go + (j0 - 1) * ge) : 0;
         Hp[k] = cell ? h0 : kBdNeg;
         Fp[k] = kBdNeg;
     }
     const int bn = n - m - lo;                                 // the position of (m, n) in row m
     if (MODE == EN_GLOBAL && (bn < 0 || bn >= B)) return;
     const int ln = bn / CPL, kn = bn % CPL;
-    int corner = kBdNeg, best_v = (int)0x80000000, best_j = 0x7fffffff;
+    int corner = kBdNeg, best_v = MODE == EN_EXTEND ? 0 : (int)0x80000000, best_i = 0, best_j = MODE == EN_EXTEND ? 0 : 0x7fffffff;
 
     for (int i0 = 0; i0 < m; i0 += 64) {
         const bool mine = i0 + lane < m;
@@ -128,7 +132,11 @@ __global__ void __launch_bounds__(64) ssw_band_kernel(const BdParams prm, int fi
                 }
                 if (wsp && lane < L) *(word_t*)(wsp + (size_t)(i - 1) * rowbytes) = (word_t)w;
             }
-            if (i == m) {
+            if (MODE == EN_EXTEND) {
+#pragma unroll
+                for (int k = 0; k < CPL; ++k)
+                    if (H[k] > best_v) { best_v = H[k]; best_i = i; best_j = jr[k]; }
+            } else if (i == m) {
                 if (MODE == EN_GLOBAL) {
                     int hn = H[0];
 #pragma unroll
@@ -150,9 +158,17 @@ __global__ void __launch_bounds__(64) ssw_band_kernel(const BdParams prm, int fi
             rc[CPL - 1] = dpp_shl1(enter, r0);
         }
     }
-    int score, ej;
+    int score, ej, ei = m;
     if (MODE == EN_GLOBAL) {
         score = __shfl(corner, ln); ej = n;
+    } else if (MODE == EN_EXTEND) {
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int v2 = __shfl_xor(best_v, d), i2 = __shfl_xor(best_i, d), j2 = __shfl_xor(best_j, d);
+            const bool take = v2 > best_v || (v2 == best_v && (i2 < best_i || (i2 == best_i && j2 < best_j)));
+            best_v = take ? v2 : best_v; best_i = take ? i2 : best_i; best_j = take ? j2 : best_j;
+        }
+        score = best_v; ei = best_i; ej = best_j;
     } else {
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) {
@@ -165,10 +181,10 @@ __global__ void __launch_bounds__(64) ssw_band_kernel(const BdParams prm, int fi
     if (lane == 0) {
         int32_t* row = prm.rows + (size_t)pi * 8;
         row[0] = score;
-        row[1] = MODE == EN_GLOBAL ? 0 : -1;                      // begins: the walk's, unless the mode fixes them
+        row[1] = en_anchored(MODE) ? 0 : -1;                      // begins: the walk's, unless the mode fixes them
         row[2] = ej - 1;
         row[3] = 0;
-        row[4] = m - 1;
+        row[4] = ei - 1;
         row[5] = 0;
         row[6] = 0;
         row[7] = (STORE && !ws_ok) ? EN_ST_NO_WALK : 0;
@@ -208,6 +224,12 @@ static void bd_launch(const BdParams& p, bool store, int first, int count, hipSt
     if (p.mode == EN_GLOBAL) {
         if (store) hipLaunchKernelGGL((ssw_band_kernel<CPL, EN_GLOBAL, true>), dim3(count), dim3(64), 0, st, p, first, count);
         else hipLaunchKernelGGL((ssw_band_kernel<CPL, EN_GLOBAL, false>), dim3(count), dim3(64), 0, st, p, first, count);
+    } else if (p.mode == EN_PREFIX) {
+        if (store) hipLaunchKernelGGL((ssw_band_kernel<CPL, EN_PREFIX, true>), dim3(count), dim3(64), 0, st, p, first, count);
+        else hipLaunchKernelGGL((ssw_band_kernel<CPL, EN_PREFIX, false>), dim3(count), dim3(64), 0, st, p, first, count);
+    } else if (p.mode == EN_EXTEND) {
+        if (store) hipLaunchKernelGGL((ssw_band_kernel<CPL, EN_EXTEND, true>), dim3(count), dim3(64), 0, st, p, first, count);
+        else hipLaunchKernelGGL((ssw_band_kernel<CPL, EN_EXTEND, false>), dim3(count), dim3(64), 0, st, p, first, count);
     } else {
         if (store) hipLaunchKernelGGL((ssw_band_kernel<CPL, EN_SEMIGLOBAL, true>), dim3(count), dim3(64), 0, st, p, first, count);
         else hipLaunchKernelGGL((ssw_band_kernel<CPL, EN_SEMIGLOBAL, false>), dim3(count), dim3(64), 0, st, p, first, count);
@@ -217,7 +239,7 @@ static void bd_launch(const BdParams& p, bool store, int first, int count, hipSt
 hipError_t launch_ssw_band(const BdParams& p, int cls, bool store, int first, int count, hipStream_t stream)
 {
     if (count <= 0) return hipSuccess;
-    if (p.mode != EN_GLOBAL && p.mode != EN_SEMIGLOBAL) return hipErrorInvalidValue;
+    if (p.mode != EN_GLOBAL && p.mode != EN_SEMIGLOBAL && p.mode != EN_PREFIX && p.mode != EN_EXTEND) return hipErrorInvalidValue;
     if (cls == 0) bd_launch<2>(p, store, first, count, stream);
     else if (cls == 1) bd_launch<4>(p, store, first, count, stream);
     else if (cls == 2) bd_launch<8>(p, store, first, count, stream);

@@ -1,4 +1,5 @@
-// ssw_ends.hip -- K1g: end-anchored affine-gap alignment of pairs (global, semiglobal, overlap) in int32 cells (gfx950).
+// ssw_ends.hip -- K1g: end-anchored affine-gap alignment of pairs (global, semiglobal, overlap; start-anchored: prefix, extend) in
+// int32 cells (gfx950).
 //
 // The row-scan form of K1w (ssw_scan_wide.hip) without its packing: one wave takes one pair, its 64 lanes own kEnCpl consecutive
 // reference columns each (a chunk of kEnChunk columns), the loop runs over the query rows, and a longer reference is walked chunk
@@ -14,6 +15,11 @@
 // is the score of an alignment (or one gap opening below it) and the host's bound (m + n) max(|s|, go, ge) < 2^30 keeps int32.
 // The mode is a template parameter: the boundary values, and which end cells are followed (the last row's running maximum keyed
 // by the smallest column, the last column's keyed by the smallest row in the lane that owns column n, the corner).
+// prefix and extend have global's boundary.  prefix ends where semiglobal does, the last row's maximum seeded with H[m][0].  extend
+// ends at the greatest H of all cells, smallest i, then smallest j, (0, 0) with 0 included: every lane keeps the best (value, i, k)
+// of its own cells of a chunk under a bare > (rows ascend, columns ascend within a row: the first is the smallest key), joins it
+// to the best it carries over the chunks by the key (a later chunk's columns are larger, its rows may be smaller), and the lanes
+// are reduced once, after the last chunk.  Boundary cells but (0, 0) are <= 0 and lose every tie to (0, 0), the seed of every lane.
 // STORE: each cell also leaves 4 bits -- H's source (0 diagonal, 1 E, 2 F; that order is the tie rule), "E opened here", "F opened
 // here" -- one 32-bit word per lane and row, and ssw_ends_walk_kernel walks them back, one lane per pair (as K4t does): the walk
 // itself is pr_walk in ssw_pairs.h, shared with K1gb, and the kernel here says where the word of a cell lies.
@@ -32,7 +38,7 @@ static_assert(kEnCpl == 8, "a lane's row of decisions is one 32-bit word: 8 colu
 template <int MODE>
 __device__ __forceinline__ int en_row0(int j, int go, int ge)
 {
-    return (MODE == EN_GLOBAL && j > 0) ? (int)(0u - (uint32_t)go - (uint32_t)(j - 1) * (uint32_t)ge) : 0;
+    return (en_anchored(MODE) && j > 0) ? (int)(0u - (uint32_t)go - (uint32_t)(j - 1) * (uint32_t)ge) : 0;
 }
 template <int MODE>
 __device__ __forceinline__ int en_col0(int i, int go, int ge)
@@ -69,6 +75,7 @@ __global__ void __launch_bounds__(64) ssw_ends_kernel(const EnParams prm, int fi
     int row_best = en_col0<MODE>(m, go, ge), row_j = 0;        // the last row's running maximum, smallest column
     int col_best = 0, col_i = 0, corner = 0;                   // the last column's (H[0][n] = 0 where it counts), smallest row; H[m][n]
     const int ln = ((n - 1) % kEnChunk) / kEnCpl, kn = ((n - 1) % kEnChunk) % kEnCpl;
+    int ext_v = 0, ext_i = 0, ext_j = 0;                       // extend: the best cell this lane has seen, seeded with (0, 0)
 
     for (int c = 0; c < nchunks; ++c) {
         const int c0 = c * kEnChunk;
@@ -92,6 +99,8 @@ __global__ void __launch_bounds__(64) ssw_ends_kernel(const EnParams prm, int fi
         int32_t* outEp = outHp + mpad;
         uint32_t* wsp = nullptr;
         if (STORE && ws_ok) wsp = (uint32_t*)(prm.ws + pr.ws_off) + (size_t)c * m * 64;
+        const int own = cols - lane * kEnCpl;                  // extend: register k holds a column of the reference while k < own
+        int cv = (int)0x80000000, ci = 0, ck = 0;              // extend: this chunk's best of the lane
 
         for (int i0 = 0; i0 < m; i0 += 64) {
             const bool mine = i0 + lane < m;
@@ -142,7 +151,12 @@ __global__ void __launch_bounds__(64) ssw_ends_kernel(const EnParams prm, int fi
                     outH = lane == rr ? sH : outH;                      // lane rr keeps row i0 + rr: one coalesced store per 64 rows
                     outE = lane == rr ? sE : outE;
                 }
-                if (MODE != EN_GLOBAL && i == m) {
+                if (MODE == EN_EXTEND) {
+#pragma unroll
+                    for (int k = 0; k < kEnCpl; ++k)
+                        if (k < own && H[k] > cv) { cv = H[k]; ci = i; ck = k; }
+                }
+                if ((MODE == EN_SEMIGLOBAL || MODE == EN_OVERLAP || MODE == EN_PREFIX) && i == m) {
                     int bv = (int)0x80000000, bj = 0x7fffffff;
 #pragma unroll
                     for (int k = 0; k < kEnCpl; ++k) {
@@ -170,6 +184,10 @@ __global__ void __launch_bounds__(64) ssw_ends_kernel(const EnParams prm, int fi
             }
             if (!last && mine) { outHp[i0 + lane] = outH; outEp[i0 + lane] = outE; }
         }
+        if (MODE == EN_EXTEND) {
+            const bool take = cv > ext_v || (cv == ext_v && ci < ext_i);
+            ext_v = take ? cv : ext_v; ext_i = take ? ci : ext_i; ext_j = take ? c0 + 1 + lane * kEnCpl + ck : ext_j;
+        }
         if (!last) {      // the next chunk reads what other lanes of this wave stored
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
             __syncthreads();
@@ -179,12 +197,21 @@ __global__ void __launch_bounds__(64) ssw_ends_kernel(const EnParams prm, int fi
     corner = __shfl(corner, ln); col_best = __shfl(col_best, ln); col_i = __shfl(col_i, ln);
     int score, ei, ej;
     if (MODE == EN_GLOBAL) { score = corner; ei = m; ej = n; }
-    else if (MODE == EN_SEMIGLOBAL || row_best >= col_best) { score = row_best; ei = m; ej = row_j; }     // last-row cells before last-column cells
+    else if (MODE == EN_EXTEND) {
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int v2 = __shfl_xor(ext_v, d), i2 = __shfl_xor(ext_i, d), j2 = __shfl_xor(ext_j, d);
+            const bool take = v2 > ext_v || (v2 == ext_v && (i2 < ext_i || (i2 == ext_i && j2 < ext_j)));
+            ext_v = take ? v2 : ext_v; ext_i = take ? i2 : ext_i; ext_j = take ? j2 : ext_j;
+        }
+        score = ext_v; ei = ext_i; ej = ext_j;
+    }
+    else if (MODE == EN_SEMIGLOBAL || MODE == EN_PREFIX || row_best >= col_best) { score = row_best; ei = m; ej = row_j; }     // last-row cells before last-column cells
     else { score = col_best; ei = col_i; ej = n; }
     if (lane == 0) {
         int32_t* row = prm.rows + (size_t)(first + x) * 8;
         row[0] = score;
-        row[1] = MODE == EN_GLOBAL ? 0 : -1;                      // begins: the walk's, unless the mode fixes them
+        row[1] = en_anchored(MODE) ? 0 : -1;                      // begins: the walk's, unless the mode fixes them
         row[2] = ej - 1;
         row[3] = MODE == EN_OVERLAP ? -1 : 0;
         row[4] = ei - 1;
@@ -230,7 +257,10 @@ hipError_t launch_ssw_ends(const EnParams& p, bool store, int first, int count, 
     if (count <= 0) return hipSuccess;
     if (p.mode == EN_GLOBAL) en_launch<EN_GLOBAL>(p, store, first, count, stream);
     else if (p.mode == EN_SEMIGLOBAL) en_launch<EN_SEMIGLOBAL>(p, store, first, count, stream);
-    else en_launch<EN_OVERLAP>(p, store, first, count, stream);
+    else if (p.mode == EN_OVERLAP) en_launch<EN_OVERLAP>(p, store, first, count, stream);
+    else if (p.mode == EN_PREFIX) en_launch<EN_PREFIX>(p, store, first, count, stream);
+    else if (p.mode == EN_EXTEND) en_launch<EN_EXTEND>(p, store, first, count, stream);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

@@ -41,7 +41,7 @@ __device__ __forceinline__ void pr_walk(int32_t* row, int mode, int m, int n, ui
     };
     for (int step = 0; step < steps && !done; ++step) {
         if (state == 0 && (i == 0 || j == 0)) {
-            if (mode == EN_GLOBAL) { emit(2, j); emit(1, i); i = 0; j = 0; }
+            if (en_anchored(mode)) { emit(2, j); emit(1, i); i = 0; j = 0; }      // prefix and extend stop at (0, 0) as global does
             else if (mode == EN_SEMIGLOBAL && j == 0) { emit(1, i); i = 0; }
             done = true;
             break;

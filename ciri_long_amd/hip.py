@@ -61,7 +61,7 @@ class EndsOpts(C.Structure):
 
 ENDS_DTYPE = np.dtype([('score', '<i4'), ('ref_begin', '<i4'), ('ref_end', '<i4'), ('query_begin', '<i4'), ('query_end', '<i4'),
                        ('cigar_len', '<i4'), ('cigar_off', '<i8')])
-ENDS_MODES = {'global': 0, 'semiglobal': 1, 'overlap': 2}
+ENDS_MODES = {'global': 0, 'semiglobal': 1, 'overlap': 2, 'prefix': 3, 'extend': 4}
 
 
 class BandOpts(C.Structure):
@@ -813,7 +813,9 @@ class _PairsPlan(_Handle):
 
 class EndsPlan(_PairsPlan):
     """Pairs resident on the GPU (codes uploaded once) for the end-anchored modes of K1g -- 'global', 'semiglobal' (the whole query in
-    any stretch of the reference), 'overlap' (end gaps free on both sequences): run() any number of times, fetch() (rows ENDS_DTYPE,
+    any stretch of the reference), 'overlap' (end gaps free on both sequences) -- and the start-anchored ones, pinned at (0, 0) and
+    free at the far end: 'prefix' (the whole query against a prefix of the reference), 'extend' (a prefix of the query against a
+    prefix of the reference, the best cell of the whole matrix; score >= 0): run() any number of times, fetch() (rows ENDS_DTYPE,
     cigars uint32).  Scores are int32 and may be negative; a span without a letter has end == begin - 1; without want_cigar no walk
     back is made and a begin the mode does not fix is -1 (include/ciri_long_hip.h)."""
     _destroy = 'clh_ends_plan_destroy'
@@ -822,7 +824,7 @@ class EndsPlan(_PairsPlan):
     def __init__(self, ctx, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode='global', want_cigar=True, workspace_bytes=0):
         _Handle.__init__(self, ctx)
         if mode not in ENDS_MODES:
-            raise ValueError('mode must be one of global, semiglobal, overlap, got %r' % (mode,))
+            raise ValueError('mode must be one of global, semiglobal, overlap, prefix, extend, got %r' % (mode,))
         q, q_off, r, r_off, mat, n_mat, _ = self._inputs(queries, query_off, refs, ref_off, mat, want_cigar)
         opts = EndsOpts(ENDS_MODES[mode], mat.ctypes.data, n_mat, int(gap_open), int(gap_extend), int(self.want_cigar), int(workspace_bytes))
         self._h = lib().clh_ends_plan_create(ctx._h, self.n, q.ctypes.data, q_off.ctypes.data, r.ctypes.data, r_off.ctypes.data, C.byref(opts))
@@ -840,8 +842,9 @@ class EndsPlan(_PairsPlan):
 
 
 class BandPlan(_PairsPlan):
-    """Pairs resident on the GPU for K1gb, the global and semiglobal programmes of EndsPlan over a band of diagonals d = j - i per
-    pair: [min(0, n - m) - band, max(0, n - m) + band], or [diagonals[k] - band, diagonals[k] + band] with a hint per pair, clipped
+    """Pairs resident on the GPU for K1gb, the global, semiglobal, prefix and extend programmes of EndsPlan over a band of diagonals
+    d = j - i per pair: [min(0, n - m) - band, max(0, n - m) + band] ([-band, band] for 'prefix' and 'extend', whose far end is
+    free), or [diagonals[k] - band, diagonals[k] + band] with a hint per pair, clipped
     to [-m, n] and at most 512 wide.  run() any number of times, fetch() (rows BAND_DTYPE, cigars uint32).  A row carries the
     clipped band and `exact`: 1 where it is proved that EndsPlan returns the same row and CIGAR (include/ciri_long_hip.h)."""
     _destroy = 'clh_band_plan_destroy'
@@ -851,7 +854,7 @@ class BandPlan(_PairsPlan):
                  workspace_bytes=0):
         _Handle.__init__(self, ctx)
         if mode not in ENDS_MODES:
-            raise ValueError('mode must be one of global, semiglobal, got %r' % (mode,))
+            raise ValueError('mode must be one of global, semiglobal, prefix, extend, got %r' % (mode,))
         q, q_off, r, r_off, mat, n_mat, diag = self._inputs(queries, query_off, refs, ref_off, mat, want_cigar, diagonals)
         if not 0 <= int(band) < 2 ** 31:
             raise ValueError('BandPlan: band must be a half-width >= 0, got %r' % (band,))

@@ -14,7 +14,9 @@ Differences, all additive:
   * sequences are encoded with a 256-entry table instead of the reference's per-base Python loop (ssw_wrap.py:234-252);
     the resulting codes are identical (A/a 0, C/c 1, G/g 2, T/t 3, everything else 4);
   * ``align_pairs_ends`` aligns pairs end to end instead of locally -- ``mode`` 'global', 'semiglobal' (the whole query in any stretch
-    of the reference) or 'overlap' (end gaps free on both sequences) -- under the same affine scores, DNA or matrix (K1g);
+    of the reference) or 'overlap' (end gaps free on both sequences), and start-anchored 'prefix' or 'extend' (pinned at the
+    first letters, free at the far end) -- under the same affine scores, DNA or matrix (K1g); ``extend_anchors`` extends both
+    ways from an anchor between letters;
   * ``align_pairs_matrix`` aligns over any alphabet of up to 32 letters with its own substitution matrix (``BLOSUM62`` for
     proteins), what the reference's ssw_init / ssw_align take and its Python wrapper does not expose.
 """
@@ -367,7 +369,12 @@ def align_pairs_ends(ref_seqs, query_seqs, mode='global', match=2, mismatch=2, g
     """n independent (reference, query) alignments anchored at the ends, in one GPU call -> one PyAlignRes per pair.
 
     mode 'global': both sequences end to end.  'semiglobal': the whole query in any stretch of the reference (a probe, an exon, a
-    junction placed inside a read).  'overlap': end gaps free on both sequences at both ends (dovetails, containment).  Scores are
+    junction placed inside a read).  'overlap': end gaps free on both sequences at both ends (dovetails, containment).
+    'prefix' and 'extend' are anchored at the start, (0, 0), and free at the far end: 'prefix' aligns the whole query against a
+    prefix of the reference (the best cell of the last row, smallest column; at match 0 and unit costs the score is minus edlib's SHW
+    distance), 'extend' a prefix of the query against a prefix of the reference (the best cell of the whole matrix, (0, 0) with
+    score 0 included, smallest query row, then smallest reference column; the score is >= 0 and the empty result has ref_end =
+    query_end = -1).  Both are defined by the full matrix, not by a z-drop or X-drop rule; ``extend_anchors`` uses 'extend'.  Scores are
     those of ``align_pairs`` -- match / mismatch, or `matrix` (n x n, row = reference letter) over `alphabet` as in
     ``align_pairs_matrix`` -- with a gap of k letters costing gap_open + (k - 1) gap_extend, gap_open >= gap_extend.
 
@@ -378,14 +385,14 @@ def align_pairs_ends(ref_seqs, query_seqs, mode='global', match=2, mismatch=2, g
     ``cigar_string`` (report_cigar) uses M / I / D, with soft clips for the query letters outside query_begin..query_end as
     ``align_pairs`` writes them.  Parity with other libraries' tie rules is not pinned."""
     if mode not in hip.ENDS_MODES:
-        raise ValueError("align_pairs_ends: mode must be 'global', 'semiglobal' or 'overlap', got %r" % (mode,))
+        raise ValueError("align_pairs_ends: mode must be 'global', 'semiglobal', 'overlap', 'prefix' or 'extend', got %r" % (mode,))
     if len(ref_seqs) != len(query_seqs):
         raise ValueError('align_pairs_ends: %d references vs %d queries' % (len(ref_seqs), len(query_seqs)))
     mat, (qd, qo), (rd, ro) = _pairs_inputs('align_pairs_ends', ref_seqs, query_seqs, match, mismatch, matrix, alphabet)
     if not ref_seqs:
         return []
     ctx = context or hip.default_context()
-    walk = bool(report_cigar) or mode != 'global'          # the begins come from the walk, unless the mode fixes them
+    walk = bool(report_cigar) or mode in ('semiglobal', 'overlap')      # the begins come from the walk, unless the mode fixes them
     rows, cig = ctx.ends_batch(qd, qo, rd, ro, mat, gap_open, gap_extend, mode=mode, want_cigar=walk)
     return _pairs_results(rows, cig, qo, walk, report_cigar)
 
@@ -397,14 +404,16 @@ def align_pairs_band(ref_seqs, query_seqs, band, mode='global', diagonals=None, 
     With i query and j reference letters consumed, only cells with lo <= j - i <= hi exist: lo = min(0, n - m) - band and hi =
     max(0, n - m) + band (the corner diagonals of the m x n pair widened by `band`), or diagonals[k] - band and diagonals[k] + band
     where a placement is known (a seed, a minimizer hit, an ``edlib.search`` location: the diagonal is reference position minus
-    query position); both clipped to [-m, n], at most 512 diagonals.  mode is 'global' or 'semiglobal'; scores, coordinates, tie
-    rules and the CIGAR are those of ``align_pairs_ends``, and every result is the best alignment that stays inside the band.  Each
+    query position); both clipped to [-m, n], at most 512 diagonals.  mode is 'global', 'semiglobal', 'prefix' or 'extend'; for the
+    last two, whose far end is free, the band without a hint is [-band, band], it must hold diagonal 0, and end cells are taken over
+    the band's cells only.  Scores, coordinates, tie rules and the CIGAR are those of ``align_pairs_ends``, and every result is the
+    best alignment that stays inside the band.  Each
     result also carries ``band`` = (lo, hi) as clipped, and ``band_exact``: True where it is proved that ``align_pairs_ends`` returns
     the same result and CIGAR (False: not proved; they may still be equal).  The cost is m x (hi - lo + 1) cells, not m x n, and
     CIGARs need half a byte per cell of the band.  A band that holds no alignment, 'overlap', and a band above 512 diagonals raise
     hip.ClhError."""
-    if mode not in ('global', 'semiglobal'):
-        raise ValueError("align_pairs_band: mode must be 'global' or 'semiglobal'%s, got %r"
+    if mode not in ('global', 'semiglobal', 'prefix', 'extend'):
+        raise ValueError("align_pairs_band: mode must be 'global', 'semiglobal', 'prefix' or 'extend'%s, got %r"
                          % (" ('overlap' with a band is not built)" if mode == 'overlap' else '', mode))
     if len(ref_seqs) != len(query_seqs):
         raise ValueError('align_pairs_band: %d references vs %d queries' % (len(ref_seqs), len(query_seqs)))
@@ -416,10 +425,108 @@ def align_pairs_band(ref_seqs, query_seqs, band, mode='global', diagonals=None, 
     if not ref_seqs:
         return []
     ctx = context or hip.default_context()
-    walk = bool(report_cigar) or mode != 'global'          # the begins come from the walk, unless the mode fixes them
+    walk = bool(report_cigar) or mode == 'semiglobal'      # the begins come from the walk, unless the mode fixes them
     rows, cig = ctx.band_batch(qd, qo, rd, ro, mat, gap_open, gap_extend, int(band), mode=mode, diagonals=diagonals, want_cigar=walk)
     out = _pairs_results(rows, cig, qo, walk, report_cigar)
     for r, res in zip(rows, out):
         res.band = (int(r['band_lo']), int(r['band_hi']))
         res.band_exact = bool(r['exact'])
+    return out
+
+
+def _merge_ops(ops):
+    """(op, length) runs with equal neighbours merged"""
+    out = []
+    for op, k in ops:
+        if k <= 0:
+            continue
+        if out and out[-1][0] == op:
+            out[-1] = (op, out[-1][1] + k)
+        else:
+            out.append((op, k))
+    return out
+
+
+def _stitch_anchor(left, right, ref_pos, query_pos, seed_len, seed_score=0):
+    """one result of extend_anchors from the 'extend' rows of its two halves: `left` of the reversed letters before the anchor,
+    `right` of the letters after it (and after the seed); each half is (score, ref_end, query_end, ops) in its own coordinates"""
+    ls, lre, lqe, lops = left
+    rs, rre, rqe, rops = right
+    ops = _merge_ops(list(reversed(lops)) + [('M', seed_len)] + list(rops))
+    return (ls + seed_score + rs, ref_pos - (lre + 1), ref_pos + seed_len + rre, query_pos - (lqe + 1), query_pos + seed_len + rqe, ops)
+
+
+def extend_anchors(ref_seqs, query_seqs, anchors, band=None, seed_len=0, match=2, mismatch=2, gap_open=3, gap_extend=1, report_cigar=False,
+                   matrix=None, alphabet=None, context=None):
+    """Extend n placements both ways, in one GPU call -> one PyAlignRes per pair.
+
+    anchors[k] = (ref_pos, query_pos) is a point between letters of pair k: what an ``edlib.search`` location, a minimizer hit or
+    an exact seed gives.  The right part is mode 'extend' of ``align_pairs_ends`` on ref[ref_pos:] against query[query_pos:]; the
+    left part is 'extend' on the reversed ref[:ref_pos] against the reversed query[:query_pos].  With seed_len > 0 the anchor is
+    the first letter of an exact seed of that many letters in both sequences: the left part ends in front of it, the right part
+    starts behind it, and seed_len M columns with their score under the matrix stand between the halves.  Both parts
+    of all pairs go to the device as one plan of 2 n pairs: K1g if band is None, else K1gb with the band [-band, band] around
+    each half's own diagonal 0.
+
+    Result: ``score`` is the sum of both parts (each >= 0) and of the seed's columns; begins and ends are in the coordinates of the sequences as given, inclusive,
+    end == begin - 1 where nothing was consumed; ``cigar_string`` (report_cigar) is the left part's ops reversed, the seed, the
+    right part's ops, equal neighbours merged, with soft clips for the query letters outside.  With a band, ``band_exact`` is True
+    only where both halves are proved equal to the unbanded result.  The left half is aligned on reversed letters, so among equal
+    scores its ties (the end cell, and diagonal before D before I in the walk) are those of the reversed problem: it is the best
+    extension to the left, but not necessarily the one a single left-to-right programme over the joined sequences would pick."""
+    n = len(ref_seqs)
+    if len(query_seqs) != n or len(anchors) != n:
+        raise ValueError('extend_anchors: %d references vs %d queries vs %d anchors' % (n, len(query_seqs), len(anchors)))
+    if int(seed_len) != seed_len or seed_len < 0:
+        raise ValueError('extend_anchors: seed_len is a number of letters >= 0, got %r' % (seed_len,))
+    if band is not None and (int(band) != band or band < 0):
+        raise ValueError('extend_anchors: band is a half-width in diagonals, an integer >= 0, got %r' % (band,))
+    seed_len = int(seed_len)
+    refs2, queries2 = [], []
+    for k in range(n):
+        rp, qp = int(anchors[k][0]), int(anchors[k][1])
+        r, q = ref_seqs[k], query_seqs[k]
+        if not (0 <= rp and rp + seed_len <= len(r) and 0 <= qp and qp + seed_len <= len(q)):
+            raise ValueError('extend_anchors: pair %d: the anchor (%d, %d) with seed_len %d lies outside the %d x %d pair'
+                             % (k, rp, qp, seed_len, len(q), len(r)))
+        refs2.append(r[:rp][::-1]); queries2.append(q[:qp][::-1])
+        refs2.append(r[rp + seed_len:]); queries2.append(q[qp + seed_len:])
+    if not n:
+        return []
+    seed_scores = [0] * n
+    if seed_len:
+        mat, (qd, qo), (rd, ro) = _pairs_inputs('extend_anchors', [ref_seqs[k][anchors[k][0]:anchors[k][0] + seed_len] for k in range(n)],
+                                                [query_seqs[k][anchors[k][1]:anchors[k][1] + seed_len] for k in range(n)], match, mismatch, matrix, alphabet)
+        edge = int(round(mat.size ** 0.5))
+        cols = np.asarray(mat, dtype=np.int64).reshape(edge, edge)[np.asarray(rd, dtype=np.int64), np.asarray(qd, dtype=np.int64)]
+        seed_scores = [int(cols[k * seed_len:(k + 1) * seed_len].sum()) for k in range(n)]
+    kw = dict(mode='extend', match=match, mismatch=mismatch, gap_open=gap_open, gap_extend=gap_extend, report_cigar=bool(report_cigar),
+              matrix=matrix, alphabet=alphabet, context=context)
+    halves = align_pairs_ends(refs2, queries2, **kw) if band is None else align_pairs_band(refs2, queries2, int(band), **kw)
+    out = []
+    for k in range(n):
+        parts = []
+        for h in (halves[2 * k], halves[2 * k + 1]):
+            ops = []
+            if report_cigar:
+                num = ''
+                for ch in h.cigar_string or '':
+                    if ch.isdigit():
+                        num += ch
+                    else:
+                        if ch != 'S':
+                            ops.append((ch, int(num)))
+                        num = ''
+            parts.append((h.score, h.ref_end, h.query_end, ops))
+        score, rb, re_, qb, qe, ops = _stitch_anchor(parts[0], parts[1], int(anchors[k][0]), int(anchors[k][1]), seed_len, seed_scores[k])
+        res = PyAlignRes.__new__(PyAlignRes)
+        res.score, res.ref_begin, res.ref_end, res.query_begin, res.query_end = score, rb, re_, qb, qe
+        res.score2 = res.ref_end2 = None
+        res.cigar_string = None
+        if report_cigar:
+            tail = len(query_seqs[k]) - qe - 1
+            res.cigar_string = ('%dS' % qb if qb > 0 else '') + ''.join('%d%s' % (c, o) for o, c in ops) + ('%dS' % tail if tail else '')
+        if band is not None:
+            res.band_exact = bool(halves[2 * k].band_exact and halves[2 * k + 1].band_exact)
+        out.append(res)
     return out

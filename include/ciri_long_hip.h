@@ -391,6 +391,14 @@ int clh_edit_search_batch(clh_ctx* ctx, int32_t ntext, const uint8_t* texts, con
  * E[i][j] == H[i][j-1] - go (F likewise), takes the remaining letters of a boundary that is not free as one gap, and stops at (0, 0)
  * (global), on row 0 (semiglobal, overlap) or column 0 (overlap).  DESIGN.md section 6 has the rules in full; parity with other
  * libraries is unpinned.
+ * Start-anchored (pinned at (0, 0), free at the far end; what seed-and-extend needs): row 0, column 0 and the walk are global's,
+ * ref_begin = query_begin = 0, the walk stops at (0, 0), letters beyond the end cell are not part of the CIGAR.  CLH_ENDS_PREFIX
+ * (the whole query against a prefix of the reference): the end cell is the greatest H[m][j], 0 <= j <= n, smallest j; at (0, 1, 1, 1)
+ * the score is minus edlib's SHW distance and ref_end its first end location.  CLH_ENDS_EXTEND (a prefix of the query against a
+ * prefix of the reference): the end cell is the greatest H[i][j] over all cells, (0, 0) with H = 0 included, smallest i, then
+ * smallest j; the score is >= 0 and the empty result has ref_end = query_end = -1 and no CIGAR.  Neither is a z-drop or X-drop
+ * heuristic: both are defined by the full matrix.  An empty side: extend 0 and empty; prefix 0 and empty without a query letter,
+ * -(go + (m - 1) ge) and mI without a reference letter.  Parity with ksw2's extension and parasail is unpinned and not claimed.
  * Row k: score (int32, may be negative); ref / query begin and end, 0-based and inclusive as in clh_align_t, end == begin - 1 for a
  * span without a letter; with want_cigar the CIGAR as cigar_len packed ops (len << 4 | op; M 0, I 1, D 2 as clh_ssw_fetch returns
  * them, M for match and mismatch, free end gaps not part of it) at cigar[cigar_off ..].  Without want_cigar no walk is made:
@@ -406,6 +414,8 @@ int clh_edit_search_batch(clh_ctx* ctx, int32_t ntext, const uint8_t* texts, con
 #define CLH_ENDS_GLOBAL     0
 #define CLH_ENDS_SEMIGLOBAL 1
 #define CLH_ENDS_OVERLAP    2
+#define CLH_ENDS_PREFIX     3
+#define CLH_ENDS_EXTEND     4
 typedef struct { int32_t mode; const int8_t* mat; int32_t n_mat; int32_t gap_open, gap_extend; int32_t want_cigar; int64_t workspace_bytes; } clh_ends_opts;
 typedef struct { int32_t score, ref_begin, ref_end, query_begin, query_end, cigar_len; int64_t cigar_off; } clh_ends_row;
 typedef struct clh_ends_plan clh_ends_plan;
@@ -420,7 +430,7 @@ int clh_ends_plan_info(clh_ends_plan* plan, int64_t* out);
 int clh_ends_batch(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off, const clh_ends_opts* opts,
                    clh_ends_row* rows, uint32_t* cigar, int64_t cigar_cap, int64_t* cigar_used);
 
-/* ---- banded end-anchored alignment of pairs around a diagonal: global, semiglobal (K1gb) ------------------------------------------
+/* ---- banded end-anchored alignment of pairs around a diagonal: global, semiglobal, prefix, extend (K1gb) ---------------------------
  * The programme of clh_ends_* over a band.  The band of pair k is a closed interval of diagonals [lo, hi], d = j - i: without a hint
  * (diag == NULL) lo = min(0, n - m) - band, hi = max(0, n - m) + band; with diag[k], lo = diag[k] - band, hi = diag[k] + band; both
  * are then clipped to [-m, n], and everything below is about the clipped band.  Every cell outside the band is minus infinity in H, E
@@ -449,7 +459,19 @@ int clh_ends_batch(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_of
  *     ub_top = s+ max(0, n - hi - 1) - 2 go - (2 (hi + 1) - (n - m) - 2) ge      if hi + 1 <= n
  *     ub_bot = s+ max(0, m + lo - 1) - 2 go - (2 (1 - lo) + (n - m) - 2) ge      if lo - 1 >= -m
  * and exact = 1 iff the banded score is STRICTLY above both, or neither applies (the band is the whole matrix).  Semiglobal rows get
- * 1 only when the band is the whole matrix.  Host arithmetic in int64.  A pair with an empty side never reaches a kernel; fetch
+ * 1 only when the band is the whole matrix.
+ * CLH_ENDS_PREFIX and CLH_ENDS_EXTEND: without a hint the band is [-band, band] (the far end is free, n - m plays no part), with
+ * diag[k] as above, clipped alike; row 0 is global's, the end cell is taken over the band's cells only.  create fails with
+ * CLH_E_ARG for a band that misses (0, 0), lo > 0 or hi < 0, and for a prefix band with lo > n - m (no end cell on row m).  Every
+ * cell (i, j) of an admitted band is reached from (0, 0): its diagonal d = j - i lies between 0 and itself inside the band, so row
+ * 0 (d >= 0) or column 0 (d < 0) from (0, 0) to the diagonal, then the diagonal down to the cell, is a path in the band.  exact:
+ * an alignment that leaves the band has a cell on diagonal hi + 1 or lo - 1 and need not come back.  Reaching hi + 1 from (0, 0)
+ * takes at least hi + 1 D letters in at least one run, which leaves at most min(m, n - hi - 1) M columns; mirrored below:
+ *     ub_top = s+ min(m, n - hi - 1) - go - hi ge        if hi + 1 <= n
+ *     ub_bot = s+ min(n, m + lo - 1) - go - (-lo) ge     if lo - 1 >= -m
+ * and exact = 1 iff the banded score is STRICTLY above every defined bound, or none is defined.  Then no cell outside the band
+ * reaches the optimum, a band cell that reaches it in the full matrix does so by an alignment inside the band, so the best cells,
+ * the tie among them and the walk are the same.  Host arithmetic in int64.  A pair with an empty side never reaches a kernel; fetch
  * states the boundary cell the band holds.  info: out[12] = {band positions a lane owns in class 0, 1, 2 (a pair is filed under the
  * first class whose 64 lanes hold its band), the greatest clipped width, shares of the batch, workspace bytes in use, those of the
  * largest pair, pairs the kernels take in class 0, 1, 2, pairs with an empty side, CIGAR ops fetch may return}.  Life cycle, error

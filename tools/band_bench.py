@@ -7,9 +7,13 @@ after a warm-up.  Standalone; bench.py is not involved.  In the same run every r
   (b) the same with CIGARs; the number of workspace shares of each route is printed
   (c) 1.25 N semiglobal placements of a 50-nt junction in 2-kb reads under (10, 4, 8, 2), the true diagonal as hint, w = 16
   (d) N / 100 pairs of 20 kb x 20 kb with CIGARs, w = 128 (K1g stores 200 MB of decisions per pair here)
+  (e) 5 000 seed-right flanks of 1 kb x 1 kb -- the query a 10 % mutated copy of the reference for 600 letters, unrelated after --
+      in the mode --mode names (default extend), score only, w = 64
+  (f) the same with CIGARs
 
 Prints one JSON line per shape and width: ms of both, cells of both (sum of m B against sum of m n), the cell rates, full / band.
-usage: python tools/band_bench.py [N=20000] [runs=10] [shapes=abcd]"""
+With CLH_LIB naming another build's libclh.so, `--mode global` times that build on the same pairs: the yardstick of (e) and (f).
+usage: python tools/band_bench.py [N=20000] [runs=10] [shapes=abcd] [--mode MODE]"""
 import json
 import os
 import sys
@@ -19,9 +23,15 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ciri_long_amd import hip, synth  # noqa: E402
 
-N = int(sys.argv[1]) if len(sys.argv) > 1 else 20000
-R = int(sys.argv[2]) if len(sys.argv) > 2 else 10
-SHAPES = sys.argv[3] if len(sys.argv) > 3 else 'abcd'
+ARGS = list(sys.argv[1:])
+MODE = 'extend'
+if '--mode' in ARGS:
+    at = ARGS.index('--mode')
+    MODE = ARGS[at + 1]
+    del ARGS[at:at + 2]
+N = int(ARGS[0]) if len(ARGS) > 0 else 20000
+R = int(ARGS[1]) if len(ARGS) > 1 else 10
+SHAPES = ARGS[2] if len(ARGS) > 2 else 'abcd'
 
 
 def timed(plan):
@@ -71,6 +81,14 @@ def copies(rng, count, length):
     return [synth.mutate(r, rng, sub=0.04, ins=0.03, dele=0.03) for r in refs], refs
 
 
+def flanks(rng, count=5000, length=1000, related=600):
+    """seed-right flanks: the query is a 10 % mutated copy of the reference's first `related` letters, then unrelated letters"""
+    refs = [rng.integers(0, 4, length).astype(np.int8) for _ in range(count)]
+    queries = [np.concatenate([synth.mutate(r[:related], rng, sub=0.04, ins=0.03, dele=0.03), rng.integers(0, 4, length).astype(np.int8)])[:length]
+               for r in refs]
+    return queries, refs
+
+
 def main():
     ctx = hip.default_context()
     rng = np.random.Generator(np.random.PCG64(20262))
@@ -94,6 +112,12 @@ def main():
     if 'd' in SHAPES:
         queries, refs = copies(rng, max(1, N // 100), 20000)
         shape(ctx, 'd: DNA 20 kb x 20 kb with CIGARs', queries, refs, hip.score_matrix(2, 2), 3, 1, 'global', True, (128,))
+    if 'e' in SHAPES or 'f' in SHAPES:
+        queries, refs = flanks(np.random.Generator(np.random.PCG64(20263)))
+        if 'e' in SHAPES:
+            shape(ctx, 'e: 1-kb seed-right flanks, related for 600 letters, score only', queries, refs, hip.score_matrix(2, 2), 3, 1, MODE, False, (64,))
+        if 'f' in SHAPES:
+            shape(ctx, 'f: the same with CIGARs', queries, refs, hip.score_matrix(2, 2), 3, 1, MODE, True, (64,))
 
 
 if __name__ == '__main__':

@@ -17,8 +17,14 @@ The reference letter of a position moves by one per row: the letters slide down 
 position per row.  Minus infinity is NEG = -2^30, an ordinary int32 that is added to like any other: the admission bound
 (`admitted`) keeps every score inside (-2^29, 2^29) and everything derived from NEG inside [-2^30 - 2^29, -2^30 + 2^29), which `run`
 checks value by value.  With `store`, each cell leaves 4 bits -- H's source (0 diagonal, 1 E, 2 F), "E opened here", "F opened
-here" -- and one lane walks them back in the band's frame: a diagonal step keeps b, a D step goes to b - 1, an I step to b + 1."""
-MODES = ('global', 'semiglobal')
+here" -- and one lane walks them back in the band's frame: a diagonal step keeps b, a D step goes to b - 1, an I step to b + 1.
+
+The start-anchored modes (tests/anchored_check.py) have global's row 0 and walk; their far end is free, so the default band is
+[-w, w] (`band_of`).  `prefix` ends where semiglobal does.  `extend` ends at the greatest H over the band's cells, smallest i, then
+smallest j: a lane keeps the best of its own cells under a bare >, seeded with (0, (0, 0)), which the cells of column 0 (<= 0)
+and minus infinity never beat, and the lanes are reduced once by the key after the last row."""
+MODES = ('global', 'semiglobal', 'prefix', 'extend')
+ANCHORED = ('global', 'prefix', 'extend')          # row 0 is one gap from (0, 0), the walk stops at (0, 0)
 NEG = -(1 << 30)
 MAX_WIDTH = 512
 
@@ -28,10 +34,28 @@ def admitted(m, n, smax):
     return (m + n + 2 * MAX_WIDTH) * max(smax, 1) < (1 << 29)
 
 
+def band_of(mode, m, n, w, diag=None):
+    """the clipped band clh_band_plan_create gives a pair"""
+    if diag is not None:
+        lo, hi = diag - w, diag + w
+    elif mode in ('prefix', 'extend'):
+        lo, hi = -w, w
+    else:
+        lo, hi = min(0, n - m) - w, max(0, n - m) + w
+    return max(lo, -m), min(hi, n)
+
+
 def exact_flag(mode, m, n, lo, hi, score, splus, go, ge):
     """the host's certificate (clh_api.hip, bd_exact)"""
     if lo <= -m and hi >= n:
         return 1
+    if mode in ('prefix', 'extend'):
+        free = True
+        if hi + 1 <= n:
+            free = free and score > splus * min(m, n - hi - 1) - go - hi * ge
+        if lo - 1 >= -m:
+            free = free and score > splus * min(n, m + lo - 1) - go - (-lo) * ge
+        return int(free)
     if mode != 'global':
         return 0
     ok = True
@@ -69,9 +93,10 @@ def run(q, r, mat, go, ge, mode, lo, hi, cpl=8, lanes=64, store=True):
     for p in range(W):
         j0 = lo + p
         cell = p < B and 0 <= j0 <= n
-        Hp.append((-(go + (j0 - 1) * ge) if (mode == 'global' and j0 > 0) else 0) if cell else NEG)
+        Hp.append((-(go + (j0 - 1) * ge) if (mode in ANCHORED and j0 > 0) else 0) if cell else NEG)
     nib = {}
     H = Hp
+    ext = [(0, 0, 0)] * lanes                        # extend: (value, i, j) of the best cell a lane has seen, seeded with (0, 0)
     for i in range(1, m + 1):
         ok = [0 <= jr[p] <= n for p in range(W)]
         F, D, T, X = [0] * W, [0] * W, [0] * W, [0] * W
@@ -101,6 +126,10 @@ def run(q, r, mat, go, ge, mode, lo, hi, cpl=8, lanes=64, store=True):
                 hu = Hp[p + 1] if p + 1 < W else NEG
                 src = 0 if H[p] == D[p] else (1 if H[p] == E[p] else 2)
                 nib[(i, p)] = src | (4 if E[p] == left - go else 0) | (8 if F[p] == hu - go else 0)
+        if mode == 'extend':
+            for p in range(W):
+                if H[p] > ext[p // cpl][0]:
+                    ext[p // cpl] = (H[p], i, jr[p])
         if i == m:
             last_ok = ok
             last_j = list(jr)
@@ -109,6 +138,12 @@ def run(q, r, mat, go, ge, mode, lo, hi, cpl=8, lanes=64, store=True):
         jr = [j + 1 for j in jr]
     if mode == 'global':
         score, end = H[n - m - lo], (m, n)
+    elif mode == 'extend':
+        best = ext[0]
+        for v2, i2, j2 in ext[1:]:
+            if v2 > best[0] or (v2 == best[0] and (i2, j2) < (best[1], best[2])):
+                best = (v2, i2, j2)
+        score, end = best[0], (best[1], best[2])
     else:
         score, end = None, None
         for p in range(W):
@@ -139,7 +174,7 @@ def walk(nib, mode, end, lo, B):
     for _ in range(end[0] + end[1] + 2):
         if state == 0:
             if i == 0 or j == 0:
-                if mode == 'global':
+                if mode in ANCHORED:
                     emit('D', j); emit('I', i); i = j = 0
                 elif j == 0:
                     emit('I', i); i = 0

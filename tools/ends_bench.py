@@ -6,9 +6,13 @@ H2D in the timed run), HIP events, the median of R runs after a warm-up.  Standa
   (b) the same with CIGARs
   (c) 1.25 N semiglobal alignments of a 50-nt junction in 2-kb reads under (10, 4, 8, 2), score only
   (d) N BLOSUM62 pairs of 100-500 residues, global, score only (11 / 1)
+  (e) 5 000 seed-right flanks of 1 kb x 1 kb -- the query a 10 % mutated copy of the reference for 600 letters, unrelated after --
+      in the mode --mode names (default extend), score only; K1g alone, no local run
+  (f) the same with CIGARs
 
 Prints one JSON line per shape: ms and cells/s (sum of m n over the pairs) of both, and the ratio local / ends of the cell rates.
-usage: python tools/ends_bench.py [N=20000] [runs=10] [shapes=abcd]"""
+With CLH_LIB naming another build's libclh.so, `--mode global` times that build on the same pairs: the yardstick of (e) and (f).
+usage: python tools/ends_bench.py [N=20000] [runs=10] [shapes=abcd] [--mode MODE]"""
 import json
 import os
 import sys
@@ -20,9 +24,15 @@ import torch  # noqa: E402
 
 from ciri_long_amd import hip, ssw_wrap, synth  # noqa: E402
 
-N = int(sys.argv[1]) if len(sys.argv) > 1 else 20000
-R = int(sys.argv[2]) if len(sys.argv) > 2 else 10
-SHAPES = sys.argv[3] if len(sys.argv) > 3 else 'abcd'
+ARGS = list(sys.argv[1:])
+MODE = 'extend'
+if '--mode' in ARGS:
+    at = ARGS.index('--mode')
+    MODE = ARGS[at + 1]
+    del ARGS[at:at + 2]
+N = int(ARGS[0]) if len(ARGS) > 0 else 20000
+R = int(ARGS[1]) if len(ARGS) > 1 else 10
+SHAPES = ARGS[2] if len(ARGS) > 2 else 'abcd'
 
 
 def ends_ms(ctx, qd, qo, rd, ro, mat, go, ge, mode, cigar):
@@ -58,10 +68,22 @@ def local_ms(ctx, qd, qo, rd, ro, mat, go, ge, cigar):
         plan.close()
 
 
-def shape(ctx, name, queries, refs, mat, go, ge, mode, cigar):
+def flanks(rng, count=5000, length=1000, related=600):
+    """seed-right flanks: the query is a 10 % mutated copy of the reference's first `related` letters, then unrelated letters"""
+    refs = [rng.integers(0, 4, length).astype(np.int8) for _ in range(count)]
+    queries = [np.concatenate([synth.mutate(r[:related], rng, sub=0.04, ins=0.03, dele=0.03), rng.integers(0, 4, length).astype(np.int8)])[:length]
+               for r in refs]
+    return queries, refs
+
+
+def shape(ctx, name, queries, refs, mat, go, ge, mode, cigar, local=True):
     qd, qo = hip.pack(queries); rd, ro = hip.pack(refs)
     cells = float(np.sum(np.diff(qo).astype(np.float64) * np.diff(ro)))
     e_ms, info = ends_ms(ctx, qd, qo, rd, ro, mat, go, ge, mode, cigar)
+    if not local:
+        print(json.dumps({'shape': name, 'pairs': len(queries), 'cells': cells, 'mode': mode, 'cigar': cigar,
+                          'ends_ms': round(e_ms, 3), 'ends_gcups': round(cells / e_ms / 1e6, 2), 'shares': info['shares']}), flush=True)
+        return
     l_ms, classes = local_ms(ctx, qd, qo, rd, ro, mat, go, ge, cigar)
     print(json.dumps({'shape': name, 'pairs': len(queries), 'cells': cells, 'mode': mode, 'cigar': cigar,
                       'ends_ms': round(e_ms, 3), 'ends_gcups': round(cells / e_ms / 1e6, 2), 'shares': info['shares'],
@@ -96,6 +118,12 @@ def main():
         refs = [rng.integers(0, 20, int(rng.integers(100, 501))).astype(np.int8) for _ in range(N)]
         queries = [rng.integers(0, 20, int(rng.integers(100, 501))).astype(np.int8) for _ in range(N)]
         shape(ctx, 'd: BLOSUM62 100-500 residues, global, 11/1', queries, refs, ssw_wrap.BLOSUM62.reshape(-1), 11, 1, 'global', False)
+    if 'e' in SHAPES or 'f' in SHAPES:
+        queries, refs = flanks(np.random.Generator(np.random.PCG64(20263)))
+        if 'e' in SHAPES:
+            shape(ctx, 'e: 1-kb seed-right flanks, related for 600 letters, score only', queries, refs, hip.score_matrix(2, 2), 3, 1, MODE, False, local=False)
+        if 'f' in SHAPES:
+            shape(ctx, 'f: the same with CIGARs', queries, refs, hip.score_matrix(2, 2), 3, 1, MODE, True, local=False)
 
 
 if __name__ == '__main__':

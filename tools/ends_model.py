@@ -13,8 +13,15 @@ on, one pair of values per row.  Per row step and lane:
 which is E[j] = max(E[j-1] - ge, H[j-1] - go) exactly when go >= ge.  No cell holds minus infinity: F of row 0 and E of column
 0 enter as H - go, which gives the same first F and E.  With `store`, each cell leaves 4 bits -- H's source (0 diagonal, 1 E, 2
 F), "E opened here", "F opened here" -- a word of cpl nibbles per lane and row, and one lane walks them back.  Values are
-checked to stay inside int32."""
-MODES = ('global', 'semiglobal', 'overlap')
+checked to stay inside int32.
+
+The start-anchored modes (tests/anchored_check.py) have global's boundary and walk.  `prefix` ends at the last row's running
+maximum, seeded with H[m][0].  `extend` ends at the greatest H of all cells, smallest i, then smallest j, (0, 0) with 0 included:
+every lane keeps the best (value, i, k) of its own cells of a chunk under a bare > (rows ascend, its columns ascend within a row),
+joins it at the end of the chunk to the best it carries by the key -- a later chunk's columns are larger, its rows may be smaller
+-- and the lanes are reduced once, after the last chunk."""
+MODES = ('global', 'semiglobal', 'overlap', 'prefix', 'extend')
+ANCHORED = ('global', 'prefix', 'extend')          # row 0 is one gap from (0, 0), the walk stops at (0, 0)
 
 
 def _i32(v):
@@ -23,7 +30,7 @@ def _i32(v):
 
 
 def _row0(mode, j, go, ge):
-    return -(go + (j - 1) * ge) if (mode == 'global' and j > 0) else 0
+    return -(go + (j - 1) * ge) if (mode in ANCHORED and j > 0) else 0
 
 
 def _col0(mode, i, go, ge):
@@ -42,6 +49,7 @@ def run(q, r, mat, go, ge, mode, cpl=8, lanes=64, store=True, extreme=None):
     row_best, row_j = _col0(mode, m, go, ge), 0           # running maximum of the last row, smallest j
     col_best, col_i = 0, 0                                # of the last column (overlap): H[0][n] = 0
     corner = None
+    ext = [(0, 0, 0)] * lanes                             # extend: (value, i, j) of the best cell a lane has seen, seeded with (0, 0)
     words = {}
     peak = 0
     for c in range(nchunks):
@@ -53,6 +61,7 @@ def run(q, r, mat, go, ge, mode, cpl=8, lanes=64, store=True, extreme=None):
         hleft = [Hp[l - 1][cpl - 1] if l else _row0(mode, c0, go, ge) for l in range(lanes)]     # H[i-1][first column - 1]
         out = []
         ln, kn = (n - 1 - c0) // cpl, (n - 1 - c0) % cpl
+        chunk_best = [None] * lanes                       # extend: (value, i, k) of this chunk's best per lane
         for i in range(1, m + 1):
             if c == 0:
                 hin = _col0(mode, i, go, ge)
@@ -106,7 +115,12 @@ def run(q, r, mat, go, ge, mode, cpl=8, lanes=64, store=True, extreme=None):
                     words[(c, i, l)] = w
             if not last:
                 out.append((H[lanes - 1][cpl - 1], E[lanes - 1][cpl - 1]))
-            if i == m and mode != 'global':
+            if mode == 'extend':
+                for l in range(lanes):
+                    for k in range(cpl):
+                        if k < cols - l * cpl and (chunk_best[l] is None or H[l][k] > chunk_best[l][0]):
+                            chunk_best[l] = (H[l][k], i, k)
+            if i == m and mode in ('semiglobal', 'overlap', 'prefix'):
                 for p in range(cols):
                     h = H[p // cpl][p % cpl]
                     if h > row_best:
@@ -119,11 +133,23 @@ def run(q, r, mat, go, ge, mode, cpl=8, lanes=64, store=True, extreme=None):
                     col_best, col_i = hn, i
             Hp, Fp, hleft = H, F, new_left
         hand[c & 1] = out
+        if mode == 'extend':
+            for l in range(lanes):
+                if chunk_best[l] is not None:
+                    cv, ci, ck = chunk_best[l]
+                    if cv > ext[l][0] or (cv == ext[l][0] and ci < ext[l][1]):
+                        ext[l] = (cv, ci, c0 + 1 + l * cpl + ck)
     if extreme is not None:
         extreme.append(peak)
     if mode == 'global':
         score, end = corner, (m, n)
-    elif mode == 'semiglobal' or row_best >= col_best:
+    elif mode == 'extend':
+        best = ext[0]
+        for v2, i2, j2 in ext[1:]:                        # the butterfly's order of comparisons does not matter: the key is total
+            if v2 > best[0] or (v2 == best[0] and (i2, j2) < (best[1], best[2])):
+                best = (v2, i2, j2)
+        score, end = best[0], (best[1], best[2])
+    elif mode in ('semiglobal', 'prefix') or row_best >= col_best:
         score, end = row_best, (m, row_j)
     else:
         score, end = col_best, (col_i, n)
@@ -132,6 +158,8 @@ def run(q, r, mat, go, ge, mode, cpl=8, lanes=64, store=True, extreme=None):
         return res
     i0, j0, ops = walk(words, mode, end, cpl, lanes)
     res.update(ref_begin=j0, query_begin=i0, cigar=ops)
+    if mode in ('prefix', 'extend'):
+        assert (i0, j0) == (0, 0)
     return res
 
 
@@ -151,7 +179,7 @@ def walk(words, mode, end, cpl, lanes):
     for _ in range(end[0] + end[1] + 2):
         if state == 0:
             if i == 0 or j == 0:
-                if mode == 'global':
+                if mode in ANCHORED:
                     emit('D', j); emit('I', i); i = j = 0
                 elif mode == 'semiglobal' and j == 0:
                     emit('I', i); i = 0
