@@ -2124,7 +2124,13 @@ static_assert(offsetof(clh_band_row, score) == offsetof(clh_ends_row, score) && 
 // what a create plans on the host
 struct PairsShape {
     int n = 0, mode = 0, n_mat = 0, go = 0, ge = 0;
+    int pieces = 1, go2 = 0, ge2 = 0;             // two-piece gap costs (clh_gap2): a gap costs the smaller of the two pieces
     bool want_cigar = false;
+    int64_t gap(int64_t k) const                  // what a gap of k >= 1 letters costs
+    {
+        const int64_t a = go + (k - 1) * ge;
+        return pieces == 2 ? std::min<int64_t>(a, go2 + (k - 1) * (int64_t)ge2) : a;
+    }
     std::vector<std::pair<int, int>> shares;      // [first, count) of each launch: the batch cut so that a share's decisions fit the workspace
     int64_t ws_bytes = 0, cig_cap = 0, max_pair_ws = 0, nempty = 0;
 };
@@ -2133,9 +2139,10 @@ struct clh_pairs_plan : clh_owned, PairsShape {
     void *d_q = nullptr, *d_r = nullptr, *d_pairs = nullptr, *d_mat = nullptr, *d_ws = nullptr, *d_rows = nullptr, *d_cig = nullptr;
 };
 
-// the arguments and options both creates take, refused in the order each always refused them; `band`: K1gb's half-width, null for K1g
+// the arguments and options both creates take, refused in the order each always refused them; `band`: K1gb's half-width, null for K1g;
+// `g2`: the second piece of the gap costs, null for one piece
 static int pairs_check_opts(const std::string& me, const clh_ctx* ctx, int32_t n, const int64_t* q_off, const int64_t* r_off, const clh_ends_opts* o,
-                            const int32_t* band)
+                            const int32_t* band, const clh_gap2* g2 = nullptr)
 {
     if (!ctx || n < 0 || !q_off || !r_off || !o || !o->mat) return fail(CLH_E_ARG, me + "bad argument");
     if (band) {
@@ -2147,13 +2154,21 @@ static int pairs_check_opts(const std::string& me, const clh_ctx* ctx, int32_t n
         return fail(CLH_E_ARG, me + (band ? "gap costs, workspace_bytes and band must not be negative" : "gap costs and workspace_bytes must not be negative"));
     if (o->gap_open < o->gap_extend)
         return fail(CLH_E_UNSUPPORTED, me + "gap_open < gap_extend: E along a row is a running maximum only when opening a gap costs at least as much as extending one; not implemented");
+    if (g2) {      // piece 1 for short gaps, piece 2 for long ones: 0 <= ge2 <= ge1 <= go1 <= go2
+        const std::string costs = " (gap_open " + std::to_string(o->gap_open) + ", gap_extend " + std::to_string(o->gap_extend) + ", gap_open2 " +
+                                  std::to_string(g2->gap_open2) + ", gap_extend2 " + std::to_string(g2->gap_extend2) + ")";
+        if (g2->gap_extend2 < 0) return fail(CLH_E_UNSUPPORTED, me + "two-piece gap costs need 0 <= gap_extend2" + costs);
+        if (g2->gap_extend2 > o->gap_extend) return fail(CLH_E_UNSUPPORTED, me + "two-piece gap costs need gap_extend2 <= gap_extend: the second piece is the one for long gaps" + costs);
+        if (o->gap_open > g2->gap_open2) return fail(CLH_E_UNSUPPORTED, me + "two-piece gap costs need gap_open <= gap_open2: the first piece is the one for short gaps" + costs);
+    }
     return 0;
 }
 
 // smax: the greatest of |s|, gap_open, gap_extend, 1, what one step moves a score by at most; *splus: max(0, greatest matrix entry)
-static int64_t pairs_scan_matrix(const clh_ends_opts* o, int64_t* splus)
+static int64_t pairs_scan_matrix(const clh_ends_opts* o, int64_t* splus, const clh_gap2* g2 = nullptr)
 {
     int64_t smax = std::max<int64_t>(std::max(o->gap_open, o->gap_extend), 1);
+    if (g2) smax = std::max<int64_t>(smax, std::max(g2->gap_open2, g2->gap_extend2));
     *splus = 0;
     for (int k = 0; k < o->n_mat * o->n_mat; ++k) { smax = std::max<int64_t>(smax, std::abs((int)o->mat[k])); *splus = std::max<int64_t>(*splus, o->mat[k]); }
     return smax;
@@ -2241,13 +2256,13 @@ static int pairs_begin_run(clh_pairs_plan* pl, void* stream_, hipStream_t* st)
 
 // what the programme gives when one side has no letter: the boundary itself
 template <typename Row>
-static void en_empty_side(int mode, int m, int n, int go, int ge, Row* row, uint32_t* op)
+static void en_empty_side(int mode, int m, int n, const PairsShape& sh, Row* row, uint32_t* op)
 {
     *op = 0;
     row->score = 0; row->ref_begin = 0; row->ref_end = -1; row->query_begin = 0; row->query_end = -1;
-    if (n > 0 && mode == CLH_ENDS_GLOBAL) { row->score = -(go + (n - 1) * ge); row->ref_end = n - 1; *op = ((uint32_t)n << 4) | 2u; }
+    if (n > 0 && mode == CLH_ENDS_GLOBAL) { row->score = (int32_t)-sh.gap(n); row->ref_end = n - 1; *op = ((uint32_t)n << 4) | 2u; }
     if (mode == CLH_ENDS_EXTEND) return;                       // the best cell of a boundary that only loses is (0, 0)
-    if (m > 0 && mode != CLH_ENDS_OVERLAP) { row->score = -(go + (m - 1) * ge); row->query_end = m - 1; *op = ((uint32_t)m << 4) | 1u; }
+    if (m > 0 && mode != CLH_ENDS_OVERLAP) { row->score = (int32_t)-sh.gap(m); row->query_end = m - 1; *op = ((uint32_t)m << 4) | 1u; }
     if (m > 0 && mode == CLH_ENDS_OVERLAP) { row->query_begin = m; row->query_end = m - 1; }
 }
 
@@ -2279,7 +2294,7 @@ static int pairs_fetch(const std::string& kind, Plan* pl, Row* rows, uint32_t* c
         const uint32_t* src = nullptr;
         int len = 0;
         if (p.m == 0 || p.n == 0) {
-            en_empty_side(pl->mode, p.m, p.n, pl->go, pl->ge, &out, &one);
+            en_empty_side(pl->mode, p.m, p.n, *pl, &out, &one);
             if (one) { src = &one; len = 1; }
         } else {
             bool bad = false;
@@ -2317,39 +2332,44 @@ struct clh_ends_plan : clh_pairs_plan {
 
 extern "C" void clh_ends_plan_destroy(clh_ends_plan* pl) { delete pl; }
 
-static int64_t en_ws_bytes(int64_t m, int64_t n)
+// a lane's row of decisions: 4 bits per cell with one piece, a byte per cell with two
+static int64_t en_ws_bytes(int64_t m, int64_t n, int pieces)
 {
     const int64_t nch = (n + clh::kEnChunk - 1) / clh::kEnChunk;
     const int64_t llast = (n - (nch - 1) * clh::kEnChunk + clh::kEnCpl - 1) / clh::kEnCpl;
-    return (4 * m * (64 * (nch - 1) + llast) + 15) & ~(int64_t)15;
+    return (4 * pieces * m * (64 * (nch - 1) + llast) + 15) & ~(int64_t)15;
 }
 
-extern "C" clh_ends_plan* clh_ends_plan_create(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off,
-                                               const clh_ends_opts* o)
+// both creates of K1g; g2: the second piece, null for one piece
+static clh_ends_plan* en_create(const std::string& me, clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off,
+                                const clh_ends_opts* o, const clh_gap2* g2)
 {
-    const std::string me = "clh_ends_plan_create: ";
-    if (pairs_check_opts(me, ctx, n, q_off, r_off, o, nullptr)) return nullptr;
+    if (pairs_check_opts(me, ctx, n, q_off, r_off, o, nullptr, g2)) return nullptr;
+    const int pieces = g2 ? 2 : 1;
     int64_t splus;
-    const int64_t smax = pairs_scan_matrix(o, &splus);
+    const int64_t smax = pairs_scan_matrix(o, &splus, g2);
     for (int k = 0; k < n; ++k) {
         const int64_t m = q_off[k + 1] - q_off[k], nn = r_off[k + 1] - r_off[k];
         if (m < 0 || nn < 0) { fail(CLH_E_ARG, me + "offsets must ascend"); return nullptr; }
         if ((m > 0 && !q) || (nn > 0 && !r)) { fail(CLH_E_ARG, me + "null argument"); return nullptr; }
         if (m + nn >= ((int64_t)1 << 30) || (m + nn) * smax >= ((int64_t)1 << 30)) {
-            fail(CLH_E_ARG, me + "pair " + std::to_string(k) + ": (m + n) * max(|s|, gap_open, gap_extend) = " + std::to_string(m + nn) + " * " +
+            fail(CLH_E_ARG, me + "pair " + std::to_string(k) + ": (m + n) * max(|s|, " + (g2 ? "gap_open, gap_extend, gap_open2, gap_extend2" : "gap_open, gap_extend") +
+                                ") = " + std::to_string(m + nn) + " * " +
                                 std::to_string(smax) + " reaches 2^30, the score range of the int32 cells");
             return nullptr;
         }
     }
     if (pairs_check_codes(me, n, q, q_off, r, r_off, o->n_mat)) return nullptr;
     PairsShape shape;
+    if (g2) { shape.pieces = 2; shape.go2 = g2->gap_open2; shape.ge2 = g2->gap_extend2; }
     std::vector<clh::EnPair> pairs;
     int64_t hand_words = 0;
     if (pairs_cut_shares(me, o, n, q_off, r_off, &shape, &pairs,
             [&](int, clh::EnPair& p, bool kernel) {
                 p.pad = 0; p.hand_off = -1;
-                if (kernel && p.n > clh::kEnChunk) { p.hand_off = hand_words; hand_words += 4 * (((int64_t)p.m + 63) & ~(int64_t)63); }
-                return kernel ? en_ws_bytes(p.m, p.n) : 0;
+                // two buffers of H and one E per piece of the last column, per row
+                if (kernel && p.n > clh::kEnChunk) { p.hand_off = hand_words; hand_words += 2 * (1 + pieces) * (((int64_t)p.m + 63) & ~(int64_t)63); }
+                return kernel ? en_ws_bytes(p.m, p.n, pieces) : 0;
             },
             [](const clh::EnPair& p) { return std::to_string(p.m) + " x " + std::to_string(p.n) + " cells"; }))
         return nullptr;
@@ -2366,12 +2386,26 @@ extern "C" clh_ends_plan* clh_ends_plan_create(clh_ctx* ctx, int32_t n, const in
     return pl;
 }
 
+extern "C" clh_ends_plan* clh_ends_plan_create(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off,
+                                               const clh_ends_opts* o)
+{
+    return en_create("clh_ends_plan_create: ", ctx, n, q, q_off, r, r_off, o, nullptr);
+}
+
+extern "C" clh_ends_plan* clh_ends_plan_create_gap2(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off,
+                                                    const clh_ends_opts* o, const clh_gap2* gap2)
+{
+    if (!gap2) return clh_ends_plan_create(ctx, n, q, q_off, r, r_off, o);
+    return en_create("clh_ends_plan_create_gap2: ", ctx, n, q, q_off, r, r_off, o, gap2);
+}
+
 extern "C" int clh_ends_plan_run(clh_ends_plan* pl, void* stream_)
 {
     if (!pl) return fail(CLH_E_ARG, "clh_ends_plan_run: null argument");
     hipStream_t st;
     if (int rc = pairs_begin_run(pl, stream_, &st)) return rc;
-    clh::EnParams p;
+    clh::En2Params p;
+    p.go2 = pl->go2; p.ge2 = pl->ge2;
     p.qry = (const int8_t*)pl->d_q; p.ref = (const int8_t*)pl->d_r;
     p.pairs = (const clh::EnPair*)pl->d_pairs; p.npairs = pl->n;
     p.mat = (const int8_t*)pl->d_mat; p.n_mat = pl->n_mat;
@@ -2381,6 +2415,11 @@ extern "C" int clh_ends_plan_run(clh_ends_plan* pl, void* stream_)
     p.rows = (int32_t*)pl->d_rows;
     p.cigar = (uint32_t*)pl->d_cig; p.cigar_cap = pl->cig_cap;
     for (const auto& sh : pl->shares) {        // in stream order: a share's walk has read the workspace before the next share fills it
+        if (pl->pieces == 2) {
+            HIPCHK(clh::launch_ssw_ends2(p, pl->want_cigar, sh.first, sh.second, st));
+            if (pl->want_cigar) HIPCHK(clh::launch_ssw_ends2_walk(p, sh.first, sh.second, st));
+            continue;
+        }
         HIPCHK(clh::launch_ssw_ends(p, pl->want_cigar, sh.first, sh.second, st));
         if (pl->want_cigar) HIPCHK(clh::launch_ssw_ends_walk(p, sh.first, sh.second, st));
     }
@@ -2417,6 +2456,17 @@ extern "C" int clh_ends_batch(clh_ctx* ctx, int32_t n, const int8_t* q, const in
     return rc;
 }
 
+extern "C" int clh_ends_batch_gap2(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off, const clh_ends_opts* opts,
+                                   const clh_gap2* gap2, clh_ends_row* rows, uint32_t* cigar, int64_t cigar_cap, int64_t* cigar_used)
+{
+    clh_ends_plan* pl = clh_ends_plan_create_gap2(ctx, n, q, q_off, r, r_off, opts, gap2);
+    if (!pl) return g_code;
+    int rc = clh_ends_plan_run(pl, nullptr);
+    if (!rc) rc = clh_ends_plan_fetch(pl, rows, cigar, cigar_cap, cigar_used);
+    delete pl;
+    return rc;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // K1gb: K1g's global, semiglobal, prefix and extend programmes over a band of diagonals per pair (ssw_band.hip)
 // ---------------------------------------------------------------------------------------------------------------
@@ -2433,16 +2483,17 @@ struct clh_band_plan : clh_pairs_plan {
 
 extern "C" void clh_band_plan_destroy(clh_band_plan* pl) { delete pl; }
 
-extern "C" clh_band_plan* clh_band_plan_create(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off,
-                                               const int32_t* diag, const clh_band_opts* bo)
+// both creates of K1gb; g2: the second piece, null for one piece
+static clh_band_plan* bd_create(const std::string& me, clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off,
+                                const int32_t* diag, const clh_band_opts* bo, const clh_gap2* g2)
 {
-    const std::string me = "clh_band_plan_create: ";
     clh_ends_opts shared;                                                      // the fields the two share (the static_asserts above)
     if (bo) memcpy(&shared, bo, sizeof shared);
     const clh_ends_opts* o = bo ? &shared : nullptr;
-    if (pairs_check_opts(me, ctx, n, q_off, r_off, o, bo ? &bo->band : nullptr)) return nullptr;
+    if (pairs_check_opts(me, ctx, n, q_off, r_off, o, bo ? &bo->band : nullptr, g2)) return nullptr;
+    const int pieces = g2 ? 2 : 1;
     int64_t splus;
-    const int64_t smax = pairs_scan_matrix(o, &splus);
+    const int64_t smax = pairs_scan_matrix(o, &splus, g2);
     const bool global = o->mode == CLH_ENDS_GLOBAL;
     const bool anchored = o->mode == CLH_ENDS_PREFIX || o->mode == CLH_ENDS_EXTEND;      // the far end is free: n - m plays no part in the band
     std::vector<std::pair<int32_t, int32_t>> bands((size_t)n);
@@ -2453,7 +2504,8 @@ extern "C" clh_band_plan* clh_band_plan_create(clh_ctx* ctx, int32_t n, const in
         if ((m > 0 && !q) || (nn > 0 && !r)) { fail(CLH_E_ARG, me + "null argument"); return nullptr; }
         const int64_t span = m + nn + 2 * clh::kBdMaxWidth;
         if (span >= ((int64_t)1 << 29) || span * smax >= ((int64_t)1 << 29)) {
-            fail(CLH_E_ARG, pk + "(m + n + " + std::to_string(2 * clh::kBdMaxWidth) + ") * max(|s|, gap_open, gap_extend) = " + std::to_string(span) + " * " +
+            fail(CLH_E_ARG, pk + "(m + n + " + std::to_string(2 * clh::kBdMaxWidth) + ") * max(|s|, " + (g2 ? "gap_open, gap_extend, gap_open2, gap_extend2" : "gap_open, gap_extend") +
+                                ") = " + std::to_string(span) + " * " +
                                 std::to_string(smax) + " reaches 2^29, the score range the banded int32 cells keep apart from minus infinity");
             return nullptr;
         }
@@ -2488,6 +2540,7 @@ extern "C" clh_band_plan* clh_band_plan_create(clh_ctx* ctx, int32_t n, const in
     }
     if (pairs_check_codes(me, n, q, q_off, r, r_off, o->n_mat)) return nullptr;
     PairsShape shape;
+    if (g2) { shape.pieces = 2; shape.go2 = g2->gap_open2; shape.ge2 = g2->gap_extend2; }
     std::vector<clh::BdPair> pairs;
     int64_t max_width = 0, nclass[clh::kBdClasses] = {0, 0, 0};
     if (pairs_cut_shares(me, o, n, q_off, r_off, &shape, &pairs,
@@ -2500,7 +2553,7 @@ extern "C" clh_band_plan* clh_band_plan_create(clh_ctx* ctx, int32_t n, const in
                 ++nclass[p.cls];
                 max_width = std::max(max_width, B);
                 const int cpl = clh::kBdCpl[p.cls];
-                return ((int64_t)p.m * ((B + cpl - 1) / cpl) * (cpl / 2) + 15) & ~(int64_t)15;
+                return ((int64_t)p.m * ((B + cpl - 1) / cpl) * (cpl / 2) * pieces + 15) & ~(int64_t)15;      // half a byte per cell and piece
             },
             [](const clh::BdPair& p) { return std::to_string(p.m) + " rows of " + std::to_string((int64_t)p.hi - p.lo + 1) + " diagonals"; }))
         return nullptr;
@@ -2528,12 +2581,26 @@ extern "C" clh_band_plan* clh_band_plan_create(clh_ctx* ctx, int32_t n, const in
     return pl;
 }
 
+extern "C" clh_band_plan* clh_band_plan_create(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off,
+                                               const int32_t* diag, const clh_band_opts* bo)
+{
+    return bd_create("clh_band_plan_create: ", ctx, n, q, q_off, r, r_off, diag, bo, nullptr);
+}
+
+extern "C" clh_band_plan* clh_band_plan_create_gap2(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off,
+                                                    const int32_t* diag, const clh_band_opts* bo, const clh_gap2* gap2)
+{
+    if (!gap2) return clh_band_plan_create(ctx, n, q, q_off, r, r_off, diag, bo);
+    return bd_create("clh_band_plan_create_gap2: ", ctx, n, q, q_off, r, r_off, diag, bo, gap2);
+}
+
 extern "C" int clh_band_plan_run(clh_band_plan* pl, void* stream_)
 {
     if (!pl) return fail(CLH_E_ARG, "clh_band_plan_run: null argument");
     hipStream_t st;
     if (int rc = pairs_begin_run(pl, stream_, &st)) return rc;
-    clh::BdParams p;
+    clh::Bd2Params p;
+    p.go2 = pl->go2; p.ge2 = pl->ge2;
     p.qry = (const int8_t*)pl->d_q; p.ref = (const int8_t*)pl->d_r;
     p.pairs = (const clh::BdPair*)pl->d_pairs; p.npairs = pl->n;
     p.order = (const int32_t*)pl->d_order; p.norder = (int32_t)pl->order.size();
@@ -2545,27 +2612,36 @@ extern "C" int clh_band_plan_run(clh_band_plan* pl, void* stream_)
     for (size_t s = 0; s < pl->shares.size(); ++s) {        // in stream order: a share's walk has read the workspace before the next share fills it
         const auto& sh = pl->shares[s];
         const auto& cl = pl->share_classes[s];
+        if (pl->pieces == 2) {
+            for (int c = 0; c < clh::kBdClasses; ++c) HIPCHK(clh::launch_ssw_band2(p, c, pl->want_cigar, cl.cfirst[c], cl.ccount[c], st));
+            if (pl->want_cigar) HIPCHK(clh::launch_ssw_band2_walk(p, sh.first, sh.second, st));
+            continue;
+        }
         for (int c = 0; c < clh::kBdClasses; ++c) HIPCHK(clh::launch_ssw_band(p, c, pl->want_cigar, cl.cfirst[c], cl.ccount[c], st));
         if (pl->want_cigar) HIPCHK(clh::launch_ssw_band_walk(p, sh.first, sh.second, st));
     }
     return pl->end_run();
 }
 
-// 1: the unbanded programme provably returns the same row and CIGAR (the argument is in the header and in DESIGN.md section 6)
-static int32_t bd_exact(int mode, int64_t m, int64_t n, int64_t lo, int64_t hi, int64_t score, int64_t splus, int64_t go, int64_t ge)
+// 1: the unbanded programme provably returns the same row and CIGAR (the argument is in the header and in DESIGN.md section 6).
+// sh.gap(L) is the cost of one gap of L letters, one piece or two: all the proofs ask of it is that it does not decrease and that
+// gap(a) + gap(b) >= gap(a + b), which go >= ge gives one piece and the admitted two-piece costs keep.
+static int32_t bd_exact(int mode, int64_t m, int64_t n, int64_t lo, int64_t hi, int64_t score, int64_t splus, const PairsShape& sh)
 {
     if (lo <= -m && hi >= n) return 1;
     if (mode == CLH_ENDS_PREFIX || mode == CLH_ENDS_EXTEND) {
         // the far end is free: an alignment that leaves the band need not come back, so one gap run and the M columns it leaves
         bool in = true;
-        if (hi + 1 <= n) in = in && score > splus * std::min<int64_t>(m, n - hi - 1) - go - hi * ge;
-        if (lo - 1 >= -m) in = in && score > splus * std::min<int64_t>(n, m + lo - 1) - go - (-lo) * ge;
+        if (hi + 1 <= n) in = in && score > splus * std::min<int64_t>(m, n - hi - 1) - sh.gap(hi + 1);
+        if (lo - 1 >= -m) in = in && score > splus * std::min<int64_t>(n, m + lo - 1) - sh.gap(1 - lo);
         return in ? 1 : 0;
     }
     if (mode != CLH_ENDS_GLOBAL) return 0;
+    // the run that reaches diagonal hi + 1 (lo - 1) and the run that comes back to diagonal n - m: a global band holds n - m, so
+    // both have at least one letter
     bool ok = true;
-    if (hi + 1 <= n) ok = ok && score > splus * std::max<int64_t>(0, n - hi - 1) - 2 * go - (2 * (hi + 1) - (n - m) - 2) * ge;
-    if (lo - 1 >= -m) ok = ok && score > splus * std::max<int64_t>(0, m + lo - 1) - 2 * go - (2 * (1 - lo) + (n - m) - 2) * ge;
+    if (hi + 1 <= n) ok = ok && score > splus * std::max<int64_t>(0, n - hi - 1) - sh.gap(hi + 1) - sh.gap(hi + 1 - (n - m));
+    if (lo - 1 >= -m) ok = ok && score > splus * std::max<int64_t>(0, m + lo - 1) - sh.gap(1 - lo) - sh.gap(n - m - lo + 1);
     return ok ? 1 : 0;
 }
 
@@ -2576,7 +2652,7 @@ extern "C" int clh_band_plan_fetch(clh_band_plan* pl, clh_band_row* rows, uint32
         // letter, whose first cell in the band is column lo
         if (pl->mode == CLH_ENDS_SEMIGLOBAL && p.m == 0) { out.ref_begin = p.lo; out.ref_end = p.lo - 1; }
         out.band_lo = p.lo; out.band_hi = p.hi; out.reserved = 0;
-        out.exact = bd_exact(pl->mode, p.m, p.n, p.lo, p.hi, out.score, pl->splus, pl->go, pl->ge);
+        out.exact = bd_exact(pl->mode, p.m, p.n, p.lo, p.hi, out.score, pl->splus, *pl);
     });
 }
 
@@ -2599,6 +2675,17 @@ extern "C" int clh_band_batch(clh_ctx* ctx, int32_t n, const int8_t* q, const in
                               const clh_band_opts* opts, clh_band_row* rows, uint32_t* cigar, int64_t cigar_cap, int64_t* cigar_used)
 {
     clh_band_plan* pl = clh_band_plan_create(ctx, n, q, q_off, r, r_off, diag, opts);
+    if (!pl) return g_code;
+    int rc = clh_band_plan_run(pl, nullptr);
+    if (!rc) rc = clh_band_plan_fetch(pl, rows, cigar, cigar_cap, cigar_used);
+    delete pl;
+    return rc;
+}
+
+extern "C" int clh_band_batch_gap2(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off, const int32_t* diag,
+                                   const clh_band_opts* opts, const clh_gap2* gap2, clh_band_row* rows, uint32_t* cigar, int64_t cigar_cap, int64_t* cigar_used)
+{
+    clh_band_plan* pl = clh_band_plan_create_gap2(ctx, n, q, q_off, r, r_off, diag, opts, gap2);
     if (!pl) return g_code;
     int rc = clh_band_plan_run(pl, nullptr);
     if (!rc) rc = clh_band_plan_fetch(pl, rows, cigar, cigar_cap, cigar_used);

@@ -332,6 +332,11 @@ struct EnParams {
 };
 hipError_t launch_ssw_ends(const EnParams& p, bool store, int first, int count, hipStream_t stream);
 hipError_t launch_ssw_ends_walk(const EnParams& p, int first, int count, hipStream_t stream);     // after the storing form of the same pairs
+// K1g under two-piece gap costs (ssw_ends2.hip): go / ge are piece 1, go2 / ge2 piece 2; a pair's hand-over is 6 x rows rounded up to 64
+// and its stored decisions one byte per cell.  A struct of its own: the one-piece kernels keep their argument block.
+struct En2Params : EnParams { int32_t go2, ge2; };
+hipError_t launch_ssw_ends2(const En2Params& p, bool store, int first, int count, hipStream_t stream);
+hipError_t launch_ssw_ends2_walk(const En2Params& p, int first, int count, hipStream_t stream);
 
 // K1gb (ssw_band.hip): K1g's global, semiglobal, prefix and extend programmes over a band of diagonals [lo, hi], d = j - i; one wave per pair in the
 // band's frame, a lane on CPL consecutive band positions b = d - lo (classes CPL 2, 4, 8: bands of up to 128, 256, 512 diagonals).
@@ -361,6 +366,11 @@ struct BdParams {
 };
 hipError_t launch_ssw_band(const BdParams& p, int cls, bool store, int first, int count, hipStream_t stream);   // order[first .. first + count)
 hipError_t launch_ssw_band_walk(const BdParams& p, int first, int count, hipStream_t stream);                   // pairs [first, first + count)
+// K1gb under two-piece gap costs (ssw_band2.hip): go / ge are piece 1, go2 / ge2 piece 2; a pair's stored decisions are one byte per cell
+// of the band.  A struct of its own: the one-piece kernels keep their argument block.
+struct Bd2Params : BdParams { int32_t go2, ge2; };
+hipError_t launch_ssw_band2(const Bd2Params& p, int cls, bool store, int first, int count, hipStream_t stream);
+hipError_t launch_ssw_band2_walk(const Bd2Params& p, int first, int count, hipStream_t stream);
 
 static constexpr int kRvStrips = 1000;  // pseudo class: RV = 32 with row strips (reads longer than 4096 bases)
 extern const int kRvClasses[];

@@ -63,4 +63,46 @@ __device__ __forceinline__ void pr_walk(int32_t* row, int mode, int m, int n, ui
     row[1] = j; row[3] = i; row[5] = nops;
 }
 
+// pr_walk for two-piece gap costs (ssw_ends2.hip).  cell(i, j) gives the byte of cell (i, j) -- bits 0..2 H's source (0 diagonal, 1 E_1,
+// 2 E_2, 3 F_1, 4 F_2: that order is the tie rule), bits 3..6 "opened here" of E_1, E_2, F_1, F_2 -- or -1 outside what was stored.  Both
+// pieces of a direction emit the same op; a gap state is left as soon as its own piece's "opened here" is set.  Steps, bounds and
+// EN_ST_NO_WALK as in pr_walk.
+template <typename Cell>
+__device__ __forceinline__ void pr_walk2(int32_t* row, int mode, int m, int n, uint32_t* out, int cig_cap, Cell cell)
+{
+    int i = row[4] + 1, j = row[2] + 1;
+    if (i < 0 || i > m || j < 0 || j > n) { row[7] = EN_ST_NO_WALK; return; }
+    const int steps = i + j + 2;
+    int state = 0, nops = 0, cur = -1, run = 0;
+    bool bad = false, done = false;
+    auto emit = [&](int op, int k) {
+        if (k <= 0) return;
+        if (op == cur) { run += k; return; }
+        if (run) { if (nops < cig_cap) out[nops++] = ((uint32_t)run << 4) | (uint32_t)cur; else bad = true; }
+        cur = op; run = k;
+    };
+    for (int step = 0; step < steps && !done; ++step) {
+        if (state == 0 && (i == 0 || j == 0)) {
+            if (en_anchored(mode)) { emit(2, j); emit(1, i); i = 0; j = 0; }
+            else if (mode == EN_SEMIGLOBAL && j == 0) { emit(1, i); i = 0; }
+            done = true;
+            break;
+        }
+        const int at = cell(i, j);
+        if (at < 0) { bad = true; break; }
+        const uint32_t b = (uint32_t)at;
+        if (state == 0) {
+            state = (int)(b & 7u);                               // a gap state takes its first letter from this same cell
+            if (state == 0) { emit(0, 1); --i; --j; continue; }
+        }
+        if (state == 1 || state == 2) { emit(2, 1); --j; if (b & (4u << state)) state = 0; }          // bit 3 for E_1, bit 4 for E_2
+        else if (state == 3 || state == 4) { emit(1, 1); --i; if (b & (4u << state)) state = 0; }     // bit 5 for F_1, bit 6 for F_2
+        else { bad = true; break; }
+    }
+    emit(-2, 1);                                                 // flush the last run
+    if (bad || !done) { row[7] = EN_ST_NO_WALK; return; }
+    for (int a = 0, c = nops - 1; a < c; ++a, --c) { const uint32_t w = out[a]; out[a] = out[c]; out[c] = w; }
+    row[1] = j; row[3] = i; row[5] = nops;
+}
+
 }  // namespace clh

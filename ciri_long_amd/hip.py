@@ -59,6 +59,17 @@ class EndsOpts(C.Structure):
                 ('want_cigar', C.c_int32), ('workspace_bytes', C.c_int64)]
 
 
+class Gap2(C.Structure):
+    _fields_ = [('gap_open2', C.c_int32), ('gap_extend2', C.c_int32)]
+
+
+def gap2_of(who, gap_open2, gap_extend2):
+    """the second piece of two-piece gap costs as libclh takes it -> Gap2, or None for one piece; the two come together"""
+    if (gap_open2 is None) != (gap_extend2 is None):
+        raise ValueError('%s: gap_open2 and gap_extend2 come together' % who)
+    return None if gap_open2 is None else Gap2(int(gap_open2), int(gap_extend2))
+
+
 ENDS_DTYPE = np.dtype([('score', '<i4'), ('ref_begin', '<i4'), ('ref_end', '<i4'), ('query_begin', '<i4'), ('query_end', '<i4'),
                        ('cigar_len', '<i4'), ('cigar_off', '<i8')])
 ENDS_MODES = {'global': 0, 'semiglobal': 1, 'overlap': 2, 'prefix': 3, 'extend': 4}
@@ -188,6 +199,17 @@ def lib():
         L.clh_ends_plan_info.argtypes = [C.c_void_p, C.c_void_p]
         L.clh_ends_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(EndsOpts), C.c_void_p,
                                      C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+        if hasattr(L, 'clh_ends_plan_create_gap2'):      # absent from a CLH_LIB build older than the two-piece gap costs: using them there raises
+            L.clh_ends_plan_create_gap2.restype = C.c_void_p
+            L.clh_ends_plan_create_gap2.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(EndsOpts),
+                                                    C.POINTER(Gap2)]
+            L.clh_ends_batch_gap2.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(EndsOpts), C.POINTER(Gap2),
+                                              C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+            L.clh_band_batch_gap2.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BandOpts),
+                                              C.POINTER(Gap2), C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+            L.clh_band_plan_create_gap2.restype = C.c_void_p
+            L.clh_band_plan_create_gap2.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BandOpts),
+                                                    C.POINTER(Gap2)]
         L.clh_band_plan_create.restype = C.c_void_p
         L.clh_band_plan_create.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BandOpts)]
         L.clh_band_plan_destroy.restype = None
@@ -518,24 +540,27 @@ class Context(object):
     def edit_search_plan(self, probes, texts, k=-1, equalities=()):
         return EditSearchPlan(self, probes, texts, k, equalities)
 
-    def ends_batch(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode='global', want_cigar=True, workspace_bytes=0):
+    def ends_batch(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode='global', want_cigar=True, workspace_bytes=0,
+                   gap_open2=None, gap_extend2=None):
         """End-anchored affine-gap alignment of the pairs (query k, reference k), packed codes and offsets as ssw_batch takes them,
         through K1g -> (rows ENDS_DTYPE, cigars uint32 packed ops).  See EndsPlan."""
-        plan = EndsPlan(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode, want_cigar, workspace_bytes)
+        plan = EndsPlan(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode, want_cigar, workspace_bytes, gap_open2, gap_extend2)
         try:
             plan.run()
             return plan.fetch()
         finally:
             plan.close()
 
-    def ends_plan(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode='global', want_cigar=True, workspace_bytes=0):
-        return EndsPlan(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode, want_cigar, workspace_bytes)
+    def ends_plan(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode='global', want_cigar=True, workspace_bytes=0,
+                  gap_open2=None, gap_extend2=None):
+        return EndsPlan(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode, want_cigar, workspace_bytes, gap_open2, gap_extend2)
 
     def band_batch(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, band, mode='global', diagonals=None, want_cigar=True,
-                   workspace_bytes=0):
+                   workspace_bytes=0, gap_open2=None, gap_extend2=None):
         """Banded end-anchored alignment of the pairs (query k, reference k) through K1gb: the programme of ends_batch over the
         diagonals within `band` of the corner diagonals, or of diagonals[k] -> (rows BAND_DTYPE, cigars uint32 packed ops).  See BandPlan."""
-        plan = BandPlan(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, band, mode, diagonals, want_cigar, workspace_bytes)
+        plan = BandPlan(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, band, mode, diagonals, want_cigar, workspace_bytes,
+                        gap_open2, gap_extend2)
         try:
             plan.run()
             return plan.fetch()
@@ -543,8 +568,9 @@ class Context(object):
             plan.close()
 
     def band_plan(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, band, mode='global', diagonals=None, want_cigar=True,
-                  workspace_bytes=0):
-        return BandPlan(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, band, mode, diagonals, want_cigar, workspace_bytes)
+                  workspace_bytes=0, gap_open2=None, gap_extend2=None):
+        return BandPlan(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, band, mode, diagonals, want_cigar, workspace_bytes,
+                        gap_open2, gap_extend2)
 
     def ccs_file(self, in_path, is_fastq, ccs_fa_path, raw_fa_path, batch_reads=0, first_record=0, max_records=-1, byte_offset=0):
         """Stage 1 from file to file in native code -> (total_reads, reads_with_consensus, reads_too_long); with
@@ -817,19 +843,27 @@ class EndsPlan(_PairsPlan):
     free at the far end: 'prefix' (the whole query against a prefix of the reference), 'extend' (a prefix of the query against a
     prefix of the reference, the best cell of the whole matrix; score >= 0): run() any number of times, fetch() (rows ENDS_DTYPE,
     cigars uint32).  Scores are int32 and may be negative; a span without a letter has end == begin - 1; without want_cigar no walk
-    back is made and a begin the mode does not fix is -1 (include/ciri_long_hip.h)."""
+    back is made and a begin the mode does not fix is -1 (include/ciri_long_hip.h).  With gap_open2 and gap_extend2 a gap of k
+    letters costs the smaller of gap_open + (k - 1) gap_extend and gap_open2 + (k - 1) gap_extend2 (0 <= gap_extend2 <= gap_extend
+    <= gap_open <= gap_open2; clh_ends_plan_create_gap2), and the stored decisions take a byte per cell instead of half a byte."""
     _destroy = 'clh_ends_plan_destroy'
     _c, _dtype = 'ends', ENDS_DTYPE
 
-    def __init__(self, ctx, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode='global', want_cigar=True, workspace_bytes=0):
+    def __init__(self, ctx, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode='global', want_cigar=True, workspace_bytes=0,
+                 gap_open2=None, gap_extend2=None):
         _Handle.__init__(self, ctx)
         if mode not in ENDS_MODES:
             raise ValueError('mode must be one of global, semiglobal, overlap, prefix, extend, got %r' % (mode,))
+        gap2 = gap2_of('EndsPlan', gap_open2, gap_extend2)
         q, q_off, r, r_off, mat, n_mat, _ = self._inputs(queries, query_off, refs, ref_off, mat, want_cigar)
         opts = EndsOpts(ENDS_MODES[mode], mat.ctypes.data, n_mat, int(gap_open), int(gap_extend), int(self.want_cigar), int(workspace_bytes))
-        self._h = lib().clh_ends_plan_create(ctx._h, self.n, q.ctypes.data, q_off.ctypes.data, r.ctypes.data, r_off.ctypes.data, C.byref(opts))
+        args = (ctx._h, self.n, q.ctypes.data, q_off.ctypes.data, r.ctypes.data, r_off.ctypes.data, C.byref(opts))
+        if gap2 is None:
+            self._h = lib().clh_ends_plan_create(*args)
+        else:
+            self._h = lib().clh_ends_plan_create_gap2(*(args + (C.byref(gap2),)))
         if not self._h:
-            raise ClhError('clh_ends_plan_create failed: %s' % last_error())
+            raise ClhError('clh_ends_plan_create%s failed: %s' % ('' if gap2 is None else '_gap2', last_error()))
 
     def info(self):
         """the geometry of the kernel: reference columns a lane owns (cpl) and columns of a chunk (a longer reference is walked chunk
@@ -846,23 +880,29 @@ class BandPlan(_PairsPlan):
     d = j - i per pair: [min(0, n - m) - band, max(0, n - m) + band] ([-band, band] for 'prefix' and 'extend', whose far end is
     free), or [diagonals[k] - band, diagonals[k] + band] with a hint per pair, clipped
     to [-m, n] and at most 512 wide.  run() any number of times, fetch() (rows BAND_DTYPE, cigars uint32).  A row carries the
-    clipped band and `exact`: 1 where it is proved that EndsPlan returns the same row and CIGAR (include/ciri_long_hip.h)."""
+    clipped band and `exact`: 1 where it is proved that EndsPlan returns the same row and CIGAR (include/ciri_long_hip.h).
+    gap_open2 and gap_extend2 are EndsPlan's two-piece gap costs (clh_band_plan_create_gap2): a byte per cell of the band."""
     _destroy = 'clh_band_plan_destroy'
     _c, _dtype = 'band', BAND_DTYPE
 
     def __init__(self, ctx, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, band, mode='global', diagonals=None, want_cigar=True,
-                 workspace_bytes=0):
+                 workspace_bytes=0, gap_open2=None, gap_extend2=None):
         _Handle.__init__(self, ctx)
         if mode not in ENDS_MODES:
             raise ValueError('mode must be one of global, semiglobal, prefix, extend, got %r' % (mode,))
+        gap2 = gap2_of('BandPlan', gap_open2, gap_extend2)
         q, q_off, r, r_off, mat, n_mat, diag = self._inputs(queries, query_off, refs, ref_off, mat, want_cigar, diagonals)
         if not 0 <= int(band) < 2 ** 31:
             raise ValueError('BandPlan: band must be a half-width >= 0, got %r' % (band,))
         opts = BandOpts(ENDS_MODES[mode], mat.ctypes.data, n_mat, int(gap_open), int(gap_extend), int(self.want_cigar), int(workspace_bytes), int(band), 0)
-        self._h = lib().clh_band_plan_create(ctx._h, self.n, q.ctypes.data, q_off.ctypes.data, r.ctypes.data, r_off.ctypes.data,
-                                             diag.ctypes.data if diag is not None else None, C.byref(opts))
+        args = (ctx._h, self.n, q.ctypes.data, q_off.ctypes.data, r.ctypes.data, r_off.ctypes.data, diag.ctypes.data if diag is not None else None,
+                C.byref(opts))
+        if gap2 is None:
+            self._h = lib().clh_band_plan_create(*args)
+        else:
+            self._h = lib().clh_band_plan_create_gap2(*(args + (C.byref(gap2),)))
         if not self._h:
-            raise ClhError('clh_band_plan_create failed: %s' % last_error())
+            raise ClhError('clh_band_plan_create%s failed: %s' % ('' if gap2 is None else '_gap2', last_error()))
 
     def info(self):
         """the classes of the kernel: band positions a lane owns (cpl; a class holds bands of up to 64 cpl diagonals); and of this plan:

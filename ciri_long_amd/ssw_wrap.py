@@ -364,8 +364,13 @@ def _pairs_results(rows, cig, qo, walk, report_cigar):
     return out
 
 
+# the two-piece gap costs of the long-read presets (-O4,24 -E2,1 at 2 / 4): keywords for align_pairs_ends, align_pairs_band and extend_anchors.  A
+# convenience; nothing is claimed about parity with any other aligner's output.
+LONG_READ_GAPS = dict(match=2, mismatch=4, gap_open=4, gap_extend=2, gap_open2=24, gap_extend2=1)
+
+
 def align_pairs_ends(ref_seqs, query_seqs, mode='global', match=2, mismatch=2, gap_open=3, gap_extend=1, report_cigar=False, matrix=None,
-                     alphabet=None, context=None):
+                     alphabet=None, context=None, gap_open2=None, gap_extend2=None):
     """n independent (reference, query) alignments anchored at the ends, in one GPU call -> one PyAlignRes per pair.
 
     mode 'global': both sequences end to end.  'semiglobal': the whole query in any stretch of the reference (a probe, an exon, a
@@ -383,7 +388,13 @@ def align_pairs_ends(ref_seqs, query_seqs, mode='global', match=2, mismatch=2, g
     column), then in the last column (smallest row); the walk back prefers the diagonal, then a reference letter against nothing
     (D), then a query letter against nothing (I), and leaves a gap as soon as it can.  ``score2`` and ``ref_end2`` are None.
     ``cigar_string`` (report_cigar) uses M / I / D, with soft clips for the query letters outside query_begin..query_end as
-    ``align_pairs`` writes them.  Parity with other libraries' tie rules is not pinned."""
+    ``align_pairs`` writes them.  Parity with other libraries' tie rules is not pinned.
+
+    gap_open2 and gap_extend2 (together) add a second piece: a gap of k letters then costs the smaller of gap_open + (k - 1)
+    gap_extend and gap_open2 + (k - 1) gap_extend2, piece 1 for short gaps and piece 2 for long ones, 0 <= gap_extend2 <=
+    gap_extend <= gap_open <= gap_open2 (``LONG_READ_GAPS`` is such a set).  The walk back then prefers the diagonal, D by piece 1,
+    D by piece 2, I by piece 1, I by piece 2; the CIGAR does not say which piece paid."""
+    two = {} if hip.gap2_of('align_pairs_ends', gap_open2, gap_extend2) is None else dict(gap_open2=gap_open2, gap_extend2=gap_extend2)
     if mode not in hip.ENDS_MODES:
         raise ValueError("align_pairs_ends: mode must be 'global', 'semiglobal', 'overlap', 'prefix' or 'extend', got %r" % (mode,))
     if len(ref_seqs) != len(query_seqs):
@@ -393,12 +404,12 @@ def align_pairs_ends(ref_seqs, query_seqs, mode='global', match=2, mismatch=2, g
         return []
     ctx = context or hip.default_context()
     walk = bool(report_cigar) or mode in ('semiglobal', 'overlap')      # the begins come from the walk, unless the mode fixes them
-    rows, cig = ctx.ends_batch(qd, qo, rd, ro, mat, gap_open, gap_extend, mode=mode, want_cigar=walk)
+    rows, cig = ctx.ends_batch(qd, qo, rd, ro, mat, gap_open, gap_extend, mode=mode, want_cigar=walk, **two)      # one piece: the call as it always was
     return _pairs_results(rows, cig, qo, walk, report_cigar)
 
 
 def align_pairs_band(ref_seqs, query_seqs, band, mode='global', diagonals=None, match=2, mismatch=2, gap_open=3, gap_extend=1, report_cigar=False,
-                     matrix=None, alphabet=None, context=None):
+                     matrix=None, alphabet=None, context=None, gap_open2=None, gap_extend2=None):
     """``align_pairs_ends`` over a band of diagonals, in one GPU call -> one PyAlignRes per pair.
 
     With i query and j reference letters consumed, only cells with lo <= j - i <= hi exist: lo = min(0, n - m) - band and hi =
@@ -411,7 +422,9 @@ def align_pairs_band(ref_seqs, query_seqs, band, mode='global', diagonals=None, 
     result also carries ``band`` = (lo, hi) as clipped, and ``band_exact``: True where it is proved that ``align_pairs_ends`` returns
     the same result and CIGAR (False: not proved; they may still be equal).  The cost is m x (hi - lo + 1) cells, not m x n, and
     CIGARs need half a byte per cell of the band.  A band that holds no alignment, 'overlap', and a band above 512 diagonals raise
-    hip.ClhError."""
+    hip.ClhError.  gap_open2 and gap_extend2 are the two-piece gap costs of ``align_pairs_ends``; CIGARs then
+    need a byte per cell of the band, and ``band_exact`` is the same certificate with a run costed by the cheaper piece."""
+    two = {} if hip.gap2_of('align_pairs_band', gap_open2, gap_extend2) is None else dict(gap_open2=gap_open2, gap_extend2=gap_extend2)
     if mode not in ('global', 'semiglobal', 'prefix', 'extend'):
         raise ValueError("align_pairs_band: mode must be 'global', 'semiglobal', 'prefix' or 'extend'%s, got %r"
                          % (" ('overlap' with a band is not built)" if mode == 'overlap' else '', mode))
@@ -426,7 +439,7 @@ def align_pairs_band(ref_seqs, query_seqs, band, mode='global', diagonals=None, 
         return []
     ctx = context or hip.default_context()
     walk = bool(report_cigar) or mode == 'semiglobal'      # the begins come from the walk, unless the mode fixes them
-    rows, cig = ctx.band_batch(qd, qo, rd, ro, mat, gap_open, gap_extend, int(band), mode=mode, diagonals=diagonals, want_cigar=walk)
+    rows, cig = ctx.band_batch(qd, qo, rd, ro, mat, gap_open, gap_extend, int(band), mode=mode, diagonals=diagonals, want_cigar=walk, **two)
     out = _pairs_results(rows, cig, qo, walk, report_cigar)
     for r, res in zip(rows, out):
         res.band = (int(r['band_lo']), int(r['band_hi']))
@@ -457,7 +470,7 @@ def _stitch_anchor(left, right, ref_pos, query_pos, seed_len, seed_score=0):
 
 
 def extend_anchors(ref_seqs, query_seqs, anchors, band=None, seed_len=0, match=2, mismatch=2, gap_open=3, gap_extend=1, report_cigar=False,
-                   matrix=None, alphabet=None, context=None):
+                   matrix=None, alphabet=None, context=None, gap_open2=None, gap_extend2=None):
     """Extend n placements both ways, in one GPU call -> one PyAlignRes per pair.
 
     anchors[k] = (ref_pos, query_pos) is a point between letters of pair k: what an ``edlib.search`` location, a minimizer hit or
@@ -473,7 +486,9 @@ def extend_anchors(ref_seqs, query_seqs, anchors, band=None, seed_len=0, match=2
     right part's ops, equal neighbours merged, with soft clips for the query letters outside.  With a band, ``band_exact`` is True
     only where both halves are proved equal to the unbanded result.  The left half is aligned on reversed letters, so among equal
     scores its ties (the end cell, and diagonal before D before I in the walk) are those of the reversed problem: it is the best
-    extension to the left, but not necessarily the one a single left-to-right programme over the joined sequences would pick."""
+    extension to the left, but not necessarily the one a single left-to-right programme over the joined sequences would pick.
+    gap_open2 and gap_extend2 are those of ``align_pairs_ends`` and ``align_pairs_band`` (two-piece gap costs)."""
+    two = {} if hip.gap2_of('extend_anchors', gap_open2, gap_extend2) is None else dict(gap_open2=gap_open2, gap_extend2=gap_extend2)
     n = len(ref_seqs)
     if len(query_seqs) != n or len(anchors) != n:
         raise ValueError('extend_anchors: %d references vs %d queries vs %d anchors' % (n, len(query_seqs), len(anchors)))
@@ -502,6 +517,7 @@ def extend_anchors(ref_seqs, query_seqs, anchors, band=None, seed_len=0, match=2
         seed_scores = [int(cols[k * seed_len:(k + 1) * seed_len].sum()) for k in range(n)]
     kw = dict(mode='extend', match=match, mismatch=mismatch, gap_open=gap_open, gap_extend=gap_extend, report_cigar=bool(report_cigar),
               matrix=matrix, alphabet=alphabet, context=context)
+    kw.update(two)
     halves = align_pairs_ends(refs2, queries2, **kw) if band is None else align_pairs_band(refs2, queries2, int(band), **kw)
     out = []
     for k in range(n):

@@ -430,6 +430,24 @@ int clh_ends_plan_info(clh_ends_plan* plan, int64_t* out);
 int clh_ends_batch(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off, const clh_ends_opts* opts,
                    clh_ends_row* rows, uint32_t* cigar, int64_t cigar_cap, int64_t* cigar_used);
 
+/* Two-piece gap costs for clh_ends_*: with gap2 a gap of k letters costs min(gap_open + (k - 1) gap_extend, gap_open2 + (k - 1)
+ * gap_extend2) -- piece 1 (the fields of clh_ends_opts) for short gaps, piece 2 for long ones.  Each direction has one state per piece,
+ *     E_p[i][j] = max(H[i][j-1] - go_p, E_p[i][j-1] - ge_p)      F_p[i][j] = max(H[i-1][j] - go_p, F_p[i-1][j] - ge_p)      p = 1, 2
+ *     H[i][j]   = max(H[i-1][j-1] + s, E_1, E_2, F_1, F_2)
+ * Modes, boundaries (a boundary gap of j letters costs the smaller piece), end cells, coordinates, empty sides and CIGAR conventions
+ * are those of clh_ends_*.  The walk prefers the diagonal, then E_1, E_2, F_1, F_2, and leaves E_p as soon as E_p[i][j] == H[i][j-1] -
+ * go_p (F_p likewise); both pieces emit the same op.  Admitted: 0 <= gap_extend2 <= gap_extend <= gap_open <= gap_open2 (equal pieces
+ * included), anything else is CLH_E_UNSUPPORTED and the message names the inequality; under these a maximal run of D or I is never
+ * cheaper split over both pieces, so the score is the best over all alignments with every run costed by the minimum.  The range
+ * bound takes the maximum over all four costs.  Stored decisions are one byte per cell, twice the one-piece figure: CLH_E_CAPACITY,
+ * the shares and info's byte counts follow.  The plan is a clh_ends_plan: run, fetch, timing, info and destroy are those above.
+ * gap2 == NULL is clh_ends_plan_create / clh_ends_batch.  clh_band_*_gap2 below are the same costs over a band. */
+typedef struct { int32_t gap_open2, gap_extend2; } clh_gap2;
+clh_ends_plan* clh_ends_plan_create_gap2(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off,
+                                         const clh_ends_opts* opts, const clh_gap2* gap2);
+int clh_ends_batch_gap2(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off, const clh_ends_opts* opts,
+                        const clh_gap2* gap2, clh_ends_row* rows, uint32_t* cigar, int64_t cigar_cap, int64_t* cigar_used);
+
 /* ---- banded end-anchored alignment of pairs around a diagonal: global, semiglobal, prefix, extend (K1gb) ---------------------------
  * The programme of clh_ends_* over a band.  The band of pair k is a closed interval of diagonals [lo, hi], d = j - i: without a hint
  * (diag == NULL) lo = min(0, n - m) - band, hi = max(0, n - m) + band; with diag[k], lo = diag[k] - band, hi = diag[k] + band; both
@@ -489,6 +507,18 @@ int clh_band_plan_info(clh_band_plan* plan, int64_t* out);
 /* create + run + fetch */
 int clh_band_batch(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off, const int32_t* diag,
                    const clh_band_opts* opts, clh_band_row* rows, uint32_t* cigar, int64_t cigar_cap, int64_t* cigar_used);
+/* Two-piece gap costs over a band: clh_gap2 as for clh_ends_*_gap2, the band, its refusals, the modes and the rows as for clh_band_*.
+ * The 2^29 bound takes the maximum over all four costs; stored decisions are one byte per cell of the band.  `exact` is the same
+ * certificate with g(L) = min(gap_open + (L - 1) gap_extend, gap_open2 + (L - 1) gap_extend2) for the cost of a run of L letters:
+ * global, ub_top = s+ max(0, n - hi - 1) - g(hi + 1) - g(hi + 1 - (n - m)) and ub_bot = s+ max(0, m + lo - 1) - g(1 - lo) - g(n - m -
+ * lo + 1); free far end, ub_top = s+ min(m, n - hi - 1) - g(hi + 1) and ub_bot = s+ min(n, m + lo - 1) - g(1 - lo); the score must be
+ * strictly above both.  The proof asks of g only that it does not decrease and that g(a) + g(b) >= g(a + b), which holds under the
+ * admitted costs.  Every row with exact == 1 equals the row of clh_ends_*_gap2.  gap2 == NULL is clh_band_plan_create / clh_band_batch. */
+clh_band_plan* clh_band_plan_create_gap2(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off,
+                                         const int32_t* diag, const clh_band_opts* opts, const clh_gap2* gap2);
+int clh_band_batch_gap2(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off, const int32_t* diag,
+                        const clh_band_opts* opts, const clh_gap2* gap2, clh_band_row* rows, uint32_t* cigar, int64_t cigar_cap, int64_t* cigar_used);
+
 
 /* ASCII -> codes exactly as ssw_wrap.py:234-252 (A/a C/c G/g T/t N/n, anything else 4), on the host. */
 void clh_encode_dna(const char* seq, int64_t len, int8_t* out);

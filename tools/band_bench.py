@@ -13,7 +13,9 @@ after a warm-up.  Standalone; bench.py is not involved.  In the same run every r
 
 Prints one JSON line per shape and width: ms of both, cells of both (sum of m B against sum of m n), the cell rates, full / band.
 With CLH_LIB naming another build's libclh.so, `--mode global` times that build on the same pairs: the yardstick of (e) and (f).
-usage: python tools/band_bench.py [N=20000] [runs=10] [shapes=abcd] [--mode MODE]"""
+--gap2 GO2,GE2 gives every K1g / K1gb plan a second gap piece; --scoring MA,MI,GO,GE replaces 2/2/3/1 in the DNA shapes a, b, e, f
+(the long-read costs: --scoring 2,4,4,2 --gap2 24,1).
+usage: python tools/band_bench.py [N=20000] [runs=10] [shapes=abcd] [--mode MODE] [--gap2 GO2,GE2] [--scoring MA,MI,GO,GE]"""
 import json
 import os
 import sys
@@ -28,6 +30,16 @@ MODE = 'extend'
 if '--mode' in ARGS:
     at = ARGS.index('--mode')
     MODE = ARGS[at + 1]
+    del ARGS[at:at + 2]
+GAP2 = {}                 # --gap2 GO2,GE2: two-piece gap costs (the second piece) for every plan of K1g and K1gb
+if '--gap2' in ARGS:
+    at = ARGS.index('--gap2')
+    GAP2 = dict(zip(('gap_open2', 'gap_extend2'), (int(x) for x in ARGS[at + 1].split(','))))
+    del ARGS[at:at + 2]
+DNA = (2, 2, 3, 1)        # --scoring MA,MI,GO,GE: match, mismatch and the (first) gap piece of the DNA shapes a, b, e, f
+if '--scoring' in ARGS:
+    at = ARGS.index('--scoring')
+    DNA = tuple(int(x) for x in ARGS[at + 1].split(','))
     del ARGS[at:at + 2]
 N = int(ARGS[0]) if len(ARGS) > 0 else 20000
 R = int(ARGS[1]) if len(ARGS) > 1 else 10
@@ -62,12 +74,12 @@ def same_rows(b_rows, b_cig, e_rows, e_cig, cigar, mode):
 def shape(ctx, name, queries, refs, mat, go, ge, mode, cigar, widths, diagonals=None):
     qd, qo = hip.pack(queries); rd, ro = hip.pack(refs)
     m, n = np.diff(qo).astype(np.float64), np.diff(ro).astype(np.float64)
-    e_ms, e_info, e_rows, e_cig = timed(ctx.ends_plan(qd, qo, rd, ro, mat, go, ge, mode=mode, want_cigar=cigar))
+    e_ms, e_info, e_rows, e_cig = timed(ctx.ends_plan(qd, qo, rd, ro, mat, go, ge, mode=mode, want_cigar=cigar, **GAP2))
     for w in widths:
-        b_ms, b_info, b_rows, b_cig = timed(ctx.band_plan(qd, qo, rd, ro, mat, go, ge, w, mode=mode, diagonals=diagonals, want_cigar=cigar))
+        b_ms, b_info, b_rows, b_cig = timed(ctx.band_plan(qd, qo, rd, ro, mat, go, ge, w, mode=mode, diagonals=diagonals, want_cigar=cigar, **GAP2))
         cells = float(np.sum(m * (b_rows['band_hi'] - b_rows['band_lo'] + 1)))
         certified = same_rows(b_rows, b_cig, e_rows, e_cig, cigar, mode)
-        print(json.dumps({'shape': name, 'pairs': len(queries), 'mode': mode, 'cigar': cigar, 'w': w,
+        print(json.dumps({'shape': name, 'pairs': len(queries), 'mode': mode, 'cigar': cigar, 'w': w, 'gap2': GAP2 or None,
                           'band_ms': round(b_ms, 3), 'band_cells': cells, 'band_gcups': round(cells / b_ms / 1e6, 2), 'band_shares': b_info['shares'],
                           'band_workspace': b_info['workspace_bytes'], 'class_pairs': b_info['class_pairs'],
                           'full_ms': round(e_ms, 3), 'full_cells': float(np.sum(m * n)), 'full_gcups': round(float(np.sum(m * n)) / e_ms / 1e6, 2),
@@ -95,9 +107,9 @@ def main():
     if 'a' in SHAPES or 'b' in SHAPES:
         queries, refs = copies(rng, N, 1000)
         if 'a' in SHAPES:
-            shape(ctx, 'a: DNA 1 kb against 10 % mutated copies, global, score only', queries, refs, hip.score_matrix(2, 2), 3, 1, 'global', False, (32, 64, 128))
+            shape(ctx, 'a: DNA 1 kb against 10 % mutated copies, global, score only', queries, refs, hip.score_matrix(*DNA[:2]), DNA[2], DNA[3], 'global', False, (32, 64, 128))
         if 'b' in SHAPES:
-            shape(ctx, 'b: the same with CIGARs', queries, refs, hip.score_matrix(2, 2), 3, 1, 'global', True, (32, 64, 128))
+            shape(ctx, 'b: the same with CIGARs', queries, refs, hip.score_matrix(*DNA[:2]), DNA[2], DNA[3], 'global', True, (32, 64, 128))
     if 'c' in SHAPES:
         n = N + N // 4
         refs = [rng.integers(0, 4, 2000).astype(np.int8) for _ in range(n)]
@@ -111,13 +123,13 @@ def main():
               diagonals=diags)
     if 'd' in SHAPES:
         queries, refs = copies(rng, max(1, N // 100), 20000)
-        shape(ctx, 'd: DNA 20 kb x 20 kb with CIGARs', queries, refs, hip.score_matrix(2, 2), 3, 1, 'global', True, (128,))
+        shape(ctx, 'd: DNA 20 kb x 20 kb with CIGARs', queries, refs, hip.score_matrix(*DNA[:2]), DNA[2], DNA[3], 'global', True, (128,))
     if 'e' in SHAPES or 'f' in SHAPES:
         queries, refs = flanks(np.random.Generator(np.random.PCG64(20263)))
         if 'e' in SHAPES:
-            shape(ctx, 'e: 1-kb seed-right flanks, related for 600 letters, score only', queries, refs, hip.score_matrix(2, 2), 3, 1, MODE, False, (64,))
+            shape(ctx, 'e: 1-kb seed-right flanks, related for 600 letters, score only', queries, refs, hip.score_matrix(*DNA[:2]), DNA[2], DNA[3], MODE, False, (64,))
         if 'f' in SHAPES:
-            shape(ctx, 'f: the same with CIGARs', queries, refs, hip.score_matrix(2, 2), 3, 1, MODE, True, (64,))
+            shape(ctx, 'f: the same with CIGARs', queries, refs, hip.score_matrix(*DNA[:2]), DNA[2], DNA[3], MODE, True, (64,))
 
 
 if __name__ == '__main__':

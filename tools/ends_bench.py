@@ -12,7 +12,9 @@ H2D in the timed run), HIP events, the median of R runs after a warm-up.  Standa
 
 Prints one JSON line per shape: ms and cells/s (sum of m n over the pairs) of both, and the ratio local / ends of the cell rates.
 With CLH_LIB naming another build's libclh.so, `--mode global` times that build on the same pairs: the yardstick of (e) and (f).
-usage: python tools/ends_bench.py [N=20000] [runs=10] [shapes=abcd] [--mode MODE]"""
+--gap2 GO2,GE2 gives every K1g / K1gb plan a second gap piece; --scoring MA,MI,GO,GE replaces 2/2/3/1 in the DNA shapes a, b, e, f
+(the long-read costs: --scoring 2,4,4,2 --gap2 24,1).
+usage: python tools/ends_bench.py [N=20000] [runs=10] [shapes=abcd] [--mode MODE] [--gap2 GO2,GE2] [--scoring MA,MI,GO,GE]"""
 import json
 import os
 import sys
@@ -30,13 +32,23 @@ if '--mode' in ARGS:
     at = ARGS.index('--mode')
     MODE = ARGS[at + 1]
     del ARGS[at:at + 2]
+GAP2 = {}                 # --gap2 GO2,GE2: two-piece gap costs (the second piece) for every plan of K1g and K1gb
+if '--gap2' in ARGS:
+    at = ARGS.index('--gap2')
+    GAP2 = dict(zip(('gap_open2', 'gap_extend2'), (int(x) for x in ARGS[at + 1].split(','))))
+    del ARGS[at:at + 2]
+DNA = (2, 2, 3, 1)        # --scoring MA,MI,GO,GE: match, mismatch and the (first) gap piece of the DNA shapes a, b, e, f
+if '--scoring' in ARGS:
+    at = ARGS.index('--scoring')
+    DNA = tuple(int(x) for x in ARGS[at + 1].split(','))
+    del ARGS[at:at + 2]
 N = int(ARGS[0]) if len(ARGS) > 0 else 20000
 R = int(ARGS[1]) if len(ARGS) > 1 else 10
 SHAPES = ARGS[2] if len(ARGS) > 2 else 'abcd'
 
 
 def ends_ms(ctx, qd, qo, rd, ro, mat, go, ge, mode, cigar):
-    plan = ctx.ends_plan(qd, qo, rd, ro, mat, go, ge, mode=mode, want_cigar=cigar)
+    plan = ctx.ends_plan(qd, qo, rd, ro, mat, go, ge, mode=mode, want_cigar=cigar, **GAP2)
     try:
         plan.run(); plan.fetch()                     # warm-up (code objects, allocator), and the rows are whole
         ms = []
@@ -82,11 +94,11 @@ def shape(ctx, name, queries, refs, mat, go, ge, mode, cigar, local=True):
     e_ms, info = ends_ms(ctx, qd, qo, rd, ro, mat, go, ge, mode, cigar)
     if not local:
         print(json.dumps({'shape': name, 'pairs': len(queries), 'cells': cells, 'mode': mode, 'cigar': cigar,
-                          'ends_ms': round(e_ms, 3), 'ends_gcups': round(cells / e_ms / 1e6, 2), 'shares': info['shares']}), flush=True)
+                          'gap2': GAP2 or None, 'ends_ms': round(e_ms, 3), 'ends_gcups': round(cells / e_ms / 1e6, 2), 'shares': info['shares']}), flush=True)
         return
     l_ms, classes = local_ms(ctx, qd, qo, rd, ro, mat, go, ge, cigar)
     print(json.dumps({'shape': name, 'pairs': len(queries), 'cells': cells, 'mode': mode, 'cigar': cigar,
-                      'ends_ms': round(e_ms, 3), 'ends_gcups': round(cells / e_ms / 1e6, 2), 'shares': info['shares'],
+                      'gap2': GAP2 or None, 'ends_ms': round(e_ms, 3), 'ends_gcups': round(cells / e_ms / 1e6, 2), 'shares': info['shares'],
                       'local_ms': round(l_ms, 3), 'local_gcups': round(cells / l_ms / 1e6, 2), 'local_classes': classes,
                       'local_over_ends': round(e_ms / l_ms, 2)}), flush=True)
 
@@ -102,9 +114,9 @@ def main():
             q = synth.mutate(r[at:at + 1000], rng, sub=0.04, ins=0.03, dele=0.03)
             queries.append(np.concatenate([q, rng.integers(0, 4, 1000).astype(np.int8)])[:1000])
         if 'a' in SHAPES:
-            shape(ctx, 'a: DNA 1 kb x 1-1.5 kb, global, score only', queries, refs, hip.score_matrix(2, 2), 3, 1, 'global', False)
+            shape(ctx, 'a: DNA 1 kb x 1-1.5 kb, global, score only', queries, refs, hip.score_matrix(*DNA[:2]), DNA[2], DNA[3], 'global', False)
         if 'b' in SHAPES:
-            shape(ctx, 'b: the same with CIGARs', queries, refs, hip.score_matrix(2, 2), 3, 1, 'global', True)
+            shape(ctx, 'b: the same with CIGARs', queries, refs, hip.score_matrix(*DNA[:2]), DNA[2], DNA[3], 'global', True)
     if 'c' in SHAPES:
         n = N + N // 4
         refs = [rng.integers(0, 4, 2000).astype(np.int8) for _ in range(n)]
@@ -121,9 +133,9 @@ def main():
     if 'e' in SHAPES or 'f' in SHAPES:
         queries, refs = flanks(np.random.Generator(np.random.PCG64(20263)))
         if 'e' in SHAPES:
-            shape(ctx, 'e: 1-kb seed-right flanks, related for 600 letters, score only', queries, refs, hip.score_matrix(2, 2), 3, 1, MODE, False, local=False)
+            shape(ctx, 'e: 1-kb seed-right flanks, related for 600 letters, score only', queries, refs, hip.score_matrix(*DNA[:2]), DNA[2], DNA[3], MODE, False, local=False)
         if 'f' in SHAPES:
-            shape(ctx, 'f: the same with CIGARs', queries, refs, hip.score_matrix(2, 2), 3, 1, MODE, True, local=False)
+            shape(ctx, 'f: the same with CIGARs', queries, refs, hip.score_matrix(*DNA[:2]), DNA[2], DNA[3], MODE, True, local=False)
 
 
 if __name__ == '__main__':
