@@ -2125,6 +2125,9 @@ static_assert(offsetof(clh_band_row, score) == offsetof(clh_ends_row, score) && 
 struct PairsShape {
     int n = 0, mode = 0, n_mat = 0, go = 0, ge = 0;
     int pieces = 1, go2 = 0, ge2 = 0;             // two-piece gap costs (clh_gap2): a gap costs the smaller of the two pieces
+    bool spliced = false;                         // intron gaps (clh_splice): K1g alone
+    int io = 0;
+    std::vector<int64_t> row0_intron;             // spliced, global: per pair without a query letter, what its reference costs as one intron (else -1)
     bool want_cigar = false;
     int64_t gap(int64_t k) const                  // what a gap of k >= 1 letters costs
     {
@@ -2255,12 +2258,16 @@ static int pairs_begin_run(clh_pairs_plan* pl, void* stream_, hipStream_t* st)
 }
 
 // what the programme gives when one side has no letter: the boundary itself
+// (intron >= 0: the spliced programme, whose row 0 is one deletion or, where that is dearer, one intron)
 template <typename Row>
-static void en_empty_side(int mode, int m, int n, const PairsShape& sh, Row* row, uint32_t* op)
+static void en_empty_side(int mode, int m, int n, const PairsShape& sh, Row* row, uint32_t* op, int64_t intron = -1)
 {
     *op = 0;
     row->score = 0; row->ref_begin = 0; row->ref_end = -1; row->query_begin = 0; row->query_end = -1;
-    if (n > 0 && mode == CLH_ENDS_GLOBAL) { row->score = (int32_t)-sh.gap(n); row->ref_end = n - 1; *op = ((uint32_t)n << 4) | 2u; }
+    if (n > 0 && mode == CLH_ENDS_GLOBAL) {
+        const bool as_intron = intron >= 0 && intron < sh.gap(n);
+        row->score = (int32_t)-(as_intron ? intron : sh.gap(n)); row->ref_end = n - 1; *op = ((uint32_t)n << 4) | (as_intron ? 3u : 2u);
+    }
     if (mode == CLH_ENDS_EXTEND) return;                       // the best cell of a boundary that only loses is (0, 0)
     if (m > 0 && mode != CLH_ENDS_OVERLAP) { row->score = (int32_t)-sh.gap(m); row->query_end = m - 1; *op = ((uint32_t)m << 4) | 1u; }
     if (m > 0 && mode == CLH_ENDS_OVERLAP) { row->query_begin = m; row->query_end = m - 1; }
@@ -2294,7 +2301,7 @@ static int pairs_fetch(const std::string& kind, Plan* pl, Row* rows, uint32_t* c
         const uint32_t* src = nullptr;
         int len = 0;
         if (p.m == 0 || p.n == 0) {
-            en_empty_side(pl->mode, p.m, p.n, *pl, &out, &one);
+            en_empty_side(pl->mode, p.m, p.n, *pl, &out, &one, pl->row0_intron.empty() ? -1 : pl->row0_intron[(size_t)k]);
             if (one) { src = &one; len = 1; }
         } else {
             bool bad = false;
@@ -2328,6 +2335,7 @@ struct clh_ends_plan : clh_pairs_plan {
     std::vector<clh::EnPair> pairs;
     int64_t hand_words = 0;
     void* d_hand = nullptr;
+    void *d_site = nullptr, *d_strand = nullptr;  // spliced: the site costs of both strands and the pairs' strands (null: all +)
 };
 
 extern "C" void clh_ends_plan_destroy(clh_ends_plan* pl) { delete pl; }
@@ -2340,20 +2348,66 @@ static int64_t en_ws_bytes(int64_t m, int64_t n, int pieces)
     return (4 * pieces * m * (64 * (nch - 1) + llast) + 15) & ~(int64_t)15;
 }
 
-// both creates of K1g; g2: the second piece, null for one piece
+// the cost of the dinucleotide (x, y) as the reference reads it, from the table ssw_spliced.hip takes (clh_device.h)
+static int64_t sp_site(const int32_t* site, int soff, int which, int x, int y)
+{
+    return site[((x | y) > 3 || (x | y) < 0) ? clh::kSpOther : soff + which + 4 * x + y];
+}
+
+// what the spliced create refuses beyond pairs_check_opts, and the table of both strands -> 0, or the code
+static int sp_check(const std::string& me, const clh_ends_opts* o, const clh_splice* sp, const int8_t* strand, int32_t n, int32_t* site, int64_t* site_max)
+{
+    if (!sp) return fail(CLH_E_ARG, me + "null splice");
+    bool dna = o->n_mat == 5;
+    for (int a = 0; dna && a < 5; ++a)
+        for (int b = 0; b < 5; ++b) {
+            const int want = (a == 4 || b == 4) ? 0 : (a == b ? o->mat[0] : o->mat[1]);
+            dna = dna && o->mat[a * 5 + b] == want;
+        }
+    if (!dna)
+        return fail(CLH_E_UNSUPPORTED, me + "spliced alignment takes the DNA match / mismatch matrix alone (5 x 5: one match score, one mismatch score, 0 against N); "
+                                            "substitution matrices over other alphabets are not built");
+    int64_t dmax = sp->other, amax = sp->other;
+    bool neg = sp->intron_open < 0 || sp->other < 0;
+    for (int k = 0; k < 16; ++k) {
+        neg = neg || sp->donor[k] < 0 || sp->acceptor[k] < 0;
+        dmax = std::max<int64_t>(dmax, sp->donor[k]); amax = std::max<int64_t>(amax, sp->acceptor[k]);
+    }
+    if (neg) return fail(CLH_E_ARG, me + "intron_open, the donor and acceptor costs and `other` must not be negative");
+    if (strand)
+        for (int k = 0; k < n; ++k)
+            if (strand[k] != 1 && strand[k] != -1) return fail(CLH_E_ARG, me + "pair " + std::to_string(k) + ": strand must be +1 or -1, got " + std::to_string((int)strand[k]));
+    *site_max = (int64_t)sp->intron_open + dmax + amax;
+    for (int x = 0; x < 4; ++x)
+        for (int y = 0; y < 4; ++y) {      // strand -: the transcript reads the complement of (y, x)
+            site[4 * x + y] = sp->donor[4 * x + y]; site[16 + 4 * x + y] = sp->acceptor[4 * x + y];
+            site[32 + 4 * x + y] = sp->acceptor[4 * (3 - y) + (3 - x)]; site[48 + 4 * x + y] = sp->donor[4 * (3 - y) + (3 - x)];
+        }
+    site[clh::kSpOther] = sp->other;
+    return 0;
+}
+
+// the creates of K1g; g2: the second piece, null for one piece; sp: intron gaps (clh_splice) with the pairs' strands, null for none
 static clh_ends_plan* en_create(const std::string& me, clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off,
-                                const clh_ends_opts* o, const clh_gap2* g2)
+                                const clh_ends_opts* o, const clh_gap2* g2, const clh_splice* sp = nullptr, const int8_t* strand = nullptr, bool spliced = false)
 {
     if (pairs_check_opts(me, ctx, n, q_off, r_off, o, nullptr, g2)) return nullptr;
-    const int pieces = g2 ? 2 : 1;
+    const int pieces = (g2 || spliced) ? 2 : 1;       // the spliced kernel stores a byte per cell and hands three values on, as two pieces do
     int64_t splus;
-    const int64_t smax = pairs_scan_matrix(o, &splus, g2);
+    int64_t smax = pairs_scan_matrix(o, &splus, g2);
+    int32_t site[clh::kSpSites];
+    if (spliced) {
+        int64_t site_max = 0;
+        if (sp_check(me, o, sp, strand, n, site, &site_max)) return nullptr;
+        smax = std::max(smax, site_max);
+    }
     for (int k = 0; k < n; ++k) {
         const int64_t m = q_off[k + 1] - q_off[k], nn = r_off[k + 1] - r_off[k];
         if (m < 0 || nn < 0) { fail(CLH_E_ARG, me + "offsets must ascend"); return nullptr; }
         if ((m > 0 && !q) || (nn > 0 && !r)) { fail(CLH_E_ARG, me + "null argument"); return nullptr; }
         if (m + nn >= ((int64_t)1 << 30) || (m + nn) * smax >= ((int64_t)1 << 30)) {
-            fail(CLH_E_ARG, me + "pair " + std::to_string(k) + ": (m + n) * max(|s|, " + (g2 ? "gap_open, gap_extend, gap_open2, gap_extend2" : "gap_open, gap_extend") +
+            fail(CLH_E_ARG, me + "pair " + std::to_string(k) + ": (m + n) * max(|s|, " +
+                                (spliced ? "gap_open, gap_extend, intron_open + dmax + amax" : g2 ? "gap_open, gap_extend, gap_open2, gap_extend2" : "gap_open, gap_extend") +
                                 ") = " + std::to_string(m + nn) + " * " +
                                 std::to_string(smax) + " reaches 2^30, the score range of the int32 cells");
             return nullptr;
@@ -2362,6 +2416,17 @@ static clh_ends_plan* en_create(const std::string& me, clh_ctx* ctx, int32_t n, 
     if (pairs_check_codes(me, n, q, q_off, r, r_off, o->n_mat)) return nullptr;
     PairsShape shape;
     if (g2) { shape.pieces = 2; shape.go2 = g2->gap_open2; shape.ge2 = g2->gap_extend2; }
+    if (spliced) {
+        shape.spliced = true; shape.io = sp->intron_open;
+        shape.row0_intron.assign((size_t)n, -1);
+        for (int k = 0; k < n && o->mode == CLH_ENDS_GLOBAL; ++k) {
+            const int64_t m = q_off[k + 1] - q_off[k], nn = r_off[k + 1] - r_off[k];
+            if (m != 0 || nn == 0) continue;
+            const int8_t* rk = r + r_off[k];
+            const int soff = (strand && strand[k] < 0) ? 32 : 0;
+            shape.row0_intron[(size_t)k] = (int64_t)sp->intron_open + sp_site(site, soff, 0, rk[0], nn > 1 ? rk[1] : 4) + sp_site(site, soff, 16, nn > 1 ? rk[nn - 2] : 4, rk[nn - 1]);
+        }
+    }
     std::vector<clh::EnPair> pairs;
     int64_t hand_words = 0;
     if (pairs_cut_shares(me, o, n, q_off, r_off, &shape, &pairs,
@@ -2379,7 +2444,13 @@ static clh_ends_plan* en_create(const std::string& me, clh_ctx* ctx, int32_t n, 
     const bool ok = pairs_upload(pl, &shape, pairs, q, q_off, r, r_off, o->mat);
     pl->pairs.swap(pairs);
     pl->d_hand = pl->alloc(sizeof(int32_t) * (size_t)std::max<int64_t>(pl->hand_words, 1));
-    if (!ok || !pl->d_hand) {
+    bool sp_ok = true;
+    if (spliced) {
+        pl->d_site = pl->upload(site, sizeof site);
+        if (strand && n) pl->d_strand = pl->upload(strand, (size_t)n);
+        sp_ok = pl->d_site && (!strand || !n || pl->d_strand);
+    }
+    if (!ok || !pl->d_hand || !sp_ok) {
         fail(CLH_E_HIP, "out of device memory or upload failed while building the ends plan");
         delete pl; return nullptr;
     }
@@ -2399,6 +2470,25 @@ extern "C" clh_ends_plan* clh_ends_plan_create_gap2(clh_ctx* ctx, int32_t n, con
     return en_create("clh_ends_plan_create_gap2: ", ctx, n, q, q_off, r, r_off, o, gap2);
 }
 
+extern "C" clh_ends_plan* clh_ends_plan_create_spliced(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off,
+                                                       const clh_ends_opts* o, const clh_splice* splice, const int8_t* strand)
+{
+    return en_create("clh_ends_plan_create_spliced: ", ctx, n, q, q_off, r, r_off, o, nullptr, splice, strand, true);
+}
+
+// the spliced plan's shares: ssw_spliced.hip, with K1g's argument block and the site costs behind it
+static int sp_run_shares(clh_ends_plan* pl, const clh::EnParams& base, hipStream_t st)
+{
+    clh::SpParams p;
+    static_cast<clh::EnParams&>(p) = base;
+    p.io = pl->io; p.site = (const int32_t*)pl->d_site; p.strand = (const int8_t*)pl->d_strand;
+    for (const auto& sh : pl->shares) {
+        HIPCHK(clh::launch_ssw_spliced(p, pl->want_cigar, sh.first, sh.second, st));
+        if (pl->want_cigar) HIPCHK(clh::launch_ssw_spliced_walk(p, sh.first, sh.second, st));
+    }
+    return 0;
+}
+
 extern "C" int clh_ends_plan_run(clh_ends_plan* pl, void* stream_)
 {
     if (!pl) return fail(CLH_E_ARG, "clh_ends_plan_run: null argument");
@@ -2414,6 +2504,10 @@ extern "C" int clh_ends_plan_run(clh_ends_plan* pl, void* stream_)
     p.ws = (uint8_t*)pl->d_ws; p.ws_cap = pl->ws_bytes;
     p.rows = (int32_t*)pl->d_rows;
     p.cigar = (uint32_t*)pl->d_cig; p.cigar_cap = pl->cig_cap;
+    if (pl->spliced) {
+        if (int rc = sp_run_shares(pl, p, st)) return rc;
+        return pl->end_run();
+    }
     for (const auto& sh : pl->shares) {        // in stream order: a share's walk has read the workspace before the next share fills it
         if (pl->pieces == 2) {
             HIPCHK(clh::launch_ssw_ends2(p, pl->want_cigar, sh.first, sh.second, st));
@@ -2460,6 +2554,17 @@ extern "C" int clh_ends_batch_gap2(clh_ctx* ctx, int32_t n, const int8_t* q, con
                                    const clh_gap2* gap2, clh_ends_row* rows, uint32_t* cigar, int64_t cigar_cap, int64_t* cigar_used)
 {
     clh_ends_plan* pl = clh_ends_plan_create_gap2(ctx, n, q, q_off, r, r_off, opts, gap2);
+    if (!pl) return g_code;
+    int rc = clh_ends_plan_run(pl, nullptr);
+    if (!rc) rc = clh_ends_plan_fetch(pl, rows, cigar, cigar_cap, cigar_used);
+    delete pl;
+    return rc;
+}
+
+extern "C" int clh_ends_batch_spliced(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off, const clh_ends_opts* opts,
+                                     const clh_splice* splice, const int8_t* strand, clh_ends_row* rows, uint32_t* cigar, int64_t cigar_cap, int64_t* cigar_used)
+{
+    clh_ends_plan* pl = clh_ends_plan_create_spliced(ctx, n, q, q_off, r, r_off, opts, splice, strand);
     if (!pl) return g_code;
     int rc = clh_ends_plan_run(pl, nullptr);
     if (!rc) rc = clh_ends_plan_fetch(pl, rows, cigar, cigar_cap, cigar_used);

@@ -337,6 +337,14 @@ hipError_t launch_ssw_ends_walk(const EnParams& p, int first, int count, hipStre
 struct En2Params : EnParams { int32_t go2, ge2; };
 hipError_t launch_ssw_ends2(const En2Params& p, bool store, int first, int count, hipStream_t stream);
 hipError_t launch_ssw_ends2_walk(const En2Params& p, int first, int count, hipStream_t stream);
+// K1g with intron gaps (ssw_spliced.hip): io opens an intron; site[0..15] / [16..31] are the start / end costs of strand + and
+// site[32..47] / [48..63] those of strand -, each indexed by the dinucleotide 4 x + y as the reference reads it, site[kSpOther] the
+// cost of a dinucleotide with a code >= 4 or off the reference; strand[k] < 0: pair k is on strand - (null: all +).  A pair's
+// hand-over is 6 x rows rounded up to 64 and its stored decisions one byte per cell, the two-piece figures.
+static constexpr int kSpOther = 64, kSpSites = 65;
+struct SpParams : EnParams { int32_t io; const int32_t* site; const int8_t* strand; };
+hipError_t launch_ssw_spliced(const SpParams& p, bool store, int first, int count, hipStream_t stream);
+hipError_t launch_ssw_spliced_walk(const SpParams& p, int first, int count, hipStream_t stream);
 
 // K1gb (ssw_band.hip): K1g's global, semiglobal, prefix and extend programmes over a band of diagonals [lo, hi], d = j - i; one wave per pair in the
 // band's frame, a lane on CPL consecutive band positions b = d - lo (classes CPL 2, 4, 8: bands of up to 128, 256, 512 diagonals).

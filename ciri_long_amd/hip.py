@@ -70,6 +70,32 @@ def gap2_of(who, gap_open2, gap_extend2):
     return None if gap_open2 is None else Gap2(int(gap_open2), int(gap_extend2))
 
 
+class Splice(C.Structure):
+    _fields_ = [('intron_open', C.c_int32), ('donor', C.c_int32 * 16), ('acceptor', C.c_int32 * 16), ('other', C.c_int32)]
+
+
+def splice_of(who, intron_open, noncanonical, donor_costs=None, acceptor_costs=None):
+    """the intron costs as libclh takes them (clh_splice): GT as donor and AG as acceptor cost 0, every other dinucleotide, and one
+    that holds an N or runs off the reference, cost `noncanonical`; the dicts override single dinucleotides as read on the transcript
+    strand, e.g. {'GC': 2}"""
+    sp = Splice()
+    if int(intron_open) < 0 or int(noncanonical) < 0:
+        raise ValueError('%s: intron_open and noncanonical must not be negative' % who)
+    sp.intron_open, sp.other = int(intron_open), int(noncanonical)
+    for table, free, over, name in ((sp.donor, 'GT', donor_costs, 'donor_costs'), (sp.acceptor, 'AG', acceptor_costs, 'acceptor_costs')):
+        for k in range(16):
+            table[k] = int(noncanonical)
+        table[4 * 'ACGT'.index(free[0]) + 'ACGT'.index(free[1])] = 0
+        for key, v in (over or {}).items():
+            key = str(key).upper()
+            if len(key) != 2 or key[0] not in 'ACGT' or key[1] not in 'ACGT':
+                raise ValueError('%s: %s names dinucleotides over ACGT, got %r' % (who, name, key))
+            if int(v) < 0:
+                raise ValueError('%s: %s[%r] must not be negative' % (who, name, key))
+            table[4 * 'ACGT'.index(key[0]) + 'ACGT'.index(key[1])] = int(v)
+    return sp
+
+
 ENDS_DTYPE = np.dtype([('score', '<i4'), ('ref_begin', '<i4'), ('ref_end', '<i4'), ('query_begin', '<i4'), ('query_end', '<i4'),
                        ('cigar_len', '<i4'), ('cigar_off', '<i8')])
 ENDS_MODES = {'global': 0, 'semiglobal': 1, 'overlap': 2, 'prefix': 3, 'extend': 4}
@@ -210,6 +236,12 @@ def lib():
             L.clh_band_plan_create_gap2.restype = C.c_void_p
             L.clh_band_plan_create_gap2.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BandOpts),
                                                     C.POINTER(Gap2)]
+        if hasattr(L, 'clh_ends_plan_create_spliced'):   # absent from a CLH_LIB build older than spliced alignment: using it there raises
+            L.clh_ends_plan_create_spliced.restype = C.c_void_p
+            L.clh_ends_plan_create_spliced.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(EndsOpts),
+                                                       C.POINTER(Splice), C.c_void_p]
+            L.clh_ends_batch_spliced.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(EndsOpts), C.POINTER(Splice),
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
         L.clh_band_plan_create.restype = C.c_void_p
         L.clh_band_plan_create.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BandOpts)]
         L.clh_band_plan_destroy.restype = None
@@ -541,10 +573,11 @@ class Context(object):
         return EditSearchPlan(self, probes, texts, k, equalities)
 
     def ends_batch(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode='global', want_cigar=True, workspace_bytes=0,
-                   gap_open2=None, gap_extend2=None):
+                   gap_open2=None, gap_extend2=None, splice=None, strand=None):
         """End-anchored affine-gap alignment of the pairs (query k, reference k), packed codes and offsets as ssw_batch takes them,
         through K1g -> (rows ENDS_DTYPE, cigars uint32 packed ops).  See EndsPlan."""
-        plan = EndsPlan(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode, want_cigar, workspace_bytes, gap_open2, gap_extend2)
+        plan = EndsPlan(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode, want_cigar, workspace_bytes, gap_open2, gap_extend2,
+                        splice, strand)
         try:
             plan.run()
             return plan.fetch()
@@ -552,8 +585,9 @@ class Context(object):
             plan.close()
 
     def ends_plan(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode='global', want_cigar=True, workspace_bytes=0,
-                  gap_open2=None, gap_extend2=None):
-        return EndsPlan(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode, want_cigar, workspace_bytes, gap_open2, gap_extend2)
+                  gap_open2=None, gap_extend2=None, splice=None, strand=None):
+        return EndsPlan(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode, want_cigar, workspace_bytes, gap_open2, gap_extend2,
+                        splice, strand)
 
     def band_batch(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, band, mode='global', diagonals=None, want_cigar=True,
                    workspace_bytes=0, gap_open2=None, gap_extend2=None):
@@ -845,16 +879,25 @@ class EndsPlan(_PairsPlan):
     cigars uint32).  Scores are int32 and may be negative; a span without a letter has end == begin - 1; without want_cigar no walk
     back is made and a begin the mode does not fix is -1 (include/ciri_long_hip.h).  With gap_open2 and gap_extend2 a gap of k
     letters costs the smaller of gap_open + (k - 1) gap_extend and gap_open2 + (k - 1) gap_extend2 (0 <= gap_extend2 <= gap_extend
-    <= gap_open <= gap_open2; clh_ends_plan_create_gap2), and the stored decisions take a byte per cell instead of half a byte."""
+    <= gap_open <= gap_open2; clh_ends_plan_create_gap2), and the stored decisions take a byte per cell instead of half a byte.
+    With `splice` (a Splice, see splice_of) a run of skipped reference letters costs the smaller of a deletion and an intron, whose
+    cost is intron_open plus the donor and acceptor costs of the dinucleotides at its ends on the pair's strand (`strand`: +1 / -1 per
+    pair, None for all +1; clh_ends_plan_create_spliced); CIGARs then hold op N (3), a byte per cell is stored, the matrix must be the
+    DNA match / mismatch one, and two-piece gap costs together with introns are not built."""
     _destroy = 'clh_ends_plan_destroy'
     _c, _dtype = 'ends', ENDS_DTYPE
 
     def __init__(self, ctx, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode='global', want_cigar=True, workspace_bytes=0,
-                 gap_open2=None, gap_extend2=None):
+                 gap_open2=None, gap_extend2=None, splice=None, strand=None):
         _Handle.__init__(self, ctx)
         if mode not in ENDS_MODES:
             raise ValueError('mode must be one of global, semiglobal, overlap, prefix, extend, got %r' % (mode,))
         gap2 = gap2_of('EndsPlan', gap_open2, gap_extend2)
+        if splice is not None:
+            self._create_spliced(ctx, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode, want_cigar, workspace_bytes, gap2, splice, strand)
+            return
+        if strand is not None:
+            raise ValueError('EndsPlan: strand comes with splice')
         q, q_off, r, r_off, mat, n_mat, _ = self._inputs(queries, query_off, refs, ref_off, mat, want_cigar)
         opts = EndsOpts(ENDS_MODES[mode], mat.ctypes.data, n_mat, int(gap_open), int(gap_extend), int(self.want_cigar), int(workspace_bytes))
         args = (ctx._h, self.n, q.ctypes.data, q_off.ctypes.data, r.ctypes.data, r_off.ctypes.data, C.byref(opts))
@@ -864,6 +907,23 @@ class EndsPlan(_PairsPlan):
             self._h = lib().clh_ends_plan_create_gap2(*(args + (C.byref(gap2),)))
         if not self._h:
             raise ClhError('clh_ends_plan_create%s failed: %s' % ('' if gap2 is None else '_gap2', last_error()))
+
+    def _create_spliced(self, ctx, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode, want_cigar, workspace_bytes, gap2, splice, strand):
+        if gap2 is not None:
+            raise ClhError('clh_ends_plan_create_spliced failed: CLH_E_UNSUPPORTED: two-piece gap costs together with introns are not built')
+        if not hasattr(lib(), 'clh_ends_plan_create_spliced'):
+            raise ClhError('clh_ends_plan_create_spliced: this libclh.so is older than spliced alignment')
+        q, q_off, r, r_off, mat, n_mat, _ = self._inputs(queries, query_off, refs, ref_off, mat, want_cigar)
+        st = None
+        if strand is not None:
+            st = np.ascontiguousarray(strand, dtype=np.int8)
+            if st.shape != (self.n,):
+                raise ValueError('EndsPlan: %d strands for %d pairs' % (st.size, self.n))
+        opts = EndsOpts(ENDS_MODES[mode], mat.ctypes.data, n_mat, int(gap_open), int(gap_extend), int(self.want_cigar), int(workspace_bytes))
+        self._h = lib().clh_ends_plan_create_spliced(ctx._h, self.n, q.ctypes.data, q_off.ctypes.data, r.ctypes.data, r_off.ctypes.data, C.byref(opts),
+                                                     C.byref(splice), st.ctypes.data if st is not None else None)
+        if not self._h:
+            raise ClhError('clh_ends_plan_create_spliced failed: %s' % last_error())
 
     def info(self):
         """the geometry of the kernel: reference columns a lane owns (cpl) and columns of a chunk (a longer reference is walked chunk

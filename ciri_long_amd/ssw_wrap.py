@@ -408,6 +408,73 @@ def align_pairs_ends(ref_seqs, query_seqs, mode='global', match=2, mismatch=2, g
     return _pairs_results(rows, cig, qo, walk, report_cigar)
 
 
+# the defaults of align_pairs_spliced as keywords: match 2, mismatch 2, a deletion 3 + 1 per further letter, an intron 12 between GT and
+# AG and 6 more per site that is not canonical.  A convenience; nothing is claimed about parity with any other aligner's output.
+SPLICED_DEFAULTS = dict(match=2, mismatch=2, gap_open=3, gap_extend=1, intron_open=12, noncanonical=6)
+
+
+def _strands(strand, n):
+    """'+', '-', +1, -1 or a sequence of them -> int8[n] of +1 / -1"""
+    one = {'+': 1, '-': -1, 1: 1, -1: -1}
+    if isinstance(strand, (str, bytes, int, np.integer)):
+        strand = [strand] * n
+    strand = list(strand)
+    if len(strand) != n or any((s.decode() if isinstance(s, bytes) else s) not in one for s in strand):
+        raise ValueError("align_pairs_spliced: strand must be '+', '-', 'both' or one of '+' / '-' per pair, got %r" % (strand[:8],))
+    return np.array([one[s.decode() if isinstance(s, bytes) else s] for s in strand], dtype=np.int8)
+
+
+def align_pairs_spliced(ref_seqs, query_seqs, mode='semiglobal', strand='+', match=2, mismatch=2, gap_open=3, gap_extend=1, intron_open=12, noncanonical=6,
+                        donor_costs=None, acceptor_costs=None, report_cigar=False, context=None, matrix=None, alphabet=None, gap_open2=None,
+                        gap_extend2=None):
+    """``align_pairs_ends`` of a transcript sequence (query) against a genomic window (reference) in which a long reference gap may be an
+    intron, in one GPU call -> one PyAlignRes per pair, each with ``.strand`` ('+' or '-').
+
+    A maximal run of skipped reference letters r[a..b] costs the smaller of gap_open + (b - a) gap_extend and intron_open + start(a) +
+    end(b): an intron costs a constant whatever its length.  On strand '+', start(a) is the donor cost of the dinucleotide r[a] r[a+1]
+    and end(b) the acceptor cost of r[b-1] r[b]; on strand '-' the transcript is the reverse complement, so the acceptor cost of the
+    complement of r[a+1] r[a] opens and the donor cost of the complement of r[b] r[b-1] closes (a canonical intron reads CT..AC).  GT
+    as donor and AG as acceptor cost 0; every other dinucleotide, and one that holds an N or runs off the window, costs `noncanonical`;
+    donor_costs / acceptor_costs override single dinucleotides as read on the transcript strand, e.g. donor_costs={'GC': 2}.  The costs
+    depend on the position alone.  A deletion and an intron are never adjacent; insertions are as in ``align_pairs_ends``, as are the
+    modes, end cells, coordinates and ties (csrc/ssw_spliced.hip; tests/spliced_check.py is the definition).
+
+    strand is '+', '-', a sequence of them (one per pair), or 'both': every pair is then aligned on both strands in the same call and
+    the higher score is kept, ties to '+'.  ``cigar_string`` (report_cigar) uses M / I / D / N with soft clips as ``align_pairs_ends``
+    writes them, which ``align.convert_cigar_string`` and ``align.get_exons`` read; among equal scores the walk prefers the diagonal,
+    then D, then N, then I, and a run on row 0 of an anchored mode is D unless N is cheaper.  DNA match / mismatch only: `matrix`,
+    `alphabet`, `gap_open2` and `gap_extend2` are named here to be refused (not built).  All costs are >= 0 and gap_open >=
+    gap_extend.  Parity with minimap2's splice model, which couples donor and acceptor and has other tie rules, is not claimed."""
+    who = 'align_pairs_spliced'
+    if matrix is not None or alphabet is not None:
+        raise ValueError('%s: substitution matrices are not supported (CLH_E_UNSUPPORTED): DNA match / mismatch only' % who)
+    if gap_open2 is not None or gap_extend2 is not None:
+        raise ValueError('%s: two-piece gap costs together with introns are not supported (CLH_E_UNSUPPORTED)' % who)
+    if mode not in hip.ENDS_MODES:
+        raise ValueError("%s: mode must be 'global', 'semiglobal', 'overlap', 'prefix' or 'extend', got %r" % (who, mode))
+    n = len(ref_seqs)
+    if len(query_seqs) != n:
+        raise ValueError('%s: %d references vs %d queries' % (who, n, len(query_seqs)))
+    if min(int(match), int(mismatch), int(gap_open), int(gap_extend)) < 0:
+        raise ValueError('%s: match, mismatch and the gap costs must not be negative' % who)
+    splice = hip.splice_of(who, intron_open, noncanonical, donor_costs, acceptor_costs)
+    both = isinstance(strand, str) and strand == 'both'
+    st = np.concatenate([np.ones(n, dtype=np.int8), -np.ones(n, dtype=np.int8)]) if both else _strands(strand, n)
+    if not n:
+        return []
+    refs, queries = (list(ref_seqs) * 2, list(query_seqs) * 2) if both else (ref_seqs, query_seqs)      # 'both': pair k and pair n + k, one plan
+    mat, (qd, qo), (rd, ro) = _pairs_inputs(who, refs, queries, match, mismatch, None, None)
+    ctx = context or hip.default_context()
+    walk = bool(report_cigar) or mode in ('semiglobal', 'overlap')      # the begins come from the walk, unless the mode fixes them
+    rows, cig = ctx.ends_batch(qd, qo, rd, ro, mat, gap_open, gap_extend, mode=mode, want_cigar=walk, splice=splice, strand=st)
+    out = _pairs_results(rows, cig, qo, walk, report_cigar)
+    for res, s in zip(out, st):
+        res.strand = '+' if s > 0 else '-'
+    if both:
+        out = [out[k] if out[k].score >= out[n + k].score else out[n + k] for k in range(n)]
+    return out
+
+
 def align_pairs_band(ref_seqs, query_seqs, band, mode='global', diagonals=None, match=2, mismatch=2, gap_open=3, gap_extend=1, report_cigar=False,
                      matrix=None, alphabet=None, context=None, gap_open2=None, gap_extend2=None):
     """``align_pairs_ends`` over a band of diagonals, in one GPU call -> one PyAlignRes per pair.

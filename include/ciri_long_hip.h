@@ -448,6 +448,40 @@ clh_ends_plan* clh_ends_plan_create_gap2(clh_ctx* ctx, int32_t n, const int8_t* 
 int clh_ends_batch_gap2(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off, const clh_ends_opts* opts,
                         const clh_gap2* gap2, clh_ends_row* rows, uint32_t* cigar, int64_t cigar_cap, int64_t* cigar_used);
 
+/* Spliced alignment for clh_ends_*: a long reference gap may be an intron, which costs a constant that depends on the dinucleotides at
+ * its two ends and not on its length.  Sequences are DNA codes A, C, G, T = 0..3, anything else 4; the matrix must be the 5 x 5 match /
+ * mismatch one (0 against code 4).  donor[4 a + b] and acceptor[4 a + b] are the costs of the dinucleotide (a, b) as read on the
+ * transcript strand, `other` that of a dinucleotide which holds a code >= 4 or runs off the reference; strand[k] is +1 or -1 (strand
+ * == NULL: all +1).  One rule: a maximal run of skipped reference letters r[a..b] (0-based, no query letter consumed in between) costs
+ *     min(gap_open + (b - a) gap_extend, intron_open + start(a) + end(b));                          insertions are unchanged
+ *     strand +:  start(a) = donor[r[a], r[a+1]]               end(b) = acceptor[r[b-1], r[b]]
+ *     strand -:  start(a) = acceptor[c(r[a+1]), c(r[a])]      end(b) = donor[c(r[b]), c(r[b-1])]      c(x) = 3 - x
+ * (a canonical intron reads CT..AC on the reference for strand -); a + 1 > n - 1 or b - 1 < 0 gives `other`.  The costs depend on the
+ * position alone: for a run of one letter the second letter of the start dinucleotide lies outside the run.  In cells, 1-based
+ * columns, don(j) = start(j - 1), acc(j) = end(j - 1):
+ *     F[i][j] = max(H[i-1][j] - go, F[i-1][j] - ge)            (I; reads the true H)
+ *     T[i][j] = max(H[i-1][j-1] + s(q_i, r_j), F[i][j])        (H without a reference gap)
+ *     E[i][j] = max(T[i][j-1] - go, E[i][j-1] - ge)            (D)
+ *     N[i][j] = max(T[i][j-1] - io - don(j), N[i][j-1])        (N; the close cost is paid on leaving)
+ *     H[i][j] = max(T[i][j], E[i][j], N[i][j] - acc(j))
+ * E and N open from T, not from H: a deletion run and an intron run are never adjacent, which makes the one rule exact; inserted
+ * letters may separate them (D, I, N).  Modes, boundaries, end cells, coordinates and empty sides are those of clh_ends_*; row 0 of the
+ * anchored modes is what the recurrences give from T[0][0] = 0, H[0][j] = -min(go + (j - 1) ge, io + don(1) + acc(j)); column 0 is
+ * unchanged.  The walk prefers, in state H, the diagonal, then E, then N, then F; in state E it emits D, moves left and leaves as soon
+ * as E[i][j] == T[i][j-1] - go, N likewise with N[i][j] == T[i][j-1] - io - don(j), emitting BAM op N (3); on leaving E or N it is in
+ * state T: the diagonal if T equals it, else F.  The anchored stop on row 0 at column j > 0 emits one run of j letters, D if the
+ * deletion is not dearer, else N: the CIGAR says which piece paid.  All costs must be >= 0 (CLH_E_ARG); a matrix of another form is
+ * CLH_E_UNSUPPORTED; the range bound is (m + n) max(|s|, gap_open, gap_extend, intron_open + dmax + amax) < 2^30 with dmax, amax the
+ * greatest donor and acceptor cost, `other` included.  Stored decisions are one byte per cell, the two-piece figure: CLH_E_CAPACITY,
+ * the shares and info's byte counts follow.  The plan is a clh_ends_plan: run, fetch, timing, info and destroy are those above.
+ * Two-piece gap costs together with introns, a band, and coupled donor-acceptor scoring are not built; parity with minimap2's splice
+ * model, which couples the two sites and has other tie rules, is not claimed. */
+typedef struct { int32_t intron_open; int32_t donor[16]; int32_t acceptor[16]; int32_t other; } clh_splice;
+clh_ends_plan* clh_ends_plan_create_spliced(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off,
+                                            const clh_ends_opts* opts, const clh_splice* splice, const int8_t* strand);
+int clh_ends_batch_spliced(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off, const clh_ends_opts* opts,
+                           const clh_splice* splice, const int8_t* strand, clh_ends_row* rows, uint32_t* cigar, int64_t cigar_cap, int64_t* cigar_used);
+
 /* ---- banded end-anchored alignment of pairs around a diagonal: global, semiglobal, prefix, extend (K1gb) ---------------------------
  * The programme of clh_ends_* over a band.  The band of pair k is a closed interval of diagonals [lo, hi], d = j - i: without a hint
  * (diag == NULL) lo = min(0, n - m) - band, hi = max(0, n - m) + band; with diag[k], lo = diag[k] - band, hi = diag[k] + band; both

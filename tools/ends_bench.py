@@ -9,12 +9,16 @@ H2D in the timed run), HIP events, the median of R runs after a warm-up.  Standa
   (e) 5 000 seed-right flanks of 1 kb x 1 kb -- the query a 10 % mutated copy of the reference for 600 letters, unrelated after --
       in the mode --mode names (default extend), score only; K1g alone, no local run
   (f) the same with CIGARs
+  (g) 2 000 spliced pairs -- the query a 600-nt cDNA of three exons mutated at 10 %, the reference a 6-kb window that holds the exons
+      around two GT..AG introns of about 2.5 kb -- semiglobal, score only; K1g alone, no local run.  With --splice IO,NC the plan is the
+      spliced one (csrc/ssw_spliced.hip); without it the same pairs run under one piece or, with --gap2, under two: the yardstick
+  (h) the same with CIGARs
 
 Prints one JSON line per shape: ms and cells/s (sum of m n over the pairs) of both, and the ratio local / ends of the cell rates.
 With CLH_LIB naming another build's libclh.so, `--mode global` times that build on the same pairs: the yardstick of (e) and (f).
 --gap2 GO2,GE2 gives every K1g / K1gb plan a second gap piece; --scoring MA,MI,GO,GE replaces 2/2/3/1 in the DNA shapes a, b, e, f
-(the long-read costs: --scoring 2,4,4,2 --gap2 24,1).
-usage: python tools/ends_bench.py [N=20000] [runs=10] [shapes=abcd] [--mode MODE] [--gap2 GO2,GE2] [--scoring MA,MI,GO,GE]"""
+(the long-read costs: --scoring 2,4,4,2 --gap2 24,1); --splice IO,NC gives every K1g plan intron gaps (intron_open, noncanonical).
+usage: python tools/ends_bench.py [N=20000] [runs=10] [shapes=abcd] [--mode MODE] [--gap2 GO2,GE2] [--scoring MA,MI,GO,GE] [--splice IO,NC]"""
 import json
 import os
 import sys
@@ -37,6 +41,11 @@ if '--gap2' in ARGS:
     at = ARGS.index('--gap2')
     GAP2 = dict(zip(('gap_open2', 'gap_extend2'), (int(x) for x in ARGS[at + 1].split(','))))
     del ARGS[at:at + 2]
+SPLICE = None             # --splice IO,NC: intron gaps for every plan of K1g (not together with --gap2)
+if '--splice' in ARGS:
+    at = ARGS.index('--splice')
+    SPLICE = tuple(int(x) for x in ARGS[at + 1].split(','))
+    del ARGS[at:at + 2]
 DNA = (2, 2, 3, 1)        # --scoring MA,MI,GO,GE: match, mismatch and the (first) gap piece of the DNA shapes a, b, e, f
 if '--scoring' in ARGS:
     at = ARGS.index('--scoring')
@@ -48,7 +57,8 @@ SHAPES = ARGS[2] if len(ARGS) > 2 else 'abcd'
 
 
 def ends_ms(ctx, qd, qo, rd, ro, mat, go, ge, mode, cigar):
-    plan = ctx.ends_plan(qd, qo, rd, ro, mat, go, ge, mode=mode, want_cigar=cigar, **GAP2)
+    more = dict(splice=hip.splice_of('ends_bench', *SPLICE)) if SPLICE else GAP2
+    plan = ctx.ends_plan(qd, qo, rd, ro, mat, go, ge, mode=mode, want_cigar=cigar, **more)
     try:
         plan.run(); plan.fetch()                     # warm-up (code objects, allocator), and the rows are whole
         ms = []
@@ -88,17 +98,34 @@ def flanks(rng, count=5000, length=1000, related=600):
     return queries, refs
 
 
+def spliced_pairs(rng, count=2000, exon=200, intron=2500, window=6000):
+    """a cDNA of three exons mutated at 10 % against the window that holds them around two GT..AG introns of about `intron` letters"""
+    queries, refs = [], []
+    for _ in range(count):
+        exons = [rng.integers(0, 4, exon).astype(np.int8) for _ in range(3)]
+        introns = []
+        for _ in range(2):
+            body = rng.integers(0, 4, intron + int(rng.integers(-100, 101))).astype(np.int8)
+            body[:2] = (2, 3); body[-2:] = (0, 2)                      # GT .. AG
+            introns.append(body)
+        core = np.concatenate([exons[0], introns[0], exons[1], introns[1], exons[2]])
+        flank = max(0, window - len(core))
+        refs.append(np.concatenate([rng.integers(0, 4, flank // 2).astype(np.int8), core, rng.integers(0, 4, flank - flank // 2).astype(np.int8)]))
+        queries.append(synth.mutate(np.concatenate(exons), rng, sub=0.04, ins=0.03, dele=0.03))
+    return queries, refs
+
+
 def shape(ctx, name, queries, refs, mat, go, ge, mode, cigar, local=True):
     qd, qo = hip.pack(queries); rd, ro = hip.pack(refs)
     cells = float(np.sum(np.diff(qo).astype(np.float64) * np.diff(ro)))
     e_ms, info = ends_ms(ctx, qd, qo, rd, ro, mat, go, ge, mode, cigar)
     if not local:
         print(json.dumps({'shape': name, 'pairs': len(queries), 'cells': cells, 'mode': mode, 'cigar': cigar,
-                          'gap2': GAP2 or None, 'ends_ms': round(e_ms, 3), 'ends_gcups': round(cells / e_ms / 1e6, 2), 'shares': info['shares']}), flush=True)
+                          'gap2': GAP2 or None, 'splice': SPLICE, 'ends_ms': round(e_ms, 3), 'ends_gcups': round(cells / e_ms / 1e6, 2), 'shares': info['shares']}), flush=True)
         return
     l_ms, classes = local_ms(ctx, qd, qo, rd, ro, mat, go, ge, cigar)
     print(json.dumps({'shape': name, 'pairs': len(queries), 'cells': cells, 'mode': mode, 'cigar': cigar,
-                      'gap2': GAP2 or None, 'ends_ms': round(e_ms, 3), 'ends_gcups': round(cells / e_ms / 1e6, 2), 'shares': info['shares'],
+                      'gap2': GAP2 or None, 'splice': SPLICE, 'ends_ms': round(e_ms, 3), 'ends_gcups': round(cells / e_ms / 1e6, 2), 'shares': info['shares'],
                       'local_ms': round(l_ms, 3), 'local_gcups': round(cells / l_ms / 1e6, 2), 'local_classes': classes,
                       'local_over_ends': round(e_ms / l_ms, 2)}), flush=True)
 
@@ -136,6 +163,13 @@ def main():
             shape(ctx, 'e: 1-kb seed-right flanks, related for 600 letters, score only', queries, refs, hip.score_matrix(*DNA[:2]), DNA[2], DNA[3], MODE, False, local=False)
         if 'f' in SHAPES:
             shape(ctx, 'f: the same with CIGARs', queries, refs, hip.score_matrix(*DNA[:2]), DNA[2], DNA[3], MODE, True, local=False)
+    if 'g' in SHAPES or 'h' in SHAPES:
+        queries, refs = spliced_pairs(np.random.Generator(np.random.PCG64(20264)))
+        if 'g' in SHAPES:
+            shape(ctx, 'g: 600-nt three-exon cDNA x 6-kb window with two introns, semiglobal, score only', queries, refs, hip.score_matrix(*DNA[:2]), DNA[2], DNA[3],
+                  'semiglobal', False, local=False)
+        if 'h' in SHAPES:
+            shape(ctx, 'h: the same with CIGARs', queries, refs, hip.score_matrix(*DNA[:2]), DNA[2], DNA[3], 'semiglobal', True, local=False)
 
 
 if __name__ == '__main__':
