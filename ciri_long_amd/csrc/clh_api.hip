@@ -2348,7 +2348,7 @@ static int64_t en_ws_bytes(int64_t m, int64_t n, int pieces)
     return (4 * pieces * m * (64 * (nch - 1) + llast) + 15) & ~(int64_t)15;
 }
 
-// the cost of the dinucleotide (x, y) as the reference reads it, from the table ssw_spliced.hip takes (clh_device.h)
+// the cost of the dinucleotide (x, y) as the reference reads it, from the table ssw_ends.hip's spliced kernels take (clh_device.h)
 static int64_t sp_site(const int32_t* site, int soff, int which, int x, int y)
 {
     return site[((x | y) > 3 || (x | y) < 0) ? clh::kSpOther : soff + which + 4 * x + y];
@@ -2476,7 +2476,7 @@ extern "C" clh_ends_plan* clh_ends_plan_create_spliced(clh_ctx* ctx, int32_t n, 
     return en_create("clh_ends_plan_create_spliced: ", ctx, n, q, q_off, r, r_off, o, nullptr, splice, strand, true);
 }
 
-// the spliced plan's shares: ssw_spliced.hip, with K1g's argument block and the site costs behind it
+// the spliced plan's shares: ssw_ends.hip's spliced kernels, with K1g's argument block and the site costs behind it
 static int sp_run_shares(clh_ends_plan* pl, const clh::EnParams& base, hipStream_t st)
 {
     clh::SpParams p;

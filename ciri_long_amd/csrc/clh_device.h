@@ -332,12 +332,12 @@ struct EnParams {
 };
 hipError_t launch_ssw_ends(const EnParams& p, bool store, int first, int count, hipStream_t stream);
 hipError_t launch_ssw_ends_walk(const EnParams& p, int first, int count, hipStream_t stream);     // after the storing form of the same pairs
-// K1g under two-piece gap costs (ssw_ends2.hip): go / ge are piece 1, go2 / ge2 piece 2; a pair's hand-over is 6 x rows rounded up to 64
+// K1g under two-piece gap costs (ssw_ends.hip, the same kernel template): go / ge are piece 1, go2 / ge2 piece 2; a pair's hand-over is 6 x rows rounded up to 64
 // and its stored decisions one byte per cell.  A struct of its own: the one-piece kernels keep their argument block.
 struct En2Params : EnParams { int32_t go2, ge2; };
 hipError_t launch_ssw_ends2(const En2Params& p, bool store, int first, int count, hipStream_t stream);
 hipError_t launch_ssw_ends2_walk(const En2Params& p, int first, int count, hipStream_t stream);
-// K1g with intron gaps (ssw_spliced.hip): io opens an intron; site[0..15] / [16..31] are the start / end costs of strand + and
+// K1g with intron gaps (ssw_ends.hip, the same kernel template): io opens an intron; site[0..15] / [16..31] are the start / end costs of strand + and
 // site[32..47] / [48..63] those of strand -, each indexed by the dinucleotide 4 x + y as the reference reads it, site[kSpOther] the
 // cost of a dinucleotide with a code >= 4 or off the reference; strand[k] < 0: pair k is on strand - (null: all +).  A pair's
 // hand-over is 6 x rows rounded up to 64 and its stored decisions one byte per cell, the two-piece figures.
@@ -374,7 +374,7 @@ struct BdParams {
 };
 hipError_t launch_ssw_band(const BdParams& p, int cls, bool store, int first, int count, hipStream_t stream);   // order[first .. first + count)
 hipError_t launch_ssw_band_walk(const BdParams& p, int first, int count, hipStream_t stream);                   // pairs [first, first + count)
-// K1gb under two-piece gap costs (ssw_band2.hip): go / ge are piece 1, go2 / ge2 piece 2; a pair's stored decisions are one byte per cell
+// K1gb under two-piece gap costs (ssw_band.hip, the same kernel template): go / ge are piece 1, go2 / ge2 piece 2; a pair's stored decisions are one byte per cell
 // of the band.  A struct of its own: the one-piece kernels keep their argument block.
 struct Bd2Params : BdParams { int32_t go2, ge2; };
 hipError_t launch_ssw_band2(const Bd2Params& p, int cls, bool store, int first, int count, hipStream_t stream);

@@ -1,7 +1,9 @@
 // ssw_pairs.h -- what K1g (ssw_ends.hip) and K1gb (ssw_band.hip) share on the device: the LDS matrix of their score kernels and the
-// one walk back over the stored decisions.  The two differ in where a cell's decisions lie, which the walk takes as a functor.
-// (The 4 decision bits of a cell and the end cell's argmax over the wave are the same text in both score kernels and stay written
-// out there: as helpers they changed the register allocation of the storing forms -- LABNOTES.md has the tables.)
+// walks back over the stored decisions, one per gap model: pr_walk (one piece), pr_walk2 (two pieces, both kernels), pr_walk_spliced
+// (intron gaps, K1g alone).  The two kernels differ in where a cell's decisions lie, which a walk takes as a functor.
+// (Each of the two score kernels is one template body for all its gap models.  The decision bits of a cell and the end cell's argmax
+// over the wave are the same text in both and stay written out there: as helpers they changed the register allocation of the storing
+// forms -- LABNOTES.md 16 and 20 have the tables.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -63,7 +65,7 @@ __device__ __forceinline__ void pr_walk(int32_t* row, int mode, int m, int n, ui
     row[1] = j; row[3] = i; row[5] = nops;
 }
 
-// pr_walk for two-piece gap costs (ssw_ends2.hip).  cell(i, j) gives the byte of cell (i, j) -- bits 0..2 H's source (0 diagonal, 1 E_1,
+// pr_walk for two-piece gap costs (ssw_ends.hip, ssw_band.hip).  cell(i, j) gives the byte of cell (i, j) -- bits 0..2 H's source (0 diagonal, 1 E_1,
 // 2 E_2, 3 F_1, 4 F_2: that order is the tie rule), bits 3..6 "opened here" of E_1, E_2, F_1, F_2 -- or -1 outside what was stored.  Both
 // pieces of a direction emit the same op; a gap state is left as soon as its own piece's "opened here" is set.  Steps, bounds and
 // EN_ST_NO_WALK as in pr_walk.
@@ -105,7 +107,7 @@ __device__ __forceinline__ void pr_walk2(int32_t* row, int mode, int m, int n, u
     row[1] = j; row[3] = i; row[5] = nops;
 }
 
-// pr_walk for spliced alignment (ssw_spliced.hip).  cell(i, j) gives the byte of cell (i, j) -- bits 0..1 H's source (0 diagonal, 1 E, 2 N,
+// pr_walk for spliced alignment (ssw_ends.hip).  cell(i, j) gives the byte of cell (i, j) -- bits 0..1 H's source (0 diagonal, 1 E, 2 N,
 // 3 F: that order is the tie rule), bit 2 T's source (0 diagonal, 1 F), bits 3..5 "opened here" of E, N, F -- or -1 outside what was
 // stored.  E emits D (2), N emits N (3); on leaving either the walk is in state T (4), H without a reference gap: the diagonal if T
 // equals it, else F, never E or N again, so that no D stands next to an N.  row0_op(j) names the op of the one run of j letters the

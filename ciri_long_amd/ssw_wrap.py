@@ -437,7 +437,7 @@ def align_pairs_spliced(ref_seqs, query_seqs, mode='semiglobal', strand='+', mat
     as donor and AG as acceptor cost 0; every other dinucleotide, and one that holds an N or runs off the window, costs `noncanonical`;
     donor_costs / acceptor_costs override single dinucleotides as read on the transcript strand, e.g. donor_costs={'GC': 2}.  The costs
     depend on the position alone.  A deletion and an intron are never adjacent; insertions are as in ``align_pairs_ends``, as are the
-    modes, end cells, coordinates and ties (csrc/ssw_spliced.hip; tests/spliced_check.py is the definition).
+    modes, end cells, coordinates and ties (csrc/ssw_ends.hip; tests/spliced_check.py is the definition).
 
     strand is '+', '-', a sequence of them (one per pair), or 'both': every pair is then aligned on both strands in the same call and
     the higher score is kept, ties to '+'.  ``cigar_string`` (report_cigar) uses M / I / D / N with soft clips as ``align_pairs_ends``

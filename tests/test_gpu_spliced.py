@@ -1,4 +1,4 @@
-"""Spliced pair alignment on the GPU: K1g with intron gaps (csrc/ssw_spliced.hip), all five modes.  Every expected value is
+"""Spliced pair alignment on the GPU: K1g with intron gaps (csrc/ssw_ends.hip), all five modes.  Every expected value is
 tests/spliced_check.py (`align`), field by field with CIGARs, through the storing route and the score-only route, and every CIGAR is
 rescored on its own; with an intron too dear to win the rows are also held to align_pairs_ends of the same device."""
 import ctypes as C

@@ -1,4 +1,4 @@
-"""Two-piece affine gap costs on the GPU: K1g (csrc/ssw_ends2.hip), all five modes over the full matrix, and K1gb (csrc/ssw_band2.hip),
+"""Two-piece affine gap costs on the GPU: K1g (csrc/ssw_ends.hip), all five modes over the full matrix, and K1gb (csrc/ssw_band.hip),
 four modes over a band.  Every expected value is tests/twopiece_check.py, field by field with CIGARs, through the storing route and
 the score-only route; rows a band certifies are also held to the two-piece K1g rows of the same device."""
 import numpy as np
@@ -264,7 +264,7 @@ def test_extend_anchors_with_the_long_read_preset_equals_the_checker_s_two_halve
     assert long_runs >= 3                # the planted events are kept as single long gaps, which piece 1 alone would not pay for
 
 
-# ---- over a band (K1gb, csrc/ssw_band2.hip) ------------------------------------------------------------------------------------------
+# ---- over a band (K1gb, csrc/ssw_band.hip) -------------------------------------------------------------------------------------------
 BAND_MODES = chk.BAND_MODES
 
 

@@ -11,7 +11,7 @@ H2D in the timed run), HIP events, the median of R runs after a warm-up.  Standa
   (f) the same with CIGARs
   (g) 2 000 spliced pairs -- the query a 600-nt cDNA of three exons mutated at 10 %, the reference a 6-kb window that holds the exons
       around two GT..AG introns of about 2.5 kb -- semiglobal, score only; K1g alone, no local run.  With --splice IO,NC the plan is the
-      spliced one (csrc/ssw_spliced.hip); without it the same pairs run under one piece or, with --gap2, under two: the yardstick
+      spliced one (csrc/ssw_ends.hip); without it the same pairs run under one piece or, with --gap2, under two: the yardstick
   (h) the same with CIGARs
 
 Prints one JSON line per shape: ms and cells/s (sum of m n over the pairs) of both, and the ratio local / ends of the cell rates.

@@ -1,4 +1,4 @@
-"""K1g with intron gaps (csrc/ssw_spliced.hip) in Python, for any geometry: the scheme of the kernel, not the definition (that is
+"""K1g with intron gaps (csrc/ssw_ends.hip) in Python, for any geometry: the scheme of the kernel, not the definition (that is
 tests/spliced_check.py).  Geometry, modes and end cells are those of tools/ends_model.py; costs = (go, ge, io, donor, acceptor, other)
 as spliced_check.make_costs builds them, strand is +1 or -1.  With don(j) = start(j - 1) and acc(j) = end(j - 1) for the 1-based column
 j, per row step and lane:

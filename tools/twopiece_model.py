@@ -1,4 +1,4 @@
-"""K1g and K1gb under two-piece gap costs (csrc/ssw_ends2.hip: `run`; csrc/ssw_band2.hip: `run_band`, in the second half of this file) in
+"""K1g and K1gb under two-piece gap costs (csrc/ssw_ends.hip: `run`; csrc/ssw_band.hip: `run_band`, in the second half of this file) in
 Python, for any geometry: the schemes of the kernels, not the definition (that is tests/twopiece_check.py).  K1g's geometry, modes
 and end cells are those of tools/ends_model.py; costs = (go1, ge1, go2, ge2).  Per row step and lane:
 
@@ -205,7 +205,7 @@ def walk(cells, mode, end):
     return i, j, [(o, k) for o, k in reversed(ops)]
 
 
-# ---- the band (csrc/ssw_band2.hip) ------------------------------------------------------------------------------------------------
+# ---- the band (csrc/ssw_band.hip) -------------------------------------------------------------------------------------------------
 # K1gb's scheme (tools/band_model.py: the frame b = d - lo, F from position b + 1 of the row before, minus infinity as the int32
 # NEG = -2^30, the sliding letters) with two pieces.  Per row step and lane:
 #     F_p[k] = max(Hprev[k+1] - go_p, F_pprev[k+1] - ge_p)            T[k] = max(Hprev[k] + s, F_1[k], F_2[k])
