@@ -2327,6 +2327,18 @@ static int pairs_fetch(const std::string& kind, Plan* pl, Row* rows, uint32_t* c
     return 0;
 }
 
+// a one-shot batch of either kind over the plan its create call returned (null: it has failed): run, fetch, delete
+template <typename Plan, typename Row>
+static int pairs_batch(Plan* pl, int (*run)(Plan*, void*), int (*fetch)(Plan*, Row*, uint32_t*, int64_t, int64_t*), Row* rows, uint32_t* cigar,
+                       int64_t cigar_cap, int64_t* cigar_used)
+{
+    if (!pl) return g_code;
+    int rc = run(pl, nullptr);
+    if (!rc) rc = fetch(pl, rows, cigar, cigar_cap, cigar_used);
+    delete pl;
+    return rc;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // K1g: end-anchored affine-gap alignment of pairs -- global, semiglobal, overlap, prefix, extend (ssw_ends.hip)
 // ---------------------------------------------------------------------------------------------------------------
@@ -2476,19 +2488,6 @@ extern "C" clh_ends_plan* clh_ends_plan_create_spliced(clh_ctx* ctx, int32_t n, 
     return en_create("clh_ends_plan_create_spliced: ", ctx, n, q, q_off, r, r_off, o, nullptr, splice, strand, true);
 }
 
-// the spliced plan's shares: ssw_ends.hip's spliced kernels, with K1g's argument block and the site costs behind it
-static int sp_run_shares(clh_ends_plan* pl, const clh::EnParams& base, hipStream_t st)
-{
-    clh::SpParams p;
-    static_cast<clh::EnParams&>(p) = base;
-    p.io = pl->io; p.site = (const int32_t*)pl->d_site; p.strand = (const int8_t*)pl->d_strand;
-    for (const auto& sh : pl->shares) {
-        HIPCHK(clh::launch_ssw_spliced(p, pl->want_cigar, sh.first, sh.second, st));
-        if (pl->want_cigar) HIPCHK(clh::launch_ssw_spliced_walk(p, sh.first, sh.second, st));
-    }
-    return 0;
-}
-
 extern "C" int clh_ends_plan_run(clh_ends_plan* pl, void* stream_)
 {
     if (!pl) return fail(CLH_E_ARG, "clh_ends_plan_run: null argument");
@@ -2504,20 +2503,24 @@ extern "C" int clh_ends_plan_run(clh_ends_plan* pl, void* stream_)
     p.ws = (uint8_t*)pl->d_ws; p.ws_cap = pl->ws_bytes;
     p.rows = (int32_t*)pl->d_rows;
     p.cigar = (uint32_t*)pl->d_cig; p.cigar_cap = pl->cig_cap;
-    if (pl->spliced) {
-        if (int rc = sp_run_shares(pl, p, st)) return rc;
-        return pl->end_run();
-    }
-    for (const auto& sh : pl->shares) {        // in stream order: a share's walk has read the workspace before the next share fills it
-        if (pl->pieces == 2) {
-            HIPCHK(clh::launch_ssw_ends2(p, pl->want_cigar, sh.first, sh.second, st));
-            if (pl->want_cigar) HIPCHK(clh::launch_ssw_ends2_walk(p, sh.first, sh.second, st));
-            continue;
+    // in stream order: a share's walk has read the workspace before the next share fills it
+    auto run_shares = [&](const auto& prm, auto launch, auto launch_walk) -> int {
+        for (const auto& sh : pl->shares) {
+            HIPCHK(launch(prm, pl->want_cigar, sh.first, sh.second, st));
+            if (pl->want_cigar) HIPCHK(launch_walk(prm, sh.first, sh.second, st));
         }
-        HIPCHK(clh::launch_ssw_ends(p, pl->want_cigar, sh.first, sh.second, st));
-        if (pl->want_cigar) HIPCHK(clh::launch_ssw_ends_walk(p, sh.first, sh.second, st));
+        return 0;
+    };
+    int rc;
+    if (pl->spliced) {      // K1g's argument block with the site costs behind it
+        clh::SpParams sp;
+        static_cast<clh::EnParams&>(sp) = p;
+        sp.io = pl->io; sp.site = (const int32_t*)pl->d_site; sp.strand = (const int8_t*)pl->d_strand;
+        rc = run_shares(sp, clh::launch_ssw_spliced, clh::launch_ssw_spliced_walk);
     }
-    return pl->end_run();
+    else if (pl->pieces == 2) rc = run_shares(p, clh::launch_ssw_ends2, clh::launch_ssw_ends2_walk);
+    else rc = run_shares(p, clh::launch_ssw_ends, clh::launch_ssw_ends_walk);      // the one-piece launchers take the block's base
+    return rc ? rc : pl->end_run();
 }
 
 extern "C" int clh_ends_plan_fetch(clh_ends_plan* pl, clh_ends_row* rows, uint32_t* cigar, int64_t cigar_cap, int64_t* cigar_used)
@@ -2542,34 +2545,19 @@ extern "C" int clh_ends_plan_info(clh_ends_plan* pl, int64_t* out)
 extern "C" int clh_ends_batch(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off, const clh_ends_opts* opts,
                               clh_ends_row* rows, uint32_t* cigar, int64_t cigar_cap, int64_t* cigar_used)
 {
-    clh_ends_plan* pl = clh_ends_plan_create(ctx, n, q, q_off, r, r_off, opts);
-    if (!pl) return g_code;
-    int rc = clh_ends_plan_run(pl, nullptr);
-    if (!rc) rc = clh_ends_plan_fetch(pl, rows, cigar, cigar_cap, cigar_used);
-    delete pl;
-    return rc;
+    return pairs_batch(clh_ends_plan_create(ctx, n, q, q_off, r, r_off, opts), clh_ends_plan_run, clh_ends_plan_fetch, rows, cigar, cigar_cap, cigar_used);
 }
 
 extern "C" int clh_ends_batch_gap2(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off, const clh_ends_opts* opts,
                                    const clh_gap2* gap2, clh_ends_row* rows, uint32_t* cigar, int64_t cigar_cap, int64_t* cigar_used)
 {
-    clh_ends_plan* pl = clh_ends_plan_create_gap2(ctx, n, q, q_off, r, r_off, opts, gap2);
-    if (!pl) return g_code;
-    int rc = clh_ends_plan_run(pl, nullptr);
-    if (!rc) rc = clh_ends_plan_fetch(pl, rows, cigar, cigar_cap, cigar_used);
-    delete pl;
-    return rc;
+    return pairs_batch(clh_ends_plan_create_gap2(ctx, n, q, q_off, r, r_off, opts, gap2), clh_ends_plan_run, clh_ends_plan_fetch, rows, cigar, cigar_cap, cigar_used);
 }
 
 extern "C" int clh_ends_batch_spliced(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off, const clh_ends_opts* opts,
                                      const clh_splice* splice, const int8_t* strand, clh_ends_row* rows, uint32_t* cigar, int64_t cigar_cap, int64_t* cigar_used)
 {
-    clh_ends_plan* pl = clh_ends_plan_create_spliced(ctx, n, q, q_off, r, r_off, opts, splice, strand);
-    if (!pl) return g_code;
-    int rc = clh_ends_plan_run(pl, nullptr);
-    if (!rc) rc = clh_ends_plan_fetch(pl, rows, cigar, cigar_cap, cigar_used);
-    delete pl;
-    return rc;
+    return pairs_batch(clh_ends_plan_create_spliced(ctx, n, q, q_off, r, r_off, opts, splice, strand), clh_ends_plan_run, clh_ends_plan_fetch, rows, cigar, cigar_cap, cigar_used);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -2714,18 +2702,19 @@ extern "C" int clh_band_plan_run(clh_band_plan* pl, void* stream_)
     p.ws = (uint8_t*)pl->d_ws; p.ws_cap = pl->ws_bytes;
     p.rows = (int32_t*)pl->d_rows;
     p.cigar = (uint32_t*)pl->d_cig; p.cigar_cap = pl->cig_cap;
-    for (size_t s = 0; s < pl->shares.size(); ++s) {        // in stream order: a share's walk has read the workspace before the next share fills it
-        const auto& sh = pl->shares[s];
-        const auto& cl = pl->share_classes[s];
-        if (pl->pieces == 2) {
-            for (int c = 0; c < clh::kBdClasses; ++c) HIPCHK(clh::launch_ssw_band2(p, c, pl->want_cigar, cl.cfirst[c], cl.ccount[c], st));
-            if (pl->want_cigar) HIPCHK(clh::launch_ssw_band2_walk(p, sh.first, sh.second, st));
-            continue;
+    // in stream order: a share's walk has read the workspace before the next share fills it
+    auto run_shares = [&](auto launch, auto launch_walk) -> int {
+        for (size_t s = 0; s < pl->shares.size(); ++s) {
+            const auto& sh = pl->shares[s];
+            const auto& cl = pl->share_classes[s];
+            for (int c = 0; c < clh::kBdClasses; ++c) HIPCHK(launch(p, c, pl->want_cigar, cl.cfirst[c], cl.ccount[c], st));
+            if (pl->want_cigar) HIPCHK(launch_walk(p, sh.first, sh.second, st));
         }
-        for (int c = 0; c < clh::kBdClasses; ++c) HIPCHK(clh::launch_ssw_band(p, c, pl->want_cigar, cl.cfirst[c], cl.ccount[c], st));
-        if (pl->want_cigar) HIPCHK(clh::launch_ssw_band_walk(p, sh.first, sh.second, st));
-    }
-    return pl->end_run();
+        return 0;
+    };
+    const int rc = pl->pieces == 2 ? run_shares(clh::launch_ssw_band2, clh::launch_ssw_band2_walk)
+                                   : run_shares(clh::launch_ssw_band, clh::launch_ssw_band_walk);      // the one-piece launchers take the block's base
+    return rc ? rc : pl->end_run();
 }
 
 // 1: the unbanded programme provably returns the same row and CIGAR (the argument is in the header and in DESIGN.md section 6).
@@ -2779,23 +2768,13 @@ extern "C" int clh_band_plan_info(clh_band_plan* pl, int64_t* out)
 extern "C" int clh_band_batch(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off, const int32_t* diag,
                               const clh_band_opts* opts, clh_band_row* rows, uint32_t* cigar, int64_t cigar_cap, int64_t* cigar_used)
 {
-    clh_band_plan* pl = clh_band_plan_create(ctx, n, q, q_off, r, r_off, diag, opts);
-    if (!pl) return g_code;
-    int rc = clh_band_plan_run(pl, nullptr);
-    if (!rc) rc = clh_band_plan_fetch(pl, rows, cigar, cigar_cap, cigar_used);
-    delete pl;
-    return rc;
+    return pairs_batch(clh_band_plan_create(ctx, n, q, q_off, r, r_off, diag, opts), clh_band_plan_run, clh_band_plan_fetch, rows, cigar, cigar_cap, cigar_used);
 }
 
 extern "C" int clh_band_batch_gap2(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off, const int32_t* diag,
                                    const clh_band_opts* opts, const clh_gap2* gap2, clh_band_row* rows, uint32_t* cigar, int64_t cigar_cap, int64_t* cigar_used)
 {
-    clh_band_plan* pl = clh_band_plan_create_gap2(ctx, n, q, q_off, r, r_off, diag, opts, gap2);
-    if (!pl) return g_code;
-    int rc = clh_band_plan_run(pl, nullptr);
-    if (!rc) rc = clh_band_plan_fetch(pl, rows, cigar, cigar_cap, cigar_used);
-    delete pl;
-    return rc;
+    return pairs_batch(clh_band_plan_create_gap2(ctx, n, q, q_off, r, r_off, diag, opts, gap2), clh_band_plan_run, clh_band_plan_fetch, rows, cigar, cigar_cap, cigar_used);
 }
 
 extern "C" void clh_encode_dna(const char* seq, int64_t len, int8_t* out)

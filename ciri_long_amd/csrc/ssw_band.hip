@@ -26,9 +26,9 @@
 // and a lane's columns ascend within a row), seeded with (0, (0, 0)), which cells of column 0 (<= 0) and positions that are no cell
 // (minus infinity) never beat, and the lanes are reduced once by the key after the last row.
 // STORE: 4 bits per cell as in K1g (H's source 0 diagonal / 1 E / 2 F, "E opened here", "F opened here"), CPL / 2 bytes per lane and
-// row, only the lanes that own a band position: m ceil(B / CPL) CPL / 2 bytes per pair.  ssw_band_walk_kernel walks them back, one
-// lane per pair: a diagonal step keeps b, a D step goes to b - 1, an I step to b + 1.  The walk itself is K1g's, pr_walk in
-// ssw_pairs.h; the kernel here says where the half-byte of a cell lies.
+// row, only the lanes that own a band position: m ceil(B / CPL) CPL / 2 bytes per pair.  ssw_band_walk_kernel<Prm> walks them back, one
+// lane per pair: a diagonal step keeps b, a D step goes to b - 1, an I step to b + 1.  The walk itself is K1g's, pr_walk<MODEL> in
+// ssw_pairs.h, and BdCells there says where the half-byte or byte of a cell lies.
 // tools/band_model.py is this scheme in Python for any geometry; tests/band_check.py is the definition.
 //
 // Two pieces (Bd2Params): a gap of k letters costs min(go + (k - 1) ge, go2 + (k - 1) ge2); go / ge / E / F are piece 1 and go2 / ge2
@@ -45,7 +45,7 @@
 // reads (the argument is in ssw_ends.hip; a band only removes cells).  The host's bound takes the maximum over all four costs.
 // STORE: one byte per cell -- bits 0..2 H's source (0 diagonal, 1 E_1, 2 E_2, 3 F_1, 4 F_2; that order is the tie rule), bits 3..6
 // "opened here" of E_1, E_2, F_1, F_2 -- CPL bytes per lane and row, only the lanes that own a band position: m ceil(B / CPL) CPL bytes
-// per pair.  ssw_band2_walk_kernel walks them back with pr_walk2 (ssw_pairs.h).  tests/twopiece_check.py is the definition.
+// per pair.  tests/twopiece_check.py is the definition.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "clh_device.h"
@@ -249,8 +249,9 @@ __global__ void __launch_bounds__(64) ssw_band_kernel(const Prm prm, int first, 
     }
 }
 
-// one lane per pair: pr_walk over the half-bytes the storing form left, row after row, in the band's frame
-__global__ void ssw_band_walk_kernel(const BdParams prm, int first, int count)
+// one lane per pair: pr_walk over the half-bytes or bytes the storing form left, where BdCells says they lie
+template <typename Prm>
+__global__ void ssw_band_walk_kernel(const Prm prm, int first, int count)
 {
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
     if (x >= count || first + x >= prm.npairs) return;
@@ -264,43 +265,10 @@ __global__ void ssw_band_walk_kernel(const BdParams prm, int first, int count)
     if (pr.cls < 0 || pr.cls >= kBdClasses) { row[7] = EN_ST_NO_WALK; return; }
     const int cpl = 2 << pr.cls;
     if (B < 1 || B > 64 * cpl) { row[7] = EN_ST_NO_WALK; return; }
-    const int64_t rowbytes = (int64_t)((B + cpl - 1) / cpl) * (cpl / 2);
-    const int64_t nbytes = (int64_t)m * rowbytes;
-    if (pr.ws_off < 0 || pr.ws_off + nbytes > prm.ws_cap || pr.cig_off < 0 || pr.cig_off + pr.cig_cap > prm.cigar_cap) { row[7] = EN_ST_NO_WALK; return; }
-    const uint8_t* ws = prm.ws + pr.ws_off;
-    pr_walk(row, prm.mode, m, n, prm.cigar + pr.cig_off, pr.cig_cap, [&](int i, int j) -> int {
-        const int b = j - i - pr.lo;
-        const int64_t bi = (int64_t)(i - 1) * rowbytes + (b >> 1);
-        if (b < 0 || b >= B || i < 1 || bi < 0 || bi >= nbytes) return -1;
-        return (int)(((uint32_t)ws[bi] >> (4 * (b & 1))) & 15u);
-    });
-}
-
-// one lane per pair: pr_walk2 over the bytes the storing form left, row after row, in the band's frame
-__global__ void ssw_band2_walk_kernel(const Bd2Params prm, int first, int count)
-{
-    const int x = blockIdx.x * blockDim.x + threadIdx.x;
-    if (x >= count || first + x >= prm.npairs) return;
-    const BdPair pr = prm.pairs[first + x];
-    const int m = pr.m, n = pr.n;
-    if (m <= 0 || n <= 0) return;
-    int32_t* row = prm.rows + (size_t)(first + x) * 8;
-    if (row[7] != 0) return;                                     // unwritten, or without stored decisions: fetch reports it
-    const int B = pr.hi - pr.lo + 1;
-    static_assert(kBdCpl[0] == 2 && kBdCpl[1] == 4 && kBdCpl[2] == 8, "the class index is log2(CPL) - 1");
-    if (pr.cls < 0 || pr.cls >= kBdClasses) { row[7] = EN_ST_NO_WALK; return; }
-    const int cpl = 2 << pr.cls;
-    if (B < 1 || B > 64 * cpl) { row[7] = EN_ST_NO_WALK; return; }
-    const int64_t rowbytes = (int64_t)((B + cpl - 1) / cpl) * cpl;
-    const int64_t nbytes = (int64_t)m * rowbytes;
-    if (pr.ws_off < 0 || pr.ws_off + nbytes > prm.ws_cap || pr.cig_off < 0 || pr.cig_off + pr.cig_cap > prm.cigar_cap) { row[7] = EN_ST_NO_WALK; return; }
-    const uint8_t* ws = prm.ws + pr.ws_off;
-    pr_walk2(row, prm.mode, m, n, prm.cigar + pr.cig_off, pr.cig_cap, [&](int i, int j) -> int {
-        const int b = j - i - pr.lo;
-        const int64_t bi = (int64_t)(i - 1) * rowbytes + b;
-        if (b < 0 || b >= B || i < 1 || bi < 0 || bi >= nbytes) return -1;
-        return (int)ws[bi];
-    });
+    BdCells<BdModel<Prm>::bits> cells(m, pr.lo, B, cpl);
+    if (pr.ws_off < 0 || pr.ws_off + cells.bytes() > prm.ws_cap || pr.cig_off < 0 || pr.cig_off + pr.cig_cap > prm.cigar_cap) { row[7] = EN_ST_NO_WALK; return; }
+    cells.ws = prm.ws + pr.ws_off;
+    pr_walk<BdModel<Prm>::two ? EN_TWO_PIECE : EN_ONE_PIECE>(row, prm.mode, m, n, prm.cigar + pr.cig_off, pr.cig_cap, cells);
 }
 
 template <typename Prm, int CPL, int MODE>
@@ -331,17 +299,17 @@ static hipError_t bd_launch(const Prm& p, int cls, bool store, int first, int co
     return hipGetLastError();
 }
 
-template <typename Prm, typename Kernel>
-static hipError_t bd_launch_walk(Kernel kernel, const Prm& p, int first, int count, hipStream_t stream)
+template <typename Prm>
+static hipError_t bd_launch_walk(const Prm& p, int first, int count, hipStream_t stream)
 {
     if (count <= 0) return hipSuccess;
-    hipLaunchKernelGGL(kernel, dim3((count + 63) / 64), dim3(64), 0, stream, p, first, count);
+    hipLaunchKernelGGL(ssw_band_walk_kernel<Prm>, dim3((count + 63) / 64), dim3(64), 0, stream, p, first, count);
     return hipGetLastError();
 }
 
 hipError_t launch_ssw_band(const BdParams& p, int cls, bool store, int first, int count, hipStream_t stream) { return bd_launch(p, cls, store, first, count, stream); }
 hipError_t launch_ssw_band2(const Bd2Params& p, int cls, bool store, int first, int count, hipStream_t stream) { return bd_launch(p, cls, store, first, count, stream); }
-hipError_t launch_ssw_band_walk(const BdParams& p, int first, int count, hipStream_t stream) { return bd_launch_walk(ssw_band_walk_kernel, p, first, count, stream); }
-hipError_t launch_ssw_band2_walk(const Bd2Params& p, int first, int count, hipStream_t stream) { return bd_launch_walk(ssw_band2_walk_kernel, p, first, count, stream); }
+hipError_t launch_ssw_band_walk(const BdParams& p, int first, int count, hipStream_t stream) { return bd_launch_walk(p, first, count, stream); }
+hipError_t launch_ssw_band2_walk(const Bd2Params& p, int first, int count, hipStream_t stream) { return bd_launch_walk(p, first, count, stream); }
 
 }  // namespace clh

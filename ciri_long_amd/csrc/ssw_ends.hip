@@ -15,8 +15,8 @@
 // of its own cells of a chunk under a bare > (rows ascend, columns ascend within a row: the first is the smallest key), joins it
 // to the best it carries over the chunks by the key (a later chunk's columns are larger, its rows may be smaller), and the lanes
 // are reduced once, after the last chunk.  Boundary cells but (0, 0) are <= 0 and lose every tie to (0, 0), the seed of every lane.
-// STORE: each cell also leaves its decisions, one word per lane and row, and the model's walk kernel walks them back, one lane per
-// pair (as K4t does): the walks themselves are in ssw_pairs.h, shared with K1gb, and the kernels here say where the word of a cell lies.
+// STORE: each cell also leaves its decisions, one word per lane and row, and ssw_ends_walk_kernel<Prm> walks them back, one lane per
+// pair (as K4t does): the walk (pr_walk<MODEL>) and where the word of a cell lies (EnCells) are in ssw_pairs.h, the walk shared with K1gb.
 // The gap model is a constant derived from the parameter block, and ssw_ends_kernel is one body for the three: the frame above is
 // written once, and what a model has of its own (boundary values, the per-chunk set-up, the incoming column, the row step, the
 // decision word, what is handed on) stands under `if constexpr`, so that an instantiation holds its model's statements and no other.
@@ -31,7 +31,7 @@
 //     E[k] = u - p ge,  H[k] = max(T[k], E[k]),  u = max(u, T[k] - go + (p + 1) ge)
 // -- E[j] = max(E[j-1] - ge, H[j-1] - go) as a max-plus scan in the frame E[p] + p ge, exact because go >= ge lets T stand for H.
 // A chunk hands H and E of its last column on.  STORE: 4 bits per cell -- H's source (0 diagonal, 1 E, 2 F; that order is the tie
-// rule), "E opened here", "F opened here" -- one 32-bit word per lane and row; ssw_ends_walk_kernel walks them back with pr_walk.
+// rule), "E opened here", "F opened here" -- one 32-bit word per lane and row.
 // tools/ends_model.py is this scheme in Python for any geometry; tests/ends_check.py is the definition.
 //
 // Two pieces (En2Params): a gap of k letters costs min(go + (k - 1) ge, go2 + (k - 1) ge2); go / ge / E / F are piece 1 below and
@@ -52,7 +52,7 @@
 // F_p reads the true H of the row above.  A chunk hands H, E_1 and E_2 of its last column on: three values per row.
 // STORE: one byte per cell -- bits 0..2 H's source (0 diagonal, 1 E_1, 2 E_2, 3 F_1, 4 F_2; that order is the tie rule), bit 3
 // "E_1 opened here", bit 4 "E_2 opened here", bit 5 "F_1 opened here", bit 6 "F_2 opened here" -- 8 bytes per lane and row, one
-// 8-byte store; ssw_ends2_walk_kernel walks them back with pr_walk2.  tests/twopiece_check.py is the definition.
+// 8-byte store; the walk loads them a byte at a time.  tests/twopiece_check.py is the definition.
 //
 // Intron gaps (SpParams): a maximal run of skipped reference letters r[a..b] costs min(go + (b - a) ge, io + start(a) + end(b)), the
 // splice-site costs start / end read from the dinucleotides at the run's two ends on the pair's strand.  With don(j) = start(j - 1)
@@ -73,7 +73,7 @@
 // column 0 enter as one opening below T, which gives the same first E and N; the host's bound takes io + dmax + amax among the costs.
 // STORE: one byte per cell -- bits 0..1 H's source (0 diagonal, 1 E, 2 N, 3 F; that order is the tie rule), bit 2 T's source (0
 // diagonal, 1 F), bit 3 "E opened here", bit 4 "N opened here", bit 5 "F opened here" -- 8 bytes per lane and row, one 8-byte store;
-// ssw_spliced_walk_kernel walks them back with pr_walk_spliced.  tools/spliced_model.py is this scheme in Python.
+// the walk holds the 8 bytes it loaded last and takes an E or N run up to 8 cells a step out of them.  tools/spliced_model.py is this scheme in Python.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "clh_device.h"
@@ -84,12 +84,12 @@ namespace clh {
 
 static_assert(kEnCpl == 8, "a lane's row of decisions is one 32-bit word (8 columns x 4 bits) or two (8 columns x 1 byte)");
 
-// the gap model of a parameter block: NH values per row are handed from chunk to chunk, a lane's row of decisions is one word_t
-enum { EN_ONE_PIECE, EN_TWO_PIECE, EN_SPLICED };
+// the gap model of a parameter block: NH values per row are handed from chunk to chunk, a lane's row of decisions is one word_t, and
+// the walk loads a cell_t at a time (EnCells in ssw_pairs.h)
 template <typename Prm> struct EnModel;
-template <> struct EnModel<EnParams> { static constexpr int model = EN_ONE_PIECE, NH = 2; typedef uint32_t word_t; };
-template <> struct EnModel<En2Params> { static constexpr int model = EN_TWO_PIECE, NH = 3; typedef uint2 word_t; };
-template <> struct EnModel<SpParams> { static constexpr int model = EN_SPLICED, NH = 3; typedef uint2 word_t; };
+template <> struct EnModel<EnParams> { static constexpr int model = EN_ONE_PIECE, NH = 2; typedef uint32_t word_t; typedef uint32_t cell_t; };
+template <> struct EnModel<En2Params> { static constexpr int model = EN_TWO_PIECE, NH = 3; typedef uint2 word_t; typedef uint8_t cell_t; };
+template <> struct EnModel<SpParams> { static constexpr int model = EN_SPLICED, NH = 3; typedef uint2 word_t; typedef uint2 cell_t; };
 
 // H[0][j]: 0 on a free row, one gap of j letters in the global mode (unsigned arithmetic: lanes past column n hold garbage, not UB)
 template <int MODE>
@@ -469,9 +469,13 @@ __global__ void __launch_bounds__(64) ssw_ends_kernel(const Prm prm, int first, 
     }
 }
 
-// one lane per pair: pr_walk over the words the storing form left, chunk after chunk, per chunk row after row, a word per lane
-__global__ void ssw_ends_walk_kernel(const EnParams prm, int first, int count)
+// one lane per pair: pr_walk over what the storing form left, where EnCells says it lies.  Spliced reads a lane's 8 bytes of a row at
+// a time: an intron is thousands of steps along one row, and each of its words is loaded once.
+template <typename Prm>
+__global__ void ssw_ends_walk_kernel(const Prm prm, int first, int count)
 {
+    constexpr int model = EnModel<Prm>::model;
+    typedef typename EnModel<Prm>::cell_t cell_t;
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
     if (x >= count || first + x >= prm.npairs) return;
     const EnPair pr = prm.pairs[first + x];
@@ -479,90 +483,22 @@ __global__ void ssw_ends_walk_kernel(const EnParams prm, int first, int count)
     if (m <= 0 || n <= 0) return;
     int32_t* row = prm.rows + (size_t)(first + x) * 8;
     if (row[7] != 0) return;                                     // unwritten, or without stored decisions: fetch reports it
-    const int nchunks = (n + kEnChunk - 1) / kEnChunk;
-    const int llast = (n - (nchunks - 1) * kEnChunk + kEnCpl - 1) / kEnCpl;
-    const int64_t nwords = (int64_t)m * ((int64_t)64 * (nchunks - 1) + llast);
-    if (pr.ws_off < 0 || pr.ws_off + 4 * nwords > prm.ws_cap || pr.cig_off < 0 || pr.cig_off + pr.cig_cap > prm.cigar_cap) { row[7] = EN_ST_NO_WALK; return; }
-    const uint32_t* ws = (const uint32_t*)(prm.ws + pr.ws_off);
-    pr_walk(row, prm.mode, m, n, prm.cigar + pr.cig_off, pr.cig_cap, [&](int i, int j) -> int {
-        const int ch = (j - 1) / kEnChunk, p = (j - 1) % kEnChunk;
-        const int L = ch == nchunks - 1 ? llast : 64;
-        const int64_t wi = (int64_t)ch * m * 64 + (int64_t)(i - 1) * L + p / kEnCpl;
-        if (wi < 0 || wi >= nwords) return -1;
-        return (int)((ws[wi] >> (4 * (p % kEnCpl))) & 15u);
-    });
-}
-
-// one lane per pair: pr_walk2 over the bytes the storing form left, chunk after chunk, per chunk row after row, 8 bytes per lane
-__global__ void ssw_ends2_walk_kernel(const En2Params prm, int first, int count)
-{
-    const int x = blockIdx.x * blockDim.x + threadIdx.x;
-    if (x >= count || first + x >= prm.npairs) return;
-    const EnPair pr = prm.pairs[first + x];
-    const int m = pr.m, n = pr.n;
-    if (m <= 0 || n <= 0) return;
-    int32_t* row = prm.rows + (size_t)(first + x) * 8;
-    if (row[7] != 0) return;                                     // unwritten, or without stored decisions: fetch reports it
-    const int nchunks = (n + kEnChunk - 1) / kEnChunk;
-    const int llast = (n - (nchunks - 1) * kEnChunk + kEnCpl - 1) / kEnCpl;
-    const int64_t nbytes = (int64_t)8 * m * ((int64_t)64 * (nchunks - 1) + llast);
-    if (pr.ws_off < 0 || pr.ws_off + nbytes > prm.ws_cap || pr.cig_off < 0 || pr.cig_off + pr.cig_cap > prm.cigar_cap) { row[7] = EN_ST_NO_WALK; return; }
-    const uint8_t* ws = prm.ws + pr.ws_off;
-    pr_walk2(row, prm.mode, m, n, prm.cigar + pr.cig_off, pr.cig_cap, [&](int i, int j) -> int {
-        const int ch = (j - 1) / kEnChunk, p = (j - 1) % kEnChunk;
-        const int L = ch == nchunks - 1 ? llast : 64;
-        const int64_t bi = ((int64_t)ch * m * 64 + (int64_t)(i - 1) * L) * kEnCpl + p;
-        if (bi < 0 || bi >= nbytes) return -1;
-        return (int)ws[bi];
-    });
-}
-
-// one lane per pair: pr_walk_spliced over the bytes the storing form left, chunk after chunk, per chunk row after row, 8 bytes per lane,
-// read 8 at a time: an intron is thousands of steps along one row, and each of its words is loaded once
-__global__ void ssw_spliced_walk_kernel(const SpParams prm, int first, int count)
-{
-    const int x = blockIdx.x * blockDim.x + threadIdx.x;
-    if (x >= count || first + x >= prm.npairs) return;
-    const EnPair pr = prm.pairs[first + x];
-    const int m = pr.m, n = pr.n;
-    if (m <= 0 || n <= 0) return;
-    int32_t* row = prm.rows + (size_t)(first + x) * 8;
-    if (row[7] != 0) return;                                     // unwritten, or without stored decisions: fetch reports it
-    const int nchunks = (n + kEnChunk - 1) / kEnChunk;
-    const int llast = (n - (nchunks - 1) * kEnChunk + kEnCpl - 1) / kEnCpl;
-    const int64_t nbytes = (int64_t)8 * m * ((int64_t)64 * (nchunks - 1) + llast);
-    if (pr.ws_off < 0 || (pr.ws_off & 7) != 0 || pr.ws_off + nbytes > prm.ws_cap || pr.cig_off < 0 || pr.cig_off + pr.cig_cap > prm.cigar_cap) { row[7] = EN_ST_NO_WALK; return; }
-    const uint2* ws = (const uint2*)(prm.ws + pr.ws_off);        // a lane's 8 bytes of a row; nbytes is a multiple of 8
-    int64_t held = -1;                                           // the word the last step read: a run along a row reads each once
-    uint2 word = make_uint2(0u, 0u);
-    const int8_t* ref = prm.ref + pr.r_off;
-    const int soff = (prm.strand && prm.strand[first + x] < 0) ? 32 : 0;
-    auto letter = [&](int pos) -> int { return (pos >= 0 && pos < n) ? ((int)ref[pos] & 31) : 4; };
-    pr_walk_spliced(row, prm.mode, m, n, prm.cigar + pr.cig_off, pr.cig_cap,
-        [&](int i, int j) -> int {
-            const int ch = (j - 1) / kEnChunk, p = (j - 1) % kEnChunk;
-            const int L = ch == nchunks - 1 ? llast : 64;
-            const int64_t wi = (int64_t)ch * m * 64 + (int64_t)(i - 1) * L + p / kEnCpl;
-            if (wi < 0 || wi * 8 + 8 > nbytes) return -1;
-            if (wi != held) { word = ws[wi]; held = wi; }
-            return (int)((((p & 4) ? word.y : word.x) >> (8 * (p & 3))) & 255u);
-        },
-        [&](int i, int j, uint32_t bit, bool* opened) -> int {      // the cells of the run from (i, j) leftwards inside the lane's word
-            const int ch = (j - 1) / kEnChunk, p = (j - 1) % kEnChunk, k = p % kEnCpl;
-            const int L = ch == nchunks - 1 ? llast : 64;
-            const int64_t wi = (int64_t)ch * m * 64 + (int64_t)(i - 1) * L + p / kEnCpl;
-            if (wi < 0 || wi * 8 + 8 > nbytes) return 0;
-            if (wi != held) { word = ws[wi]; held = wi; }
-            const uint64_t both = ((uint64_t)word.y << 32) | word.x;
-            const uint64_t set = both & (0x0101010101010101ull * bit) & (~0ull >> (8 * (7 - k)));      // "opened here" of columns 0 .. k of the word
-            *opened = set != 0;
-            return set ? k - (63 - __builtin_clzll(set)) / 8 + 1 : k + 1;
-        },
-        [&](int j) -> int {      // the run of j letters on row 0: D (2) if the deletion is not dearer, else N (3)
+    EnCells<cell_t> cells(m, n);
+    if (pr.ws_off < 0 || (sizeof(cell_t) == 8 && (pr.ws_off & 7) != 0) || pr.ws_off + cells.bytes() > prm.ws_cap ||
+        pr.cig_off < 0 || pr.cig_off + pr.cig_cap > prm.cigar_cap) { row[7] = EN_ST_NO_WALK; return; }
+    cells.ws = (const cell_t*)(prm.ws + pr.ws_off);
+    if constexpr (model == EN_SPLICED) {
+        const int8_t* ref = prm.ref + pr.r_off;
+        const int soff = (prm.strand && prm.strand[first + x] < 0) ? 32 : 0;
+        auto letter = [&](int pos) -> int { return (pos >= 0 && pos < n) ? ((int)ref[pos] & 31) : 4; };
+        pr_walk<model>(row, prm.mode, m, n, prm.cigar + pr.cig_off, pr.cig_cap, cells, [&](int j) -> int {
+            // the run of j letters on row 0: D (2) if the deletion is not dearer, else N (3)
             const int64_t del = (int64_t)prm.go + (int64_t)(j - 1) * prm.ge;
             const int64_t intron = (int64_t)prm.io + sp_site(prm.site, soff, 0, letter(0), letter(1)) + sp_site(prm.site, soff, 16, letter(j - 2), letter(j - 1));
             return del <= intron ? 2 : 3;
         });
+    }
+    else pr_walk<model>(row, prm.mode, m, n, prm.cigar + pr.cig_off, pr.cig_cap, cells);
 }
 
 template <typename Prm, int MODE>
@@ -585,19 +521,19 @@ static hipError_t en_launch(const Prm& p, bool store, int first, int count, hipS
     return hipGetLastError();
 }
 
-template <typename Prm, typename Kernel>
-static hipError_t en_launch_walk(Kernel kernel, const Prm& p, int first, int count, hipStream_t stream)
+template <typename Prm>
+static hipError_t en_launch_walk(const Prm& p, int first, int count, hipStream_t stream)
 {
     if (count <= 0) return hipSuccess;
-    hipLaunchKernelGGL(kernel, dim3((count + 63) / 64), dim3(64), 0, stream, p, first, count);
+    hipLaunchKernelGGL(ssw_ends_walk_kernel<Prm>, dim3((count + 63) / 64), dim3(64), 0, stream, p, first, count);
     return hipGetLastError();
 }
 
 hipError_t launch_ssw_ends(const EnParams& p, bool store, int first, int count, hipStream_t stream) { return en_launch(p, store, first, count, stream); }
 hipError_t launch_ssw_ends2(const En2Params& p, bool store, int first, int count, hipStream_t stream) { return en_launch(p, store, first, count, stream); }
 hipError_t launch_ssw_spliced(const SpParams& p, bool store, int first, int count, hipStream_t stream) { return en_launch(p, store, first, count, stream); }
-hipError_t launch_ssw_ends_walk(const EnParams& p, int first, int count, hipStream_t stream) { return en_launch_walk(ssw_ends_walk_kernel, p, first, count, stream); }
-hipError_t launch_ssw_ends2_walk(const En2Params& p, int first, int count, hipStream_t stream) { return en_launch_walk(ssw_ends2_walk_kernel, p, first, count, stream); }
-hipError_t launch_ssw_spliced_walk(const SpParams& p, int first, int count, hipStream_t stream) { return en_launch_walk(ssw_spliced_walk_kernel, p, first, count, stream); }
+hipError_t launch_ssw_ends_walk(const EnParams& p, int first, int count, hipStream_t stream) { return en_launch_walk(p, first, count, stream); }
+hipError_t launch_ssw_ends2_walk(const En2Params& p, int first, int count, hipStream_t stream) { return en_launch_walk(p, first, count, stream); }
+hipError_t launch_ssw_spliced_walk(const SpParams& p, int first, int count, hipStream_t stream) { return en_launch_walk(p, first, count, stream); }
 
 }  // namespace clh

@@ -1,9 +1,12 @@
 // ssw_pairs.h -- what K1g (ssw_ends.hip) and K1gb (ssw_band.hip) share on the device: the LDS matrix of their score kernels and the
-// walks back over the stored decisions, one per gap model: pr_walk (one piece), pr_walk2 (two pieces, both kernels), pr_walk_spliced
-// (intron gaps, K1g alone).  The two kernels differ in where a cell's decisions lie, which a walk takes as a functor.
-// (Each of the two score kernels is one template body for all its gap models.  The decision bits of a cell and the end cell's argmax
-// over the wave are the same text in both and stay written out there: as helpers they changed the register allocation of the storing
-// forms -- LABNOTES.md 16 and 20 have the tables.)
+// walk back over the stored decisions.  pr_walk<MODEL> is one body for the three gap models (one piece, two pieces, intron gaps): the
+// frame is written once, and what a model has of its own is a few constants (PrModel) and, for spliced, two branches under
+// `if constexpr`.  Where the decisions of a cell lie is the geometry's: EnCells (K1g) and BdCells (K1gb), which the walk takes as a
+// functor.  They check rows, columns and the plane's bounds themselves and state the plane's size, and the walk kernels' guards use
+// that same expression.  Walk and locators are __host__ __device__: tests/walk_host.hip runs them on the CPU over random planes.
+// (Each of the two score kernels is one template body for all its gap models.  The storing side of the layout, the decision bits of
+// a cell and the end cell's argmax over the wave stay written out there: as helpers they changed the register allocation of the
+// storing forms -- LABNOTES.md 16 and 20 have the tables.  The walk is one lane per pair, far from the row loop.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -23,55 +26,38 @@ __device__ __forceinline__ void pr_load_matrix(int* smat, const int8_t* mat, int
     __syncthreads();
 }
 
-// One lane walks one pair's stored decisions back from the end cell its score kernel left in `row` (tie rules: diagonal, then E,
-// then F; a gap is left as soon as "opened here" is set), writes the CIGAR (BAM ops M 0, I 1, D 2) and the begins; at most
-// i + j + 2 steps.  cell(i, j) gives the 4 bits of cell (i, j), or -1 where the cell is outside what was stored.  Whatever
-// does not add up sets EN_ST_NO_WALK, which fetch reports.  The caller has checked the pair's own geometry and that `out` holds cig_cap ops.
-template <typename Cell>
-__device__ __forceinline__ void pr_walk(int32_t* row, int mode, int m, int n, uint32_t* out, int cig_cap, Cell cell)
-{
-    int i = row[4] + 1, j = row[2] + 1;
-    if (i < 0 || i > m || j < 0 || j > n) { row[7] = EN_ST_NO_WALK; return; }
-    const int steps = i + j + 2;
-    int state = 0, nops = 0, cur = -1, run = 0;
-    bool bad = false, done = false;
-    auto emit = [&](int op, int k) {
-        if (k <= 0) return;
-        if (op == cur) { run += k; return; }
-        if (run) { if (nops < cig_cap) out[nops++] = ((uint32_t)run << 4) | (uint32_t)cur; else bad = true; }
-        cur = op; run = k;
-    };
-    for (int step = 0; step < steps && !done; ++step) {
-        if (state == 0 && (i == 0 || j == 0)) {
-            if (en_anchored(mode)) { emit(2, j); emit(1, i); i = 0; j = 0; }      // prefix and extend stop at (0, 0) as global does
-            else if (mode == EN_SEMIGLOBAL && j == 0) { emit(1, i); i = 0; }
-            done = true;
-            break;
-        }
-        const int at = cell(i, j);
-        if (at < 0) { bad = true; break; }
-        const uint32_t nib = (uint32_t)at;
-        if (state == 0) {
-            state = (int)(nib & 3u);                             // a gap state takes its first letter from this same cell
-            if (state == 0) { emit(0, 1); --i; --j; continue; }
-        }
-        if (state == 1) { emit(2, 1); --j; if (nib & 4u) state = 0; }
-        else if (state == 2) { emit(1, 1); --i; if (nib & 8u) state = 0; }
-        else { bad = true; break; }
-    }
-    emit(-2, 1);                                                 // flush the last run
-    if (bad || !done) { row[7] = EN_ST_NO_WALK; return; }
-    for (int a = 0, b = nops - 1; a < b; ++a, --b) { const uint32_t w = out[a]; out[a] = out[b]; out[b] = w; }
-    row[1] = j; row[3] = i; row[5] = nops;
-}
+// The gap model of a parameter block (EnModel in ssw_ends.hip, BdModel in ssw_band.hip name it), and what it means to the walk.
+// A stored cell holds H's source in its low bits -- 0 the diagonal, then the model's gap states in the order of its tie rule -- and
+// above them one "opened here" bit per gap state, in the same order:
+//     one piece   4 bits   source 0..1: 1 E, 2 F;                     bit 2 E, bit 3 F
+//     two pieces  a byte   source 0..2: 1 E_1, 2 E_2, 3 F_1, 4 F_2;   bits 3..6 E_1, E_2, F_1, F_2
+//     spliced     a byte   source 0..1: 1 E, 2 N, 3 F;                bit 2 T's source (0 diagonal, 1 F);  bits 3..5 E, N, F
+// The first n_ref gap states take a reference letter (op D, 2; spliced N: op N, 3), the others up to n_gap a query letter (op I, 1).
+enum { EN_ONE_PIECE, EN_TWO_PIECE, EN_SPLICED };
+template <int MODEL> struct PrModel {
+    static constexpr uint32_t src_mask = MODEL == EN_TWO_PIECE ? 7u : 3u;
+    static constexpr int n_ref = MODEL == EN_ONE_PIECE ? 1 : 2, n_gap = MODEL == EN_ONE_PIECE ? 2 : (MODEL == EN_TWO_PIECE ? 4 : 3);
+    static constexpr uint32_t open1 = MODEL == EN_ONE_PIECE ? 4u : 8u;      // "opened here" of gap state s is open1 << (s - 1)
+    static constexpr int T = 4;                                             // spliced alone: the state H without a reference gap
+};
 
-// pr_walk for two-piece gap costs (ssw_ends.hip, ssw_band.hip).  cell(i, j) gives the byte of cell (i, j) -- bits 0..2 H's source (0 diagonal, 1 E_1,
-// 2 E_2, 3 F_1, 4 F_2: that order is the tie rule), bits 3..6 "opened here" of E_1, E_2, F_1, F_2 -- or -1 outside what was stored.  Both
-// pieces of a direction emit the same op; a gap state is left as soon as its own piece's "opened here" is set.  Steps, bounds and
-// EN_ST_NO_WALK as in pr_walk.
-template <typename Cell>
-__device__ __forceinline__ void pr_walk2(int32_t* row, int mode, int m, int n, uint32_t* out, int cig_cap, Cell cell)
+struct PrRow0D { __host__ __device__ int operator()(int) const { return 2; } };     // the run on row 0 is a deletion
+
+// One lane walks one pair's stored decisions back from the end cell its score kernel left in `row`, writes the CIGAR (BAM ops M 0,
+// I 1, D 2, N 3; equal neighbours merged) and the begins; at most i + j + 2 steps, each of which consumes a letter.  The tie rule is
+// the order of the sources; a gap state takes its first letter from the cell that names it and is left as soon as its own "opened
+// here" is set.  cell(i, j) gives the stored bits of cell (i, j), or -1 where the cell is outside what was stored.  A gap state that
+// stands on row 0 or column 0, a source that names no state, a CIGAR of more than cig_cap runs, a walk that does not stop: whatever
+// does not add up sets EN_ST_NO_WALK, which fetch reports.  The caller has checked that `out` holds cig_cap ops.
+// Spliced: on leaving E or N the walk is in state T: the diagonal if T equals it, else F, never E or N again, so that no D stands
+// next to an N.  cell.run_left(i, j, bit, &opened) gives how many cells of the E or N run that stands on (i, j) lie in the stored word
+// of that cell, from column j leftwards up to and including the first whose `bit` ("opened here") is set, or 0 outside what was stored:
+// an intron is thousands of cells along one row, taken 8 at a step.  row0_op(j) names the op of the one run of j letters that the
+// anchored stop on row 0 emits; the other models neither have run_left nor pass a row0_op.
+template <int MODEL, typename Cell, typename Row0 = PrRow0D>
+__host__ __device__ __forceinline__ void pr_walk(int32_t* row, int mode, int m, int n, uint32_t* out, int cig_cap, Cell& cell, Row0 row0_op = Row0())
 {
+    typedef PrModel<MODEL> M;
     int i = row[4] + 1, j = row[2] + 1;
     if (i < 0 || i > m || j < 0 || j > n) { row[7] = EN_ST_NO_WALK; return; }
     const int steps = i + j + 2;
@@ -84,82 +70,113 @@ __device__ __forceinline__ void pr_walk2(int32_t* row, int mode, int m, int n, u
         cur = op; run = k;
     };
     for (int step = 0; step < steps && !done; ++step) {
-        if (state == 0 && (i == 0 || j == 0)) {
-            if (en_anchored(mode)) { emit(2, j); emit(1, i); i = 0; j = 0; }
+        if ((state == 0 || (MODEL == EN_SPLICED && state == M::T)) && (i == 0 || j == 0)) {     // on column 0 T is H; state T never stands on row 0
+            if (en_anchored(mode)) { if (j > 0) emit(row0_op(j), j); emit(1, i); i = 0; j = 0; }      // prefix and extend stop at (0, 0) as global does
             else if (mode == EN_SEMIGLOBAL && j == 0) { emit(1, i); i = 0; }
             done = true;
             break;
         }
-        const int at = cell(i, j);
+        const int at = cell(i, j);                               // -1 on row 0 and column 0: a gap state on the boundary does not add up
         if (at < 0) { bad = true; break; }
         const uint32_t b = (uint32_t)at;
         if (state == 0) {
-            state = (int)(b & 7u);                               // a gap state takes its first letter from this same cell
+            state = (int)(b & M::src_mask);                      // a gap state takes its first letter from this same cell
             if (state == 0) { emit(0, 1); --i; --j; continue; }
-        }
-        if (state == 1 || state == 2) { emit(2, 1); --j; if (b & (4u << state)) state = 0; }          // bit 3 for E_1, bit 4 for E_2
-        else if (state == 3 || state == 4) { emit(1, 1); --i; if (b & (4u << state)) state = 0; }     // bit 5 for F_1, bit 6 for F_2
-        else { bad = true; break; }
-    }
-    emit(-2, 1);                                                 // flush the last run
-    if (bad || !done) { row[7] = EN_ST_NO_WALK; return; }
-    for (int a = 0, c = nops - 1; a < c; ++a, --c) { const uint32_t w = out[a]; out[a] = out[c]; out[c] = w; }
-    row[1] = j; row[3] = i; row[5] = nops;
-}
-
-// pr_walk for spliced alignment (ssw_ends.hip).  cell(i, j) gives the byte of cell (i, j) -- bits 0..1 H's source (0 diagonal, 1 E, 2 N,
-// 3 F: that order is the tie rule), bit 2 T's source (0 diagonal, 1 F), bits 3..5 "opened here" of E, N, F -- or -1 outside what was
-// stored.  E emits D (2), N emits N (3); on leaving either the walk is in state T (4), H without a reference gap: the diagonal if T
-// equals it, else F, never E or N again, so that no D stands next to an N.  row0_op(j) names the op of the one run of j letters the
-// anchored stop on row 0 emits.  run(i, j, bit, &opened) gives how many cells of the E or N run that stands on (i, j) lie in the
-// stored word of that cell, from column j leftwards up to and including the first whose `bit` ("opened here") is set, or 0 outside what
-// was stored: an intron is thousands of cells along one row, taken 8 at a step.  Every step consumes a letter; steps, bounds and
-// EN_ST_NO_WALK as in pr_walk.
-template <typename Cell, typename Run, typename Row0>
-__device__ __forceinline__ void pr_walk_spliced(int32_t* row, int mode, int m, int n, uint32_t* out, int cig_cap, Cell cell, Run run_left, Row0 row0_op)
-{
-    int i = row[4] + 1, j = row[2] + 1;
-    if (i < 0 || i > m || j < 0 || j > n) { row[7] = EN_ST_NO_WALK; return; }
-    const int steps = i + j + 2;
-    int state = 0, nops = 0, cur = -1, run = 0;
-    bool bad = false, done = false;
-    auto emit = [&](int op, int k) {
-        if (k <= 0) return;
-        if (op == cur) { run += k; return; }
-        if (run) { if (nops < cig_cap) out[nops++] = ((uint32_t)run << 4) | (uint32_t)cur; else bad = true; }
-        cur = op; run = k;
-    };
-    for (int step = 0; step < steps && !done; ++step) {
-        if ((state == 0 || state == 4) && (i == 0 || j == 0)) {      // on column 0 T is H; state T never stands on row 0
-            if (en_anchored(mode)) { if (j > 0) emit(row0_op(j), j); emit(1, i); i = 0; j = 0; }
-            else if (mode == EN_SEMIGLOBAL && j == 0) { emit(1, i); i = 0; }
-            done = true;
-            break;
-        }
-        if (i <= 0 || j <= 0) { bad = true; break; }              // a gap state on the boundary: the stored bits do not add up
-        const int at = cell(i, j);
-        if (at < 0) { bad = true; break; }
-        const uint32_t b = (uint32_t)at;
-        if (state == 0) {
-            state = (int)(b & 3u);                               // a gap state takes its first letter from this same cell
-            if (state == 0) { emit(0, 1); --i; --j; continue; }
-        } else if (state == 4) {
+        } else if (MODEL == EN_SPLICED && state == M::T) {
             if (!(b & 4u)) { emit(0, 1); --i; --j; state = 0; continue; }
             state = 3;
         }
-        if (state == 1 || state == 2) {
-            bool opened = false;
-            const int k = run_left(i, j, state == 1 ? 8u : 16u, &opened);
-            if (k <= 0 || k > j) { bad = true; break; }
-            emit(state == 1 ? 2 : 3, k); j -= k;
-            if (opened) state = 4;
+        const uint32_t open = (M::open1 >> 1) << state;          // state >= 1 here
+        if (state <= M::n_ref) {
+            if constexpr (MODEL == EN_SPLICED) {
+                bool opened = false;
+                const int k = cell.run_left(i, j, open, &opened);
+                if (k <= 0 || k > j) { bad = true; break; }
+                emit(state == 1 ? 2 : 3, k); j -= k;
+                if (opened) state = M::T;
+            }
+            else { emit(2, 1); --j; if (b & open) state = 0; }
         }
-        else { emit(1, 1); --i; if (b & 32u) state = 0; }
+        else if (state <= M::n_gap) { emit(1, 1); --i; if (b & open) state = 0; }
+        else { bad = true; break; }
     }
     emit(-2, 1);                                                 // flush the last run
     if (bad || !done) { row[7] = EN_ST_NO_WALK; return; }
     for (int a = 0, c = nops - 1; a < c; ++a, --c) { const uint32_t w = out[a]; out[a] = out[c]; out[c] = w; }
     row[1] = j; row[3] = i; row[5] = nops;
 }
+
+// Where the decisions of cell (i, j) lie in what K1g's storing form left of a pair: chunk after chunk, per chunk row after row, a
+// word of kEnCpl cells per lane that owns a column, nwords of them.  Word is what the walk loads: uint32_t, a word of half-bytes; uint8_t,
+// one byte of a word of bytes; uint2, a word of bytes, held: a run along a row loads each word once.  The constructor is given
+// the pair, the caller checks that bytes() lie inside the workspace and sets ws.  -1 outside rows 1..m and columns 1..n, which is the
+// plane exactly: the word of such a cell has an index below nwords (chunk by chunk: (i - 1) L + p / kEnCpl < m L).
+template <typename Word>
+struct EnCells {
+    const Word* ws = nullptr;
+    int m, n, nchunks, llast;
+    int64_t nwords, held = -1;
+    Word word;                                               // uint2 alone: the word loaded last, and its index
+    __host__ __device__ EnCells(int m_, int n_) : m(m_), n(n_), nchunks((n_ + kEnChunk - 1) / kEnChunk), word()
+    {
+        llast = (n - (nchunks - 1) * kEnChunk + kEnCpl - 1) / kEnCpl;
+        nwords = (int64_t)m * ((int64_t)64 * (nchunks - 1) + llast);
+    }
+    __host__ __device__ int64_t bytes() const { return (sizeof(Word) == 4 ? 4 : 8) * nwords; }
+    // the index of the lane's word that holds cell (i, j), *k the cell's place in it; -1 outside the plane
+    __host__ __device__ int64_t locate(int i, int j, int* k) const
+    {
+        const uint32_t r = (uint32_t)(i - 1), c = (uint32_t)(j - 1);                              // unsigned: row 0 and column 0 wrap, shifts and masks
+        if (r >= (uint32_t)m || c >= (uint32_t)n) return -1;
+        const uint32_t ch = c / kEnChunk, p = c % kEnChunk;
+        const int L = (int)ch == nchunks - 1 ? llast : 64;
+        *k = (int)(p % kEnCpl);
+        return (int64_t)ch * m * 64 + (int64_t)r * L + p / kEnCpl;
+    }
+    __host__ __device__ void hold(int64_t wi)
+    {
+        static_assert(sizeof(Word) == 8, "only the uint2 functor holds a word");
+        if (wi != held) { word = ws[wi]; held = wi; }
+    }
+    __host__ __device__ int operator()(int i, int j)
+    {
+        int k;
+        const int64_t wi = locate(i, j, &k);
+        if (wi < 0) return -1;
+        if constexpr (sizeof(Word) == 4) return (int)((ws[wi] >> (4 * k)) & 15u);
+        else if constexpr (sizeof(Word) == 1) return (int)ws[wi * kEnCpl + k];
+        else { hold(wi); return (int)((((k & 4) ? word.y : word.x) >> (8 * (k & 3))) & 255u); }
+    }
+    __host__ __device__ int run_left(int i, int j, uint32_t bit, bool* opened)      // pr_walk states it
+    {
+        static_assert(sizeof(Word) == 8, "run_left reads the held uint2");
+        int k;
+        const int64_t wi = locate(i, j, &k);
+        if (wi < 0) return 0;
+        hold(wi);
+        const uint64_t both = ((uint64_t)word.y << 32) | word.x;
+        const uint64_t set = both & (0x0101010101010101ull * bit) & (~0ull >> (8 * (7 - k)));      // "opened here" of columns 0 .. k of the word
+        *opened = set != 0;
+        return set ? k - (63 - __builtin_clzll(set)) / 8 + 1 : k + 1;
+    }
+};
+
+// The same for K1gb: row after row in the band's frame, position b = j - i - lo of B, cells of BITS bits (4 or 8), cpl of them per lane
+// that owns a position.  -1 outside rows 1..m, on column 0 and outside the band: a position below B lies inside its row's bytes.
+template <int BITS>
+struct BdCells {
+    const uint8_t* ws = nullptr;
+    int m, lo, B;
+    int64_t rowbytes, nbytes;
+    __host__ __device__ BdCells(int m_, int lo_, int B_, int cpl) : m(m_), lo(lo_), B(B_), rowbytes((int64_t)((B_ + cpl - 1) / cpl) * (cpl * BITS / 8)), nbytes(m_ * rowbytes) {}
+    __host__ __device__ int64_t bytes() const { return nbytes; }
+    __host__ __device__ int operator()(int i, int j) const
+    {
+        const uint32_t r = (uint32_t)(i - 1), b = (uint32_t)(j - i - lo);                         // unsigned: row 0 and a position below 0 wrap
+        if (r >= (uint32_t)m || j < 1 || b >= (uint32_t)B) return -1;
+        const int64_t bi = (int64_t)r * rowbytes + (BITS == 4 ? b >> 1 : b);
+        return BITS == 4 ? (int)(((uint32_t)ws[bi] >> (4 * (b & 1))) & 15u) : (int)ws[bi];
+    }
+};
 
 }  // namespace clh

@@ -285,6 +285,31 @@ def run_capacity(m, n):
     return min(m + n, 2 * min(m, n) + 1)
 
 
+_max_runs_rows = {}
+
+
+def max_runs_rows(geom):
+    """-> (refs, queries, rows) of the max-runs pairs, rows[k] = (score, ref_begin, ref_end, query_begin, query_end, cigar text) as the
+    one-piece checker states it (computed once).  Whatever plan aligns these pairs globally under costs that amount to
+    MAX_RUNS_SCORING -- a second piece equal to the first, an intron too dear to open, a band that holds the whole matrix -- walks
+    back through another instantiation of the walk and has to return the same rows, each with run_capacity(m, n) runs."""
+    key = (geom['cpl'], geom['chunk'])
+    if key not in _max_runs_rows:
+        cases = max_runs(geom)
+        wants = [expected(c) for c in cases]
+        _max_runs_rows[key] = ([c.ref for c in cases], [c.query for c in cases], [chk.as_tuple(w)[:5] + (chk.cigar_text(w['cigar']),) for w in wants])
+    return _max_runs_rows[key]
+
+
+def check_max_runs(got, geom):
+    """`got`: the PyAlignRes of the max-runs pairs from a plan as max_runs_rows describes"""
+    refs, queries, rows = max_runs_rows(geom)
+    assert len(got) == len(rows)
+    for k, (g, r, q, row) in enumerate(zip(got, refs, queries, rows)):
+        assert (g.score, g.ref_begin, g.ref_end, g.query_begin, g.query_end, g.cigar_string) == row, (k, r, q)
+        assert len(chk.parse_cigar(g.cigar_string)) == run_capacity(len(q), len(r)), (k, r, q, g.cigar_string)
+
+
 # ------------------------------------------------------------------------------------------------------------------------------
 # shares: a plan cuts its batch so that the stored decisions of a share fit the workspace
 # ------------------------------------------------------------------------------------------------------------------------------

@@ -165,6 +165,18 @@ def test_bands_clipped_to_the_whole_matrix_are_exact_and_equal_the_full_matrix_k
                 assert (int(r['score']), int(r['ref_begin']), int(r['ref_end']), int(r['query_begin']), int(r['query_end']), ops) == ec.as_tuple(x)
 
 
+def test_cigars_with_as_many_runs_as_the_host_reserves():
+    """the walk over half-bytes in the band's frame writes its last run at nops == cig_cap - 1: the one-piece K1g checker's rows,
+    over a band that clips to the whole matrix (the widest pair spans 156 diagonals)"""
+    import ends_edges as E
+    from ciri_long_amd import ssw_wrap
+    refs, queries, _ = E.max_runs_rows(E.HOST_GEOM)
+    ma, mi, go, ge = E.MAX_RUNS_SCORING
+    got = ssw_wrap.align_pairs_band(refs, queries, 128, mode='global', match=ma, mismatch=mi, gap_open=go, gap_extend=ge, report_cigar=True)
+    E.check_max_runs(got, E.HOST_GEOM)
+    assert all(g.band_exact for g in got)
+
+
 @pytest.mark.parametrize('ge', ['2', '0', 'go'])
 def test_gaps_of_exactly_the_half_width_touch_hi_then_lo_and_one_less_loses_them(ge):
     rng = chk.rng_for('gpu band edge gaps', ge)

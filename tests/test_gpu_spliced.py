@@ -214,6 +214,17 @@ def test_ties_between_a_deletion_and_an_intron_resolve_to_d():
     assert not any(('N', 2) in w['cigar'] or ('N', 1) in w['cigar'] for w in wants)
 
 
+def test_cigars_with_as_many_runs_as_the_host_reserves():
+    """the spliced walk writes its last run at nops == cig_cap - 1: with an intron too dear to open, the one-piece checker's rows"""
+    import ends_edges as E
+    from ciri_long_amd import ssw_wrap
+    refs, queries, _ = E.max_runs_rows(E.HOST_GEOM)
+    ma, mi, go, ge = E.MAX_RUNS_SCORING
+    got = ssw_wrap.align_pairs_spliced(refs, queries, mode='global', strand='+', match=ma, mismatch=mi, gap_open=go, gap_extend=ge, intron_open=1000,
+                                       noncanonical=0, report_cigar=True)
+    E.check_max_runs(got, E.HOST_GEOM)
+
+
 def test_a_short_gap_is_a_deletion_and_a_long_one_an_intron_in_the_same_pair():
     rng = chk.rng_for('gpu spliced mixed')
     refs, queries = [], []

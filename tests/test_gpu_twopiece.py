@@ -264,6 +264,17 @@ def test_extend_anchors_with_the_long_read_preset_equals_the_checker_s_two_halve
     assert long_runs >= 3                # the planted events are kept as single long gaps, which piece 1 alone would not pay for
 
 
+def test_cigars_with_as_many_runs_as_the_host_reserves():
+    """the walk over bytes writes its last run at nops == cig_cap - 1: the one-piece checker's rows at (1, 0, 1, 0)"""
+    import ends_edges as E
+    from ciri_long_amd import ssw_wrap
+    refs, queries, _ = E.max_runs_rows(E.HOST_GEOM)
+    ma, mi, go, ge = E.MAX_RUNS_SCORING
+    got = ssw_wrap.align_pairs_ends(refs, queries, mode='global', match=ma, mismatch=mi, gap_open=go, gap_extend=ge, gap_open2=go, gap_extend2=ge,
+                                    report_cigar=True)
+    E.check_max_runs(got, E.HOST_GEOM)
+
+
 # ---- over a band (K1gb, csrc/ssw_band.hip) -------------------------------------------------------------------------------------------
 BAND_MODES = chk.BAND_MODES
 
@@ -304,6 +315,18 @@ def _full(refs, queries, mode, costs, match=2, mismatch=4):
     from ciri_long_amd import ssw_wrap
     return ssw_wrap.align_pairs_ends(refs, queries, mode=mode, match=match, mismatch=mismatch, gap_open=costs[0], gap_extend=costs[1], gap_open2=costs[2],
                                      gap_extend2=costs[3], report_cigar=True)
+
+
+def test_band_cigars_with_as_many_runs_as_the_host_reserves():
+    """as above over a band that clips to the whole matrix (the widest pair spans 156 diagonals)"""
+    import ends_edges as E
+    from ciri_long_amd import ssw_wrap
+    refs, queries, _ = E.max_runs_rows(E.HOST_GEOM)
+    ma, mi, go, ge = E.MAX_RUNS_SCORING
+    got = ssw_wrap.align_pairs_band(refs, queries, 128, mode='global', match=ma, mismatch=mi, gap_open=go, gap_extend=ge, gap_open2=go, gap_extend2=ge,
+                                    report_cigar=True)
+    E.check_max_runs(got, E.HOST_GEOM)
+    assert all(g.band_exact for g in got)
 
 
 WIDTHS = [(1, 0, 0), (2, 0, 1), (127, 63, 0), (128, 63, 1), (129, 64, 0), (255, 127, 0), (256, 127, 1), (257, 128, 0), (511, 255, 0), (512, 255, 1)]

@@ -231,7 +231,7 @@ def run(q, r, mat, costs, mode, strand=1, cpl=8, lanes=64, store=True, fault=Non
 
 
 def walk(cells, mode, end, row0_op):
-    """one lane walks the stored bytes back (pr_walk_spliced of csrc/ssw_pairs.h): states 0 H, 1 E, 2 N, 3 F, 4 T; every step consumes a
+    """one lane walks the stored bytes back (pr_walk<EN_SPLICED> of csrc/ssw_pairs.h): states 0 H, 1 E, 2 N, 3 F, 4 T; every step consumes a
     letter, at most i + j + 2 steps.  (The kernel takes the cells of an E or N run that share a stored word in one step, up to the
     first "opened here" bit: the same cells in the same order.)"""
     i, j = end

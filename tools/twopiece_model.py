@@ -169,7 +169,7 @@ def run(q, r, mat, costs, mode, cpl=8, lanes=64, store=True, fault=None):
 
 
 def walk(cells, mode, end):
-    """one lane walks the stored bytes back (pr_walk2 of csrc/ssw_pairs.h); at most i + j + 2 steps"""
+    """one lane walks the stored bytes back (pr_walk<EN_TWO_PIECE> of csrc/ssw_pairs.h); at most i + j + 2 steps"""
     i, j = end
     ops, state = [], 0
 
