@@ -105,6 +105,17 @@ typedef struct {
 
 typedef struct { int algorithm, m, n, g, e, q, c, subtype, min_cov; } par;   /* subtype 0 linear, 1 affine, 2 convex */
 
+/* what clo_poa_shape reports of one alignment: the end cell (rank, column; 0, 0: none) and the longest runs of horizontal steps
+ * (bases without a node) and of vertical steps (nodes without a base) of its back-track, border steps of the global mode included */
+typedef struct { int bi, bj, hrun, vrun, h, v; } walk;
+static void walk_step(walk *w, int di, int dj)               /* one step of the back-track: di / dj = the row / the column changed */
+{
+    if (!w) return;
+    if (di && dj) { w->h = 0; w->v = 0; }
+    else if (dj) { w->v = 0; if (++w->h > w->hrun) w->hrun = w->h; }
+    else { w->h = 0; if (++w->v > w->vrun) w->vrun = w->v; }
+}
+
 static inline int imax(int a, int b) { return a > b ? a : b; }
 
 static void g_init(graph *g, int cap)
@@ -193,7 +204,7 @@ static void topo_sort(graph *g)
  * alignment.  pn[j] (j = 0..L-1) = node the base j is aligned to, or -1.  [*jb, *je] = the bases the alignment holds
  * (jb > je: none), *steps = its number of pairs.  Pairs (node, no base) do not change the graph (AddAlignment skips them)
  * and are only counted.  *score = end-cell score. */
-static void align_linear(const graph *g, const uint8_t *s, int L, const par *P, int32_t *pn, int *score, int *jb, int *je, int *steps)
+static void align_linear(const graph *g, const uint8_t *s, int L, const par *P, int32_t *pn, int *score, int *jb, int *je, int *steps, walk *wk)
 {
     const int N = g->n, W = L + 1, sw = P->algorithm == 0, nw = P->algorithm == 1;
     int32_t *H = (int32_t *)malloc(sizeof(int32_t) * (size_t)(N + 1) * W);
@@ -223,6 +234,7 @@ static void align_linear(const graph *g, const uint8_t *s, int L, const par *P, 
     }
     for (int j = 0; j < L; ++j) pn[j] = -1;
     *score = best;
+    if (wk) { wk->bi = bi; wk->bj = bj; }
     int i = bi, j = bj, ns = 0;
     while ((sw && H[(size_t)i * W + j] != 0) || (nw && (i != 0 || j != 0)) || (P->algorithm == 2 && i != 0 && j != 0)) {
         const int h = H[(size_t)i * W + j];
@@ -239,13 +251,14 @@ static void align_linear(const graph *g, const uint8_t *s, int L, const par *P, 
         if (!found) break;                                   /* cannot happen */
         if (pj != j && pi != i) pn[j - 1] = g->order[i - 1];
         ++ns;
+        walk_step(wk, pi != i, pj != j);
         i = pi; j = pj;
     }
     *jb = j; *je = bj - 1; *steps = ns;
     free(H); free(pr);
 }
 
-static void align_gotoh(const graph *g, const uint8_t *s, int L, const par *P, int32_t *pn, int *score, int *jb, int *je, int *steps)
+static void align_gotoh(const graph *g, const uint8_t *s, int L, const par *P, int32_t *pn, int *score, int *jb, int *je, int *steps, walk *wk)
 {
     const int N = g->n, W = L + 1, sw = P->algorithm == 0, nw = P->algorithm == 1, ov = P->algorithm == 2, cx = P->subtype == 2;
     const int ge = P->g, ee = P->e, qq = P->q, cc = P->c;
@@ -295,6 +308,7 @@ static void align_gotoh(const graph *g, const uint8_t *s, int L, const par *P, i
     }
     for (int j = 0; j < L; ++j) pn[j] = -1;
     *score = best;
+    if (wk) { wk->bi = bi; wk->bj = bj; }
     /* back-track */
     int i = bi, j = bj, ns = 0;
     while ((sw && H[(size_t)i * W + j] != 0) || (nw && (i != 0 || j != 0)) || (ov && i != 0 && j != 0)) {
@@ -326,10 +340,12 @@ static void align_gotoh(const graph *g, const uint8_t *s, int L, const par *P, i
         if (!found) break;                                   /* cannot happen */
         if (pi != i && pj != j) pn[j - 1] = g->order[i - 1];
         ++ns;
+        walk_step(wk, pi != i, pj != j);
         i = pi; j = pj;
         if (ext_left) {
             for (;;) {
                 --j; ++ns;                                    /* one more base without a node */
+                walk_step(wk, 0, 1);
                 const size_t b = (size_t)i * W + j;
                 if (E[b] + ee != E[b + 1] && (!cx || Q[b] + cc != Q[b + 1])) break;
             }
@@ -349,6 +365,7 @@ static void align_gotoh(const graph *g, const uint8_t *s, int L, const par *P, i
                     if (hit) { ni = pr[k]; break; }
                 }
                 i = ni; ++ns;                                 /* one more node without a base */
+                walk_step(wk, 1, 0);
                 if (stop || i == 0) break;
             }
         }
@@ -464,9 +481,10 @@ static int parse_par(const int32_t *pp, par *P)
  * implementation limit, -2 on invalid parameters, -3 where spoa throws (an alignment without a base).  msa (may be NULL)
  * receives one row of *ncols characters ('-' = 45, else the letter) per NON-EMPTY sequence, row-major, if it fits msa_cap
  * (else -1).  scores (may be NULL) receives the end-cell score of every alignment (0 for an empty sequence).
- * rank_out (may be NULL): node ids in the final rank order, preceded by their count (capacity: total letters + 1). */
-int clo_poa_ranked(int32_t nseq, const int8_t *seqs_, const int32_t *off, const int32_t *params, int8_t *cons, int32_t cap,
-                   int8_t *msa, int64_t msa_cap, int32_t *ncols, int32_t *scores, int32_t *rank_out)
+ * rank_out (may be NULL): node ids in the final rank order, preceded by their count (capacity: total letters + 1).
+ * node_shape / seq_shape: see clo_poa_shape. */
+static int poa_run(int32_t nseq, const int8_t *seqs_, const int32_t *off, const int32_t *params, int8_t *cons, int32_t cap,
+                   int8_t *msa, int64_t msa_cap, int32_t *ncols, int32_t *scores, int32_t *rank_out, int32_t *node_shape, int32_t *seq_shape)
 {
     const uint8_t *seqs = (const uint8_t *)seqs_;
     par P;
@@ -479,12 +497,15 @@ int clo_poa_ranked(int32_t nseq, const int8_t *seqs_, const int32_t *off, const 
     for (int s = 0; s < nseq && rc == 0; ++s) {
         const int L = off[s + 1] - off[s];
         if (scores) scores[s] = 0;
+        if (seq_shape) memset(seq_shape + 4 * s, 0, 4 * sizeof(int32_t));
         if (L == 0) continue;
         int sc = 0, jb = 0, je = -1, steps = 0;
+        walk wk = {0, 0, 0, 0, 0, 0};
         if (g.n == 0) { for (int j = 0; j < L; ++j) pn[j] = -1; }
-        else if (P.subtype == 0) align_linear(&g, seqs + off[s], L, &P, pn, &sc, &jb, &je, &steps);
-        else align_gotoh(&g, seqs + off[s], L, &P, pn, &sc, &jb, &je, &steps);
+        else if (P.subtype == 0) align_linear(&g, seqs + off[s], L, &P, pn, &sc, &jb, &je, &steps, &wk);
+        else align_gotoh(&g, seqs + off[s], L, &P, pn, &sc, &jb, &je, &steps, &wk);
         if (scores) scores[s] = sc;
+        if (seq_shape) { seq_shape[4 * s] = wk.bi; seq_shape[4 * s + 1] = wk.bj; seq_shape[4 * s + 2] = wk.hrun; seq_shape[4 * s + 3] = wk.vrun; }
         rc = fuse(&g, seqs + off[s], L, pn, jb, je, steps, used + off[s]);
         if (rc == 0) {
             if (L >= 2) for (int j = 0; j < L; ++j) g.cov[used[off[s] + j]] += 1;
@@ -504,6 +525,13 @@ int clo_poa_ranked(int32_t nseq, const int8_t *seqs_, const int32_t *off, const 
         free(path);
     }
     if (len >= 0 && rank_out) { rank_out[0] = g.n; for (int i = 0; i < g.n; ++i) rank_out[1 + i] = g.order[i]; }
+    if (len >= 0 && node_shape)
+        for (int i = 0; i < g.n; ++i) {
+            const int v = g.order[i];
+            int wmax = 0, dmax = 0;
+            for (int k = 0; k < g.tail[v].n; ++k) { wmax = imax(wmax, g.wt[v].v[k]); dmax = imax(dmax, i + 1 - g.rank[g.tail[v].v[k]]); }
+            node_shape[4 * i] = g.tail[v].n; node_shape[4 * i + 1] = g.al[v].n + 1; node_shape[4 * i + 2] = wmax; node_shape[4 * i + 3] = dmax;
+        }
     if (len >= 0 && ncols) {
         int32_t *col = (int32_t *)malloc(sizeof(int32_t) * (size_t)(g.n + 1));
         int nc = 0;
@@ -532,6 +560,28 @@ int clo_poa_ranked(int32_t nseq, const int8_t *seqs_, const int32_t *off, const 
     free(pn); free(used);
     g_free(&g);
     return len;
+}
+
+int clo_poa_ranked(int32_t nseq, const int8_t *seqs, const int32_t *off, const int32_t *params, int8_t *cons, int32_t cap,
+                   int8_t *msa, int64_t msa_cap, int32_t *ncols, int32_t *scores, int32_t *rank_out)
+{
+    return poa_run(nseq, seqs, off, params, cons, cap, msa, msa_cap, ncols, scores, rank_out, NULL, NULL);
+}
+
+/* the shape of what clo_poa_ranked computes (the same code): node_shape receives, per node of the final graph in rank order, its
+ * in-degree, the members of its aligned set (itself included), its largest in-edge weight and its largest rank distance to a
+ * predecessor (0 without in-edges) -- 4 values each, capacity 4 * total letters; seq_shape receives, per sequence, the end cell of
+ * its alignment (rank, column; 0, 0 for the first and for an empty one) and the longest horizontal and vertical run of its walk.
+ * returns the number of nodes, or the negative codes of clo_poa_ranked. */
+int clo_poa_shape(int32_t nseq, const int8_t *seqs, const int32_t *off, const int32_t *params, int32_t *node_shape, int32_t *seq_shape)
+{
+    const int total = off[nseq];
+    int8_t *cons = (int8_t *)malloc((size_t)total + 8);
+    int32_t *rank = (int32_t *)malloc(sizeof(int32_t) * ((size_t)total + 2));
+    const int rc = poa_run(nseq, seqs, off, params, cons, total + 8, NULL, 0, NULL, NULL, rank, node_shape, seq_shape);
+    const int n = rc < 0 ? rc : rank[0];
+    free(cons); free(rank);
+    return n;
 }
 
 int clo_poa(int32_t nseq, const int8_t *seqs, const int32_t *off, const int32_t *params, int8_t *cons, int32_t cap,

@@ -173,6 +173,8 @@ def _ccs_lib():
         lib.clo_poa.restype = C.c_int
         lib.clo_poa.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64,
                                 C.c_void_p, C.c_void_p]
+        lib.clo_poa_shape.restype = C.c_int
+        lib.clo_poa_shape.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.clo_ccs_segments.restype = C.c_int
         lib.clo_ccs_segments.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib._ccs_ready = True
@@ -244,6 +246,31 @@ def oracle_poa(seqs, algorithm=0, genmsa=False, m=10, n=-4, g=-8, e=-2, q=-24, c
     if with_order:
         res += ([int(x) for x in order[1:1 + int(order[0])]] if k >= 0 else None,)
     return res
+
+
+def oracle_poa_shape(seqs, algorithm=0, m=10, n=-4, g=-8, e=-2, q=-24, c=-1):
+    """oracle/poa_oracle.c: clo_poa_shape -- the shape of the graph and of the walks that oracle_poa(seqs, algorithm, ..., m, n, g, e, q, c)
+    computes (the same code).  seqs: str / bytes, letters as they are.  -> dict of int arrays: per node of the final graph in rank
+    order 'indeg', 'aligned' (members of its aligned set, itself included), 'weight' (largest in-edge weight), 'dist' (largest rank
+    distance to a predecessor, 0 without one); per sequence 'end' ((rank, column) of the end cell; (0, 0) for the first), 'hrun' and
+    'vrun' (longest horizontal / vertical run of its walk).  None where an implementation limit was hit."""
+    arrs = [np.frombuffer(s.encode('latin-1') if isinstance(s, str) else bytes(s), dtype=np.int8) for s in seqs]
+    off = np.zeros(len(arrs) + 1, dtype=np.int32)
+    np.cumsum([len(a) for a in arrs], out=off[1:])
+    data = np.ascontiguousarray(np.concatenate(arrs)) if arrs and off[-1] else np.zeros(1, dtype=np.int8)
+    par = np.array([algorithm, m, n, g, e, q, c, 0], dtype=np.int32)
+    nodes = np.zeros((int(off[-1]) + 1, 4), dtype=np.int32)
+    per_seq = np.zeros((len(arrs) + 1, 4), dtype=np.int32)
+    k = _ccs_lib().clo_poa_shape(len(arrs), data.ctypes.data, off.ctypes.data, par.ctypes.data, nodes.ctypes.data, per_seq.ctypes.data)
+    if k == -2:
+        raise ValueError('invalid poa parameters')
+    if k == -3:
+        raise ValueError('alignment without a base (spoa throws)')
+    if k < 0:
+        return None
+    nodes, per_seq = nodes[:k], per_seq[:len(arrs)]
+    return {'indeg': nodes[:, 0].copy(), 'aligned': nodes[:, 1].copy(), 'weight': nodes[:, 2].copy(), 'dist': nodes[:, 3].copy(),
+            'end': [(int(a), int(b)) for a, b in per_seq[:, :2]], 'hrun': per_seq[:, 2].copy(), 'vrun': per_seq[:, 3].copy()}
 
 
 def oracle_edit_distance(x, y):
