@@ -3,8 +3,8 @@
 //
 // Same answers as ssw_wavefront.hip (reference: libs/striped_smith_waterman/ssw.c:123-345 sw_sse2_byte, :371-546 sw_sse2_word,
 // and the forward + reverse orchestration of ssw_align, ssw.c:779-849; row-major statement: oracle/rowmajor_spec.c).
-// The lanes own reference columns, the loop runs over the read's rows (see ssw_scan.hip for the layout of a chunk, the prefix
-// maximum that carries the gap along a row, and the hand-over between chunks).  What is different here:
+// The lanes own reference columns, the loop runs over the read's rows (ssw_rowscan.h: the layout of a chunk, the row step, the prefix
+// maximum that carries the gap along a row, and the hand-over between chunks).  What is this kernel's own:
 //   * two regimes, chosen per alignment as ssw_align does (ssw.c:804-822): the 16-bit pass when the 8-bit pass would overflow
 //     (the byte-regime pass runs first, as in the reference, and hands over when it overflows);
 //   * the byte regime in 16-bit arithmetic: the exact recurrence, rows padded to 16, abandoned as soon as a column maximum +
@@ -19,44 +19,29 @@
 // 11 packed operations per cell pair (gap_open == gap_extend) or 15, plus ~45 per row step of 1024 columns.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <type_traits>
 #include <algorithm>
-#include "clh_device.h"
-#include "clh_device_ops.h"
+#include "ssw_rowscan.h"
 
 namespace clh {
 
 namespace {
 
-
-
 #ifndef SCANW_WAVES
-#define SCANW_WAVES 3      // measured on C2: 2 -> 12.6 ms, 3 -> 12.2 ms, 4 -> 15.1 ms (at 3 the spills stay outside the row loop)
+#define SCANW_WAVES 3      // measured on C2: 2 -> 12.6 ms, 3 -> 12.2 ms, 4 -> 15.1 ms (at 3 the spills stay outside the row loop: none in the row step of
+                           // any chunk width; the boundary-row step, at most 14 rows of a word pass, reloads a few values -- LABNOTES 23)
 #endif
-static constexpr int W_CPR_MAX = 8;
-static constexpr int W_PROF_WORDS = 6 * W_CPR_MAX * 64;      // uint32 per wave: [query code 0..5][register][lane]
 static constexpr int W_NB = 7;                               // stripe boundaries of a word pass
-static constexpr int W_INF = 0x7fffffff;
+static constexpr int W_INF = RS_INF;
 
-struct WIn {
-    const int8_t* read;   // first row's base
-    int rstep;            // +1 / -1
-    int L;                // rows of the read
-    int rows;             // rows processed (L padded with wildcard rows)
+struct WIn : RsIn {
     int S;                // word regime with gap_open == gap_extend: the stripe length (rows S, 2S, .. 7S are boundary rows); else 0
-    const int8_t* ref;    // first column's base
-    int cstep;            // +1 / -1
-    int comp;
-    int ncols;
     int rcomp;            // transposed form only: the ROWS are reference bases, complemented when set (ref_code)
-    int terminate;        // column maximum that ends the pass (ssw.c:296, 489); 1 << 30 = never
     int overflow_at;      // byte regime: a column maximum >= this abandons the pass (255 - bias); 1 << 30 = never
-    uint16_t* colmax;     // per-column maxima (indexed by column), or nullptr
 };
-struct WOut { int max, col, row, overflow; };
+struct WOut : RsOut { int overflow; };
 
 struct WMem {
-    uint32_t* prof;       // LDS: W_PROF_WORDS
+    uint32_t* prof;       // LDS: RS_PROF_WORDS
     const int* mat;       // LDS: [6 reference codes][8 query codes]
     uint32_t* bnd;        // HBM: boundary rows of the chunk, [W_NB][2 (Hm, Hf)][CPR][64 lanes] packed registers
     short* cH;            // HBM: [2][rows_cap]: final H of the chunk's last column per row (parity of the chunk)
@@ -73,8 +58,6 @@ template <int CPR, bool GEQ, bool WORD, bool TR = false>
 __device__ bool scanw_chunk(const WIn& in, const WMem& mem, const int c0, const int parity, const bool first, const bool more,
                             const int gapO, const int gapE, int& best_score, int& best_col, int& best_row, int& tcol)
 {
-    constexpr int VEC = CPR < 4 ? CPR : 4;       // registers per LDS read
-    constexpr int NCH = CPR / VEC;
     constexpr bool QUIRK = WORD && GEQ;
     const int lane = threadIdx.x & 63;
     const int K = CPR * gapE;                    // what a gap loses across one virtual lane
@@ -84,35 +67,8 @@ __device__ bool scanw_chunk(const WIn& in, const WMem& mem, const int c0, const 
 #pragma unroll
     for (int t = 0; t < CPR; ++t) tgE[t] = dup16(t * gapE);
 
-    // ---- profile of the chunk's columns: prof[q][c][lane][VEC], entry = scores of the row base q against the two columns
-    {
-        int rlo[CPR], rhi[CPR];
-#pragma unroll
-        for (int t = 0; t < CPR; ++t) {
-            const int jlo = c0 + 2 * CPR * lane + t, jhi = jlo + CPR;
-            const int blo = jlo < in.ncols ? (int)in.ref[(int64_t)jlo * in.cstep] : 0, bhi = jhi < in.ncols ? (int)in.ref[(int64_t)jhi * in.cstep] : 0;
-            if constexpr (TR) {      // a column is a read base: its code as the row loop of the plain form takes it
-                const int clo = blo & 7, chi = bhi & 7;
-                rlo[t] = jlo < in.ncols ? (clo > 5 ? 5 : clo) : 5;
-                rhi[t] = jhi < in.ncols ? (chi > 5 ? 5 : chi) : 5;
-            } else {
-                rlo[t] = jlo < in.ncols ? ref_code(blo, in.comp) : 5;
-                rhi[t] = jhi < in.ncols ? ref_code(bhi, in.comp) : 5;
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < 6; ++q)
-#pragma unroll
-            for (int t = 0; t < CPR; ++t) {
-                // mat is [reference code][read code]: transposed, the row letter q is the reference's
-                const int slo = TR ? mem.mat[q * 8 + rlo[t]] : mem.mat[rlo[t] * 8 + q], shi = TR ? mem.mat[q * 8 + rhi[t]] : mem.mat[rhi[t] * 8 + q];
-                mem.prof[((q * NCH + t / VEC) * 64 + lane) * VEC + (t % VEC)] = (uint32_t)(slo & 0xffff) | ((uint32_t)shi << 16);
-            }
-    }
-    const short* cHin = mem.cH + (parity ^ 1) * mem.rows_cap;
-    const short* cEin = mem.cE + (parity ^ 1) * mem.rows_cap;
-    short* cHout = mem.cH + parity * mem.rows_cap;
-    short* cEout = mem.cE + parity * mem.rows_cap;
+    rs_profile_fill<CPR, TR>(in, mem.mat, mem.prof, c0);
+    const RsHand hand(mem.cH, mem.cE, parity, mem.rows_cap);
     __syncthreads();
 
     uint32_t Hp[CPR], Hd[QUIRK ? CPR : 1], Fst[GEQ ? 1 : CPR], cmv[CPR], cmr[CPR];
@@ -125,12 +81,9 @@ __device__ bool scanw_chunk(const WIn& in, const WMem& mem, const int c0, const 
     for (int rb = 0; rb < in.rows && !overflow; rb += 64) {
         const int row = rb + lane;
         int qv = 5;
-        if (row < in.L) {
-            if constexpr (TR) qv = ref_code((int)in.read[(int64_t)row * in.rstep], in.rcomp);
-            else { const int c = (int)in.read[(int64_t)row * in.rstep] & 7; qv = c > 5 ? 5 : c; }
-        }
-        int hbv = 0, ebv = 0;
-        if (!first && row < in.rows) { hbv = cHin[row]; ebv = cEin[row]; }
+        if (row < in.L) qv = TR ? ref_code((int)in.read[(int64_t)row * in.rstep], in.rcomp) : rs_read_code((int)in.read[(int64_t)row * in.rstep]);
+        int hbv, ebv;
+        hand.load(first, row, in.rows, hbv, ebv);
         const int cnt = in.rows - rb < 64 ? in.rows - rb : 64;
         int cobH = 0, cobE = 0;
         // one row.  SLOW (the word regime with gap_open == gap_extend only): the rows around a stripe boundary -- `bnd`: a boundary
@@ -138,50 +91,20 @@ __device__ bool scanw_chunk(const WIn& in, const WMem& mem, const int c0, const 
         auto step = [&](const int i, auto slow_c, const bool bnd, const bool dd) {
             constexpr bool SLOW = decltype(slow_c)::value;
             const int q = __builtin_amdgcn_readlane(qv, i), hb = __builtin_amdgcn_readlane(hbv, i), eb = __builtin_amdgcn_readlane(ebv, i);
-            uint32_t P[CPR];
-            {
-                const uint32_t* pp = mem.prof + (q * NCH * 64 + lane) * VEC;
+            uint32_t P[CPR], R[CPR], U;
+            rs_profile_row<CPR>(mem.prof, q, lane, P);
+            if constexpr (SLOW) {
+                uint32_t dsrc[CPR];
 #pragma unroll
-                for (int c = 0; c < NCH; ++c) {
-                    if constexpr (VEC == 4) { const uint4 v = *(const uint4*)(pp + c * 64 * VEC); P[4 * c] = v.x; P[4 * c + 1] = v.y; P[4 * c + 2] = v.z; P[4 * c + 3] = v.w; }
-                    else { const uint2 v = *(const uint2*)(pp + c * 64 * VEC); P[0] = v.x; P[1] = v.y; }
-                }
-            }
-            uint32_t dsrc[CPR];
-#pragma unroll
-            for (int t = 0; t < CPR; ++t) { dsrc[t] = Hp[t]; if constexpr (SLOW) dsrc[t] = dd ? Hd[t] : Hp[t]; }
-            const uint32_t d0 = hand_down(dsrc[CPR - 1], prev_hb);
-            uint32_t R[CPR];
-            uint32_t e = 0, U;
-#pragma unroll
-            for (int t = 0; t < CPR; ++t) {
-                const uint32_t tt = pk_adds(t == 0 ? d0 : dsrc[t - 1], P[t]);
-                uint32_t X;
-                if constexpr (GEQ) {
-                    uint32_t Fv = pk_subus(Hp[t], gO2);
-                    if constexpr (SLOW) Fv = bnd ? 0u : Fv;                           // a boundary row: the gap from the row above stays out of the main value
-                    X = pk_max(tt, Fv);
-                } else { const uint32_t Fv = pk_max(pk_subus(Fst[t], gE2), pk_subus(Hp[t], gO2)); Fst[t] = Fv; X = pk_max(tt, Fv); }
-                if (t == 0) R[0] = X;
-                else if constexpr (GEQ) R[t] = pk_max(X, pk_subus(R[t - 1], gO2));
-                else { e = pk_max(pk_subus(e, gE2), pk_subus(R[t - 1], gO2)); R[t] = pk_max(X, e); }
-            }
-            if (GEQ) U = pk_subus(R[CPR - 1], gO2);
-            else U = pk_max(pk_subus(e, gE2), pk_subus(R[CPR - 1], gO2));
-            const int Blo = (int)(U & 0xffffu) + kLo, Bhi = (int)(U >> 16) + kLo + K;
-            const int inc = wave_prefix_max(Blo > Bhi ? Blo : Bhi);
-            const int fill = eb - K;
-            int exc = dpp_shr1(fill, inc);
-            exc = exc > fill ? exc : fill;
-            const int einLo = exc - kLo + K;
-            const int m2 = exc > Blo ? exc : Blo;
-            const int einHi = m2 - kLo;
-            const uint32_t Ein = ((uint32_t)einLo & 0xffffu) | ((uint32_t)einHi << 16);
+                for (int t = 0; t < CPR; ++t) dsrc[t] = dd ? Hd[t] : Hp[t];
+                U = rs_row<CPR, GEQ, true>(dsrc, prev_hb, Hp, Fst, P, gO2, gE2, R, bnd);       // a boundary row: the gap from the row above stays out of the main value
+            } else U = rs_row<CPR, GEQ>(Hp, prev_hb, Hp, Fst, P, gO2, gE2, R);
+            const RsCarry cy = rs_lane_carry(U, eb, K, kLo);
             const uint32_t rowc = dup16(rb + i);
             uint32_t last = 0;
 #pragma unroll
             for (int t = 0; t < CPR; ++t) {
-                const uint32_t h = pk_max(R[t], pk_subs(Ein, tgE[t]));
+                const uint32_t h = pk_max(R[t], pk_subs(cy.Ein, tgE[t]));
                 bool keyed = true;
                 if constexpr (SLOW) {
                     if (bnd) {
@@ -204,13 +127,7 @@ __device__ bool scanw_chunk(const WIn& in, const WMem& mem, const int c0, const 
                 if (t == CPR - 1) { last = h; if constexpr (SLOW) last = bnd ? Hd[t] : h; }
             }
             prev_hb = hb;
-            if (more) {   // the chunk's last column: final H, and the E that enters the next chunk's first column
-                const int outH = (int)((uint32_t)__builtin_amdgcn_readlane((int)last, 63) >> 16);
-                int outE = __builtin_amdgcn_readlane(inc, 63);
-                outE = (outE > fill ? outE : fill) - 127 * K;
-                outE = outE < 0 ? 0 : outE;
-                const uint32_t li = lane_is(lane, i); cobH = set_lane(cobH, outH, li); cobE = set_lane(cobE, outE, li);
-            }
+            if (more) rs_handover_out(last, cy, K, i, cobH, cobE);      // (the FINAL H of the chunk's last column)
         };
         int i = 0;
         while (i < cnt) {
@@ -227,7 +144,7 @@ __device__ bool scanw_chunk(const WIn& in, const WMem& mem, const int c0, const 
                 }
             }
         }
-        if (more && lane < cnt) { cHout[rb + lane] = (short)cobH; cEout[rb + lane] = (short)cobE; }
+        hand.store(more, rb, cnt, cobH, cobE);
         if constexpr (!WORD) {   // byte regime: a column maximum at 255 - bias abandons the pass
             uint32_t mx = cmv[0];
 #pragma unroll
@@ -387,7 +304,7 @@ __device__ bool scanw_align_tr(const SswParams& p, const int8_t* read, const int
 // bytes of HBM workspace of one K1w task (SswTask.dir_off into SswParams.dirs): boundary rows of a chunk + the two hand-over arrays
 size_t scanw_task_bytes(int read_len) {
     const size_t rows_cap = ((size_t)read_len + 16 + 63) & ~(size_t)63;
-    return (size_t)W_NB * 2 * W_CPR_MAX * 64 * 4 + 2 * 2 * rows_cap * 2 + 256;
+    return (size_t)W_NB * 2 * RS_CPR_MAX * 64 * 4 + 2 * 2 * rows_cap * 2 + 256;
 }
 
 // Which forward pass first?  The reference runs the byte pass and, if a cell reached 255 - bias, the word pass (ssw.c:804-809).  The
@@ -499,18 +416,17 @@ __device__ __forceinline__ void scanw_mem_at(WMem& mem, uint8_t* ws, int L)
 {
     mem.rows_cap = (int)((((size_t)L + 16 + 63) & ~(size_t)63));
     mem.bnd = (uint32_t*)ws;
-    mem.cH = (short*)(mem.bnd + W_NB * 2 * W_CPR_MAX * 64);
+    mem.cH = (short*)(mem.bnd + W_NB * 2 * RS_CPR_MAX * 64);
     mem.cE = mem.cH + 2 * mem.rows_cap;
 }
 
 #define SCANW_LDS_SETUP \
-    __shared__ __attribute__((aligned(16))) uint32_t s_prof[W_PROF_WORDS]; \
+    __shared__ __attribute__((aligned(16))) uint32_t s_prof[RS_PROF_WORDS]; \
     __shared__ int s_mat[48]; \
     const int lane = threadIdx.x & 63; \
-    if (lane < 48) { const int b = lane >> 3, q = lane & 7; s_mat[lane] = (b < p.n && q < p.n) ? (int)p.mat[b * p.n + q] : 0; } \
-    __syncthreads(); \
     WMem mem; \
-    mem.prof = s_prof; mem.mat = s_mat;
+    mem.prof = s_prof; mem.mat = s_mat; \
+    rs_stage_matrix(p.mat, p.n, s_mat);
 
 // persistent workgroups pull the class's tasks (heaviest first) from a counter; the HBM workspace belongs to the workgroup, not to the
 // task (a batch of a million alignments needs no more of it than one of three thousand)
@@ -519,11 +435,7 @@ __global__ void __launch_bounds__(64, SCANW_WAVES) ssw_scanw_kernel(const SswPar
 {
     SCANW_LDS_SETUP
     uint8_t* const ws = p.dirs + ws_off + (long long)blockIdx.x * ws_slot;
-    for (;;) {
-        int idx = 0;
-        if (lane == 0) idx = atomicAdd(counter, 1);
-        idx = __builtin_amdgcn_readfirstlane(idx);
-        if (idx >= ntasks) break;
+    for (int idx; (idx = rs_next(counter)) < ntasks;) {
         const SswTask task = p.tasks[idx];
         scanw_mem_at(mem, ws, task.read_len);
         SswResult res;
@@ -540,11 +452,7 @@ __global__ void __launch_bounds__(64, SCANW_WAVES) ssw_scanw_tr_kernel(const Ssw
 {
     SCANW_LDS_SETUP
     uint8_t* const ws = p.dirs + ws_off + (long long)blockIdx.x * ws_slot;
-    for (;;) {
-        int idx = 0;
-        if (lane == 0) idx = atomicAdd(counter, 1);
-        idx = __builtin_amdgcn_readfirstlane(idx);
-        if (idx >= ntasks) break;
+    for (int idx; (idx = rs_next(counter)) < ntasks;) {
         const SswTask task = p.tasks[idx];
         scanw_mem_at(mem, ws, 64);
         SswResult res;
@@ -630,11 +538,7 @@ __global__ void __launch_bounds__(64, SCANW_WAVES) ssw_scanw_queue_kernel(const 
     const int total = count_arg >= 0 ? count_arg : p.pf_ctl->qcount;
     int* const next = count_arg >= 0 ? &p.pf_ctl->seed_next : &p.pf_ctl->qnext;
     uint8_t* const ws = p.dirs + p.ws_dirs_off + (int64_t)blockIdx.x * p.ws_slot_bytes;
-    for (;;) {
-        int idx = 0;
-        if (lane == 0) idx = atomicAdd(next, 1);
-        idx = __builtin_amdgcn_readfirstlane(idx);
-        if (idx >= total) break;
+    for (int idx; (idx = rs_next(next)) < total;) {
         const WsTask wt = p.ws_tasks[first + idx];
         if (wt.task < 0) continue;
         const SswTask task = p.tasks[wt.task];
@@ -657,14 +561,12 @@ __global__ void __launch_bounds__(64) ssw_scanw_pick_kernel(const SswParams p)
     const SswTask task = p.tasks[a];
     const PfWin pt = p.pf_win[a];
     const int R = task.ref_len, L = task.read_len;
-    const int span = L + (L * p.max_match + p.gapE - 1) / p.gapE;
-    const int overlap = span + 32;
-    int own = (R + 63) / 64; own = own < 8192 ? 8192 : own; own = own < 2 * overlap ? 2 * overlap : own;
-    const int nstatic = (R + own - 1) / own;
+    const RsSlices ss = rs_static_slices<true>(p, R, L);
     SswResult* const rows = p.results + p.ws_row0 + a * kWsRows;
     const int ub = p.pf_out[a].s0, seed_block = p.pf_out[a].first;
     // mode 1: tasks as they come (byte first); 2: word regime only; 3: both
-    int mode = 3, S0 = 0, thr = 0, nrun = 0, pruned = 0, ov_c = overlap;
+    int mode = 3, S0 = 0;
+    RsPick pk; pk.ov_c = ss.overlap;
     const uint16_t* D = p.ws_bound ? p.ws_bound + pt.d_off : nullptr;
     if (p.score_size == 1) mode = 1;             // the caller asked for the word pass alone: one regime by construction
     if (p.pf_dmin) {
@@ -673,73 +575,25 @@ __global__ void __launch_bounds__(64) ssw_scanw_pick_kernel(const SswParams p)
         else if (r0.status & CLH_STATUS_WORD) { mode = 2; S0 = r0.score1; }
         else { mode = 3; S0 = rows[1].score1; }
         if (r0.status & CLH_STATUS_OVERFLOW8) S0 = 0;      // score_size 0 and an overflow: the whole window decides (static slices)
-        if (S0 > 0) {
-            const int cc = p.max_match < p.gapE ? p.max_match : p.gapE;
-            thr = (p.max_match * L - S0) / cc;
-            // (an alignment that scores S0 or more spans at most L + (M L - S0) / gapE columns: the candidate regions start that far early)
-            const int span_s0 = L + (p.max_match * L - S0) / p.gapE + 32;
-            ov_c = span_s0 < overlap ? span_s0 : overlap;
-            long long cost = 0;
-            for (int g = 0; g < pt.nsub; g += 64) {
-                const int k = g + lane;
-                const unsigned long long m = __ballot(k < pt.nsub && (int)D[k] <= thr);
-                nrun += __popcll(m & ~(m << 1));
-                cost += (long long)__popcll(m) * kPfBlock;
-            }
-            cost += (long long)nrun * ov_c;
-            pruned = nrun <= 64 && cost < (long long)R + (long long)nstatic * overlap;
-        }
+        if (S0 > 0) pk = rs_pick_count(p, D, pt.nsub, R, L, S0, ss, 64);      // (at most 64 candidate regions: the alignment's scratch rows, kWsRows)
     }
-    const int count = pruned ? nrun : nstatic;
+    const int count = pk.pruned ? pk.nrun : ss.nstatic;
     const int per = mode == 3 ? 2 : 1;
-    int first = 0;
-    if (lane == 0) {
-        first = atomicAdd(&p.pf_ctl->qcount, count * per);
-        if (pruned) atomicAdd(&p.pf_ctl->n_pruned, 1);
-        atomicAdd(&p.pf_ctl->cols_window, (unsigned long long)R);
-    }
-    first = __builtin_amdgcn_readfirstlane(first);
-    WsTask* q = p.ws_tasks + 2 * gridDim.x + first;
+    WsTask* q = p.ws_tasks + 2 * gridDim.x + rs_pick_reserve(p, count * per, pk.pruned, R);
     unsigned long long cols = 0;
-    // reuse: the run is the seed block alone -- its region is the seed's, whose rows are there already (the seed that overflowed IS
-    // the word-regime row: the byte pass was abandoned and the word pass ran)
-    auto emit = [&](int k, int b0, int b1, bool reuse) {
+    // region k of the alignment owns [b0, b1) and starts ov columns early.  reuse: the run is the seed block alone -- its region is the
+    // seed's, whose rows are there already (the seed that overflowed IS the word-regime row: the byte pass was abandoned and the word pass ran)
+    auto emit = [&](const int k, const int b0, const int b1, const int ov, const bool reuse) {
         WsTask t;
-        const int ovx = pruned ? ov_c : overlap;
-        t.task = reuse ? -1 : a; t.c_begin = b0 - ovx < 0 ? 0 : b0 - ovx; t.c_end = b1; t.pad0 = t.pad1 = t.pad2 = 0;
+        t.task = reuse ? -1 : a; t.c_begin = b0 - ov < 0 ? 0 : b0 - ov; t.c_end = b1; t.pad0 = t.pad1 = t.pad2 = 0;
         if (mode != 2) { t.row = 2 + 2 * k; t.force_word = 0; q[per * k] = t; if (reuse) rows[2 + 2 * k] = rows[0]; }
         if (mode != 1) { t.row = 3 + 2 * k; t.force_word = 1; q[per * k + per - 1] = t; if (reuse) rows[3 + 2 * k] = rows[mode == 2 ? 0 : 1]; }
         if (!reuse) cols += (unsigned long long)(t.c_end - t.c_begin) * per;
     };
-    if (pruned) {
-        int done = 0;
-        for (int g = 0; g < pt.nsub; g += 64) {
-            const int k = g + lane;
-            const unsigned long long m = __ballot(k < pt.nsub && (int)D[k] <= thr);
-            const unsigned long long starts = m & ~(m << 1);
-            if ((starts >> lane) & 1ull) {
-                const unsigned long long rest = ~(m >> lane);
-                const int len = rest ? __builtin_ctzll(rest) : 64 - lane;
-                const int rank = done + __popcll(starts & ((1ull << lane) - 1ull));
-                int b0 = k * kPfBlock - pt.phase, b1 = (k + len) * kPfBlock - pt.phase;
-                b0 = b0 < 0 ? 0 : b0; b1 = b1 > R ? R : b1;
-                emit(rank, b0, b1, len == 1 && k == seed_block);
-            }
-            done += __popcll(starts);
-        }
-    } else {
-        for (int sidx = lane; sidx < nstatic; sidx += 64) {
-            const long long b = (long long)sidx * own;
-            emit(sidx, (int)b, (int)(b + own > R ? R : b + own), false);
-        }
-    }
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) cols += __shfl_xor(cols, d);
-    if (lane == 0) {
-        atomicAdd(&p.pf_ctl->cols_scanned, cols);
-        PfOut o; o.first = mode; o.count = count; o.s0 = S0; o.pruned = pruned;
-        p.pf_out[a] = o;
-    }
+    if (pk.pruned) rs_for_each_run(D, pt.nsub, pk.thr, pt.phase, R, [&](int rank, int b0, int b1, int len, int k) { emit(rank, b0, b1, pk.ov_c, len == 1 && k == seed_block); });
+    else rs_for_each_static(ss, R, [&](int k, int b0, int b1) { emit(k, b0, b1, ss.overlap, false); });
+    PfOut o; o.first = mode; o.count = count; o.s0 = S0; o.pruned = pk.pruned;
+    rs_pick_close(p, cols, o);
 }
 
 __global__ void __launch_bounds__(64) ssw_scanw_combine_kernel(const SswParams p)
@@ -756,25 +610,16 @@ __global__ void __launch_bounds__(64) ssw_scanw_combine_kernel(const SswParams p
         if (lane < po.count) ov = (rows[2 + 2 * lane].status & (CLH_STATUS_WORD | CLH_STATUS_OVERFLOW8)) != 0;
         use_word = __ballot(ov) != 0ull;
     }
-    int v = -1, c = 0x7fffffff, k = 0x7fffffff;
+    int v = -1, c = W_INF, k = W_INF;
     if (lane < po.count) {
         const SswResult r = rows[2 + 2 * lane + (use_word ? 1 : 0)];
         v = r.score1; k = lane;
-        c = r.score1 > 0 ? r.ref_end1 + r.ref_end2 : 0x7fffffff;
+        c = r.score1 > 0 ? r.ref_end1 + r.ref_end2 : W_INF;
     }
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int v2 = __shfl_xor(v, d), c2 = __shfl_xor(c, d), k2 = __shfl_xor(k, d);
-        const bool take = v2 > v || (v2 == v && (c2 < c || (c2 == c && k2 < k)));
-        v = take ? v2 : v; c = take ? c2 : c; k = take ? k2 : k;
-    }
+    rs_best_of(v, c, k);
     if (lane == 0) {
         SswResult r = rows[2 + 2 * k + (use_word ? 1 : 0)];
-        const int base = r.ref_end2;
-        if (r.score1 > 0) {
-            r.ref_end1 += base;
-            if (r.ref_begin1 >= 0) r.ref_begin1 += base;
-        }
+        rs_shift_row(r, r.ref_end2);
         r.ref_end2 = task.mask_len >= 15 ? 0 : -1;
         // score_size 0 and an overflow somewhere in the window: the reference returns NULL (ssw.c:810-813)
         if (p.score_size == 0) {
@@ -789,33 +634,31 @@ __global__ void __launch_bounds__(64) ssw_scanw_combine_kernel(const SswParams p
 // (the first stage of the prefilter has been launched by the caller when with_prefilter is set)
 hipError_t launch_ssw_scanw_filtered(bool geq, const SswParams& p, int ntasks, int nworkgroups, bool with_prefilter, hipStream_t stream)
 {
-    if (geq) {
-        hipLaunchKernelGGL((ssw_scanw_seed_kernel<true>), dim3(ntasks), dim3(64), 0, stream, p);
-        if (with_prefilter) hipLaunchKernelGGL((ssw_scanw_queue_kernel<true>), dim3(std::min(nworkgroups, 2 * ntasks)), dim3(64), 0, stream, p, 0, 2 * ntasks);
-        hipLaunchKernelGGL((ssw_scanw_pick_kernel<true>), dim3(ntasks), dim3(64), 0, stream, p);
-        hipLaunchKernelGGL((ssw_scanw_queue_kernel<true>), dim3(nworkgroups), dim3(64), 0, stream, p, 2 * ntasks, -1);
-    } else {
-        hipLaunchKernelGGL((ssw_scanw_seed_kernel<false>), dim3(ntasks), dim3(64), 0, stream, p);
-        if (with_prefilter) hipLaunchKernelGGL((ssw_scanw_queue_kernel<false>), dim3(std::min(nworkgroups, 2 * ntasks)), dim3(64), 0, stream, p, 0, 2 * ntasks);
-        hipLaunchKernelGGL((ssw_scanw_pick_kernel<false>), dim3(ntasks), dim3(64), 0, stream, p);
-        hipLaunchKernelGGL((ssw_scanw_queue_kernel<false>), dim3(nworkgroups), dim3(64), 0, stream, p, 2 * ntasks, -1);
-    }
-    hipLaunchKernelGGL(ssw_scanw_combine_kernel, dim3(ntasks), dim3(64), 0, stream, p);
-    return hipGetLastError();
+    return with_geq(geq, [&](auto g) {
+        constexpr bool G = decltype(g)::value;
+        hipLaunchKernelGGL((ssw_scanw_seed_kernel<G>), dim3(ntasks), dim3(64), 0, stream, p);
+        if (with_prefilter) hipLaunchKernelGGL((ssw_scanw_queue_kernel<G>), dim3(std::min(nworkgroups, 2 * ntasks)), dim3(64), 0, stream, p, 0, 2 * ntasks);
+        hipLaunchKernelGGL((ssw_scanw_pick_kernel<G>), dim3(ntasks), dim3(64), 0, stream, p);
+        hipLaunchKernelGGL((ssw_scanw_queue_kernel<G>), dim3(nworkgroups), dim3(64), 0, stream, p, 2 * ntasks, -1);
+        hipLaunchKernelGGL(ssw_scanw_combine_kernel, dim3(ntasks), dim3(64), 0, stream, p);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_ssw_scanw_tr(bool geq, const SswParams& p, int ntasks, int nworkgroups, int* counter, long long ws_off, int ws_slot, hipStream_t stream)
 {
-    if (geq) hipLaunchKernelGGL((ssw_scanw_tr_kernel<true>), dim3(nworkgroups), dim3(64), 0, stream, p, ntasks, counter, ws_off, ws_slot);
-    else hipLaunchKernelGGL((ssw_scanw_tr_kernel<false>), dim3(nworkgroups), dim3(64), 0, stream, p, ntasks, counter, ws_off, ws_slot);
-    return hipGetLastError();
+    return with_geq(geq, [&](auto g) {
+        hipLaunchKernelGGL((ssw_scanw_tr_kernel<decltype(g)::value>), dim3(nworkgroups), dim3(64), 0, stream, p, ntasks, counter, ws_off, ws_slot);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_ssw_scanw(bool geq, const SswParams& p, int ntasks, int nworkgroups, int* counter, long long ws_off, int ws_slot, hipStream_t stream)
 {
-    if (geq) hipLaunchKernelGGL((ssw_scanw_kernel<true>), dim3(nworkgroups), dim3(64), 0, stream, p, ntasks, counter, ws_off, ws_slot);
-    else hipLaunchKernelGGL((ssw_scanw_kernel<false>), dim3(nworkgroups), dim3(64), 0, stream, p, ntasks, counter, ws_off, ws_slot);
-    return hipGetLastError();
+    return with_geq(geq, [&](auto g) {
+        hipLaunchKernelGGL((ssw_scanw_kernel<decltype(g)::value>), dim3(nworkgroups), dim3(64), 0, stream, p, ntasks, counter, ws_off, ws_slot);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace clh

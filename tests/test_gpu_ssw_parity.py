@@ -927,3 +927,58 @@ def test_long_reads_on_long_windows_behind_the_prefilter_vs_oracle(ctx, scheme):
                 continue
             got = (int(r2['score1']), int(r2['ref_begin1']), int(r2['ref_end1']), int(r2['read_begin1']), int(r2['read_end1']))
             assert got == (want['score'], want['ref_begin'], want['ref_end'], want['query_begin'], want['query_end']), (ss, k, len(q), got)
+
+
+_WIDE_EDGE_R = [255, 256, 257, 511, 512, 513, 1023, 1024, 1025, 1300, 2049, 3100]
+_WIDE_EDGE_L = [255, 256, 300, 440, 441, 600, 1000]
+
+
+def _wide_chunk_edge_cases():
+    """(windows, reads) for test_row_scan_wide_chunk_edges_vs_oracle: every window width against every read length; by turns a copy of a
+    window stretch with 5 % of its bases mutated, one with 20 %, and an unrelated read -- one of those against a window with an N run, one
+    with its clip planted twice.  Every read has exactly its length L (the copy sits between random flanks)."""
+    rng = np.random.default_rng(4100)
+    refs, qs = [], []
+    for R in _WIDE_EDGE_R:
+        for L in _WIDE_EDGE_L:
+            k = len(qs)
+            ref = _rnd(rng, R)
+            if k % 3 < 2:
+                n = min(L, R - 10)
+                st = int(rng.integers(0, R - n + 1))
+                core = _mut(ref[st:st + n], rng, 0.05 if k % 3 == 0 else 0.2)[:L]
+                a = int(rng.integers(0, L - len(core) + 1))
+                q = _rnd(rng, a) + core + _rnd(rng, L - a - len(core))
+            else:
+                q = _rnd(rng, L)
+                if k == 8:                       # an N run in the window
+                    ref = ref[:R // 3] + 'N' * 7 + ref[R // 3 + 7:]
+                if k == 44:                      # a clip of the read twice in the window: the first end column wins (ssw.c:283)
+                    ref = ref[:100] + q[50:250] + ref[300:500] + q[50:250] + ref[700:]
+            assert len(q) == L and len(ref) == R
+            refs.append(ref); qs.append(q)
+    return refs, qs
+
+
+@pytest.mark.parametrize('scheme', [(1, 1, 1, 1), (2, 2, 3, 1), (10, 4, 8, 2)])
+def test_row_scan_wide_chunk_edges_vs_oracle(ctx, scheme):
+    """K1w (csrc/ssw_scan_wide.hip) where its chunks meet: windows on and around the chunk widths (256 / 512 / 1024 columns) and of several
+    chunks -- the hand-over of the last column through HBM, and with 1/1/1/1 the word regime's stripe-boundary rows at a chunk seam -- against
+    reads of 255..1000 bases; 440 and 441 bases straddle the reverse pass's first-chunk width (L + L/8 + 16) at 512.  With and without the
+    second-best score; every alignment runs in class -3."""
+    from ciri_long_amd import hip
+    m, x, o, e = scheme
+    refs, qs = _wide_chunk_edge_cases()
+    want = [oracle_align(ref, q, *scheme) for ref, q in zip(refs, qs)]
+    if scheme == (1, 1, 1, 1):                   # both regimes: the byte pass stands, and it overflows (score + bias >= 255, ssw.c:804-809)
+        assert any(w['score'] + 1 >= 255 for w in want) and any(w['score'] + 1 < 255 for w in want)
+    rd, ro = hip.pack(qs); fd, fo = hip.pack(refs)
+    for s2 in (True, False):
+        plan = ctx.plan(ro, fo, hip.score_matrix(m, x), o, e, flag=1, score_size=2, want_score2=s2, want_cigar=False)
+        assert sum(c for rv, c, _a, _b in plan.segments() if rv == -3) == len(qs)
+        plan.close()
+        rows, _ = ctx.ssw_batch(rd, ro, fd, fo, hip.score_matrix(m, x), o, e, want_score2=s2, want_cigar=False)
+        for k, (w, r) in enumerate(zip(want, rows)):
+            got = _row_tuple(r)
+            exp = (w['score'], w['score2'] if s2 else 0, w['ref_begin'], w['ref_end'], w['query_begin'], w['query_end'], w['ref_end2'] if s2 else got[6])
+            assert got == exp, (k, len(qs[k]), len(refs[k]), s2, got, exp)

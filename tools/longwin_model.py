@@ -2,7 +2,8 @@
 region, the WINDOW's regime decided as ssw.c:804-809 decides it, candidate regions as complete alignments of the read against a stretch
 of the window, the best row.  A region task is `align(window[cb:ce], read, score_size)` -- the caller passes the checker (the oracle:
 score_size 2 = the reference's order of passes, 1 = the word pass alone, as K1w's force_word) -- so the model states exactly the
-decision logic the kernels implement and tests/test_longwin_model.py holds it to the whole-window answer.
+decision logic the kernels implement (ssw_scanw_pick_kernel, ssw_scanw_combine_kernel; the candidate runs and the static slices they
+share with K1s: csrc/ssw_rowscan.h, rs_pick_count and rs_static_slices) and tests/test_longwin_model.py holds it to the whole-window answer.
 
 Which regime (the reference decides on the whole window: any column at 255 - bias in the byte pass):
   mode 1  M L - c min D + bias < 255: no cell of the window can overflow -- byte regime, tasks as they come;

@@ -159,7 +159,8 @@ def prefilter_forward(ref, read, mat, n, gapO, gapE, phase=0, cap=None, chunk=25
     # (when the second stage is worth its cost is a matter of time only -- the kernel: candidates over an eighth of the window and a threshold
     # below what the indel distance is on random text, ~0.55 L; stage2_always: whenever the first stage leaves anything, for the tests)
     if two_stage and S0 > 0 and (stage2_always or ((len(runs) > cap or cost >= R + nstatic * overlap or cost > R // stage2_share) and 20 * thr < 11 * L)):
-        # the unit-cost bound leaves too much of the window: the indel distance over it (csrc/ssw_scan.hip: pf_pick_emit, ssw_scan_pick2_kernel)
+        # the unit-cost bound leaves too much of the window: the indel distance over it (csrc/ssw_scan.hip: pf_pick_emit, ssw_scan_pick2_kernel;
+        # the runs, their cost and the cap: csrc/ssw_rowscan.h, rs_pick_count)
         info['second_stage'] = True
         dmin = block_minima(indel_semiglobal(ref, read, mat, n, gapE), phase)
         runs = candidate_runs(dmin, thr)
@@ -190,7 +191,8 @@ def prefilter_forward(ref, read, mat, n, gapO, gapE, phase=0, cap=None, chunk=25
 # 0 <= M L_k - c d_k(anything).  Hence
 #        H(j) <= sum over k of ( M L_k - c min over j' in [j - span, j] of d_k(j') )  =  M L - c D(j),
 # and per block of columns D(block b) >= sum over k of the minimum of piece k's block minima over blocks b - sb .. b,
-# sb = ceil(span / 256).  csrc/ssw_scan_wide.hip (ssw_scanw_seed_kernel / ssw_scanw_pick_kernel) uses exactly this sum.
+# sb = ceil(span / 256).  csrc/ssw_scan_wide.hip (ssw_scanw_seed_kernel / ssw_scanw_pick_kernel,
+# the runs through csrc/ssw_rowscan.h: rs_pick_count, rs_for_each_run) uses exactly this sum.
 def piece_rows(L, max_rows=254):
     """row ranges [(row0, rows)] of the pieces: as few as fit max_rows, equal sizes"""
     K = (L + max_rows - 1) // max_rows

@@ -1,4 +1,4 @@
-"""numpy model of K1s (csrc/ssw_scan.hip): the 8-bit Smith-Waterman pass walked row by row with the reference columns in
+"""numpy model of K1s (csrc/ssw_scan.hip: scan_chunk, scan_pass; the row step they share with K1w: csrc/ssw_rowscan.h): the 8-bit Smith-Waterman pass walked row by row with the reference columns in
 parallel -- the horizontal gap E as a prefix maximum in the frame where an extension costs nothing, per column the running
 maximum over the rows kept as (H << 8 | 255 - row), the window in chunks that hand their last column to the next chunk, and
 the forward pass of a long window cut into overlapping slices.  tests/test_scan_model.py holds it to the oracle
