@@ -16,6 +16,7 @@
 #include "../../include/ciri_long_hip.h"
 #include "../../include/ssw_legacy.h"
 #include "clh_device.h"
+#include "ssw_pairs.h"
 
 static thread_local std::string g_err;
 static thread_local int g_code = CLH_E_ARG;            // the code of the last failure: what a batch call returns when its plan was refused
@@ -2347,6 +2348,8 @@ struct clh_ends_plan : clh_pairs_plan {
     std::vector<clh::EnPair> pairs;
     int64_t hand_words = 0;
     void* d_hand = nullptr;
+    bool recompute = false;                       // CIGARs by the recompute route (CLH_ENDS_CIGAR_RECOMPUTE): a share's block holds EnKept blocks
+    std::vector<int> share_rounds;                // recompute: per share, the greatest chunk count among its pairs
     void *d_site = nullptr, *d_strand = nullptr;  // spliced: the site costs of both strands and the pairs' strands (null: all +)
 };
 
@@ -2441,20 +2444,33 @@ static clh_ends_plan* en_create(const std::string& me, clh_ctx* ctx, int32_t n, 
     }
     std::vector<clh::EnPair> pairs;
     int64_t hand_words = 0;
+    const bool recompute = o->want_cigar == CLH_ENDS_CIGAR_RECOMPUTE;
     if (pairs_cut_shares(me, o, n, q_off, r_off, &shape, &pairs,
             [&](int, clh::EnPair& p, bool kernel) {
                 p.pad = 0; p.hand_off = -1;
+                // recompute: every chunk's last column is kept in the pair's block of the workspace, beside one chunk's plane and the walk's record
+                if (recompute) return kernel ? clh::EnKept(p.m, p.n, 1 + pieces, 4 * pieces).total : 0;
                 // two buffers of H and one E per piece of the last column, per row
                 if (kernel && p.n > clh::kEnChunk) { p.hand_off = hand_words; hand_words += 2 * (1 + pieces) * (((int64_t)p.m + 63) & ~(int64_t)63); }
                 return kernel ? en_ws_bytes(p.m, p.n, pieces) : 0;
             },
-            [](const clh::EnPair& p) { return std::to_string(p.m) + " x " + std::to_string(p.n) + " cells"; }))
+            [&](const clh::EnPair& p) {
+                return std::to_string(p.m) + " x " + std::to_string(p.n) + " cells" +
+                       (recompute ? std::string(" (recompute route: kept chunk columns, one chunk's plane and the walk's record)") : std::string());
+            }))
         return nullptr;
     if (hipSetDevice(ctx->device) != hipSuccess) { fail(CLH_E_HIP, "hipSetDevice failed"); return nullptr; }
     clh_ends_plan* pl = new clh_ends_plan(ctx);
     pl->hand_words = hand_words;
     const bool ok = pairs_upload(pl, &shape, pairs, q, q_off, r, r_off, o->mat);
     pl->pairs.swap(pairs);
+    pl->recompute = recompute;
+    for (const auto& sh : pl->shares) {
+        int64_t nmax = 0;
+        for (int k = sh.first; k < sh.first + sh.second; ++k)
+            if (pl->pairs[(size_t)k].m > 0) nmax = std::max<int64_t>(nmax, pl->pairs[(size_t)k].n);
+        pl->share_rounds.push_back((int)((nmax + clh::kEnChunk - 1) / clh::kEnChunk));
+    }
     pl->d_hand = pl->alloc(sizeof(int32_t) * (size_t)std::max<int64_t>(pl->hand_words, 1));
     bool sp_ok = true;
     if (spliced) {
@@ -2504,8 +2520,11 @@ extern "C" int clh_ends_plan_run(clh_ends_plan* pl, void* stream_)
     p.rows = (int32_t*)pl->d_rows;
     p.cigar = (uint32_t*)pl->d_cig; p.cigar_cap = pl->cig_cap;
     // in stream order: a share's walk has read the workspace before the next share fills it
-    auto run_shares = [&](const auto& prm, auto launch, auto launch_walk) -> int {
-        for (const auto& sh : pl->shares) {
+    // (recompute: a share is the keeping score pass and then, chunk after chunk leftwards, the tile form and a round of the walk)
+    auto run_shares = [&](const auto& prm, auto launch, auto launch_walk, auto launch_retrace) -> int {
+        for (size_t s = 0; s < pl->shares.size(); ++s) {
+            const auto& sh = pl->shares[s];
+            if (pl->want_cigar && pl->recompute) { HIPCHK(launch_retrace(prm, sh.first, sh.second, pl->share_rounds[s], st)); continue; }
             HIPCHK(launch(prm, pl->want_cigar, sh.first, sh.second, st));
             if (pl->want_cigar) HIPCHK(launch_walk(prm, sh.first, sh.second, st));
         }
@@ -2516,10 +2535,10 @@ extern "C" int clh_ends_plan_run(clh_ends_plan* pl, void* stream_)
         clh::SpParams sp;
         static_cast<clh::EnParams&>(sp) = p;
         sp.io = pl->io; sp.site = (const int32_t*)pl->d_site; sp.strand = (const int8_t*)pl->d_strand;
-        rc = run_shares(sp, clh::launch_ssw_spliced, clh::launch_ssw_spliced_walk);
+        rc = run_shares(sp, clh::launch_ssw_spliced, clh::launch_ssw_spliced_walk, clh::launch_ssw_spliced_retrace);
     }
-    else if (pl->pieces == 2) rc = run_shares(p, clh::launch_ssw_ends2, clh::launch_ssw_ends2_walk);
-    else rc = run_shares(p, clh::launch_ssw_ends, clh::launch_ssw_ends_walk);      // the one-piece launchers take the block's base
+    else if (pl->pieces == 2) rc = run_shares(p, clh::launch_ssw_ends2, clh::launch_ssw_ends2_walk, clh::launch_ssw_ends2_retrace);
+    else rc = run_shares(p, clh::launch_ssw_ends, clh::launch_ssw_ends_walk, clh::launch_ssw_ends_retrace);      // the one-piece launchers take the block's base
     return rc ? rc : pl->end_run();
 }
 

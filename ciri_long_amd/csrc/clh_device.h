@@ -346,6 +346,14 @@ struct SpParams : EnParams { int32_t io; const int32_t* site; const int8_t* stra
 hipError_t launch_ssw_spliced(const SpParams& p, bool store, int first, int count, hipStream_t stream);
 hipError_t launch_ssw_spliced_walk(const SpParams& p, int first, int count, hipStream_t stream);
 
+// K1g's recompute route for CIGARs (ssw_ends.hip built with CLH_EN_RETRACE; EnKept in ssw_pairs.h is the pair's block): ws_off names a
+// block of kept chunk columns, one chunk's plane and the walk's resume record in place of the whole plane, hand_off is not read.
+// One call issues the keeping score pass of pairs [first, first + count) and then `rounds` times the tile form and one round of the
+// walk; a pair moves one chunk back per round, so the greatest chunk count among the pairs is enough rounds.
+hipError_t launch_ssw_ends_retrace(const EnParams& p, int first, int count, int rounds, hipStream_t stream);
+hipError_t launch_ssw_ends2_retrace(const En2Params& p, int first, int count, int rounds, hipStream_t stream);
+hipError_t launch_ssw_spliced_retrace(const SpParams& p, int first, int count, int rounds, hipStream_t stream);
+
 // K1gb (ssw_band.hip): K1g's global, semiglobal, prefix and extend programmes over a band of diagonals [lo, hi], d = j - i; one wave per pair in the
 // band's frame, a lane on CPL consecutive band positions b = d - lo (classes CPL 2, 4, 8: bands of up to 128, 256, 512 diagonals).
 // tools/band_model.py states the scheme.

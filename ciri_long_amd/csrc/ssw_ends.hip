@@ -129,9 +129,15 @@ __device__ __forceinline__ int sp_row0(int j, int go, int ge, int iod1, int a)
     return -(del < intron ? del : intron);
 }
 
-template <typename Prm, int MODE, bool STORE>
+// FORM: the score pass alone; the storing form; and the two passes of the recompute route -- the keeping form, the score pass with
+// every chunk's hand-over kept in a slot of its own (slot c written by chunk c, read by chunk c + 1) in the pair's block of the
+// workspace, which also leaves the walk's fresh resume record; and the tile form, the storing row step over the one chunk and the
+// rows 1..i that the record names, its incoming column from kept slot c - 1, its words in the block's one-chunk plane (EnTile).
+enum { EN_SCORE = 0, EN_STORE = 1, EN_KEEP = 2, EN_TILE = 3 };
+template <typename Prm, int MODE, int FORM>
 __global__ void __launch_bounds__(64) ssw_ends_kernel(const Prm prm, int first, int count)
 {
+    constexpr bool STORE = FORM == EN_STORE || FORM == EN_TILE, KEPT = FORM == EN_KEEP || FORM == EN_TILE;
     constexpr int model = EnModel<Prm>::model, NH = EnModel<Prm>::NH;
     typedef typename EnModel<Prm>::word_t word_t;
     __shared__ int smat[32 * 32];                    // [query code][reference code]
@@ -152,13 +158,33 @@ __global__ void __launch_bounds__(64) ssw_ends_kernel(const Prm prm, int first, 
     const int nchunks = (n + kEnChunk - 1) / kEnChunk;
     const int mpad = (m + 63) & ~63;
     // hand-over buffers of this pair: [buffer 0 / 1][H, E / H, E_1, E_2 / T, E, N][mpad]
-    if (nchunks > 1 && (pr.hand_off < 0 || pr.hand_off + (int64_t)(2 * NH) * mpad > prm.hand_cap)) return;
-    int32_t* hand = prm.hand + (nchunks > 1 ? pr.hand_off : 0);
+    int32_t* hand;
+    int32_t* rec = nullptr;                          // kept forms: the walk's resume record
+    word_t* tile = nullptr;                          // tile form: the one-chunk plane
+    int tc = 0, ti = 0;                              // tile form: the chunk and the row limit
+    if constexpr (!KEPT) {
+        if (nchunks > 1 && (pr.hand_off < 0 || pr.hand_off + (int64_t)(2 * NH) * mpad > prm.hand_cap)) return;
+        hand = prm.hand + (nchunks > 1 ? pr.hand_off : 0);
+    } else {
+        const EnKept lay(m, n, NH, (int)sizeof(word_t));
+        if (!lay.fits(pr.ws_off, prm.ws_cap)) return;            // the keeping form leaves the row unwritten, and every later pass returns here too
+        hand = (int32_t*)(prm.ws + pr.ws_off);
+        rec = (int32_t*)(prm.ws + pr.ws_off + lay.rec_off);
+        if constexpr (FORM == EN_TILE) {
+            if (prm.rows[(size_t)(first + x) * 8 + 7] != 0 || rec[EN_REC_DONE] != 0 || rec[EN_REC_J] <= 0) return;
+            tile = (word_t*)(prm.ws + pr.ws_off + lay.plane_off);
+            tc = rec[EN_REC_CHUNK]; ti = rec[EN_REC_I];
+            tc = tc < 0 ? 0 : (tc > nchunks - 1 ? nchunks - 1 : tc);
+            ti = ti > m ? m : ti;
+            if (ti <= 0) return;
+        }
+    }
+    const int mr = FORM == EN_TILE ? ti : m;         // the rows of the pass
     const int8_t* qry = prm.qry + pr.q_off;
     const int8_t* ref = prm.ref + pr.r_off;
     auto letter = [&](int pos) -> int { return (pos >= 0 && pos < n) ? ((int)ref[pos] & 31) : 4; };      // spliced; 0-based; 4 off the reference
     bool ws_ok = true;
-    if (STORE) {
+    if (FORM == EN_STORE) {
         const int llast = (n - (nchunks - 1) * kEnChunk + kEnCpl - 1) / kEnCpl;
         const int64_t need = (int64_t)sizeof(word_t) * m * ((int64_t)64 * (nchunks - 1) + llast);
         ws_ok = pr.ws_off >= 0 && (pr.ws_off & (int64_t)(sizeof(word_t) - 1)) == 0 && pr.ws_off + need <= prm.ws_cap;
@@ -177,7 +203,7 @@ __global__ void __launch_bounds__(64) ssw_ends_kernel(const Prm prm, int first, 
         iod1 = io + sp_site(site, soff, 0, letter(0), letter(1));
     }
 
-    for (int c = 0; c < nchunks; ++c) {
+    for (int c = FORM == EN_TILE ? tc : 0; c < (FORM == EN_TILE ? tc + 1 : nchunks); ++c) {
         const int c0 = c * kEnChunk;
         const bool last = c == nchunks - 1;
         const int cols = last ? n - c0 : kEnChunk;
@@ -229,26 +255,27 @@ __global__ void __launch_bounds__(64) ssw_ends_kernel(const Prm prm, int first, 
             }
             hleft = dpp_shr1(h0_in, Hp[kEnCpl - 1]);
         }
-        const int32_t* in0 = hand + (size_t)((c + 1) & 1) * NH * mpad;   // written by chunk c - 1; the third of each only where NH == 3
+        const int32_t* in0 = hand + (size_t)(KEPT ? (c > 0 ? c - 1 : 0) : (c + 1) & 1) * NH * mpad;   // written by chunk c - 1; the third of each only where NH == 3
         const int32_t* in1 = in0 + mpad;
         const int32_t* in2 = in1 + mpad;
-        int32_t* out0 = hand + (size_t)(c & 1) * NH * mpad;
+        int32_t* out0 = hand + (size_t)(KEPT ? c : c & 1) * NH * mpad;       // dereferenced by a chunk that hands on alone
         int32_t* out1 = out0 + mpad;
         int32_t* out2 = out1 + mpad;
         word_t* wsp = nullptr;
-        if (STORE && ws_ok) wsp = (word_t*)(prm.ws + pr.ws_off) + (size_t)c * m * 64;
+        if (FORM == EN_STORE && ws_ok) wsp = (word_t*)(prm.ws + pr.ws_off) + (size_t)c * m * 64;
+        if (FORM == EN_TILE) wsp = tile;
         const int own = cols - lane * kEnCpl;                  // extend: register k holds a column of the reference while k < own
         int cv = (int)0x80000000, ci = 0, ck = 0;              // extend: this chunk's best of the lane
 
-        for (int i0 = 0; i0 < m; i0 += 64) {
-            const bool mine = i0 + lane < m;
+        for (int i0 = 0; i0 < mr; i0 += 64) {
+            const bool mine = i0 + lane < mr;
             const int qv = mine ? ((int)qry[i0 + lane] & 31) : 0;
             int vin0 = 0, vin1 = 0, vin2 = 0, vout0 = 0, vout1 = 0, vout2 = 0;     // the NH values of rows i0 .. i0 + 63, row i0 + lane in this lane: in and out
             if (c > 0 && mine) {
                 vin0 = in0[i0 + lane]; vin1 = in1[i0 + lane];
                 if constexpr (NH == 3) vin2 = in2[i0 + lane];
             }
-            const int rows = m - i0 < 64 ? m - i0 : 64;
+            const int rows = mr - i0 < 64 ? mr - i0 : 64;
             for (int rr = 0; rr < rows; ++rr) {
                 const int i = i0 + rr + 1;
                 const int qc = __builtin_amdgcn_readlane(qv, rr);
@@ -382,7 +409,7 @@ __global__ void __launch_bounds__(64) ssw_ends_kernel(const Prm prm, int first, 
                         if (wsp && lane < L) wsp[(size_t)(i - 1) * L + lane] = make_uint2(w[0], w[1]);
                     }
                 }
-                if (!last) {
+                if (FORM != EN_TILE && !last) {
                     // what lane 63 hands on of its last column: H (spliced: T), E, and E_2 or N
                     const int s0 = __builtin_amdgcn_readlane(model == EN_SPLICED ? T[kEnCpl - 1] : H[kEnCpl - 1], 63);
                     const int s1 = __builtin_amdgcn_readlane(E[kEnCpl - 1], 63);
@@ -393,12 +420,12 @@ __global__ void __launch_bounds__(64) ssw_ends_kernel(const Prm prm, int first, 
                     vout1 = lane == rr ? s1 : vout1;
                     if constexpr (NH == 3) vout2 = lane == rr ? s2 : vout2;
                 }
-                if (MODE == EN_EXTEND) {
+                if (FORM != EN_TILE && MODE == EN_EXTEND) {
 #pragma unroll
                     for (int k = 0; k < kEnCpl; ++k)
                         if (k < own && H[k] > cv) { cv = H[k]; ci = i; ck = k; }
                 }
-                if ((MODE == EN_SEMIGLOBAL || MODE == EN_OVERLAP || MODE == EN_PREFIX) && i == m) {
+                if (FORM != EN_TILE && (MODE == EN_SEMIGLOBAL || MODE == EN_OVERLAP || MODE == EN_PREFIX) && i == m) {
                     int bv = (int)0x80000000, bj = 0x7fffffff;
 #pragma unroll
                     for (int k = 0; k < kEnCpl; ++k) {
@@ -413,7 +440,7 @@ __global__ void __launch_bounds__(64) ssw_ends_kernel(const Prm prm, int first, 
                     }
                     if (bv > row_best) { row_best = bv; row_j = bj; }
                 }
-                if (last && (MODE == EN_OVERLAP || i == m)) {
+                if (FORM != EN_TILE && last && (MODE == EN_OVERLAP || i == m)) {
                     int hn = H[0];
 #pragma unroll
                     for (int k = 1; k < kEnCpl; ++k) hn = k == kn ? H[k] : hn;
@@ -427,21 +454,22 @@ __global__ void __launch_bounds__(64) ssw_ends_kernel(const Prm prm, int first, 
                 }
                 hleft = nleft;
             }
-            if (!last && mine) {
+            if (FORM != EN_TILE && !last && mine) {
                 out0[i0 + lane] = vout0; out1[i0 + lane] = vout1;
                 if constexpr (NH == 3) out2[i0 + lane] = vout2;
             }
         }
-        if (MODE == EN_EXTEND) {
+        if (FORM != EN_TILE && MODE == EN_EXTEND) {
             const bool take = cv > ext_v || (cv == ext_v && ci < ext_i);
             ext_v = take ? cv : ext_v; ext_i = take ? ci : ext_i; ext_j = take ? c0 + 1 + lane * kEnCpl + ck : ext_j;
         }
-        if (!last) {      // the next chunk reads what other lanes of this wave stored
+        if (FORM != EN_TILE && !last) {      // the next chunk reads what other lanes of this wave stored
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
             __syncthreads();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         }
     }
+    if (FORM == EN_TILE) return;                     // the tile form tracks no end cell and writes no row
     corner = __shfl(corner, ln); col_best = __shfl(col_best, ln); col_i = __shfl(col_i, ln);
     int score, ei, ej;
     if (MODE == EN_GLOBAL) { score = corner; ei = m; ej = n; }
@@ -465,7 +493,11 @@ __global__ void __launch_bounds__(64) ssw_ends_kernel(const Prm prm, int first, 
         row[4] = ei - 1;
         row[5] = 0;
         row[6] = 0;
-        row[7] = (STORE && !ws_ok) ? EN_ST_NO_WALK : 0;
+        row[7] = (FORM == EN_STORE && !ws_ok) ? EN_ST_NO_WALK : 0;
+        if constexpr (FORM == EN_KEEP) {              // the fresh record: the walk starts at the end cell, in its chunk
+            rec[EN_REC_DONE] = 0; rec[EN_REC_CHUNK] = ej > 0 ? (ej - 1) / kEnChunk : 0; rec[EN_REC_I] = ei; rec[EN_REC_J] = ej;
+            rec[EN_REC_STATE] = 0; rec[EN_REC_CUR] = -1; rec[EN_REC_RUN] = 0; rec[EN_REC_NOPS] = 0; rec[EN_REC_STEPS] = ei + ej + 2;
+        }
     }
 }
 
@@ -501,11 +533,82 @@ __global__ void ssw_ends_walk_kernel(const Prm prm, int first, int count)
     else pr_walk<model>(row, prm.mode, m, n, prm.cigar + pr.cig_off, pr.cig_cap, cells);
 }
 
+// The recompute route's walk, one lane per pair: a round of pr_walk_round over the tile the tile form has just filled for the
+// chunk in the pair's record.  Chunk and row limit are clamped as the tile form clamps them; a record that disagrees is refused there.
+template <typename Prm>
+__global__ void ssw_ends_rewalk_kernel(const Prm prm, int first, int count, int last_round)
+{
+    constexpr int model = EnModel<Prm>::model, NH = EnModel<Prm>::NH;
+    typedef typename EnModel<Prm>::cell_t cell_t;
+    typedef typename EnModel<Prm>::word_t word_t;
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= count || first + x >= prm.npairs) return;
+    const EnPair pr = prm.pairs[first + x];
+    const int m = pr.m, n = pr.n;
+    if (m <= 0 || n <= 0) return;
+    int32_t* row = prm.rows + (size_t)(first + x) * 8;
+    if (row[7] != 0) return;                                     // unwritten, or refused in an earlier round: fetch reports it
+    const EnKept lay(m, n, NH, (int)sizeof(word_t));
+    if (!lay.fits(pr.ws_off, prm.ws_cap) || pr.cig_off < 0 || pr.cig_off + pr.cig_cap > prm.cigar_cap) { row[7] = EN_ST_NO_WALK; return; }
+    int32_t* rec = (int32_t*)(prm.ws + pr.ws_off + lay.rec_off);
+    if (rec[EN_REC_DONE] != 0) return;
+    const int nchunks = (n + kEnChunk - 1) / kEnChunk;
+    int c = rec[EN_REC_CHUNK], ilim = rec[EN_REC_I];
+    c = c < 0 ? 0 : (c > nchunks - 1 ? nchunks - 1 : c);
+    ilim = ilim > m ? m : (ilim < 0 ? 0 : ilim);
+    EnTile<cell_t> cells(m, n, c, ilim);
+    cells.ws = (const cell_t*)(prm.ws + pr.ws_off + lay.plane_off);
+    if constexpr (model == EN_SPLICED) {
+        const int8_t* ref = prm.ref + pr.r_off;
+        const int soff = (prm.strand && prm.strand[first + x] < 0) ? 32 : 0;
+        auto letter = [&](int pos) -> int { return (pos >= 0 && pos < n) ? ((int)ref[pos] & 31) : 4; };
+        pr_walk_round<model>(rec, row, prm.mode, m, n, prm.cigar + pr.cig_off, pr.cig_cap, cells, c, last_round != 0, [&](int j) -> int {
+            const int64_t del = (int64_t)prm.go + (int64_t)(j - 1) * prm.ge;
+            const int64_t intron = (int64_t)prm.io + sp_site(prm.site, soff, 0, letter(0), letter(1)) + sp_site(prm.site, soff, 16, letter(j - 2), letter(j - 1));
+            return del <= intron ? 2 : 3;
+        });
+    }
+    else pr_walk_round<model>(rec, row, prm.mode, m, n, prm.cigar + pr.cig_off, pr.cig_cap, cells, c, last_round != 0);
+}
+
+#ifdef CLH_EN_RETRACE
+// the recompute route's launchers, an object of their own (the Makefile builds this file twice): 30 more instantiations of the body
+template <typename Prm, int FORM>
+static hipError_t en_launch_form(const Prm& p, int first, int count, hipStream_t st)
+{
+    if (p.mode == EN_GLOBAL) hipLaunchKernelGGL((ssw_ends_kernel<Prm, EN_GLOBAL, FORM>), dim3(count), dim3(64), 0, st, p, first, count);
+    else if (p.mode == EN_SEMIGLOBAL) hipLaunchKernelGGL((ssw_ends_kernel<Prm, EN_SEMIGLOBAL, FORM>), dim3(count), dim3(64), 0, st, p, first, count);
+    else if (p.mode == EN_OVERLAP) hipLaunchKernelGGL((ssw_ends_kernel<Prm, EN_OVERLAP, FORM>), dim3(count), dim3(64), 0, st, p, first, count);
+    else if (p.mode == EN_PREFIX) hipLaunchKernelGGL((ssw_ends_kernel<Prm, EN_PREFIX, FORM>), dim3(count), dim3(64), 0, st, p, first, count);
+    else if (p.mode == EN_EXTEND) hipLaunchKernelGGL((ssw_ends_kernel<Prm, EN_EXTEND, FORM>), dim3(count), dim3(64), 0, st, p, first, count);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+// the keeping score pass of a share, then `rounds` times the tile form and a round of the walk, in stream order
+template <typename Prm>
+static hipError_t en_launch_retrace(const Prm& p, int first, int count, int rounds, hipStream_t stream)
+{
+    if (count <= 0) return hipSuccess;
+    hipError_t e = en_launch_form<Prm, EN_KEEP>(p, first, count, stream);
+    for (int r = 0; r < rounds && e == hipSuccess; ++r) {
+        e = en_launch_form<Prm, EN_TILE>(p, first, count, stream);
+        if (e != hipSuccess) break;
+        hipLaunchKernelGGL(ssw_ends_rewalk_kernel<Prm>, dim3((count + 63) / 64), dim3(64), 0, stream, p, first, count, r == rounds - 1 ? 1 : 0);
+        e = hipGetLastError();
+    }
+    return e;
+}
+
+hipError_t launch_ssw_ends_retrace(const EnParams& p, int first, int count, int rounds, hipStream_t stream) { return en_launch_retrace(p, first, count, rounds, stream); }
+hipError_t launch_ssw_ends2_retrace(const En2Params& p, int first, int count, int rounds, hipStream_t stream) { return en_launch_retrace(p, first, count, rounds, stream); }
+hipError_t launch_ssw_spliced_retrace(const SpParams& p, int first, int count, int rounds, hipStream_t stream) { return en_launch_retrace(p, first, count, rounds, stream); }
+#else
 template <typename Prm, int MODE>
 static void en_launch_mode(const Prm& p, bool store, int first, int count, hipStream_t st)
 {
-    if (store) hipLaunchKernelGGL((ssw_ends_kernel<Prm, MODE, true>), dim3(count), dim3(64), 0, st, p, first, count);
-    else hipLaunchKernelGGL((ssw_ends_kernel<Prm, MODE, false>), dim3(count), dim3(64), 0, st, p, first, count);
+    if (store) hipLaunchKernelGGL((ssw_ends_kernel<Prm, MODE, EN_STORE>), dim3(count), dim3(64), 0, st, p, first, count);
+    else hipLaunchKernelGGL((ssw_ends_kernel<Prm, MODE, EN_SCORE>), dim3(count), dim3(64), 0, st, p, first, count);
 }
 
 template <typename Prm>
@@ -535,5 +638,6 @@ hipError_t launch_ssw_spliced(const SpParams& p, bool store, int first, int coun
 hipError_t launch_ssw_ends_walk(const EnParams& p, int first, int count, hipStream_t stream) { return en_launch_walk(p, first, count, stream); }
 hipError_t launch_ssw_ends2_walk(const En2Params& p, int first, int count, hipStream_t stream) { return en_launch_walk(p, first, count, stream); }
 hipError_t launch_ssw_spliced_walk(const SpParams& p, int first, int count, hipStream_t stream) { return en_launch_walk(p, first, count, stream); }
+#endif
 
 }  // namespace clh

@@ -1,8 +1,9 @@
 // ssw_pairs.h -- what K1g (ssw_ends.hip) and K1gb (ssw_band.hip) share on the device: the LDS matrix of their score kernels and the
-// walk back over the stored decisions.  pr_walk<MODEL> is one body for the three gap models (one piece, two pieces, intron gaps): the
+// walk back over the stored decisions.  The walk (pr_walk_steps, entered as pr_walk<MODEL> over everything that was stored and as
+// pr_walk_round<MODEL> over one chunk's plane at a time) is one body for the three gap models (one piece, two pieces, intron gaps): the
 // frame is written once, and what a model has of its own is a few constants (PrModel) and, for spliced, two branches under
-// `if constexpr`.  Where the decisions of a cell lie is the geometry's: EnCells (K1g) and BdCells (K1gb), which the walk takes as a
-// functor.  They check rows, columns and the plane's bounds themselves and state the plane's size, and the walk kernels' guards use
+// `if constexpr`.  Where the decisions of a cell lie is the geometry's: EnCells and EnTile (K1g) and BdCells (K1gb), which the walk
+// takes as a functor.  They check rows, columns and the plane's bounds themselves and state the plane's size, and the walk kernels' guards use
 // that same expression.  Walk and locators are __host__ __device__: tests/walk_host.hip runs them on the CPU over random planes.
 // (Each of the two score kernels is one template body for all its gap models.  The storing side of the layout, the decision bits of
 // a cell and the end cell's argmax over the wave stay written out there: as helpers they changed the register allocation of the
@@ -54,14 +55,27 @@ struct PrRow0D { __host__ __device__ int operator()(int) const { return 2; } }; 
 // of that cell, from column j leftwards up to and including the first whose `bit` ("opened here") is set, or 0 outside what was stored:
 // an intron is thousands of cells along one row, taken 8 at a step.  row0_op(j) names the op of the one run of j letters that the
 // anchored stop on row 0 emits; the other models neither have run_left nor pass a row0_op.
-template <int MODEL, typename Cell, typename Row0 = PrRow0D>
-__host__ __device__ __forceinline__ void pr_walk(int32_t* row, int mode, int m, int n, uint32_t* out, int cig_cap, Cell& cell, Row0 row0_op = Row0())
+// The walk is written once, as a round over a record (pr_walk_steps): rec holds where the walk stands -- (i, j), the state, the open
+// run (cur, run), the ops written and the steps left -- and TILED says whether `cell` is one chunk's plane (K1g's recompute route,
+// pr_walk_round) or everything that was stored (pr_walk, whose record is a local that never leaves the registers).  A tiled round
+// that needs a cell left of its tile (0 < j <= c0) saves the record, names chunk c - 1 and returns: the open run is in the record,
+// so a run across a chunk edge is one op, and so are the steps left, so the budget is spent once.  A record that does not add up for
+// the tile it is resumed on, and a pair still open when `last_round` ends, is EN_ST_NO_WALK.
+enum { EN_REC_DONE, EN_REC_CHUNK, EN_REC_I, EN_REC_J, EN_REC_STATE, EN_REC_CUR, EN_REC_RUN, EN_REC_NOPS, EN_REC_STEPS, kEnRecWords = 12 };
+template <int MODEL, bool TILED, typename Cell, typename Row0>
+__host__ __device__ __forceinline__ void pr_walk_steps(int32_t* rec, int32_t* row, int mode, int m, int n, uint32_t* out, int cig_cap, Cell& cell,
+                                                       int c, bool last_round, Row0 row0_op)
 {
     typedef PrModel<MODEL> M;
-    int i = row[4] + 1, j = row[2] + 1;
-    if (i < 0 || i > m || j < 0 || j > n) { row[7] = EN_ST_NO_WALK; return; }
-    const int steps = i + j + 2;
-    int state = 0, nops = 0, cur = -1, run = 0;
+    const int c0 = TILED ? c * kEnChunk : 0;
+    int i = rec[EN_REC_I], j = rec[EN_REC_J], state = rec[EN_REC_STATE], cur = rec[EN_REC_CUR], run = rec[EN_REC_RUN], nops = rec[EN_REC_NOPS];
+    int steps = rec[EN_REC_STEPS];
+    if constexpr (TILED) {
+        rec[EN_REC_DONE] = 1;                                    // unless this round suspends
+        if (rec[EN_REC_CHUNK] != c || c < 0 || i < 0 || i > m || j < (c ? c0 + 1 : 0) || j > n || j > c0 + kEnChunk ||
+            state < 0 || (state > M::n_gap && !(MODEL == EN_SPLICED && state == M::T)) || cur < -1 || cur > 3 || run < 0 || (run > 0 && cur < 0) ||
+            nops < 0 || nops > cig_cap || steps < 0 || steps > m + n + 2) { row[7] = EN_ST_NO_WALK; return; }
+    }
     bool bad = false, done = false;
     auto emit = [&](int op, int k) {
         if (k <= 0) return;
@@ -69,12 +83,21 @@ __host__ __device__ __forceinline__ void pr_walk(int32_t* row, int mode, int m, 
         if (run) { if (nops < cig_cap) out[nops++] = ((uint32_t)run << 4) | (uint32_t)cur; else bad = true; }
         cur = op; run = k;
     };
-    for (int step = 0; step < steps && !done; ++step) {
+    for (; steps > 0 && !done; --steps) {
         if ((state == 0 || (MODEL == EN_SPLICED && state == M::T)) && (i == 0 || j == 0)) {     // on column 0 T is H; state T never stands on row 0
             if (en_anchored(mode)) { if (j > 0) emit(row0_op(j), j); emit(1, i); i = 0; j = 0; }      // prefix and extend stop at (0, 0) as global does
             else if (mode == EN_SEMIGLOBAL && j == 0) { emit(1, i); i = 0; }
             done = true;
             break;
+        }
+        if constexpr (TILED) {
+            if (j > 0 && j <= c0) {                              // the cell lies in the chunk before this one: the next round's
+                if (last_round) break;
+                rec[EN_REC_CHUNK] = c - 1; rec[EN_REC_I] = i; rec[EN_REC_J] = j; rec[EN_REC_STATE] = state; rec[EN_REC_CUR] = cur;
+                rec[EN_REC_RUN] = run; rec[EN_REC_NOPS] = nops; rec[EN_REC_STEPS] = steps;
+                if (bad) row[7] = EN_ST_NO_WALK; else rec[EN_REC_DONE] = 0;
+                return;
+            }
         }
         const int at = cell(i, j);                               // -1 on row 0 and column 0: a gap state on the boundary does not add up
         if (at < 0) { bad = true; break; }
@@ -102,8 +125,28 @@ __host__ __device__ __forceinline__ void pr_walk(int32_t* row, int mode, int m, 
     }
     emit(-2, 1);                                                 // flush the last run
     if (bad || !done) { row[7] = EN_ST_NO_WALK; return; }
-    for (int a = 0, c = nops - 1; a < c; ++a, --c) { const uint32_t w = out[a]; out[a] = out[c]; out[c] = w; }
+    for (int a = 0, z = nops - 1; a < z; ++a, --z) { const uint32_t w = out[a]; out[a] = out[z]; out[z] = w; }
     row[1] = j; row[3] = i; row[5] = nops;
+}
+
+// the walk over everything that was stored, from the end cell in `row`
+template <int MODEL, typename Cell, typename Row0 = PrRow0D>
+__host__ __device__ __forceinline__ void pr_walk(int32_t* row, int mode, int m, int n, uint32_t* out, int cig_cap, Cell& cell, Row0 row0_op = Row0())
+{
+    const int i = row[4] + 1, j = row[2] + 1;
+    if (i < 0 || i > m || j < 0 || j > n) { row[7] = EN_ST_NO_WALK; return; }
+    int32_t rec[kEnRecWords] = {0, 0, i, j, 0, -1, 0, 0, i + j + 2};
+    pr_walk_steps<MODEL, false>(rec, row, mode, m, n, out, cig_cap, cell, 0, true, row0_op);
+}
+
+// one round of the walk over the tile of chunk c (EnTile); rec is the pair's resume record, which the keeping score pass leaves fresh:
+// the end cell, its chunk, state 0, no open run, i + j + 2 steps
+template <int MODEL, typename Cell, typename Row0 = PrRow0D>
+__host__ __device__ __forceinline__ void pr_walk_round(int32_t* rec, int32_t* row, int mode, int m, int n, uint32_t* out, int cig_cap, Cell& cell,
+                                                       int c, bool last_round, Row0 row0_op = Row0())
+{
+    if (rec[EN_REC_DONE] != 0) return;
+    pr_walk_steps<MODEL, true>(rec, row, mode, m, n, out, cig_cap, cell, c, last_round, row0_op);
 }
 
 // Where the decisions of cell (i, j) lie in what K1g's storing form left of a pair: chunk after chunk, per chunk row after row, a
@@ -156,6 +199,72 @@ struct EnCells {
         hold(wi);
         const uint64_t both = ((uint64_t)word.y << 32) | word.x;
         const uint64_t set = both & (0x0101010101010101ull * bit) & (~0ull >> (8 * (7 - k)));      // "opened here" of columns 0 .. k of the word
+        *opened = set != 0;
+        return set ? k - (63 - __builtin_clzll(set)) / 8 + 1 : k + 1;
+    }
+};
+
+// The recompute route of K1g (ssw_ends.hip): what a pair holds in its share of the workspace in place of the whole plane.  First the
+// last column of every chunk but the last, slot c written by chunk c of the keeping score pass (NH int32 values per row, rows rounded
+// up to 64: `slot` bytes each); then the plane of one chunk, which the tile form fills for the rows the walk can still reach (a word
+// per lane and row, as EnCells has a chunk: room for all m rows of 64 lanes); then the walk's resume record.  Host and kernels size
+// and check the block with this one expression.
+struct EnKept {
+    int64_t slot, plane_off, rec_off, total;                 // bytes
+    __host__ __device__ EnKept(int m, int n, int nh, int word_bytes)
+    {
+        const int64_t mpad = ((int64_t)m + 63) & ~(int64_t)63, nchunks = ((int64_t)n + kEnChunk - 1) / kEnChunk;
+        slot = 4 * nh * mpad;
+        plane_off = slot * (nchunks - 1);
+        rec_off = plane_off + (int64_t)word_bytes * m * 64;
+        total = (rec_off + 4 * kEnRecWords + 15) & ~(int64_t)15;
+    }
+    __host__ __device__ bool fits(int64_t ws_off, int64_t ws_cap) const { return ws_off >= 0 && (ws_off & 15) == 0 && ws_off + total <= ws_cap; }
+};
+
+// EnCells for the plane of one chunk: rows 1..ilim of chunk c of the pair, the words of a row side by side as the tile form stores
+// them.  -1 above the row limit and left or right of the chunk: the word of any other cell has an index below ilim L <= 64 m.
+template <typename Word>
+struct EnTile {
+    const Word* ws = nullptr;
+    int c0, cols, L, ilim;
+    int64_t held = -1;
+    Word word;
+    __host__ __device__ EnTile(int m, int n, int c, int ilim_) : c0(c * kEnChunk), ilim(ilim_ < m ? ilim_ : m), word()
+    {
+        cols = n - c0 < kEnChunk ? n - c0 : kEnChunk;
+        L = (cols + kEnCpl - 1) / kEnCpl;
+    }
+    __host__ __device__ int64_t locate(int i, int j, int* k) const
+    {
+        const uint32_t r = (uint32_t)(i - 1), p = (uint32_t)(j - 1 - c0);                         // unsigned: what lies above or left wraps
+        if (r >= (uint32_t)ilim || cols <= 0 || p >= (uint32_t)cols) return -1;
+        *k = (int)(p % kEnCpl);
+        return (int64_t)r * L + p / kEnCpl;
+    }
+    __host__ __device__ void hold(int64_t wi)
+    {
+        static_assert(sizeof(Word) == 8, "only the uint2 functor holds a word");
+        if (wi != held) { word = ws[wi]; held = wi; }
+    }
+    __host__ __device__ int operator()(int i, int j)
+    {
+        int k;
+        const int64_t wi = locate(i, j, &k);
+        if (wi < 0) return -1;
+        if constexpr (sizeof(Word) == 4) return (int)((ws[wi] >> (4 * k)) & 15u);
+        else if constexpr (sizeof(Word) == 1) return (int)ws[wi * kEnCpl + k];
+        else { hold(wi); return (int)((((k & 4) ? word.y : word.x) >> (8 * (k & 3))) & 255u); }
+    }
+    __host__ __device__ int run_left(int i, int j, uint32_t bit, bool* opened)      // ends at the word's first cell, hence at the tile's left edge
+    {
+        static_assert(sizeof(Word) == 8, "run_left reads the held uint2");
+        int k;
+        const int64_t wi = locate(i, j, &k);
+        if (wi < 0) return 0;
+        hold(wi);
+        const uint64_t both = ((uint64_t)word.y << 32) | word.x;
+        const uint64_t set = both & (0x0101010101010101ull * bit) & (~0ull >> (8 * (7 - k)));
         *opened = set != 0;
         return set ? k - (63 - __builtin_clzll(set)) / 8 + 1 : k + 1;
     }

@@ -99,6 +99,7 @@ def splice_of(who, intron_open, noncanonical, donor_costs=None, acceptor_costs=N
 ENDS_DTYPE = np.dtype([('score', '<i4'), ('ref_begin', '<i4'), ('ref_end', '<i4'), ('query_begin', '<i4'), ('query_end', '<i4'),
                        ('cigar_len', '<i4'), ('cigar_off', '<i8')])
 ENDS_MODES = {'global': 0, 'semiglobal': 1, 'overlap': 2, 'prefix': 3, 'extend': 4}
+ENDS_TRACEBACKS = {'stored': 1, 'recompute': 2}      # clh_ends_opts.want_cigar: CLH_ENDS_CIGAR_STORED, CLH_ENDS_CIGAR_RECOMPUTE
 
 
 class BandOpts(C.Structure):
@@ -573,11 +574,11 @@ class Context(object):
         return EditSearchPlan(self, probes, texts, k, equalities)
 
     def ends_batch(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode='global', want_cigar=True, workspace_bytes=0,
-                   gap_open2=None, gap_extend2=None, splice=None, strand=None):
+                   gap_open2=None, gap_extend2=None, splice=None, strand=None, traceback='stored'):
         """End-anchored affine-gap alignment of the pairs (query k, reference k), packed codes and offsets as ssw_batch takes them,
         through K1g -> (rows ENDS_DTYPE, cigars uint32 packed ops).  See EndsPlan."""
         plan = EndsPlan(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode, want_cigar, workspace_bytes, gap_open2, gap_extend2,
-                        splice, strand)
+                        splice, strand, traceback)
         try:
             plan.run()
             return plan.fetch()
@@ -585,9 +586,9 @@ class Context(object):
             plan.close()
 
     def ends_plan(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode='global', want_cigar=True, workspace_bytes=0,
-                  gap_open2=None, gap_extend2=None, splice=None, strand=None):
+                  gap_open2=None, gap_extend2=None, splice=None, strand=None, traceback='stored'):
         return EndsPlan(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode, want_cigar, workspace_bytes, gap_open2, gap_extend2,
-                        splice, strand)
+                        splice, strand, traceback)
 
     def band_batch(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, band, mode='global', diagonals=None, want_cigar=True,
                    workspace_bytes=0, gap_open2=None, gap_extend2=None):
@@ -883,15 +884,23 @@ class EndsPlan(_PairsPlan):
     With `splice` (a Splice, see splice_of) a run of skipped reference letters costs the smaller of a deletion and an intron, whose
     cost is intron_open plus the donor and acceptor costs of the dinucleotides at its ends on the pair's strand (`strand`: +1 / -1 per
     pair, None for all +1; clh_ends_plan_create_spliced); CIGARs then hold op N (3), a byte per cell is stored, the matrix must be the
-    DNA match / mismatch one, and two-piece gap costs together with introns are not built."""
+    DNA match / mismatch one, and two-piece gap costs together with introns are not built.
+    traceback names the route to the CIGARs: 'stored' keeps the decisions of every cell of a pair (half a byte or a byte per cell of
+    m x n) in the workspace; 'recompute' keeps the last column of every chunk of 512 reference columns, computes the decisions again
+    one chunk at a time and resumes the walk chunk after chunk (CLH_ENDS_CIGAR_RECOMPUTE): the same rows and CIGARs, bit for bit, from
+    a 32nd to a 43rd of the memory per chunk, at the price of computing the cells the walk can reach twice.  It pays from about four
+    chunks on; no routing is made between the two."""
     _destroy = 'clh_ends_plan_destroy'
     _c, _dtype = 'ends', ENDS_DTYPE
 
     def __init__(self, ctx, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode='global', want_cigar=True, workspace_bytes=0,
-                 gap_open2=None, gap_extend2=None, splice=None, strand=None):
+                 gap_open2=None, gap_extend2=None, splice=None, strand=None, traceback='stored'):
         _Handle.__init__(self, ctx)
         if mode not in ENDS_MODES:
             raise ValueError('mode must be one of global, semiglobal, overlap, prefix, extend, got %r' % (mode,))
+        if traceback not in ENDS_TRACEBACKS:
+            raise ValueError("traceback must be 'stored' or 'recompute', got %r" % (traceback,))
+        self.traceback = traceback
         gap2 = gap2_of('EndsPlan', gap_open2, gap_extend2)
         if splice is not None:
             self._create_spliced(ctx, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode, want_cigar, workspace_bytes, gap2, splice, strand)
@@ -899,7 +908,8 @@ class EndsPlan(_PairsPlan):
         if strand is not None:
             raise ValueError('EndsPlan: strand comes with splice')
         q, q_off, r, r_off, mat, n_mat, _ = self._inputs(queries, query_off, refs, ref_off, mat, want_cigar)
-        opts = EndsOpts(ENDS_MODES[mode], mat.ctypes.data, n_mat, int(gap_open), int(gap_extend), int(self.want_cigar), int(workspace_bytes))
+        opts = EndsOpts(ENDS_MODES[mode], mat.ctypes.data, n_mat, int(gap_open), int(gap_extend), ENDS_TRACEBACKS[self.traceback] if self.want_cigar else 0,
+                        int(workspace_bytes))
         args = (ctx._h, self.n, q.ctypes.data, q_off.ctypes.data, r.ctypes.data, r_off.ctypes.data, C.byref(opts))
         if gap2 is None:
             self._h = lib().clh_ends_plan_create(*args)
@@ -919,7 +929,8 @@ class EndsPlan(_PairsPlan):
             st = np.ascontiguousarray(strand, dtype=np.int8)
             if st.shape != (self.n,):
                 raise ValueError('EndsPlan: %d strands for %d pairs' % (st.size, self.n))
-        opts = EndsOpts(ENDS_MODES[mode], mat.ctypes.data, n_mat, int(gap_open), int(gap_extend), int(self.want_cigar), int(workspace_bytes))
+        opts = EndsOpts(ENDS_MODES[mode], mat.ctypes.data, n_mat, int(gap_open), int(gap_extend), ENDS_TRACEBACKS[self.traceback] if self.want_cigar else 0,
+                        int(workspace_bytes))
         self._h = lib().clh_ends_plan_create_spliced(ctx._h, self.n, q.ctypes.data, q_off.ctypes.data, r.ctypes.data, r_off.ctypes.data, C.byref(opts),
                                                      C.byref(splice), st.ctypes.data if st is not None else None)
         if not self._h:
@@ -928,11 +939,12 @@ class EndsPlan(_PairsPlan):
     def info(self):
         """the geometry of the kernel: reference columns a lane owns (cpl) and columns of a chunk (a longer reference is walked chunk
         after chunk); and of this plan: shares the batch was cut into so that a share's stored decisions fit the workspace, workspace
-        bytes in use, those of the largest pair, pairs the kernels take, pairs with an empty side, CIGAR ops fetch may return"""
+        bytes in use, those of the largest pair, pairs the kernels take, pairs with an empty side, CIGAR ops fetch may return; the
+        byte counts and the shares are those of the route to the CIGARs in use, `traceback` (None without want_cigar: no route is in use)"""
         out = (C.c_int64 * 8)()
         _check(lib().clh_ends_plan_info(self._h, out), 'clh_ends_plan_info')
         return {'cpl': int(out[0]), 'chunk': int(out[1]), 'shares': int(out[2]), 'workspace_bytes': int(out[3]), 'max_pair_bytes': int(out[4]),
-                'kernel_pairs': int(out[5]), 'empty_pairs': int(out[6]), 'cigar_cap': int(out[7])}
+                'kernel_pairs': int(out[5]), 'empty_pairs': int(out[6]), 'cigar_cap': int(out[7]), 'traceback': self.traceback if self.want_cigar else None}
 
 
 class BandPlan(_PairsPlan):

@@ -370,7 +370,7 @@ LONG_READ_GAPS = dict(match=2, mismatch=4, gap_open=4, gap_extend=2, gap_open2=2
 
 
 def align_pairs_ends(ref_seqs, query_seqs, mode='global', match=2, mismatch=2, gap_open=3, gap_extend=1, report_cigar=False, matrix=None,
-                     alphabet=None, context=None, gap_open2=None, gap_extend2=None):
+                     alphabet=None, context=None, gap_open2=None, gap_extend2=None, traceback='stored'):
     """n independent (reference, query) alignments anchored at the ends, in one GPU call -> one PyAlignRes per pair.
 
     mode 'global': both sequences end to end.  'semiglobal': the whole query in any stretch of the reference (a probe, an exon, a
@@ -393,8 +393,16 @@ def align_pairs_ends(ref_seqs, query_seqs, mode='global', match=2, mismatch=2, g
     gap_open2 and gap_extend2 (together) add a second piece: a gap of k letters then costs the smaller of gap_open + (k - 1)
     gap_extend and gap_open2 + (k - 1) gap_extend2, piece 1 for short gaps and piece 2 for long ones, 0 <= gap_extend2 <=
     gap_extend <= gap_open <= gap_open2 (``LONG_READ_GAPS`` is such a set).  The walk back then prefers the diagonal, D by piece 1,
-    D by piece 2, I by piece 1, I by piece 2; the CIGAR does not say which piece paid."""
+    D by piece 2, I by piece 1, I by piece 2; the CIGAR does not say which piece paid.
+
+    traceback: 'stored' keeps the decisions of every cell of a pair on the device for the walk back; 'recompute' keeps one column per
+    512 reference columns and computes the decisions again chunk by chunk -- the same results from a fraction of the memory, for
+    pairs whose reference is thousands of letters long (``hip.EndsPlan``)."""
     two = {} if hip.gap2_of('align_pairs_ends', gap_open2, gap_extend2) is None else dict(gap_open2=gap_open2, gap_extend2=gap_extend2)
+    if traceback not in hip.ENDS_TRACEBACKS:
+        raise ValueError("align_pairs_ends: traceback must be 'stored' or 'recompute', got %r" % (traceback,))
+    if traceback != 'stored':
+        two = dict(two, traceback=traceback)
     if mode not in hip.ENDS_MODES:
         raise ValueError("align_pairs_ends: mode must be 'global', 'semiglobal', 'overlap', 'prefix' or 'extend', got %r" % (mode,))
     if len(ref_seqs) != len(query_seqs):
@@ -426,7 +434,7 @@ def _strands(strand, n):
 
 def align_pairs_spliced(ref_seqs, query_seqs, mode='semiglobal', strand='+', match=2, mismatch=2, gap_open=3, gap_extend=1, intron_open=12, noncanonical=6,
                         donor_costs=None, acceptor_costs=None, report_cigar=False, context=None, matrix=None, alphabet=None, gap_open2=None,
-                        gap_extend2=None):
+                        gap_extend2=None, traceback='stored'):
     """``align_pairs_ends`` of a transcript sequence (query) against a genomic window (reference) in which a long reference gap may be an
     intron, in one GPU call -> one PyAlignRes per pair, each with ``.strand`` ('+' or '-').
 
@@ -444,8 +452,11 @@ def align_pairs_spliced(ref_seqs, query_seqs, mode='semiglobal', strand='+', mat
     writes them, which ``align.convert_cigar_string`` and ``align.get_exons`` read; among equal scores the walk prefers the diagonal,
     then D, then N, then I, and a run on row 0 of an anchored mode is D unless N is cheaper.  DNA match / mismatch only: `matrix`,
     `alphabet`, `gap_open2` and `gap_extend2` are named here to be refused (not built).  All costs are >= 0 and gap_open >=
-    gap_extend.  Parity with minimap2's splice model, which couples donor and acceptor and has other tie rules, is not claimed."""
+    gap_extend.  Parity with minimap2's splice model, which couples donor and acceptor and has other tie rules, is not claimed.
+    traceback is ``align_pairs_ends``'s: 'recompute' is the route for a cDNA against a gene locus of tens of kilobases."""
     who = 'align_pairs_spliced'
+    if traceback not in hip.ENDS_TRACEBACKS:
+        raise ValueError("%s: traceback must be 'stored' or 'recompute', got %r" % (who, traceback))
     if matrix is not None or alphabet is not None:
         raise ValueError('%s: substitution matrices are not supported (CLH_E_UNSUPPORTED): DNA match / mismatch only' % who)
     if gap_open2 is not None or gap_extend2 is not None:
@@ -466,7 +477,8 @@ def align_pairs_spliced(ref_seqs, query_seqs, mode='semiglobal', strand='+', mat
     mat, (qd, qo), (rd, ro) = _pairs_inputs(who, refs, queries, match, mismatch, None, None)
     ctx = context or hip.default_context()
     walk = bool(report_cigar) or mode in ('semiglobal', 'overlap')      # the begins come from the walk, unless the mode fixes them
-    rows, cig = ctx.ends_batch(qd, qo, rd, ro, mat, gap_open, gap_extend, mode=mode, want_cigar=walk, splice=splice, strand=st)
+    route = {} if traceback == 'stored' else dict(traceback=traceback)
+    rows, cig = ctx.ends_batch(qd, qo, rd, ro, mat, gap_open, gap_extend, mode=mode, want_cigar=walk, splice=splice, strand=st, **route)
     out = _pairs_results(rows, cig, qo, walk, report_cigar)
     for res, s in zip(out, st):
         res.strand = '+' if s > 0 else '-'
@@ -537,7 +549,7 @@ def _stitch_anchor(left, right, ref_pos, query_pos, seed_len, seed_score=0):
 
 
 def extend_anchors(ref_seqs, query_seqs, anchors, band=None, seed_len=0, match=2, mismatch=2, gap_open=3, gap_extend=1, report_cigar=False,
-                   matrix=None, alphabet=None, context=None, gap_open2=None, gap_extend2=None):
+                   matrix=None, alphabet=None, context=None, gap_open2=None, gap_extend2=None, traceback='stored'):
     """Extend n placements both ways, in one GPU call -> one PyAlignRes per pair.
 
     anchors[k] = (ref_pos, query_pos) is a point between letters of pair k: what an ``edlib.search`` location, a minimizer hit or
@@ -554,8 +566,13 @@ def extend_anchors(ref_seqs, query_seqs, anchors, band=None, seed_len=0, match=2
     only where both halves are proved equal to the unbanded result.  The left half is aligned on reversed letters, so among equal
     scores its ties (the end cell, and diagonal before D before I in the walk) are those of the reversed problem: it is the best
     extension to the left, but not necessarily the one a single left-to-right programme over the joined sequences would pick.
-    gap_open2 and gap_extend2 are those of ``align_pairs_ends`` and ``align_pairs_band`` (two-piece gap costs)."""
+    gap_open2 and gap_extend2 are those of ``align_pairs_ends`` and ``align_pairs_band`` (two-piece gap costs); traceback is that of
+    ``align_pairs_ends`` and goes with band=None alone: the band's planes are already m x B."""
     two = {} if hip.gap2_of('extend_anchors', gap_open2, gap_extend2) is None else dict(gap_open2=gap_open2, gap_extend2=gap_extend2)
+    if traceback not in hip.ENDS_TRACEBACKS:
+        raise ValueError("extend_anchors: traceback must be 'stored' or 'recompute', got %r" % (traceback,))
+    if traceback != 'stored' and band is not None:
+        raise ValueError("extend_anchors: traceback=%r goes with band=None: K1gb has the stored route alone" % (traceback,))
     n = len(ref_seqs)
     if len(query_seqs) != n or len(anchors) != n:
         raise ValueError('extend_anchors: %d references vs %d queries vs %d anchors' % (n, len(query_seqs), len(anchors)))
@@ -585,6 +602,8 @@ def extend_anchors(ref_seqs, query_seqs, anchors, band=None, seed_len=0, match=2
     kw = dict(mode='extend', match=match, mismatch=mismatch, gap_open=gap_open, gap_extend=gap_extend, report_cigar=bool(report_cigar),
               matrix=matrix, alphabet=alphabet, context=context)
     kw.update(two)
+    if traceback != 'stored':
+        kw['traceback'] = traceback
     halves = align_pairs_ends(refs2, queries2, **kw) if band is None else align_pairs_band(refs2, queries2, int(band), **kw)
     out = []
     for k in range(n):

@@ -410,7 +410,20 @@ int clh_edit_search_batch(clh_ctx* ctx, int32_t ntext, const uint8_t* texts, con
  * with CLH_E_CAPACITY when cigar_cap (ops) is too small -- info's out[7] always suffices -- and with CLH_E_HIP if a kernel left a row
  * unwritten (never a value).  info: out[8] = {columns a lane owns, columns of a chunk (a longer reference is walked chunk after
  * chunk), shares of the batch, workspace bytes in use, those of the largest pair, pairs the kernels take, pairs with an empty side,
- * CIGAR ops fetch may return}.  Life cycle, error codes and `stream` as clh_edit_align_plan_*. */
+ * CIGAR ops fetch may return}.  Life cycle, error codes and `stream` as clh_edit_align_plan_*.
+ * want_cigar: 0 no CIGARs; 1 (and any other non-zero value) the stored route described above; CLH_ENDS_CIGAR_RECOMPUTE (2) the
+ * recompute route, for clh_ends_plan_create, _gap2 and _spliced and their _batch forms alike.  Rows and CIGARs are bit for bit the
+ * stored route's; what differs is the workspace.  The score pass keeps the last column of every chunk of 512 columns but the last, the
+ * decisions are computed again one chunk at a time, for the rows the walk can still reach, and the walk is resumed chunk after chunk
+ * leftwards.  With mpad = (m + 63) & ~63, nchunks = ceil(n / 512), NH = 2 (one piece) or 3 (two pieces, spliced) and W = 4 (one
+ * piece) or 8 bytes, a pair needs
+ *     4 NH mpad (nchunks - 1)  kept columns  +  W m 64  one chunk's plane  +  48  the walk's resume record,   rounded up to 16,
+ * where the stored route needs W m (64 (nchunks - 1) + lanes of the last chunk).  That sum is what is held against workspace_bytes
+ * -- CLH_E_CAPACITY names it for a pair that exceeds it alone -- what the shares are cut by and what info's out[2..4] report.
+ * Below about four chunks it saves little, and it computes every cell the walk can reach a second time: the choice is the caller's,
+ * no routing is made.  clh_band_* has no such route: there every non-zero want_cigar is the stored route. */
+#define CLH_ENDS_CIGAR_STORED    1
+#define CLH_ENDS_CIGAR_RECOMPUTE 2
 #define CLH_ENDS_GLOBAL     0
 #define CLH_ENDS_SEMIGLOBAL 1
 #define CLH_ENDS_OVERLAP    2

@@ -13,12 +13,18 @@ H2D in the timed run), HIP events, the median of R runs after a warm-up.  Standa
       around two GT..AG introns of about 2.5 kb -- semiglobal, score only; K1g alone, no local run.  With --splice IO,NC the plan is the
       spliced one (csrc/ssw_ends.hip); without it the same pairs run under one piece or, with --gap2, under two: the yardstick
   (h) the same with CIGARs
+  (j) 50 pairs of 20 kb x 20 kb -- the query a 10 % mutated copy of the reference -- global, with CIGARs; K1g alone
+  (k) K spliced pairs (--kpairs, default 100) -- a 2-kb cDNA of four exons mutated at 10 % against a 60-kb window that holds them around
+      three GT..AG introns of about 15 kb -- semiglobal, with CIGARs; K1g alone.  The workload the recompute route is for.
 
 Prints one JSON line per shape: ms and cells/s (sum of m n over the pairs) of both, and the ratio local / ends of the cell rates.
 With CLH_LIB naming another build's libclh.so, `--mode global` times that build on the same pairs: the yardstick of (e) and (f).
 --gap2 GO2,GE2 gives every K1g / K1gb plan a second gap piece; --scoring MA,MI,GO,GE replaces 2/2/3/1 in the DNA shapes a, b, e, f
 (the long-read costs: --scoring 2,4,4,2 --gap2 24,1); --splice IO,NC gives every K1g plan intron gaps (intron_open, noncanonical).
-usage: python tools/ends_bench.py [N=20000] [runs=10] [shapes=abcd] [--mode MODE] [--gap2 GO2,GE2] [--scoring MA,MI,GO,GE] [--splice IO,NC]"""
+--traceback stored|recompute names the route to the CIGARs of every K1g plan (default stored; a CLH_LIB build older than the route takes
+stored alone); each line then also carries the route, the workspace bytes in use and those of the largest pair.
+usage: python tools/ends_bench.py [N=20000] [runs=10] [shapes=abcd] [--mode MODE] [--gap2 GO2,GE2] [--scoring MA,MI,GO,GE] [--splice IO,NC]
+                                  [--traceback ROUTE] [--kpairs K]"""
 import json
 import os
 import sys
@@ -51,6 +57,16 @@ if '--scoring' in ARGS:
     at = ARGS.index('--scoring')
     DNA = tuple(int(x) for x in ARGS[at + 1].split(','))
     del ARGS[at:at + 2]
+TRACEBACK = 'stored'      # --traceback stored|recompute: the route to the CIGARs of every K1g plan
+if '--traceback' in ARGS:
+    at = ARGS.index('--traceback')
+    TRACEBACK = ARGS[at + 1]
+    del ARGS[at:at + 2]
+KPAIRS = 100              # --kpairs K: pairs of shape k
+if '--kpairs' in ARGS:
+    at = ARGS.index('--kpairs')
+    KPAIRS = int(ARGS[at + 1])
+    del ARGS[at:at + 2]
 N = int(ARGS[0]) if len(ARGS) > 0 else 20000
 R = int(ARGS[1]) if len(ARGS) > 1 else 10
 SHAPES = ARGS[2] if len(ARGS) > 2 else 'abcd'
@@ -58,6 +74,7 @@ SHAPES = ARGS[2] if len(ARGS) > 2 else 'abcd'
 
 def ends_ms(ctx, qd, qo, rd, ro, mat, go, ge, mode, cigar):
     more = dict(splice=hip.splice_of('ends_bench', *SPLICE)) if SPLICE else GAP2
+    more = dict(more, traceback=TRACEBACK) if TRACEBACK != 'stored' else more
     plan = ctx.ends_plan(qd, qo, rd, ro, mat, go, ge, mode=mode, want_cigar=cigar, **more)
     try:
         plan.run(); plan.fetch()                     # warm-up (code objects, allocator), and the rows are whole
@@ -98,17 +115,17 @@ def flanks(rng, count=5000, length=1000, related=600):
     return queries, refs
 
 
-def spliced_pairs(rng, count=2000, exon=200, intron=2500, window=6000):
-    """a cDNA of three exons mutated at 10 % against the window that holds them around two GT..AG introns of about `intron` letters"""
+def spliced_pairs(rng, count=2000, exon=200, intron=2500, window=6000, nexons=3):
+    """a cDNA of `nexons` exons mutated at 10 % against the window that holds them around GT..AG introns of about `intron` letters"""
     queries, refs = [], []
     for _ in range(count):
-        exons = [rng.integers(0, 4, exon).astype(np.int8) for _ in range(3)]
+        exons = [rng.integers(0, 4, exon).astype(np.int8) for _ in range(nexons)]
         introns = []
-        for _ in range(2):
+        for _ in range(nexons - 1):
             body = rng.integers(0, 4, intron + int(rng.integers(-100, 101))).astype(np.int8)
             body[:2] = (2, 3); body[-2:] = (0, 2)                      # GT .. AG
             introns.append(body)
-        core = np.concatenate([exons[0], introns[0], exons[1], introns[1], exons[2]])
+        core = np.concatenate([x for pair in zip(exons, introns + [exons[0][:0]]) for x in pair])
         flank = max(0, window - len(core))
         refs.append(np.concatenate([rng.integers(0, 4, flank // 2).astype(np.int8), core, rng.integers(0, 4, flank - flank // 2).astype(np.int8)]))
         queries.append(synth.mutate(np.concatenate(exons), rng, sub=0.04, ins=0.03, dele=0.03))
@@ -121,7 +138,8 @@ def shape(ctx, name, queries, refs, mat, go, ge, mode, cigar, local=True):
     e_ms, info = ends_ms(ctx, qd, qo, rd, ro, mat, go, ge, mode, cigar)
     if not local:
         print(json.dumps({'shape': name, 'pairs': len(queries), 'cells': cells, 'mode': mode, 'cigar': cigar,
-                          'gap2': GAP2 or None, 'splice': SPLICE, 'ends_ms': round(e_ms, 3), 'ends_gcups': round(cells / e_ms / 1e6, 2), 'shares': info['shares']}), flush=True)
+                          'gap2': GAP2 or None, 'splice': SPLICE, 'ends_ms': round(e_ms, 3), 'ends_gcups': round(cells / e_ms / 1e6, 2), 'shares': info['shares'], 'traceback': TRACEBACK,
+                          'workspace_bytes': info['workspace_bytes'], 'max_pair_bytes': info['max_pair_bytes']}), flush=True)
         return
     l_ms, classes = local_ms(ctx, qd, qo, rd, ro, mat, go, ge, cigar)
     print(json.dumps({'shape': name, 'pairs': len(queries), 'cells': cells, 'mode': mode, 'cigar': cigar,
@@ -170,6 +188,15 @@ def main():
                   'semiglobal', False, local=False)
         if 'h' in SHAPES:
             shape(ctx, 'h: the same with CIGARs', queries, refs, hip.score_matrix(*DNA[:2]), DNA[2], DNA[3], 'semiglobal', True, local=False)
+    if 'j' in SHAPES:
+        jr = np.random.Generator(np.random.PCG64(20265))
+        refs = [jr.integers(0, 4, 20000).astype(np.int8) for _ in range(50)]
+        queries = [synth.mutate(r, jr, sub=0.04, ins=0.03, dele=0.03) for r in refs]
+        shape(ctx, 'j: 20 kb x 20 kb, global, with CIGARs', queries, refs, hip.score_matrix(*DNA[:2]), DNA[2], DNA[3], 'global', True, local=False)
+    if 'k' in SHAPES:
+        queries, refs = spliced_pairs(np.random.Generator(np.random.PCG64(20266)), count=KPAIRS, exon=500, intron=15000, window=60000, nexons=4)
+        shape(ctx, 'k: 2-kb four-exon cDNA x 60-kb window with three introns, semiglobal, with CIGARs', queries, refs, hip.score_matrix(*DNA[:2]), DNA[2], DNA[3],
+              'semiglobal', True, local=False)
 
 
 if __name__ == '__main__':
