@@ -80,8 +80,16 @@ static void kmer_codes(const int8_t *seq, int L, int k, int32_t *h)
     }
 }
 
-/* step 1+2.  cuts[0..ncuts) are the boundaries after 0 (b1, b2, ...); returns period or 0 */
-int clo_ccs_segments(const int8_t *seq, int32_t L, int32_t *cuts, int32_t *ncuts, int32_t *k_used, int32_t *support)
+/* What a run of the step decided and how close each decision was (clo_ccs_trace; tests/ccs_edges.py builds its inputs on it).
+   period[]: bestd, best, offsets tied at best, harmonics evaluated, cuts made, p0, 0, 0, then per evaluated q: q, e, s[e], 2*s[e] - best.
+   cut[n][]: b, lo, hi | the vote v, its score, deltas with that score, of those with the same |delta - prev| | did the anchor stage
+   run | the chosen i, delta and its dist | anchors at the minimal dist, of those with the same i, of those with the same |delta - prev|. */
+#define CLO_CCS_TRACE_PERIOD 40
+#define CLO_CCS_TRACE_CUT 16
+typedef struct { int32_t *period, *cut; } ccs_trace_t;
+
+/* step 1+2.  cuts[0..ncuts) are the boundaries after 0 (b1, b2, ...); returns period or 0.  tr: optional record of the run */
+static int ccs_segments(const int8_t *seq, int32_t L, int32_t *cuts, int32_t *ncuts, int32_t *k_used, int32_t *support, const ccs_trace_t *tr)
 {
     *ncuts = 0; *k_used = 0; *support = 0;
     if (L < 2 * CCS_DMIN) return 0;
@@ -106,6 +114,11 @@ int clo_ccs_segments(const int8_t *seq, int32_t L, int32_t *cuts, int32_t *ncuts
             sm[d] = s;
             if (s > best) { best = s; bestd = d; }
         }
+        if (tr) {
+            int tied = 0;
+            for (int d = CCS_DMIN; d <= dmax; ++d) tied += sm[d] == best;
+            tr->period[0] = bestd; tr->period[1] = best; tr->period[2] = tied; tr->period[3] = 0;
+        }
         if (best >= CCS_MIN_SUPPORT) {
             p0 = bestd; kk = k; *support = best;
             for (int q = 2; q <= 8; ++q) {                     /* harmonics: prefer the fundamental */
@@ -114,6 +127,7 @@ int clo_ccs_segments(const int8_t *seq, int32_t L, int32_t *cuts, int32_t *ncuts
                 int eb = -1, es = -1;
                 for (int e = imax(c - 3, CCS_DMIN); e <= imin(c + 3, dmax); ++e) if (sm[e] > es) { es = sm[e]; eb = e; }
                 if (eb >= 0 && 2 * es >= best) p0 = eb;
+                if (tr) { int32_t *r = tr->period + 8 + 4 * tr->period[3]++; r[0] = q; r[1] = eb; r[2] = es; r[3] = 2 * es - best; }
             }
         }
         free(sm);
@@ -139,6 +153,13 @@ int clo_ccs_segments(const int8_t *seq, int32_t L, int32_t *cuts, int32_t *ncuts
             if (sc > vs || (sc == vs && abs(delta - prev) < abs(v - prev))) { vs = sc; v = delta; }   /* equal distance keeps the smaller delta */
         }
         int cut = v;
+        int32_t *r = tr ? tr->cut + CLO_CCS_TRACE_CUT * n : NULL;
+        if (r) {
+            memset(r, 0, sizeof(int32_t) * CLO_CCS_TRACE_CUT);
+            r[0] = b; r[1] = lo; r[2] = hi; r[3] = v; r[4] = vs; r[7] = vs > 0; r[8] = -1; r[9] = v; r[10] = -1;
+            for (int delta = lo; delta <= hi; ++delta)
+                if (hist[delta - lo] == vs) { ++r[5]; r[6] += abs(delta - prev) == abs(v - prev); }
+        }
         if (vs > 0) {
             /* b. the anchor nearest to b among those the vote does not rule out */
             int bd = 1 << 30, bi = -1, ba = 0, bdel = 0;
@@ -152,6 +173,17 @@ int clo_ccs_segments(const int8_t *seq, int32_t L, int32_t *cuts, int32_t *ncuts
                 }
             }
             cut = bdel;
+            if (r) {
+                r[8] = bi; r[9] = bdel; r[10] = bd;
+                for (int i = i0; i < i1; ++i) {
+                    if (h[i] < 0 || abs(i + CCS_K / 2 - b) != bd) continue;
+                    for (int delta = imax(lo, v - CCS_GUARD); delta <= imin(hi, v + CCS_GUARD) && i + delta < L; ++delta) {
+                        if (h[i + delta] != h[i]) continue;
+                        ++r[11];
+                        if (i == bi) { ++r[12]; r[13] += abs(delta - prev) == ba; }
+                    }
+                }
+            }
         }
         b += cut;
         prev = cut;
@@ -160,8 +192,23 @@ int clo_ccs_segments(const int8_t *seq, int32_t L, int32_t *cuts, int32_t *ncuts
     free(hist);
     free(h); free(cnt);
     *ncuts = n;
+    if (tr) { tr->period[4] = n; tr->period[5] = p0; }
     if (n < 2) { *ncuts = 0; return 0; }
     return p0;
+}
+
+int clo_ccs_segments(const int8_t *seq, int32_t L, int32_t *cuts, int32_t *ncuts, int32_t *k_used, int32_t *support)
+{
+    return ccs_segments(seq, L, cuts, ncuts, k_used, support, NULL);
+}
+
+/* the same run with its record: period[CLO_CCS_TRACE_PERIOD], cut[CCS_MAX_CUTS][CLO_CCS_TRACE_CUT] (rows of the cuts made, also where
+   fewer than two of them leave the read without a repeat) */
+int clo_ccs_trace(const int8_t *seq, int32_t L, int32_t *cuts, int32_t *ncuts, int32_t *k_used, int32_t *support, int32_t *period, int32_t *cut)
+{
+    const ccs_trace_t tr = {period, cut};
+    memset(period, 0, sizeof(int32_t) * CLO_CCS_TRACE_PERIOD);
+    return ccs_segments(seq, L, cuts, ncuts, k_used, support, &tr);
 }
 
 /* step 3 lives in poa_oracle.c */

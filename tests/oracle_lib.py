@@ -198,6 +198,40 @@ def oracle_find_consensus(seq):
     return seg, decode(out[:n]), period.value
 
 
+_TRACE_CUT = ('b', 'lo', 'hi', 'v', 'score', 'score_tied', 'score_dist_tied', 'anchor_ran', 'i', 'delta', 'dist', 'dist_tied', 'i_tied',
+              'a_tied')
+
+
+def oracle_ccs_trace(seq):
+    """oracle/ccs_oracle.c: clo_ccs_trace -- the run of clo_ccs_segments on `seq` (str or int8 codes) with its record (the same code).
+    -> dict: 'period' (0 = no repeat), 'cuts' (list), 'support'; 'bestd', 'best', 'tied' (offsets whose smoothed count equals best),
+    'p0' (the period the cuts were searched with; set even where fewer than two cuts leave 'period' 0), 'harmonics' (one dict q, e, s,
+    margin = 2 s[e] - best per evaluated q) and 'cut' (one dict per cut made: b, lo, hi, the vote v, its score, score_tied,
+    score_dist_tied, anchor_ran, the chosen i, delta, dist, and dist_tied, i_tied, a_tied of the anchor's keys)."""
+    s = np.ascontiguousarray(encode(seq) if not isinstance(seq, np.ndarray) else seq, dtype=np.int8)
+    lib = _ccs_lib()
+    lib.clo_ccs_trace.restype = C.c_int
+    lib.clo_ccs_trace.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6
+    cuts = np.zeros(64, dtype=np.int32)
+    nc, k, sup = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    per = np.zeros(40, dtype=np.int32)
+    cut = np.zeros((64, 16), dtype=np.int32)
+    p = lib.clo_ccs_trace(s.ctypes.data, len(s), cuts.ctypes.data, C.byref(nc), C.byref(k), C.byref(sup), per.ctypes.data, cut.ctypes.data)
+    return {'period': int(p), 'cuts': [int(x) for x in cuts[:nc.value]], 'support': sup.value,
+            'bestd': int(per[0]), 'best': int(per[1]), 'tied': int(per[2]), 'p0': int(per[5]),
+            'harmonics': [dict(zip(('q', 'e', 's', 'margin'), (int(x) for x in per[8 + 4 * j:12 + 4 * j]))) for j in range(int(per[3]))],
+            'cut': [dict(zip(_TRACE_CUT, (int(x) for x in cut[j]))) for j in range(int(per[4]))]}
+
+
+def oracle_ccs_segments(seq):
+    """oracle/ccs_oracle.c: clo_ccs_segments -> (period, cuts, support); (0, [], 0) without a repeat"""
+    s = np.ascontiguousarray(encode(seq) if not isinstance(seq, np.ndarray) else seq, dtype=np.int8)
+    cuts = np.zeros(64, dtype=np.int32)
+    nc, k, sup = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    p = _ccs_lib().clo_ccs_segments(s.ctypes.data, len(s), cuts.ctypes.data, C.byref(nc), C.byref(k), C.byref(sup))
+    return int(p), [int(x) for x in cuts[:nc.value]], sup.value if p else 0
+
+
 POA_DEFAULT = (10, -4, -8, -2, -24, -1)       # the scores of every reference call site (collapse.py:267,504; tests/test_poa.py:30)
 
 
