@@ -1,7 +1,7 @@
 // clh_device_ops.h -- the packed-16 arithmetic and the cross-lane moves the row-form kernels share (ssw_wavefront.hip, ssw_scan.hip,
 // ssw_scan_wide.hip, ssw_traceback_rows.hip, ccs_poa.hip), and the few helpers every Smith-Waterman kernel file would otherwise repeat
-// (the LDS-only barrier, the staged substitution matrix, the masked second best).  Device code only; all but the last are one or a few
-// gfx950 instructions.
+// (the LDS-only barrier, the staged substitution matrix, the masked second best, and what the two K1b tracebacks share: whether a CIGAR
+// is wanted, the band doubling's state and stop rule).  Device code only; the arithmetic and the moves are one or a few gfx950 instructions.
 //
 // Two DP cells per 32-bit lane register: the 16-bit halves are independent chains (v_pk_add_i16 clamp, v_pk_max_i16, v_pk_sub_u16 clamp --
 // the saturating arithmetic of the reference's SSE2 passes, libs/striped_smith_waterman/ssw.c:123-345, 371-546).  A lane's low half sits
@@ -9,6 +9,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "clh_device.h"
 
 namespace clh {
 namespace {
@@ -144,6 +145,28 @@ __device__ inline void second_best(const uint16_t* colmax, int refLen, int end_r
     score2 = bv;
     ref_end2 = bv > 0 ? bp : 0;
 }
+
+// Is a CIGAR wanted at all (ssw.c:840-869)?  `res`: the score pass's row (wave-uniform); `bad`: the status bits that rule one out.
+__device__ __forceinline__ bool cigar_wanted(const SswParams& p, const SswResult& res, int bad)
+{
+    return !((res.status & bad) || (7 & p.flag) == 0 || ((2 & p.flag) != 0 && res.score1 < p.filters) ||
+             ((4 & p.flag) != 0 && (res.ref_end1 - res.ref_begin1 > p.filterd || res.read_end1 - res.read_begin1 > p.filterd)));
+}
+
+// The band doubling of the reference's traceback (ssw.c:560-632): the band half-width, the running maximum (never reset) and the
+// number of iterations made.  advance() closes an iteration whose maximum was `it` (ssw.c:631-632): true = next band, w doubled;
+// false = stop, w stays the final band.
+struct BandDoubling {
+    int w, maxv, niter;
+    __device__ __forceinline__ bool advance(int it, int score, int readLen)
+    {
+        ++niter; maxv = it > maxv ? it : maxv;
+        const long long w2 = 2ll * w;
+        if (!(maxv < score && w2 < 2ll * readLen)) return false;
+        w = (int)w2;
+        return true;
+    }
+};
 
 }  // namespace
 }  // namespace clh

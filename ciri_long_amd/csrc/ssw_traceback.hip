@@ -127,11 +127,7 @@ __device__ void tb_antidiagonal(const SswParams& p, const typename T::mat_t* sma
         if (lane == 0) p.results[task.out_index].status = res.status;
     }
 
-    // (CLH_STATUS_BAD_CODE: K1a's score kernels set it, no other)
-    const bool no_cigar = (res.status & (CLH_STATUS_OVERFLOW8 | CLH_STATUS_BAD_CODE)) || (7 & p.flag) == 0 ||
-                          ((2 & p.flag) != 0 && res.score1 < p.filters) ||
-                          ((4 & p.flag) != 0 && (res.ref_end1 - res.ref_begin1 > p.filterd || res.read_end1 - res.read_begin1 > p.filterd));
-    if (no_cigar) {
+    if (!cigar_wanted(p, res, CLH_STATUS_OVERFLOW8 | CLH_STATUS_BAD_CODE)) {      // (BAD_CODE: K1a's score kernels set it, no other)
         if (lane == 0) { *cig_len = 0; p.results[task.out_index].status = res.status | CLH_STATUS_NO_CIGAR; }
         return;
     }
@@ -168,24 +164,21 @@ __device__ void tb_antidiagonal(const SswParams& p, const typename T::mat_t* sma
     const int8_t* const sread = staged ? sseq : read;
     const int8_t* const sref = staged ? sseq + readLen : ref;
     auto ref_at = [&](int j) -> int { return (staged || !T::kDna) ? (int)sref[j] : ref_code((int)ref[(int64_t)j * rdir], rc); };
-    int w = refLen > readLen ? refLen - readLen : readLen - refLen;
-    w += 1;
+    BandDoubling bd = {(refLen > readLen ? refLen - readLen : readLen - refLen) + 1, 0, 0};
     const int nAD = readLen + refLen - 1;
-    int maxv = 0;
     uint8_t* dir = nullptr;
-    int status = 0, niter = 0;
+    int status = 0;
     bool covered = false;
     unsigned long long last_at = 0;
 
     for (;;) {
+        const int w = bd.w, niter = bd.niter;
         const int stride_w = ad_stride(w, readLen, refLen);
         if (covered) {
             // the previous iteration's band already held every cell: this one would recompute identical values into an
             // identical layout (the reference does recompute; only its flat indexing, i.e. w, differs)
             if (lane == 0 && niter < 24) { hist_at[niter] = last_at; hist_w[niter] = w; }
-            ++niter;
-            w *= 2;
-            if (!(maxv < score && w < 2 * readLen)) break;
+            if (!bd.advance(0, score, readLen)) break;
             continue;
         }
         const bool ring = w + 3 <= wsp;   // the active rows of an anti-diagonal span <= w+1 rows
@@ -202,7 +195,6 @@ __device__ void tb_antidiagonal(const SswParams& p, const typename T::mat_t* sma
         dir = pool.base + at;
         last_at = at;
         if (lane == 0 && niter < 24) { hist_at[niter] = at; hist_w[niter] = w; }
-        ++niter;
         covered = w >= readLen && w >= refLen;
         int itmax = 0;
         for (int a = 0; a < nAD; ++a) {
@@ -248,9 +240,7 @@ __device__ void tb_antidiagonal(const SswParams& p, const typename T::mat_t* sma
         __syncthreads();
         for (int k = 0; k < (nt >> 6); ++k) itmax = s_max[k] > itmax ? s_max[k] : itmax;
         itmax = __builtin_amdgcn_readfirstlane(itmax);
-        maxv = itmax > maxv ? itmax : maxv;
-        w *= 2;
-        if (!(maxv < score && w < 2 * readLen)) break;
+        if (!bd.advance(itmax, score, readLen)) break;
     }
     if (status) {
         if (lane == 0) {
@@ -259,7 +249,7 @@ __device__ void tb_antidiagonal(const SswParams& p, const typename T::mat_t* sma
         }
         return;
     }
-    w /= 2;
+    const int w = bd.w, niter = bd.niter;      // the final band
     // the walk reads direction bytes other waves stored: the stores must have reached L2 and this CU's L1 must not serve old lines
     // (a workgroup-scope fence does not wait for them: the last anti-diagonals' bytes could still be in flight)
     __threadfence();

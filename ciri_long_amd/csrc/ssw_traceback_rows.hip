@@ -25,6 +25,18 @@
 // cross the waves through LDS, two light barriers per row); the narrow launch hands over the state of its doubling loop, the next
 // three iterations of every handed-over alignment run side by side (ssw_traceback_rows_wide_pass_kernel), the loop is replayed over
 // their maxima and wave 0 walks (ssw_traceback_rows_wide_kernel).  The walk takes runs of diagonal moves in one step.
+//
+// The file, top to bottom.  Each of these has one definition, whichever launch uses it:
+//   tb_rows_pass<CP, DIRS, COLS, NW>   one band iteration, one wave or a workgroup (tb_rows_iter / tb_rows_iter_mw pick CP and the layout);
+//   TbPlane, tb_plane_store / _load    an iteration's codes in the pool, and the 8-int record that carries one through the pool or LDS;
+//   tb_pool_take, tb_make_plane<NW>    pool space, and an iteration with codes into it (NW = 1 one wave, NW = kMw the workgroup);
+//   tb_rows_setup, tb_finish           the alignment's row and aligned parts; leaving a launch without a CIGAR (one status bit says why);
+//   tb_rows_walk<MAXCP, MW>            the walk back, resumable when the workgroup has to fetch an earlier iteration's codes;
+//   BandDoubling (clh_device_ops.h)    the loop's state and its stop rule (ssw.c:631-632), driven by tb_rows_one's loop (first iteration
+//                                      score-only, the final band once more for its codes, the `covered` shortcut) and by
+//                                      tb_rows_wide_one's replay over the pass records and its continuation;
+//   tb_rows_one / tb_rows_wide_pass / tb_rows_wide_one (setup, replay, continue, walk; tb_narrow_planes on the walk's first request),
+//   the three kernels and the two launchers.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <algorithm>
@@ -32,15 +44,7 @@
 #include "clh_device_ops.h"
 
 namespace clh {
-
-#ifdef CLH_TBW_TRACE
-__device__ long long g_tbw_dbg[8 * 1024];
-__device__ int g_tbw_n;
-#endif
-
 namespace {
-
-
 
 static constexpr uint32_t SEL_NONE = 0x0c0c0c0cu;      // v_perm selector 0x0c = constant 0: "no reference base here"
 
@@ -79,7 +83,7 @@ __device__ int tb_rows_pass(const TbIn& in, const int w, uint8_t* dir, TbX* xs =
     const int gl = wave * 64 + lane;                    // the lane's place among all the virtual lanes of the row
     const int shiftc = COLS ? 0 : NV - 1 - 2 * w;
     const int gO = in.gO, gE = in.gE;
-    const uint32_t gO2 = dup16(gO), gE2 = dup16(gE), bias2 = dup16(in.bias), xfix = dup16(gO - gE), dG2 = dup16(gO - gE);
+    const uint32_t gO2 = dup16(gO), gE2 = dup16(gE), bias2 = dup16(in.bias), dG2 = dup16(gO - gE);
     const int K = CP * gE, kLo = 2 * gl * K;
     uint32_t inb[CP], refsel[CP], Hp[CP], Ep[CP];      // inb: offsets inside the band (COLS: the lane's two column numbers)
 #pragma unroll
@@ -162,7 +166,7 @@ __device__ int tb_rows_pass(const TbIn& in, const int w, uint8_t* dir, TbX* xs =
                 inv[t] = pk_sra15(refsel[t] << 12);                           // selector bit 3: no base in this cell
                 if constexpr (COLS) inv[t] |= bandinv[t];
                 inv[t] = mask_keep(inv[t]);                                      // (a mask, used as one: clh_device_ops.h, pk_lt_mask)
-                c[t] = pk_subs(bfi_keep(inv[t], xfix, X[t]), gO2);                 // what the cell offers its right neighbour's F; an absent cell: -gapE
+                c[t] = pk_subs(bfi_keep(inv[t], dG2, X[t]), gO2);                 // what the cell offers its right neighbour's F; an absent cell: -gapE
             }
             // F: prefix maximum over the offsets (frame in which crossing a virtual lane costs nothing)
             uint32_t f[CP];
@@ -221,24 +225,12 @@ __device__ int tb_rows_pass(const TbIn& in, const int w, uint8_t* dir, TbX* xs =
                     x[t] = (mgt & bfi_keep(mef, 0x00010001u, 0x00020002u)) | (mde[t] & 0x00040004u) | (mdf & 0x00080008u);
                 }
                 uint8_t* drow = dir + (size_t)i * rowbytes + (size_t)(gl - first_lane) * CP;
-                if (gl < first_lane) {}
-                else if constexpr (CP == 1) { *drow = (uint8_t)((x[0] & 0xfu) | ((x[0] >> 12) & 0xf0u)); }
-                else if constexpr (CP == 2) { const uint32_t y = x[0] | (x[1] << 4); *(uint16_t*)drow = (uint16_t)((y & 0xffu) | ((y >> 8) & 0xff00u)); }
-                else {
-                    // bytes of the lane: the low halves' offsets (two per byte), then the high halves'
-                    uint32_t y[CP / 2], wd[CP / 4];
-#pragma unroll
-                    for (int m = 0; m < CP / 2; ++m) y[m] = x[2 * m] | (x[2 * m + 1] << 4);
-                    if constexpr (CP == 4) wd[0] = __builtin_amdgcn_perm(y[1], y[0], 0x06020400u);
-                    else {
-#pragma unroll
-                        for (int g = 0; g < CP / 8; ++g) {
-                            wd[g] = __builtin_amdgcn_perm(y[4 * g + 1], y[4 * g], 0x0c0c0400u) | __builtin_amdgcn_perm(y[4 * g + 3], y[4 * g + 2], 0x04000c0cu);
-                            wd[CP / 8 + g] = __builtin_amdgcn_perm(y[4 * g + 1], y[4 * g], 0x0c0c0602u) | __builtin_amdgcn_perm(y[4 * g + 3], y[4 * g + 2], 0x06020c0cu);
-                        }
-                    }
-#pragma unroll
-                    for (int g = 0; g < CP / 4; ++g) ((uint32_t*)drow)[g] = wd[g];
+                // bytes of the lane: the low halves' offsets (two per byte), then the high halves'
+                static_assert(CP == 1 || CP == 2 || CP == 4, "one, two or four registers per lane");
+                if (gl >= first_lane) {
+                    if constexpr (CP == 1) { *drow = (uint8_t)((x[0] & 0xfu) | ((x[0] >> 12) & 0xf0u)); }
+                    else if constexpr (CP == 2) { const uint32_t y = x[0] | (x[1] << 4); *(uint16_t*)drow = (uint16_t)((y & 0xffu) | ((y >> 8) & 0xff00u)); }
+                    else *(uint32_t*)drow = __builtin_amdgcn_perm(x[2] | (x[3] << 4), x[0] | (x[1] << 4), 0x06020400u);
                 }
             }
 #pragma unroll
@@ -257,8 +249,8 @@ __device__ int tb_rows_pass(const TbIn& in, const int w, uint8_t* dir, TbX* xs =
     return best;
 }
 
-// one wave, bands up to 128*MAXCP cells (MAXCP = 4)
-template <int MAXCP, bool DIRS>
+// one wave, bands up to 512 cells
+template <bool DIRS>
 __device__ int tb_rows_iter(const TbIn& in, int w, uint8_t* dir)
 {
     if (2 * w + 1 <= 128) return tb_rows_pass<1, DIRS, false>(in, w, dir);
@@ -286,12 +278,9 @@ __device__ __forceinline__ bool fits_mw(int w, int refLen, int readLen)
     return refLen <= 256 * kMw && w + readLen < 32000;       // by column: i + w must fit 16 bits
 }
 
-}  // namespace
-
-namespace {
-
-// the direction codes of one band iteration in the pool: geometry as in tb_rows_pass
+// the direction codes of one band iteration in the pool: geometry as in tb_rows_pass.  w = -1: no plane
 struct TbPlane { int w, by_col, shiftc, nb0, nvb, rowbytes; uint8_t* dir; };
+static constexpr TbPlane kNoPlane = {-1, 0, 0, 0, 0, 0, nullptr};
 __device__ __forceinline__ void tb_plane_geom(TbPlane& pl, int w, bool by_col, int cpf, int nv)
 {
     pl.w = w; pl.by_col = by_col;
@@ -304,44 +293,59 @@ __device__ __forceinline__ unsigned long long tb_plane_bytes(const TbPlane& pl, 
     return ((unsigned long long)readLen * (unsigned long long)pl.rowbytes + 64ull + 63ull) & ~63ull;   // + 64: the walk reads 16 bytes from a row's start
 }
 
-// computes iteration w with direction codes into fresh pool space (one wave; the codes are then read by this wave only);
-// false: pool exhausted.  itmax: the iteration's maximum.
-template <int MAXCP>
-__device__ bool tb_make_plane(const TbIn& in, const int w, uint8_t* pool_base, unsigned long long* pool_head, unsigned long long pool_size, TbPlane& pl, int* itmax = nullptr)
+// A plane as 8 ints (a pool record, an LDS slot), dir as its pool offset: the only code that knows the layout.  UNIFORM: the loaded
+// plane sits in scalar registers.
+__device__ __forceinline__ unsigned long long join64(int lo, int hi) { return (unsigned long long)(unsigned)lo | ((unsigned long long)(unsigned)hi << 32); }
+__device__ __forceinline__ void tb_plane_store(int* q, const TbPlane& pl, const uint8_t* pool_base)
 {
-    const int lane = threadIdx.x & 63;
-    const int cpf = cp_of(w);
-    tb_plane_geom(pl, w, false, cpf, 128 * cpf);
-    const unsigned long long need = tb_plane_bytes(pl, in.readLen);
-    unsigned long long at = 0;
-    if (lane == 0) at = atomicAdd(pool_head, need);
-    at = (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(at & 0xffffffffull)) | ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(at >> 32)) << 32);
-    if (at + need > pool_size) return false;
-    pl.dir = pool_base + at;
-    const int it = tb_rows_iter<MAXCP, true>(in, w, pl.dir);
-    if (itmax) *itmax = it;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    return true;
+    const unsigned long long off = pl.dir ? (unsigned long long)(pl.dir - pool_base) : 0ull;
+    q[0] = pl.w; q[1] = pl.by_col; q[2] = pl.shiftc; q[3] = pl.nb0; q[4] = pl.nvb; q[5] = pl.rowbytes; q[6] = (int)(off & 0xffffffffull); q[7] = (int)(off >> 32);
 }
-// the same by the whole workgroup (every wave calls it with the same arguments and gets the same answers)
-__device__ bool tb_make_plane_mw(const TbIn& in, const int w, uint8_t* pool_base, unsigned long long* pool_head, unsigned long long pool_size, TbPlane& pl, TbX* xs, int* itmax = nullptr)
+template <bool UNIFORM = false>
+__device__ __forceinline__ TbPlane tb_plane_load(const int* q, uint8_t* pool_base)
 {
-    const bool by_col = 2 * w + 1 > 256 * kMw;
-    const int cpf = (by_col ? in.refLen <= 128 * kMw : 2 * w + 1 <= 128 * kMw) ? 1 : 2;
-    tb_plane_geom(pl, w, by_col, cpf, 128 * cpf * kMw);
+    int v[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = UNIFORM ? __builtin_amdgcn_readfirstlane(q[k]) : q[k];
+    return TbPlane{v[0], v[1], v[2], v[3], v[4], v[5], pool_base + join64(v[6], v[7])};
+}
+
+// `need` bytes of the pool for the wave (NW = 1) or the workgroup; `at`: their offset, in scalar registers.  false: pool exhausted
+template <int NW>
+__device__ __forceinline__ bool tb_pool_take(const unsigned long long need, unsigned long long* pool_head, const unsigned long long pool_size, TbX* xs, unsigned long long& at)
+{
+    at = 0;
+    if constexpr (NW > 1) {
+        if (threadIdx.x == 0) xs->at = atomicAdd(pool_head, need);
+        __syncthreads();
+        at = xs->at;
+        __syncthreads();
+    } else if ((threadIdx.x & 63) == 0) at = atomicAdd(pool_head, need);
+    at = join64(__builtin_amdgcn_readfirstlane((int)(at & 0xffffffffull)), __builtin_amdgcn_readfirstlane((int)(at >> 32)));
+    return at + need <= pool_size;
+}
+
+// computes iteration w with direction codes into fresh pool space; false: pool exhausted.  itmax: the iteration's maximum.
+// NW = 1: one wave (the codes are then read by this wave only).  NW = kMw: the whole workgroup (every wave calls it with the same
+// arguments and gets the same answers; any wave may read the codes afterwards: the barrier between the fences)
+template <int NW>
+__device__ bool tb_make_plane(const TbIn& in, const int w, uint8_t* pool_base, unsigned long long* pool_head, unsigned long long pool_size, TbPlane& pl, TbX* xs = nullptr, int* itmax = nullptr)
+{
+    if constexpr (NW > 1) {
+        const bool by_col = 2 * w + 1 > 256 * kMw;
+        const int cpf = (by_col ? in.refLen <= 128 * kMw : 2 * w + 1 <= 128 * kMw) ? 1 : 2;
+        tb_plane_geom(pl, w, by_col, cpf, 128 * cpf * kMw);
+    } else tb_plane_geom(pl, w, false, cp_of(w), 128 * cp_of(w));
     const unsigned long long need = tb_plane_bytes(pl, in.readLen);
-    if (threadIdx.x == 0) xs->at = atomicAdd(pool_head, need);
-    __syncthreads();
-    unsigned long long at = xs->at;
-    __syncthreads();
-    at = (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(at & 0xffffffffull)) | ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(at >> 32)) << 32);
-    if (at + need > pool_size) return false;
+    unsigned long long at;
+    if (!tb_pool_take<NW>(need, pool_head, pool_size, xs, at)) return false;
     pl.dir = pool_base + at;
-    const int it = tb_rows_iter_mw<true>(in, w, pl.dir, xs);
+    int it;
+    if constexpr (NW > 1) it = tb_rows_iter_mw<true>(in, w, pl.dir, xs);
+    else it = tb_rows_iter<true>(in, w, pl.dir);
     if (itmax) *itmax = it;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    __syncthreads();
+    if constexpr (NW > 1) __syncthreads();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     return true;
 }
@@ -349,6 +353,12 @@ __device__ bool tb_make_plane_mw(const TbIn& in, const int w, uint8_t* pool_base
 // What both launches do first: the row of the score pass, whether a CIGAR is wanted at all (ssw.c:840-869), the aligned parts.
 // Returns false when the alignment is finished (no CIGAR / the 1x1 problem).
 struct TbJob { SswTask task; SswResult res; uint32_t* cig; int* cig_len; TbIn in; };
+// the alignment leaves the launch without a CIGAR: length 0 and the status bit that says why, or which launch takes it from here
+__device__ __forceinline__ void tb_finish(const SswParams& p, const TbJob& jb, const bool writer, const int status_bit)
+{
+    if (writer) { *jb.cig_len = 0; p.results[jb.task.out_index].status = jb.res.status | status_bit; }
+}
+__device__ __forceinline__ bool tb_frames_fit(const SswParams& p) { return p.gapE <= 60 && p.gapO <= 255; }      // the frames of the F scan are 16-bit
 __device__ __forceinline__ bool tb_rows_setup(const SswParams& p, const uint2* s_tab, const int task_index, const bool clear_big, const bool writer, TbJob& jb)
 {
     jb.task = p.tasks[task_index];
@@ -362,19 +372,13 @@ __device__ __forceinline__ bool tb_rows_setup(const SswParams& p, const uint2* s
     if (clear_big) res.status &= ~CLH_STATUS_NEED_BIG;      // set by the narrow launch that handed this alignment over
     jb.cig = p.cigars + task.cigar_off;
     jb.cig_len = p.cigar_len + task.out_index;
-    const bool no_cigar = (res.status & CLH_STATUS_OVERFLOW8) || (7 & p.flag) == 0 ||
-                          ((2 & p.flag) != 0 && res.score1 < p.filters) ||
-                          ((4 & p.flag) != 0 && (res.ref_end1 - res.ref_begin1 > p.filterd || res.read_end1 - res.read_begin1 > p.filterd));
-    if (no_cigar) {
-        if (writer) { *jb.cig_len = 0; p.results[task.out_index].status = res.status | CLH_STATUS_NO_CIGAR; }
-        return false;
-    }
+    if (!cigar_wanted(p, res, CLH_STATUS_OVERFLOW8)) { tb_finish(p, jb, writer, CLH_STATUS_NO_CIGAR); return false; }
     if (res.ref_begin1 < 0) {   // score 0: the reference's 1x1 problem never enters its traceback loop -> 1M
         if (writer) { jb.cig[0] = (1u << 4); *jb.cig_len = 1; }
         return false;
     }
     if (res.score1 >= 32767) {   // saturated by the 16-bit pass: the reference's int DP counts past the 16-bit frame -> the int32 traceback
-        if (writer) { *jb.cig_len = 0; p.results[task.out_index].status = res.status | CLH_STATUS_NEED_W32; }
+        tb_finish(p, jb, writer, CLH_STATUS_NEED_W32);
         return false;
     }
     TbIn& in = jb.in;
@@ -417,6 +421,10 @@ __device__ int tb_rows_walk(const SswParams& p, const TbJob& jb, const TbPlane& 
     int ib = k.ib, pb = k.pb;
     uint32_t pw0 = k.pw0, pw1 = k.pw1, pw2 = k.pw2, pw3 = k.pw3;
     int need_w = 0;
+    auto emit = [&](int len, int o) {       // one CIGAR entry, written by lane 0 while there is room; counted anyway
+        if (nops < task.cigar_cap && lane == 0) cig[nops] = ((uint32_t)len << 4) | (uint32_t)o;
+        ++nops;
+    };
     while (i > 0) {
         int nb;
         if (!(j >= 0 && j <= i + w && j >= i - w && j < refLen)) {
@@ -441,7 +449,7 @@ __device__ int tb_rows_walk(const SswParams& p, const TbJob& jb, const TbPlane& 
                         if constexpr (MW) {
                             if (!fits_mw((int)wk, refLen, readLen)) { fail = 2; break; }
                             need_w = (int)wk; break;
-                        } else if (!fits(MAXCP, (int)wk) || !tb_make_plane<MAXCP>(in, (int)wk, pool_base, pool_head, pool_size, old)) { fail = 2; break; }
+                        } else if (!fits(MAXCP, (int)wk) || !tb_make_plane<1>(in, (int)wk, pool_base, pool_head, pool_size, old)) { fail = 2; break; }
                     }
                     pl = have ? have : &old;
                 }
@@ -480,10 +488,7 @@ __device__ int tb_rows_walk(const SswParams& p, const TbJob& jb, const TbPlane& 
             int r = ~dm == 0ull ? 64 : __builtin_ctzll(~dm);
             r = r < 64 - src ? r : 64 - src; r = r < i ? r : i; r = r < j + 1 ? r : j + 1;
             if (r >= 2) {
-                if (prev_op != 0) {
-                    if (nops < task.cigar_cap && lane == 0) cig[nops] = ((uint32_t)run << 4) | (uint32_t)prev_op;
-                    ++nops; prev_op = 0; run = 0;
-                }
+                if (prev_op != 0) { emit(run, prev_op); prev_op = 0; run = 0; }
                 run += r; i -= r; j -= r; op = 0;
                 continue;
             }
@@ -501,10 +506,7 @@ __device__ int tb_rows_walk(const SswParams& p, const TbJob& jb, const TbPlane& 
             default: --j; state = 2; op = 2; break;
         }
         if (op == prev_op) ++run;
-        else {
-            if (nops < task.cigar_cap && lane == 0) cig[nops] = ((uint32_t)run << 4) | (uint32_t)prev_op;
-            ++nops; prev_op = op; run = 1;
-        }
+        else { emit(run, prev_op); prev_op = op; run = 1; }
     }
     if (MW && need_w) {
         k.i = i; k.j = j; k.state = state; k.run = run; k.nops = nops; k.op = op; k.prev_op = prev_op; k.ib = ib; k.pb = pb; k.need_w = need_w;
@@ -512,23 +514,10 @@ __device__ int tb_rows_walk(const SswParams& p, const TbJob& jb, const TbPlane& 
         return 3;
     }
     if (fail == 2) return 2;
-    if (fail) {
-        if (lane == 0) { *jb.cig_len = 0; p.results[task.out_index].status = jb.res.status | CLH_STATUS_TRACE_ERR; }
-        return 0;
-    }
-    if (op == 0) {                                   // ssw.c:697-714
-        if (nops < task.cigar_cap && lane == 0) cig[nops] = ((uint32_t)(run + 1) << 4);
-        ++nops;
-    } else {
-        if (nops < task.cigar_cap && lane == 0) cig[nops] = ((uint32_t)run << 4) | (uint32_t)op;
-        ++nops;
-        if (nops < task.cigar_cap && lane == 0) cig[nops] = (1u << 4);
-        ++nops;
-    }
-    if (nops > task.cigar_cap) {
-        if (lane == 0) { *jb.cig_len = 0; p.results[task.out_index].status = jb.res.status | CLH_STATUS_CIGAR_TRUNC; }
-        return 0;
-    }
+    if (fail) { tb_finish(p, jb, lane == 0, CLH_STATUS_TRACE_ERR); return 0; }
+    if (op == 0) emit(run + 1, 0);                   // ssw.c:697-714
+    else { emit(run, op); emit(1, 0); }
+    if (nops > task.cigar_cap) { tb_finish(p, jb, lane == 0, CLH_STATUS_CIGAR_TRUNC); return 0; }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");       // lane 0's entries, read back by every lane of this wave
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     for (int q = lane; q < nops / 2; q += 64) {      // reverse in place, ssw.c:716-725
@@ -543,6 +532,16 @@ __device__ int tb_rows_walk(const SswParams& p, const TbJob& jb, const TbPlane& 
 // and leave {maximum, plane} in a record in the pool: ints [0, kSpec) the maxima (or a code below), then 8 ints per plane.
 static constexpr int kSpec = 3, kSpecBytes = 128;
 static constexpr int TB_NONE = -1, TB_UNFIT = -2, TB_NOPOOL = -3, TB_NOTRUN = -5;
+// the record behind the handle the hand-over state carries (its pool offset in 64-byte units, plus one; 0: none), and plane j in it
+__device__ __forceinline__ int* tb_spec_rec(uint8_t* pool_base, int handle) { return (int*)(pool_base + ((unsigned long long)(handle - 1) << 6)); }
+__device__ __forceinline__ int* tb_spec_plane(int* rec, int j) { return rec + 4 + 8 * j; }
+// the hand-over state of list entry k {band, running maximum, iterations made, record handle}, in scalar registers
+__device__ __forceinline__ int4 tb_state_load(const int* state, int k)
+{
+    int4 st = *(const int4*)(state + 4 * (size_t)k);
+    st.x = __builtin_amdgcn_readfirstlane(st.x); st.y = __builtin_amdgcn_readfirstlane(st.y); st.z = __builtin_amdgcn_readfirstlane(st.z); st.w = __builtin_amdgcn_readfirstlane(st.w);
+    return st;
+}
 
 // One alignment, one wave: bands up to 512 cells (the launch over all alignments, 4 waves per SIMD).  What this width cannot
 // take goes on `next_list` together with the state of the band doubling, so that the wide launch goes on where this one stopped.
@@ -556,8 +555,8 @@ __device__ void tb_rows_one(const SswParams& p, const uint2* s_tab, uint8_t* poo
     const SswResult& res = jb.res;
     const TbIn& in = jb.in;
     auto hand_over = [&](int w_next, int maxv, int done) {
+        tb_finish(p, jb, lane == 0, CLH_STATUS_NEED_BIG);
         if (lane == 0) {
-            *jb.cig_len = 0; p.results[jb.task.out_index].status = res.status | CLH_STATUS_NEED_BIG;
             const int slot = atomicAdd(next_n, 1);
             next_list[slot] = task_index;
             const unsigned long long at = atomicAdd(pool_head, (unsigned long long)kSpecBytes);      // where the wide launch's passes leave their results
@@ -571,42 +570,38 @@ __device__ void tb_rows_one(const SswParams& p, const uint2* s_tab, uint8_t* poo
         }
     };
     const int readLen = in.readLen, refLen = in.refLen, score = res.score1;
-    int w = (refLen > readLen ? refLen - readLen : readLen - refLen) + 1;
-    const int w0 = w;
-    if (p.gapE > 60 || p.gapO > 255) { hand_over(w0, 0, 0); return; }       // the frames of the F scan are 16-bit
+    const int w0 = (refLen > readLen ? refLen - readLen : readLen - refLen) + 1;
+    if (!tb_frames_fit(p)) { hand_over(w0, 0, 0); return; }
 
     // ---- band doubling (ssw.c:560-632).  The first iteration score-only (it is the last one for a fifth of C2's alignments, and
     // the narrowest); every later one with direction codes, so that the last is not run twice -------------------------
-    int maxv = 0, niter = 0;
+    BandDoubling bd = {w0, 0, 0};
     bool covered = false;
-    TbPlane fin, old;
-    old = TbPlane{-1, 0, 0, 0, 0, 0, nullptr}; fin = old;
-    auto no_pool = [&]() { if (lane == 0) { *jb.cig_len = 0; p.results[jb.task.out_index].status = res.status | CLH_STATUS_CIGAR_TRUNC; } };
+    TbPlane fin = kNoPlane, old = kNoPlane;
     for (bool last = false;;) {                        // last: the final band once more, for its codes (one call site of the pass with codes)
-        if (!last) ++niter;
         if (last || !covered) {
-            if (!fits(MAXCP, w)) { hand_over(w, maxv, niter - 1); return; }
+            if (!last && !fits(MAXCP, bd.w)) { hand_over(bd.w, bd.maxv, bd.niter); return; }
             int it = 0;
-            if (niter == 1 && !last) it = tb_rows_iter<MAXCP, false>(in, w, nullptr);
+            if (bd.niter == 0) it = tb_rows_iter<false>(in, bd.w, nullptr);
             else {
                 if (fin.w > 0) old = fin;
-                if (!tb_make_plane<MAXCP>(in, w, pool_base, pool_head, pool_size, fin, &it)) { no_pool(); return; }
+                if (!tb_make_plane<1>(in, bd.w, pool_base, pool_head, pool_size, fin, nullptr, &it)) { tb_finish(p, jb, lane == 0, CLH_STATUS_CIGAR_TRUNC); return; }
             }
             if (last) break;
-            maxv = it > maxv ? it : maxv;
-            covered = w >= readLen && w >= refLen;      // a wider band holds the same cells: same values
+            bd.maxv = it > bd.maxv ? it : bd.maxv;
+            covered = bd.w >= readLen && bd.w >= refLen;      // a wider band holds the same cells: same values
         }
-        w *= 2;
-        if (!(maxv < score && w < 2 * readLen)) {
-            w /= 2;
-            if (!fits(MAXCP, w)) { hand_over(w, maxv, niter - 1); return; }      // (the iteration of this band once more over there: same values)
-            if (fin.w == w) break;
+        // (the maximum joined above, `it` not kept live past the pass: a covered iteration has none of its own, and with `it` at
+        // loop scope the kernel spills half as many scalar registers again around the inlined passes; LABNOTES 25)
+        if (!bd.advance(bd.maxv, score, readLen)) {
+            if (!fits(MAXCP, bd.w)) { hand_over(bd.w, bd.maxv, bd.niter - 1); return; }      // (the iteration of this band once more over there: same values)
+            if (fin.w == bd.w) break;
             last = true;                               // the first iteration was the last, or the band went on doubling over the same cells
         }
     }
     TbWalk wk;
     tb_walk_init(wk, readLen, refLen);
-    if (tb_rows_walk<MAXCP, false>(p, jb, fin, old, nullptr, 0, wk, niter, w0, w, pool_base, pool_head, pool_size) == 2) hand_over(w0, 0, 0);   // pool exhausted or an earlier band this launch cannot hold
+    if (tb_rows_walk<MAXCP, false>(p, jb, fin, old, nullptr, 0, wk, bd.niter, w0, bd.w, pool_base, pool_head, pool_size) == 2) hand_over(w0, 0, 0);   // pool exhausted or an earlier band this launch cannot hold
 }
 
 // One band pass of a handed-over alignment, a workgroup of kMw waves (the band split over the waves, tb_rows_iter_mw): iteration
@@ -618,12 +613,11 @@ __device__ void tb_rows_wide_pass(const SswParams& p, const uint2* s_tab, TbX* x
                                   const int task_index, const int4 st, const int j)
 {
     if (st.w <= 0) return;
-    int* const rec = (int*)(pool_base + ((unsigned long long)(st.w - 1) << 6));
-    const bool writer = threadIdx.x == 0;
+    int* const rec = tb_spec_rec(pool_base, st.w);
     TbJob jb;
     int it = TB_NONE;
-    TbPlane pl = TbPlane{-1, 0, 0, 0, 0, 0, nullptr};
-    if (tb_rows_setup(p, s_tab, task_index, true, false, jb) && !(p.gapE > 60 || p.gapO > 255)) {
+    TbPlane pl = kNoPlane;
+    if (tb_rows_setup(p, s_tab, task_index, true, false, jb) && tb_frames_fit(p)) {
         const long long wj = (long long)st.x << j;
         if (j == 0 || wj < 2ll * jb.in.readLen) {      // (ssw.c:632: the doubling gets here only while w < 2 readLen)
             // a pass that may not be needed (j > 0) leaves the last quarter of the pool to those that are
@@ -636,19 +630,41 @@ __device__ void tb_rows_wide_pass(const SswParams& p, const uint2* s_tab, TbX* x
             }
             if (wj > 0x3fffffff || !fits_mw((int)wj, jb.in.refLen, jb.in.readLen)) it = TB_UNFIT;
             else if (j > 0 && used + (unsigned long long)jb.in.readLen * 1100ull > pool_size - pool_size / 4) it = TB_NOTRUN;
-            else { int m = 0; it = tb_make_plane_mw(jb.in, (int)wj, pool_base, pool_head, pool_size, pl, xs, &m) ? m : (j > 0 ? TB_NOTRUN : TB_NOPOOL); }
+            else { int m = 0; it = tb_make_plane<kMw>(jb.in, (int)wj, pool_base, pool_head, pool_size, pl, xs, &m) ? m : (j > 0 ? TB_NOTRUN : TB_NOPOOL); }
         }
     }
-    if (writer) {
-        const unsigned long long off = pl.dir ? (unsigned long long)(pl.dir - pool_base) : 0ull;
-        int* q = rec + 4 + 8 * j;
-        q[0] = pl.w; q[1] = pl.by_col; q[2] = pl.shiftc; q[3] = pl.nb0; q[4] = pl.nvb; q[5] = pl.rowbytes; q[6] = (int)(off & 0xffffffffull); q[7] = (int)(off >> 32);
-        rec[j] = it;
-    }
+    if (threadIdx.x == 0) { tb_plane_store(tb_spec_plane(rec, j), pl, pool_base); rec[j] = it; }
 }
 
-// The rest of a handed-over alignment, a workgroup of kMw waves: the doubling loop replayed over the passes' maxima (and gone on
-// with, pass by pass, if they did not reach the end), then wave 0 walks; when it wants the codes of an iteration that is not at
+// The first time the wide walk leaves the band: the codes of ALL the narrow launch's iterations (it ran them without), one band per
+// wave side by side -- a walk that reads stale codes once tends to do so in several iterations' areas.  The planes join `kept`
+// (through the waves' LDS slots: every wave keeps the same table); true: the plane with band `want` is among them now.
+static constexpr int kNKept = 4 + kMw;                 // the codes of earlier iterations at hand
+__device__ __forceinline__ bool tb_narrow_planes(const TbIn& in, TbX* xs, uint8_t* pool_base, unsigned long long* pool_head, unsigned long long pool_size,
+                                                 const int w0, const int niter, TbPlane* kept, int& nkept, const int want)
+{
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    TbPlane mine = kNoPlane;
+    const long long wq = (long long)w0 << wave;
+    bool have = wave >= niter - 1 || wq > 255 || !fits(4, (int)wq);
+    for (int u = 0; u < nkept; ++u) have = have || kept[u].w == (int)wq;
+    if (!have && !tb_make_plane<1>(in, (int)wq, pool_base, pool_head, pool_size, mine)) mine.w = -1;
+    if ((threadIdx.x & 63) == 0) tb_plane_store(xs->lz[wave], mine, pool_base);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    __syncthreads();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    for (int v = 0; v < kMw; ++v) {
+        const TbPlane t = tb_plane_load(xs->lz[v], pool_base);
+        if (t.w > 0 && nkept < kNKept) kept[nkept++] = t;
+    }
+    __syncthreads();
+    bool now = false;
+    for (int u = 0; u < nkept; ++u) now = now || kept[u].w == want;
+    return now;
+}
+
+// The rest of a handed-over alignment, a workgroup of kMw waves: setup; the doubling loop replayed over the passes' maxima; gone on
+// with, pass by pass, if they did not reach the end; then wave 0 walks, and when it wants the codes of an iteration that is not at
 // hand the whole workgroup computes them and it goes on.  What this launch cannot take goes on `next_list`.
 __device__ void tb_rows_wide_one(const SswParams& p, const uint2* s_tab, TbX* xs, uint8_t* pool_base, unsigned long long* pool_head, unsigned long long pool_size,
                                  const int task_index, const int4 st, const int nspec, int* next_n, int* next_list)
@@ -659,120 +675,55 @@ __device__ void tb_rows_wide_one(const SswParams& p, const uint2* s_tab, TbX* xs
     const bool go = tb_rows_setup(p, s_tab, task_index, true, writer, jb);
     __syncthreads();                                   // every wave has the row before wave 0 may change its status
     if (!go) return;
-    const SswResult& res = jb.res;
     const TbIn& in = jb.in;
     auto hand_over = [&]() {
-        if (writer) { *jb.cig_len = 0; p.results[jb.task.out_index].status = res.status | CLH_STATUS_NEED_BIG; next_list[atomicAdd(next_n, 1)] = task_index; }
+        tb_finish(p, jb, writer, CLH_STATUS_NEED_BIG);
+        if (writer) next_list[atomicAdd(next_n, 1)] = task_index;
     };
-    auto no_pool = [&]() {
-        if (writer) { *jb.cig_len = 0; p.results[jb.task.out_index].status = res.status | CLH_STATUS_CIGAR_TRUNC; }
-    };
-    const int readLen = in.readLen, refLen = in.refLen, score = res.score1;
+    const int readLen = in.readLen, refLen = in.refLen, score = jb.res.score1;
     const int w0 = (refLen > readLen ? refLen - readLen : readLen - refLen) + 1;
-    if (p.gapE > 60 || p.gapO > 255) { hand_over(); return; }
-    long long w = st.x;
-    int maxv = st.y, niter = st.z;
-    constexpr int NKEPT = 4 + kMw;                     // the codes of earlier iterations at hand
-    TbPlane fin, old, kept[NKEPT];
+    if (!tb_frames_fit(p)) { hand_over(); return; }
+    BandDoubling bd = {st.x, st.y, st.z};              // where the narrow launch stopped
+    TbPlane fin = kNoPlane, old = kNoPlane, kept[kNKept];
     int nkept = 0;
-    bool narrow_made = false;
-    old = TbPlane{-1, 0, 0, 0, 0, 0, nullptr}; fin = old;
-#ifdef CLH_TBW_TRACE
-    const long long tw0 = __builtin_readcyclecounter();
-    long long t_walk = 0, t_lazy = 0; int n_lazy = 0;
-#endif
-    bool done = false;
-    if (st.w > 0) {                                    // what the passes left
-        const int* rec = (const int*)(pool_base + ((unsigned long long)(st.w - 1) << 6));
-        for (int j = 0; j < nspec && !done; ++j) {
+    auto keep_fin = [&]() { if (fin.w > 0 && nkept < kNKept) kept[nkept++] = fin; };
+    bool more = true;
+    if (st.w > 0) {                                    // ---- replay: what the passes left
+        int* const rec = tb_spec_rec(pool_base, st.w);
+        for (int j = 0; j < nspec && more; ++j) {
             const int v = __builtin_amdgcn_readfirstlane(rec[j]);
             if (v == TB_NOTRUN || v == TB_NONE) break;
             if (v == TB_UNFIT) { hand_over(); return; }
-            if (v == TB_NOPOOL) { no_pool(); return; }
-            if (fin.w > 0 && nkept < NKEPT) kept[nkept++] = fin;
-            const int* q = rec + 4 + 8 * j;
-            fin.w = __builtin_amdgcn_readfirstlane(q[0]); fin.by_col = __builtin_amdgcn_readfirstlane(q[1]); fin.shiftc = __builtin_amdgcn_readfirstlane(q[2]);
-            fin.nb0 = __builtin_amdgcn_readfirstlane(q[3]); fin.nvb = __builtin_amdgcn_readfirstlane(q[4]); fin.rowbytes = __builtin_amdgcn_readfirstlane(q[5]);
-            fin.dir = pool_base + ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane(q[6]) | ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane(q[7]) << 32));
-            ++niter; maxv = v > maxv ? v : maxv;
-            if (!(maxv < score && 2 * w < 2ll * readLen)) done = true;
-            else w *= 2;
+            if (v == TB_NOPOOL) { tb_finish(p, jb, writer, CLH_STATUS_CIGAR_TRUNC); return; }
+            keep_fin();
+            fin = tb_plane_load<true>(tb_spec_plane(rec, j), pool_base);
+            more = bd.advance(v, score, readLen);
         }
     }
-    while (!done) {                                    // ssw.c:560-632 from there on
-        if (w > 0x3fffffff || !fits_mw((int)w, refLen, readLen)) { hand_over(); return; }
-        if (fin.w > 0 && nkept < NKEPT) kept[nkept++] = fin;
+    while (more) {                                     // ---- continue: ssw.c:560-632 from there on, pass by pass
+        // (advance() doubles w only below readLen: the first test can only meet a handed-over st.x)
+        if (bd.w > 0x3fffffff || !fits_mw(bd.w, refLen, readLen)) { hand_over(); return; }
+        keep_fin();
         int it = 0;
-        if (!tb_make_plane_mw(in, (int)w, pool_base, pool_head, pool_size, fin, xs, &it)) { no_pool(); return; }
-        ++niter; maxv = it > maxv ? it : maxv;
-        if (!(maxv < score && 2 * w < 2ll * readLen)) break;
-        w *= 2;
+        if (!tb_make_plane<kMw>(in, bd.w, pool_base, pool_head, pool_size, fin, xs, &it)) { tb_finish(p, jb, writer, CLH_STATUS_CIGAR_TRUNC); return; }
+        more = bd.advance(it, score, readLen);
     }
-    TbWalk wk;
+    TbWalk wk;                                         // ---- walk: wave 0; cmd = the band whose codes it wants from the workgroup
     tb_walk_init(wk, readLen, refLen);
-#ifdef CLH_TBW_TRACE
-    const long long tw2 = __builtin_readcyclecounter();
-#endif
-    for (;;) {
+    for (bool narrow_made = false;;) {
         int rc = 0;
-#ifdef CLH_TBW_TRACE
-        const long long ta = __builtin_readcyclecounter();
-#endif
-        if (wave == 0) rc = tb_rows_walk<4, true>(p, jb, fin, old, kept, nkept, wk, niter, w0, (int)w, pool_base, pool_head, pool_size);
+        if (wave == 0) rc = tb_rows_walk<4, true>(p, jb, fin, old, kept, nkept, wk, bd.niter, w0, bd.w, pool_base, pool_head, pool_size);
         if (writer) xs->cmd = rc == 3 ? wk.need_w : (rc == 2 ? -1 : 0);
         __syncthreads();
         const int cmd = xs->cmd;
         __syncthreads();
-#ifdef CLH_TBW_TRACE
-        const long long tb_ = __builtin_readcyclecounter();
-        t_walk += tb_ - ta;
-        if (cmd == 0 && writer) {
-            const int slot = atomicAdd(&g_tbw_n, 1) & 1023;
-            long long* d = g_tbw_dbg + 8 * slot;
-            d[0] = ((long long)readLen << 32) | (unsigned)refLen; d[1] = ((long long)w0 << 32) | (unsigned)w; d[2] = ((long long)niter << 32) | (unsigned)n_lazy;
-            d[3] = tw2 - tw0; d[4] = 0; d[5] = t_walk; d[6] = t_lazy; d[7] = st.x;
-        }
-#endif
         if (cmd == 0) return;
         if (cmd < 0) { hand_over(); return; }
         if (!narrow_made) {
-            // the first time the walk leaves the band: the codes of ALL the narrow launch's iterations (it ran them without),
-            // one band per wave side by side -- a walk that reads stale codes once tends to do so in several iterations' areas
             narrow_made = true;
-            TbPlane mine = TbPlane{-1, 0, 0, 0, 0, 0, nullptr};
-            const long long wq = (long long)w0 << wave;
-            bool have = wave >= niter - 1 || wq > 255 || !fits(4, (int)wq);
-            for (int u = 0; u < nkept; ++u) have = have || kept[u].w == (int)wq;
-            if (!have && !tb_make_plane<4>(in, (int)wq, pool_base, pool_head, pool_size, mine)) mine.w = -1;
-            if ((threadIdx.x & 63) == 0) {
-                const unsigned long long off = mine.dir ? (unsigned long long)(mine.dir - pool_base) : 0ull;
-                int* q = xs->lz[wave];
-                q[0] = mine.w; q[1] = mine.by_col; q[2] = mine.shiftc; q[3] = mine.nb0; q[4] = mine.nvb; q[5] = mine.rowbytes; q[6] = (int)(off & 0xffffffffull); q[7] = (int)(off >> 32);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            __syncthreads();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            for (int v = 0; v < kMw; ++v) {
-                const int* q = xs->lz[v];
-                if (q[0] <= 0 || nkept >= NKEPT) continue;
-                TbPlane& t = kept[nkept++];
-                t.w = q[0]; t.by_col = q[1]; t.shiftc = q[2]; t.nb0 = q[3]; t.nvb = q[4]; t.rowbytes = q[5];
-                t.dir = pool_base + ((unsigned long long)(unsigned)q[6] | ((unsigned long long)(unsigned)q[7] << 32));
-            }
-            __syncthreads();
-            bool now = false;
-            for (int u = 0; u < nkept; ++u) now = now || kept[u].w == cmd;
-            if (now) {
-#ifdef CLH_TBW_TRACE
-                t_lazy += __builtin_readcyclecounter() - tb_; ++n_lazy;
-#endif
-                continue;
-            }
+            if (tb_narrow_planes(in, xs, pool_base, pool_head, pool_size, w0, bd.niter, kept, nkept, cmd)) continue;
         }
-        if (!tb_make_plane_mw(in, cmd, pool_base, pool_head, pool_size, old, xs)) { hand_over(); return; }
-#ifdef CLH_TBW_TRACE
-        t_lazy += __builtin_readcyclecounter() - tb_; ++n_lazy;
-#endif
+        if (!tb_make_plane<kMw>(in, cmd, pool_base, pool_head, pool_size, old, xs)) { hand_over(); return; }
     }
 }
 
@@ -814,9 +765,7 @@ __global__ void __launch_bounds__(64 * kMw, 1) ssw_traceback_rows_wide_pass_kern
     const int n = __builtin_amdgcn_readfirstlane(*n_small), nspec = tb_nspec(n);
     for (int item = (int)blockIdx.x; item < n * nspec; item += (int)gridDim.x) {
         const int k = item / nspec, j = item % nspec;
-        int4 st = *(const int4*)(state_small + 4 * (size_t)k);
-        st.x = __builtin_amdgcn_readfirstlane(st.x); st.y = __builtin_amdgcn_readfirstlane(st.y); st.z = __builtin_amdgcn_readfirstlane(st.z); st.w = __builtin_amdgcn_readfirstlane(st.w);
-        tb_rows_wide_pass(p, s_tab, &s_x, pool_base, pool_head, pool_size, __builtin_amdgcn_readfirstlane(list_small[k]), st, j);
+        tb_rows_wide_pass(p, s_tab, &s_x, pool_base, pool_head, pool_size, __builtin_amdgcn_readfirstlane(list_small[k]), tb_state_load(state_small, k), j);
         __syncthreads();
     }
 }
@@ -828,9 +777,7 @@ __global__ void __launch_bounds__(64 * kMw, 1) ssw_traceback_rows_wide_kernel(co
     tb_rows_table(p, s_tab);
     const int n = __builtin_amdgcn_readfirstlane(*n_small), nspec = tb_nspec(n);
     for (int k = (int)blockIdx.x; k < n; k += (int)gridDim.x) {
-        int4 st = *(const int4*)(state_small + 4 * (size_t)k);
-        st.x = __builtin_amdgcn_readfirstlane(st.x); st.y = __builtin_amdgcn_readfirstlane(st.y); st.z = __builtin_amdgcn_readfirstlane(st.z); st.w = __builtin_amdgcn_readfirstlane(st.w);
-        tb_rows_wide_one(p, s_tab, &s_x, pool_base, pool_head, pool_size, __builtin_amdgcn_readfirstlane(list_small[k]), st, nspec, n_big, list_big);
+        tb_rows_wide_one(p, s_tab, &s_x, pool_base, pool_head, pool_size, __builtin_amdgcn_readfirstlane(list_small[k]), tb_state_load(state_small, k), nspec, n_big, list_big);
         __syncthreads();
     }
 }
@@ -859,15 +806,3 @@ hipError_t launch_traceback_rows_wide(const SswParams& p, int task_base, int nta
 }
 
 }  // namespace clh
-
-#ifdef CLH_TBW_TRACE
-// trace builds only (tools/dev/c2_tbw.py): per handed-over alignment {lengths, bands, iterations, clocks of the rounds / the final plane / the walk / the planes the walk asked for}
-extern "C" __attribute__((visibility("default"))) int clh_debug_tbw(long long* out, int reset)
-{
-    int n = 0;
-    if (hipMemcpyFromSymbol(&n, HIP_SYMBOL(clh::g_tbw_n), sizeof(int)) != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(clh::g_tbw_dbg), sizeof(long long) * 8 * 1024) != hipSuccess) return -1;
-    if (reset) { const int z = 0; (void)hipMemcpyToSymbol(HIP_SYMBOL(clh::g_tbw_n), &z, sizeof(int)); }
-    return n;
-}
-#endif

@@ -23,6 +23,46 @@ def _run(ctx, refs, queries, scheme, **kw):
     return rows, cig
 
 
+def _run_plan(ctx, refs, queries, scheme):
+    """as _run with its defaults, through a plan: also (handed to the wide row traceback, handed on to the anti-diagonal one)"""
+    import torch
+    from ciri_long_amd import hip
+    m, x, o, e = scheme
+    rd, ro = hip.pack(queries)
+    fd, fo = hip.pack(refs)
+    d_r = torch.from_numpy(rd.view(np.uint8)).cuda(); d_f = torch.from_numpy(fd.view(np.uint8)).cuda()
+    ts = torch.cuda.Stream()
+    plan = ctx.plan(ro, fo, hip.score_matrix(m, x), o, e, flag=1, score_size=2, want_score2=True, want_cigar=True)
+    plan.run(d_r.data_ptr(), d_f.data_ptr(), ts.cuda_stream)
+    rows, cig = plan.fetch()
+    counts = tuple(int(c) for c in plan.traceback_counts())
+    plan.close()
+    return rows, cig, counts
+
+
+# plan.traceback_counts() of the seeded batches below, as commit 6ae9854 (the last one before the row traceback's text was
+# reworked) produced them.  Every failure of the row form ends in "hand over" and a correct CIGAR from the anti-diagonal kernel,
+# so only these counts see a row form that hands over more than it must.  They are a function of the inputs alone (band widths
+# and walks; the pool only through exhaustion, which these sizes are far from).  The last entry is (2, 2): both long alignments of
+# that batch belong to the anti-diagonal kernel whatever the row form does, so it pins the count and says nothing about the wide walk.
+_TB_COUNTS = {
+    ('wide_bands', (1, 1, 1, 1)): (26, 9),
+    ('wide_bands', (2, 2, 3, 1)): (27, 7),
+    ('wide_bands', (10, 4, 8, 2)): (25, 4),
+    ('many_doublings', False): (25, 1),
+    ('many_doublings', True): (300, 0),
+    ('stale_walk',): (2, 0),
+    ('short_read_wide_reference', 0): (2, 2),
+}
+
+
+def _check_tb_counts(key, counts):
+    import os
+    print('traceback_counts', key, tuple(int(c) for c in counts))
+    if not os.environ.get('CLH_NO_TB_ROWS'):      # the A/B switch sends everything through the anti-diagonal kernel
+        assert tuple(int(c) for c in counts) == _TB_COUNTS[key], (key, counts)
+
+
 def _row_tuple(r):
     return (int(r['score1']), int(r['score2']), int(r['ref_begin1']), int(r['ref_end1']), int(r['read_begin1']),
             int(r['read_end1']), int(r['ref_end2']))
@@ -422,6 +462,7 @@ def test_cigars_of_wide_bands_row_traceback_vs_oracle(ctx, scheme):
     import os
     if not os.environ.get('CLH_NO_TB_ROWS'):      # the A/B switch sends everything through the anti-diagonal kernel
         assert wide >= nwide > 5 and anti <= wide // 2 + 2, (wide, anti, nwide)
+    _check_tb_counts(('wide_bands', scheme), (wide, anti))
 
 
 @pytest.mark.parametrize('many', [False, True])
@@ -473,6 +514,7 @@ def test_wide_bands_many_doublings_and_long_hand_over_lists(ctx, many):
     import os
     if not os.environ.get('CLH_NO_TB_ROWS'):
         assert wide > (256 if many else 10), (wide, anti)
+    _check_tb_counts(('many_doublings', many), (wide, anti))
 
 
 @pytest.mark.parametrize('scheme', [(1, 1, 1, 1), (2, 3, 5, 2), (1, 1, 3, 1)])
@@ -530,7 +572,8 @@ def test_stale_walk_goldens(ctx):
     refs = [c['ref'] for c in cases]; qs = [c['query'] for c in cases]
     for _ in range(12):
         ref = _rnd(rng, 1500); refs.append(ref); qs.append(_mut(ref[200:1100], rng, 0.1))
-    rows, cig = _run(ctx, refs, qs, (1, 1, 1, 1))
+    rows, cig, counts = _run_plan(ctx, refs, qs, (1, 1, 1, 1))
+    _check_tb_counts(('stale_walk',), counts)
     for c, r in zip(cases, rows):
         w = c['want']
         assert _row_tuple(r) == (w['score'], w['score2'], w['ref_begin'], w['ref_end'], w['query_begin'], w['query_end'], w['ref_end2']), (c['rank'], c['index'])
@@ -611,9 +654,10 @@ def test_short_read_spanning_thousands_of_reference_bases(ctx):
     import os
     with gzip.open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'stale_walk_golden.json.gz'), 'rt') as f:
         cases = json.load(f)['wide_reference_cases']
-    for c in cases:
+    for n, c in enumerate(cases):
         scheme = (c['match'], c['mismatch'], c['gap_open'], c['gap_extend'])
-        rows, cig = _run(ctx, [c['ref']] * 3, [c['query'], c['query'][:100], c['query']], scheme)
+        rows, cig, counts = _run_plan(ctx, [c['ref']] * 3, [c['query'], c['query'][:100], c['query']], scheme)
+        _check_tb_counts(('short_read_wide_reference', n), counts)
         for r in (rows[0], rows[2]):
             w = c['want']
             assert _row_tuple(r) == (w['score'], w['score2'], w['ref_begin'], w['ref_end'], w['query_begin'], w['query_end'], w['ref_end2'])

@@ -27,20 +27,6 @@ for k in range(9):
     rows, cig = plan.fetch()
     el = time.perf_counter() - t0
     if k >= 2: best = min(best, el)
-if name.startswith('trace'):
-    import ctypes
-    lib = ctypes.CDLL(hip.SO_PATH)
-    buf = (ctypes.c_longlong * 8192)()
-    lib.clh_debug_tbw(buf, 1)
-    plan.run(d_r.data_ptr(), d_w.data_ptr(), st); plan.fetch()
-    n = lib.clh_debug_tbw(buf, 1)
-    a = np.array(buf[:8 * n], dtype=np.int64).reshape(n, 8)
-    tot = a[:, 3] + a[:, 4] + a[:, 5] + a[:, 6]
-    print('handed-over alignments traced: %%d; clocks (M) median %%.2f, max %%.2f' %% (n, np.median(tot) / 1e6, tot.max() / 1e6))
-    for r in a[np.argsort(-tot)][:8]:
-        print('  read %%d ref %%d  w0 %%d -> w %%d  niter %%d  state w %%d | rounds %%.2f  final plane %%.2f  walk %%.2f  lazy planes %%d: %%.2f (M clocks)' %% (r[0] >> 32, r[0] & 0xffffffff, r[1] >> 32, r[1] & 0xffffffff, r[2] >> 32, r[7], r[3] / 1e6, r[4] / 1e6, r[5] / 1e6, r[2] & 0xffffffff, r[6] / 1e6))
-    r = a[np.argsort(tot)][n // 2]
-    print('  median: read %%d ref %%d  w0 %%d -> w %%d  niter %%d | rounds %%.2f  final plane %%.2f  walk %%.2f  lazy %%.2f' %% (r[0] >> 32, r[0] & 0xffffffff, r[1] >> 32, r[1] & 0xffffffff, r[2] >> 32, r[3] / 1e6, r[4] / 1e6, r[5] / 1e6, r[6] / 1e6))
 crc = zlib.crc32(cig.tobytes(), zlib.crc32(rows.tobytes())) & 0xffffffff
 plan.set_profiling(True)
 acc = None
