@@ -2141,6 +2141,8 @@ struct PairsShape {
 struct clh_pairs_plan : clh_owned, PairsShape {
     using clh_owned::clh_owned;
     void *d_q = nullptr, *d_r = nullptr, *d_pairs = nullptr, *d_mat = nullptr, *d_ws = nullptr, *d_rows = nullptr, *d_cig = nullptr;
+    float gather_ms = -1;                         // the windows form: HIP-event time of the gather at create, and the letters it moved
+    int64_t gather_letters = 0;
 };
 
 // the arguments and options both creates take, refused in the order each always refused them; `band`: K1gb's half-width, null for K1g;
@@ -2178,10 +2180,55 @@ static int64_t pairs_scan_matrix(const clh_ends_opts* o, int64_t* splus, const c
     return smax;
 }
 
+// Where the reference letters of a create come from: host codes (r, r_off), or windows of a resident genome that the device gathers
+// into the plan's reference buffer (genome_gather.h).  Everything behind a create reads start and len alone.
+struct PairsRefs {
+    const int8_t* r = nullptr; const int64_t* r_off = nullptr;                                      // the strings form
+    clh_genome* genome = nullptr;                                                                   // the windows form
+    const int64_t* win_off = nullptr; const int32_t* win_len = nullptr; const uint8_t* win_flags = nullptr;
+    std::vector<int64_t> start, len;              // reference k in the plan's buffer: its first code, its letters
+    int64_t total = 0;                            // bytes of the buffer
+    // what pairs_check_opts takes for r_off: the windows form has none to miss
+    const int64_t* off_arg(const int64_t* q_off) const { return genome ? q_off : r_off; }
+};
+static PairsRefs refs_strings(const int8_t* r, const int64_t* r_off) { PairsRefs f; f.r = r; f.r_off = r_off; return f; }
+static PairsRefs refs_windows(clh_genome* g, const int64_t* off, const int32_t* len, const uint8_t* flags)
+{
+    PairsRefs f; f.genome = g; f.win_off = off; f.win_len = len; f.win_flags = flags; return f;
+}
+
+// start, len and total, after pairs_check_opts.  Strings: the offsets as given (a descending pair is refused by the create's own
+// loop).  Windows: each checked against the genome, and started on a 16-byte boundary so that the gather stores whole words.
+static int pairs_ref_spans(const std::string& me, int32_t n, int n_mat, PairsRefs* f)
+{
+    f->start.resize((size_t)n); f->len.resize((size_t)n);
+    if (!f->genome) {
+        for (int k = 0; k < n; ++k) { f->start[(size_t)k] = f->r_off[k] - f->r_off[0]; f->len[(size_t)k] = f->r_off[k + 1] - f->r_off[k]; }
+        f->total = n ? f->r_off[n] - f->r_off[0] : 0;
+        return 0;
+    }
+    if (n > 0 && (!f->win_off || !f->win_len || !f->win_flags)) return fail(CLH_E_ARG, me + "null argument");
+    if (n_mat != 5)
+        return fail(CLH_E_UNSUPPORTED, me + "windows of the resident genome are DNA codes: the matrix must be 5 x 5, n_mat is " + std::to_string(n_mat) +
+                                            "; substitution matrices over other alphabets take their references as strings");
+    for (int k = 0; k < n; ++k) {
+        const int64_t off = f->win_off[k], len = f->win_len[k];
+        if (len < 0 || off < 0 || off + len > f->genome->len)
+            return fail(CLH_E_ARG, me + "pair " + std::to_string(k) + ": the window [" + std::to_string(off) + ", " + std::to_string(off) + " + " + std::to_string(len) +
+                                       ") lies outside the genome of " + std::to_string(f->genome->len) + " bases");
+        if (f->win_flags[k] > 3)
+            return fail(CLH_E_ARG, me + "pair " + std::to_string(k) + ": window flags must be 0..3 (bit 0 reversed, bit 1 complemented), got " + std::to_string((int)f->win_flags[k]));
+        f->start[(size_t)k] = f->total; f->len[(size_t)k] = len;
+        f->total += (len + clh::kGatherWord - 1) & ~(int64_t)(clh::kGatherWord - 1);
+    }
+    return 0;
+}
+
+// r_off null: the queries alone (the windows form, whose reference codes the gather makes)
 static int pairs_check_codes(const std::string& me, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off, int n_mat)
 {
     for (int k = 0; k < n; ++k) {
-        for (int side = 0; side < 2; ++side) {
+        for (int side = 0; side < (r_off ? 2 : 1); ++side) {
             const int8_t* s = side ? r : q;
             const int64_t* off = side ? r_off : q_off;
             for (int64_t x = off[k]; x < off[k + 1]; ++x)
@@ -2197,7 +2244,7 @@ static int pairs_check_codes(const std::string& me, int32_t n, const int8_t* q, 
 // and returns the bytes its stored decisions need (read only where CIGARs are wanted and the kernels take the pair); cells(pair)
 // words them for the refusal of a pair that is above the workspace alone.
 template <typename Pair, typename Own, typename Cells>
-static int pairs_cut_shares(const std::string& me, const clh_ends_opts* o, int32_t n, const int64_t* q_off, const int64_t* r_off, PairsShape* sh,
+static int pairs_cut_shares(const std::string& me, const clh_ends_opts* o, int32_t n, const int64_t* q_off, const PairsRefs& refs, PairsShape* sh,
                             std::vector<Pair>* pairs, Own own, Cells cells)
 {
     sh->n = n; sh->mode = o->mode; sh->n_mat = o->n_mat; sh->go = o->gap_open; sh->ge = o->gap_extend; sh->want_cigar = o->want_cigar != 0;
@@ -2207,8 +2254,8 @@ static int pairs_cut_shares(const std::string& me, const clh_ends_opts* o, int32
     int64_t share = 0;
     for (int k = 0; k < n; ++k) {
         Pair& p = (*pairs)[(size_t)k];
-        const int64_t m = q_off[k + 1] - q_off[k], nn = r_off[k + 1] - r_off[k];
-        p.q_off = q_off[k] - q_off[0]; p.r_off = r_off[k] - r_off[0];
+        const int64_t m = q_off[k + 1] - q_off[k], nn = refs.len[(size_t)k];
+        p.q_off = q_off[k] - q_off[0]; p.r_off = refs.start[(size_t)k];
         p.m = (int32_t)m; p.n = (int32_t)nn;
         p.ws_off = -1; p.cig_off = sh->cig_cap; p.cig_cap = 0;
         const bool kernel = m > 0 && nn > 0;
@@ -2234,20 +2281,60 @@ static int pairs_cut_shares(const std::string& me, const clh_ends_opts* o, int32
 
 // the plan takes over what was planned and uploads what both kinds have; false: a block is missing
 template <typename Pair>
-static bool pairs_upload(clh_pairs_plan* pl, PairsShape* sh, const std::vector<Pair>& pairs, const int8_t* q, const int64_t* q_off, const int8_t* r,
-                         const int64_t* r_off, const int8_t* mat)
+static bool pairs_upload(clh_pairs_plan* pl, PairsShape* sh, const std::vector<Pair>& pairs, const int8_t* q, const int64_t* q_off, const PairsRefs& refs,
+                         const int8_t* mat)
 {
     static_cast<PairsShape&>(*pl) = std::move(*sh);
     const int n = pl->n;
-    const int64_t tq = n ? q_off[n] - q_off[0] : 0, tr = n ? r_off[n] - r_off[0] : 0;
+    const int64_t tq = n ? q_off[n] - q_off[0] : 0;
     pl->d_q = pl->upload(q ? q + q_off[0] : nullptr, (size_t)tq);
-    pl->d_r = pl->upload(r ? r + r_off[0] : nullptr, (size_t)tr);
+    pl->d_r = refs.genome ? pl->alloc((size_t)refs.total) : pl->upload(refs.r ? refs.r + refs.r_off[0] : nullptr, (size_t)refs.total);
     pl->d_pairs = pl->upload(pairs.data(), sizeof(Pair) * pairs.size());
     pl->d_mat = pl->upload(mat, (size_t)pl->n_mat * pl->n_mat);
     pl->d_ws = pl->alloc((size_t)std::max<int64_t>(pl->ws_bytes, 1));
     pl->d_rows = pl->alloc(32 * (size_t)std::max(n, 1));
     pl->d_cig = pl->alloc(sizeof(uint32_t) * (size_t)std::max<int64_t>(pl->cig_cap, 1));
     return pl->d_q && pl->d_r && pl->d_pairs && pl->d_mat && pl->d_ws && pl->d_rows && pl->d_cig;
+}
+
+// the windows form: the device fills the plan's reference buffer from the resident genome, once, here; the plan is ready on return
+static int pairs_gather(const std::string& me, clh_pairs_plan* pl, const PairsRefs& refs)
+{
+    if (!refs.genome) return 0;
+    const int n = pl->n;
+    std::vector<clh::GatherTask> tasks((size_t)n);
+    std::vector<int32_t> tile_task;
+    int64_t tiles = 0;
+    for (int k = 0; k < n; ++k) {
+        tasks[(size_t)k] = clh::GatherTask{refs.win_off[k], refs.start[(size_t)k], (int32_t)refs.len[(size_t)k], (int32_t)refs.win_flags[k], tiles};
+        const int64_t nt = clh::gather_tiles(refs.len[(size_t)k]);
+        tile_task.insert(tile_task.end(), (size_t)nt, (int32_t)k);
+        tiles += nt;
+    }
+    if (!tiles) return 0;
+    void* d_tasks = pl->upload(tasks.data(), sizeof(clh::GatherTask) * tasks.size());
+    void* d_tiles = pl->upload(tile_task.data(), sizeof(int32_t) * tile_task.size());
+    if (!d_tasks || !d_tiles) return fail(CLH_E_HIP, me + "out of device memory or upload failed for the gather's tasks");
+    hipStream_t st = pl->ctx->stream;
+    hipEvent_t ev[2];
+    for (auto& e : ev) HIPCHK(pl->event(&e));
+    HIPCHK(hipEventRecord(ev[0], st));
+    HIPCHK(clh::launch_genome_gather((const uint8_t*)refs.genome->d_codes, refs.genome->len, (const clh::GatherTask*)d_tasks, n, (const int32_t*)d_tiles, tiles,
+                                     (int8_t*)pl->d_r, refs.total, st));
+    HIPCHK(hipEventRecord(ev[1], st));
+    HIPCHK(hipStreamSynchronize(st));      // the tables go back to the allocator, and a run may use another stream
+    HIPCHK(hipEventElapsedTime(&pl->gather_ms, ev[0], ev[1]));
+    for (int k = 0; k < n; ++k) pl->gather_letters += refs.len[(size_t)k];
+    pl->free_block(d_tasks); pl->free_block(d_tiles);
+    return 0;
+}
+
+static int pairs_gather_timing(const std::string& me, const clh_pairs_plan* pl, float* ms, int64_t* letters)
+{
+    if (!pl || !ms || !letters) return fail(CLH_E_ARG, me + "null argument");
+    if (pl->gather_ms < 0) return fail(CLH_E_ARG, me + "no gather to time: the plan's references are strings, or its windows hold no letter");
+    *ms = pl->gather_ms; *letters = pl->gather_letters;
+    return 0;
 }
 
 // the start of a run of either kind; every row starts as "unwritten": what a kernel did not store is reported by fetch, never returned
@@ -2403,10 +2490,11 @@ static int sp_check(const std::string& me, const clh_ends_opts* o, const clh_spl
 }
 
 // the creates of K1g; g2: the second piece, null for one piece; sp: intron gaps (clh_splice) with the pairs' strands, null for none
-static clh_ends_plan* en_create(const std::string& me, clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off,
+static clh_ends_plan* en_create(const std::string& me, clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, PairsRefs refs,
                                 const clh_ends_opts* o, const clh_gap2* g2, const clh_splice* sp = nullptr, const int8_t* strand = nullptr, bool spliced = false)
 {
-    if (pairs_check_opts(me, ctx, n, q_off, r_off, o, nullptr, g2)) return nullptr;
+    if (pairs_check_opts(me, ctx, n, q_off, refs.off_arg(q_off), o, nullptr, g2)) return nullptr;
+    if (pairs_ref_spans(me, n, o->n_mat, &refs)) return nullptr;
     const int pieces = (g2 || spliced) ? 2 : 1;       // the spliced kernel stores a byte per cell and hands three values on, as two pieces do
     int64_t splus;
     int64_t smax = pairs_scan_matrix(o, &splus, g2);
@@ -2417,9 +2505,9 @@ static clh_ends_plan* en_create(const std::string& me, clh_ctx* ctx, int32_t n, 
         smax = std::max(smax, site_max);
     }
     for (int k = 0; k < n; ++k) {
-        const int64_t m = q_off[k + 1] - q_off[k], nn = r_off[k + 1] - r_off[k];
+        const int64_t m = q_off[k + 1] - q_off[k], nn = refs.len[(size_t)k];
         if (m < 0 || nn < 0) { fail(CLH_E_ARG, me + "offsets must ascend"); return nullptr; }
-        if ((m > 0 && !q) || (nn > 0 && !r)) { fail(CLH_E_ARG, me + "null argument"); return nullptr; }
+        if ((m > 0 && !q) || (nn > 0 && !refs.genome && !refs.r)) { fail(CLH_E_ARG, me + "null argument"); return nullptr; }
         if (m + nn >= ((int64_t)1 << 30) || (m + nn) * smax >= ((int64_t)1 << 30)) {
             fail(CLH_E_ARG, me + "pair " + std::to_string(k) + ": (m + n) * max(|s|, " +
                                 (spliced ? "gap_open, gap_extend, intron_open + dmax + amax" : g2 ? "gap_open, gap_extend, gap_open2, gap_extend2" : "gap_open, gap_extend") +
@@ -2428,24 +2516,29 @@ static clh_ends_plan* en_create(const std::string& me, clh_ctx* ctx, int32_t n, 
             return nullptr;
         }
     }
-    if (pairs_check_codes(me, n, q, q_off, r, r_off, o->n_mat)) return nullptr;
+    if (pairs_check_codes(me, n, q, q_off, refs.r, refs.r_off, o->n_mat)) return nullptr;
     PairsShape shape;
     if (g2) { shape.pieces = 2; shape.go2 = g2->gap_open2; shape.ge2 = g2->gap_extend2; }
+    // spliced, global, no query letter: the reference as one intron, from its first two and last two letters (`edge`: 0, 1, n - 2, n - 1)
+    auto row0_intron = [&](int k, int64_t nn, const int8_t* edge) {
+        const int soff = (strand && strand[k] < 0) ? 32 : 0;
+        return (int64_t)sp->intron_open + sp_site(site, soff, 0, edge[0], nn > 1 ? edge[1] : 4) + sp_site(site, soff, 16, nn > 1 ? edge[2] : 4, edge[3]);
+    };
     if (spliced) {
         shape.spliced = true; shape.io = sp->intron_open;
         shape.row0_intron.assign((size_t)n, -1);
-        for (int k = 0; k < n && o->mode == CLH_ENDS_GLOBAL; ++k) {
-            const int64_t m = q_off[k + 1] - q_off[k], nn = r_off[k + 1] - r_off[k];
+        for (int k = 0; k < n && o->mode == CLH_ENDS_GLOBAL && !refs.genome; ++k) {
+            const int64_t m = q_off[k + 1] - q_off[k], nn = refs.len[(size_t)k];
             if (m != 0 || nn == 0) continue;
-            const int8_t* rk = r + r_off[k];
-            const int soff = (strand && strand[k] < 0) ? 32 : 0;
-            shape.row0_intron[(size_t)k] = (int64_t)sp->intron_open + sp_site(site, soff, 0, rk[0], nn > 1 ? rk[1] : 4) + sp_site(site, soff, 16, nn > 1 ? rk[nn - 2] : 4, rk[nn - 1]);
+            const int8_t* rk = refs.r + refs.r_off[k];
+            const int8_t edge[4] = {rk[0], nn > 1 ? rk[1] : (int8_t)4, nn > 1 ? rk[nn - 2] : (int8_t)4, rk[nn - 1]};
+            shape.row0_intron[(size_t)k] = row0_intron(k, nn, edge);
         }
     }
     std::vector<clh::EnPair> pairs;
     int64_t hand_words = 0;
     const bool recompute = o->want_cigar == CLH_ENDS_CIGAR_RECOMPUTE;
-    if (pairs_cut_shares(me, o, n, q_off, r_off, &shape, &pairs,
+    if (pairs_cut_shares(me, o, n, q_off, refs, &shape, &pairs,
             [&](int, clh::EnPair& p, bool kernel) {
                 p.pad = 0; p.hand_off = -1;
                 // recompute: every chunk's last column is kept in the pair's block of the workspace, beside one chunk's plane and the walk's record
@@ -2462,7 +2555,7 @@ static clh_ends_plan* en_create(const std::string& me, clh_ctx* ctx, int32_t n, 
     if (hipSetDevice(ctx->device) != hipSuccess) { fail(CLH_E_HIP, "hipSetDevice failed"); return nullptr; }
     clh_ends_plan* pl = new clh_ends_plan(ctx);
     pl->hand_words = hand_words;
-    const bool ok = pairs_upload(pl, &shape, pairs, q, q_off, r, r_off, o->mat);
+    const bool ok = pairs_upload(pl, &shape, pairs, q, q_off, refs, o->mat);
     pl->pairs.swap(pairs);
     pl->recompute = recompute;
     for (const auto& sh : pl->shares) {
@@ -2482,26 +2575,53 @@ static clh_ends_plan* en_create(const std::string& me, clh_ctx* ctx, int32_t n, 
         fail(CLH_E_HIP, "out of device memory or upload failed while building the ends plan");
         delete pl; return nullptr;
     }
+    if (pairs_gather(me, pl, refs)) { delete pl; return nullptr; }
+    // the windows form of row0_intron: the same four letters, read back from what the gather wrote
+    for (int k = 0; k < n && spliced && o->mode == CLH_ENDS_GLOBAL && refs.genome; ++k) {
+        const int64_t nn = pl->pairs[(size_t)k].n;
+        if (pl->pairs[(size_t)k].m != 0 || nn == 0) continue;
+        const int8_t* dk = (const int8_t*)pl->d_r + pl->pairs[(size_t)k].r_off;
+        int8_t edge[4] = {4, 4, 4, 4};
+        const int64_t head = std::min<int64_t>(nn, 2);
+        if (hipMemcpy(edge, dk, (size_t)head, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(edge + 4 - head, dk + nn - head, (size_t)head, hipMemcpyDeviceToHost) != hipSuccess) {
+            fail(CLH_E_HIP, me + "reading back the window's edge letters failed");
+            delete pl; return nullptr;
+        }
+        pl->row0_intron[(size_t)k] = row0_intron(k, nn, edge);
+    }
     return pl;
 }
 
 extern "C" clh_ends_plan* clh_ends_plan_create(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off,
                                                const clh_ends_opts* o)
 {
-    return en_create("clh_ends_plan_create: ", ctx, n, q, q_off, r, r_off, o, nullptr);
+    return en_create("clh_ends_plan_create: ", ctx, n, q, q_off, refs_strings(r, r_off), o, nullptr);
 }
 
 extern "C" clh_ends_plan* clh_ends_plan_create_gap2(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off,
                                                     const clh_ends_opts* o, const clh_gap2* gap2)
 {
     if (!gap2) return clh_ends_plan_create(ctx, n, q, q_off, r, r_off, o);
-    return en_create("clh_ends_plan_create_gap2: ", ctx, n, q, q_off, r, r_off, o, gap2);
+    return en_create("clh_ends_plan_create_gap2: ", ctx, n, q, q_off, refs_strings(r, r_off), o, gap2);
 }
 
 extern "C" clh_ends_plan* clh_ends_plan_create_spliced(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off,
                                                        const clh_ends_opts* o, const clh_splice* splice, const int8_t* strand)
 {
-    return en_create("clh_ends_plan_create_spliced: ", ctx, n, q, q_off, r, r_off, o, nullptr, splice, strand, true);
+    return en_create("clh_ends_plan_create_spliced: ", ctx, n, q, q_off, refs_strings(r, r_off), o, nullptr, splice, strand, true);
+}
+
+// K1g on windows of the resident genome: gap2 for two pieces, splice (with strand, which may be null) for introns, both null for neither
+extern "C" clh_ends_plan* clh_ends_plan_create_windows(clh_genome* genome, int32_t n, const int8_t* q, const int64_t* q_off, const int64_t* win_off,
+                                                       const int32_t* win_len, const uint8_t* win_flags, const clh_ends_opts* o, const clh_gap2* gap2,
+                                                       const clh_splice* splice, const int8_t* strand)
+{
+    const std::string me = "clh_ends_plan_create_windows: ";
+    if (!genome) { fail(CLH_E_ARG, me + "null genome"); return nullptr; }
+    if (gap2 && splice) { fail(CLH_E_UNSUPPORTED, me + "two-piece gap costs together with introns are not built"); return nullptr; }
+    if (strand && !splice) { fail(CLH_E_ARG, me + "strand comes with splice"); return nullptr; }
+    return en_create(me, genome->ctx, n, q, q_off, refs_windows(genome, win_off, win_len, win_flags), o, gap2, splice, strand, splice != nullptr);
 }
 
 extern "C" int clh_ends_plan_run(clh_ends_plan* pl, void* stream_)
@@ -2553,6 +2673,11 @@ extern "C" int clh_ends_plan_timing(clh_ends_plan* pl, float* ms)
     return pl->elapsed(ms);
 }
 
+extern "C" int clh_ends_plan_gather_timing(clh_ends_plan* pl, float* ms, int64_t* letters)
+{
+    return pairs_gather_timing("clh_ends_plan_gather_timing: ", pl, ms, letters);
+}
+
 extern "C" int clh_ends_plan_info(clh_ends_plan* pl, int64_t* out)
 {
     if (!pl || !out) return fail(CLH_E_ARG, "clh_ends_plan_info: null argument");
@@ -2596,13 +2721,14 @@ struct clh_band_plan : clh_pairs_plan {
 extern "C" void clh_band_plan_destroy(clh_band_plan* pl) { delete pl; }
 
 // both creates of K1gb; g2: the second piece, null for one piece
-static clh_band_plan* bd_create(const std::string& me, clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off,
+static clh_band_plan* bd_create(const std::string& me, clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, PairsRefs refs,
                                 const int32_t* diag, const clh_band_opts* bo, const clh_gap2* g2)
 {
     clh_ends_opts shared;                                                      // the fields the two share (the static_asserts above)
     if (bo) memcpy(&shared, bo, sizeof shared);
     const clh_ends_opts* o = bo ? &shared : nullptr;
-    if (pairs_check_opts(me, ctx, n, q_off, r_off, o, bo ? &bo->band : nullptr, g2)) return nullptr;
+    if (pairs_check_opts(me, ctx, n, q_off, refs.off_arg(q_off), o, bo ? &bo->band : nullptr, g2)) return nullptr;
+    if (pairs_ref_spans(me, n, o->n_mat, &refs)) return nullptr;
     const int pieces = g2 ? 2 : 1;
     int64_t splus;
     const int64_t smax = pairs_scan_matrix(o, &splus, g2);
@@ -2610,10 +2736,10 @@ static clh_band_plan* bd_create(const std::string& me, clh_ctx* ctx, int32_t n, 
     const bool anchored = o->mode == CLH_ENDS_PREFIX || o->mode == CLH_ENDS_EXTEND;      // the far end is free: n - m plays no part in the band
     std::vector<std::pair<int32_t, int32_t>> bands((size_t)n);
     for (int k = 0; k < n; ++k) {
-        const int64_t m = q_off[k + 1] - q_off[k], nn = r_off[k + 1] - r_off[k];
+        const int64_t m = q_off[k + 1] - q_off[k], nn = refs.len[(size_t)k];
         const std::string pk = me + "pair " + std::to_string(k) + ": ";
         if (m < 0 || nn < 0) { fail(CLH_E_ARG, me + "offsets must ascend"); return nullptr; }
-        if ((m > 0 && !q) || (nn > 0 && !r)) { fail(CLH_E_ARG, me + "null argument"); return nullptr; }
+        if ((m > 0 && !q) || (nn > 0 && !refs.genome && !refs.r)) { fail(CLH_E_ARG, me + "null argument"); return nullptr; }
         const int64_t span = m + nn + 2 * clh::kBdMaxWidth;
         if (span >= ((int64_t)1 << 29) || span * smax >= ((int64_t)1 << 29)) {
             fail(CLH_E_ARG, pk + "(m + n + " + std::to_string(2 * clh::kBdMaxWidth) + ") * max(|s|, " + (g2 ? "gap_open, gap_extend, gap_open2, gap_extend2" : "gap_open, gap_extend") +
@@ -2650,12 +2776,12 @@ static clh_band_plan* bd_create(const std::string& me, clh_ctx* ctx, int32_t n, 
         }
         bands[(size_t)k] = {(int32_t)lo, (int32_t)hi};
     }
-    if (pairs_check_codes(me, n, q, q_off, r, r_off, o->n_mat)) return nullptr;
+    if (pairs_check_codes(me, n, q, q_off, refs.r, refs.r_off, o->n_mat)) return nullptr;
     PairsShape shape;
     if (g2) { shape.pieces = 2; shape.go2 = g2->gap_open2; shape.ge2 = g2->gap_extend2; }
     std::vector<clh::BdPair> pairs;
     int64_t max_width = 0, nclass[clh::kBdClasses] = {0, 0, 0};
-    if (pairs_cut_shares(me, o, n, q_off, r_off, &shape, &pairs,
+    if (pairs_cut_shares(me, o, n, q_off, refs, &shape, &pairs,
             [&](int k, clh::BdPair& p, bool kernel) -> int64_t {
                 p.lo = bands[(size_t)k].first; p.hi = bands[(size_t)k].second; p.cls = -1;
                 if (!kernel) return 0;
@@ -2683,27 +2809,38 @@ static clh_band_plan* bd_create(const std::string& me, clh_ctx* ctx, int32_t n, 
     clh_band_plan* pl = new clh_band_plan(ctx);
     pl->splus = splus; pl->max_width = max_width;
     for (int c = 0; c < clh::kBdClasses; ++c) pl->nclass[c] = nclass[c];
-    const bool ok = pairs_upload(pl, &shape, pairs, q, q_off, r, r_off, o->mat);
+    const bool ok = pairs_upload(pl, &shape, pairs, q, q_off, refs, o->mat);
     pl->pairs.swap(pairs); pl->order.swap(order); pl->share_classes.swap(share_classes);
     pl->d_order = pl->upload(pl->order.data(), sizeof(int32_t) * pl->order.size());
     if (!ok || !pl->d_order) {
         fail(CLH_E_HIP, "out of device memory or upload failed while building the band plan");
         delete pl; return nullptr;
     }
+    if (pairs_gather(me, pl, refs)) { delete pl; return nullptr; }
     return pl;
 }
 
 extern "C" clh_band_plan* clh_band_plan_create(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off,
                                                const int32_t* diag, const clh_band_opts* bo)
 {
-    return bd_create("clh_band_plan_create: ", ctx, n, q, q_off, r, r_off, diag, bo, nullptr);
+    return bd_create("clh_band_plan_create: ", ctx, n, q, q_off, refs_strings(r, r_off), diag, bo, nullptr);
 }
 
 extern "C" clh_band_plan* clh_band_plan_create_gap2(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off,
                                                     const int32_t* diag, const clh_band_opts* bo, const clh_gap2* gap2)
 {
     if (!gap2) return clh_band_plan_create(ctx, n, q, q_off, r, r_off, diag, bo);
-    return bd_create("clh_band_plan_create_gap2: ", ctx, n, q, q_off, r, r_off, diag, bo, gap2);
+    return bd_create("clh_band_plan_create_gap2: ", ctx, n, q, q_off, refs_strings(r, r_off), diag, bo, gap2);
+}
+
+// K1gb on windows of the resident genome; gap2 may be null
+extern "C" clh_band_plan* clh_band_plan_create_windows(clh_genome* genome, int32_t n, const int8_t* q, const int64_t* q_off, const int64_t* win_off,
+                                                       const int32_t* win_len, const uint8_t* win_flags, const int32_t* diag, const clh_band_opts* bo,
+                                                       const clh_gap2* gap2)
+{
+    const std::string me = "clh_band_plan_create_windows: ";
+    if (!genome) { fail(CLH_E_ARG, me + "null genome"); return nullptr; }
+    return bd_create(me, genome->ctx, n, q, q_off, refs_windows(genome, win_off, win_len, win_flags), diag, bo, gap2);
 }
 
 extern "C" int clh_band_plan_run(clh_band_plan* pl, void* stream_)
@@ -2773,6 +2910,11 @@ extern "C" int clh_band_plan_timing(clh_band_plan* pl, float* ms)
 {
     if (!pl || !ms || !pl->ran) return fail(CLH_E_ARG, "clh_band_plan_timing: no run to time");
     return pl->elapsed(ms);
+}
+
+extern "C" int clh_band_plan_gather_timing(clh_band_plan* pl, float* ms, int64_t* letters)
+{
+    return pairs_gather_timing("clh_band_plan_gather_timing: ", pl, ms, letters);
 }
 
 extern "C" int clh_band_plan_info(clh_band_plan* pl, int64_t* out)

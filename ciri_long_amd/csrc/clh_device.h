@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "genome_gather.h"
 
 namespace clh {
 
@@ -224,6 +225,9 @@ hipError_t launch_splice_scan(const uint8_t* codes, const uint8_t* ascii, const 
                               const SpliceSites& sites, int32_t* out, hipStream_t stream);
 hipError_t launch_genome_count_n(const uint8_t* codes, const unsigned int* pre_n, const long long* off, const long long* len, long long* out, int n, hipStream_t stream);
 static constexpr int kGenomeBlock = 256;     // bases per entry of the N prefix table
+// the gather of genome_gather.h: task k writes its window's len codes 0..4 to dst + dst_off; tile_task names the task of every work item
+hipError_t launch_genome_gather(const uint8_t* codes, long long genome_len, const GatherTask* tasks, int ntasks, const int32_t* tile_task, long long ntiles,
+                                int8_t* dst, long long dst_cap, hipStream_t stream);
 hipError_t launch_edit_distance(const uint8_t* seqs, const EdTask* tasks, int ntasks, int G, int planes, int32_t* out, int8_t* carry_ws, hipStream_t stream);
 
 // edit_matrix.hip: all pairs of groups of strings, in front of K4

@@ -10,6 +10,10 @@
 // 243-250), bit 3 lower-case a/c/g/t (revcomp() complements upper case only, utils.py:118-120, while the encoder folds
 // case: a lower-case base of a minus-strand window is reversed but NOT complemented in the reference, and here),
 // bit 4 upper-case 'N' (the only character Counter(window)['N'] counts).
+//
+// genome_gather_kernel copies windows out of this layout into the reference buffer of a pair plan (K1g, K1gb, spliced) as plain codes
+// 0..4, reversed and / or complemented.  It drops bits 3 and 4, so a lower-case base IS complemented there: those modes have no
+// call site in the reference to be bit-equal with (genome_gather.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "clh_device.h"
@@ -81,6 +85,34 @@ __global__ void __launch_bounds__(64) genome_count_n_kernel(const uint8_t* __res
         for (long long i = s; i < e; ++i) cnt += (codes[i] >> 4) & 1;
     }
     out[w] = cnt;
+}
+
+// The gather (genome_gather.h): one wave per work item, a tile of kGatherTile destination bytes of one window; a lane moves
+// kGatherTile / 1024 destination words (gather_move_word), each from the two aligned source words that cover it (one 16-byte load
+// each, one 16-byte store).  tile_task[item] is the item's task; the tile inside it follows from the task's first_tile.  Every load is of a whole
+// aligned word inside the genome's allocation (gather_word) and every store is checked against dst_cap, whatever the tasks hold.
+__global__ void __launch_bounds__(256) genome_gather_kernel(const uint8_t* __restrict__ codes, long long src_cap, const GatherTask* __restrict__ tasks,
+                                                            int ntasks, const int32_t* __restrict__ tile_task, long long ntiles,
+                                                            int8_t* __restrict__ dst, long long dst_cap)
+{
+    const long long item = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (item >= ntiles) return;
+    const int k = __builtin_amdgcn_readfirstlane(tile_task[item]);
+    if (k < 0 || k >= ntasks) return;
+    const GatherTask t = tasks[k];
+    const long long word0 = (item - t.first_tile) * (kGatherTile / kGatherWord) + (threadIdx.x & 63);
+#pragma unroll
+    for (int u = 0; u < kGatherTile / (64 * kGatherWord); ++u) gather_move_word(codes, src_cap, t, word0 + 64 * u, dst, dst_cap);
+}
+
+hipError_t launch_genome_gather(const uint8_t* codes, long long genome_len, const GatherTask* tasks, int ntasks, const int32_t* tile_task, long long ntiles,
+                                int8_t* dst, long long dst_cap, hipStream_t stream)
+{
+    if (ntasks <= 0 || ntiles <= 0) return hipSuccess;
+    if ((dst_cap > 0 && ((uintptr_t)dst & (kGatherWord - 1))) || ((uintptr_t)codes & (kGatherWord - 1))) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(genome_gather_kernel, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, stream, codes, (long long)gather_src_cap(genome_len), tasks,
+                       ntasks, tile_task, ntiles, dst, dst_cap);
+    return hipGetLastError();
 }
 
 hipError_t launch_genome_encode(const char* ascii, uint8_t* codes, unsigned int* block_n, long long len, hipStream_t stream)

@@ -243,6 +243,15 @@ def lib():
                                                        C.POINTER(Splice), C.c_void_p]
             L.clh_ends_batch_spliced.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(EndsOpts), C.POINTER(Splice),
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+        if hasattr(L, 'clh_ends_plan_create_windows'):   # absent from a CLH_LIB build older than pair plans on genome windows: using them there raises
+            L.clh_ends_plan_create_windows.restype = C.c_void_p
+            L.clh_ends_plan_create_windows.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(EndsOpts),
+                                                       C.POINTER(Gap2), C.POINTER(Splice), C.c_void_p]
+            L.clh_ends_plan_gather_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int64)]
+            L.clh_band_plan_gather_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int64)]
+            L.clh_band_plan_create_windows.restype = C.c_void_p
+            L.clh_band_plan_create_windows.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.POINTER(BandOpts), C.POINTER(Gap2)]
         L.clh_band_plan_create.restype = C.c_void_p
         L.clh_band_plan_create.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BandOpts)]
         L.clh_band_plan_destroy.restype = None
@@ -574,11 +583,11 @@ class Context(object):
         return EditSearchPlan(self, probes, texts, k, equalities)
 
     def ends_batch(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode='global', want_cigar=True, workspace_bytes=0,
-                   gap_open2=None, gap_extend2=None, splice=None, strand=None, traceback='stored'):
+                   gap_open2=None, gap_extend2=None, splice=None, strand=None, traceback='stored', windows=None):
         """End-anchored affine-gap alignment of the pairs (query k, reference k), packed codes and offsets as ssw_batch takes them,
         through K1g -> (rows ENDS_DTYPE, cigars uint32 packed ops).  See EndsPlan."""
         plan = EndsPlan(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode, want_cigar, workspace_bytes, gap_open2, gap_extend2,
-                        splice, strand, traceback)
+                        splice, strand, traceback, windows)
         try:
             plan.run()
             return plan.fetch()
@@ -586,16 +595,16 @@ class Context(object):
             plan.close()
 
     def ends_plan(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode='global', want_cigar=True, workspace_bytes=0,
-                  gap_open2=None, gap_extend2=None, splice=None, strand=None, traceback='stored'):
+                  gap_open2=None, gap_extend2=None, splice=None, strand=None, traceback='stored', windows=None):
         return EndsPlan(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode, want_cigar, workspace_bytes, gap_open2, gap_extend2,
-                        splice, strand, traceback)
+                        splice, strand, traceback, windows)
 
     def band_batch(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, band, mode='global', diagonals=None, want_cigar=True,
-                   workspace_bytes=0, gap_open2=None, gap_extend2=None):
+                   workspace_bytes=0, gap_open2=None, gap_extend2=None, windows=None):
         """Banded end-anchored alignment of the pairs (query k, reference k) through K1gb: the programme of ends_batch over the
         diagonals within `band` of the corner diagonals, or of diagonals[k] -> (rows BAND_DTYPE, cigars uint32 packed ops).  See BandPlan."""
         plan = BandPlan(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, band, mode, diagonals, want_cigar, workspace_bytes,
-                        gap_open2, gap_extend2)
+                        gap_open2, gap_extend2, windows)
         try:
             plan.run()
             return plan.fetch()
@@ -603,9 +612,9 @@ class Context(object):
             plan.close()
 
     def band_plan(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, band, mode='global', diagonals=None, want_cigar=True,
-                  workspace_bytes=0, gap_open2=None, gap_extend2=None):
+                  workspace_bytes=0, gap_open2=None, gap_extend2=None, windows=None):
         return BandPlan(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, band, mode, diagonals, want_cigar, workspace_bytes,
-                        gap_open2, gap_extend2)
+                        gap_open2, gap_extend2, windows)
 
     def ccs_file(self, in_path, is_fastq, ccs_fa_path, raw_fa_path, batch_reads=0, first_record=0, max_records=-1, byte_offset=0):
         """Stage 1 from file to file in native code -> (total_reads, reads_with_consensus, reads_too_long); with
@@ -832,14 +841,34 @@ class _PairsPlan(_Handle):
     prefix (`_c`, as in clh_<_c>_plan_run) and the dtype of its rows."""
     _c = _dtype = None
 
-    def _inputs(self, queries, query_off, refs, ref_off, mat, want_cigar, diagonals=None):
+    def _inputs(self, queries, query_off, refs, ref_off, mat, want_cigar, diagonals=None, windows=None):
         """-> (codes and offsets as contiguous arrays, the flat int8 matrix, its edge, the diagonals as int32 or None); sets n and
-        want_cigar"""
+        want_cigar.  With `windows` = (Genome, offsets, lengths, flags) the references are windows of a resident genome instead of
+        refs and ref_off, which must then be None: r is the Genome and r_off the three arrays (int64, int32, uint8), kept alive here"""
         who = type(self).__name__
-        q = np.ascontiguousarray(queries, dtype=np.int8); r = np.ascontiguousarray(refs, dtype=np.int8)
-        q_off = np.ascontiguousarray(query_off, dtype=np.int64); r_off = np.ascontiguousarray(ref_off, dtype=np.int64)
-        if len(q_off) != len(r_off) or len(q_off) < 1:
-            raise ValueError('%s: the two offset tables differ in length' % who)
+        q = np.ascontiguousarray(queries, dtype=np.int8)
+        q_off = np.ascontiguousarray(query_off, dtype=np.int64)
+        if windows is not None:
+            if refs is not None or ref_off is not None:
+                raise ValueError('%s: the references are either refs and ref_off or windows, not both' % who)
+            if not hasattr(lib(), 'clh_ends_plan_create_windows'):
+                raise ClhError('%s: this libclh.so is older than pair plans on genome windows' % who)
+            genome, off, ln, flags = windows
+            if not isinstance(genome, Genome) or not genome._h:
+                raise ValueError('%s: windows = (hip.Genome, offsets, lengths, flags)' % who)
+            if genome.ctx is not self.ctx:
+                raise ValueError('%s: the genome lives on another context' % who)
+            r = genome
+            r_off = (np.ascontiguousarray(off, dtype=np.int64), np.ascontiguousarray(ln, dtype=np.int32), np.ascontiguousarray(flags, dtype=np.uint8))
+            if len(q_off) < 1 or any(a.shape != (len(q_off) - 1,) for a in r_off):
+                raise ValueError('%s: %d query offsets need %d window offsets, lengths and flags' % (who, len(q_off), len(q_off) - 1))
+        else:
+            if refs is None or ref_off is None:
+                raise ValueError('%s: the references are refs and ref_off, or windows' % who)
+            r = np.ascontiguousarray(refs, dtype=np.int8)
+            r_off = np.ascontiguousarray(ref_off, dtype=np.int64)
+            if len(q_off) != len(r_off) or len(q_off) < 1:
+                raise ValueError('%s: the two offset tables differ in length' % who)
         self.n = len(q_off) - 1
         self.want_cigar = bool(want_cigar)
         diag = None
@@ -871,6 +900,13 @@ class _PairsPlan(_Handle):
         the walks, of every share of the batch"""
         return self._timing('clh_%s_plan_timing' % self._c)
 
+    def gather_timing(self):
+        """a plan made with windows=: (HIP-event milliseconds of the gather that filled its reference buffer, letters moved)"""
+        name = 'clh_%s_plan_gather_timing' % self._c
+        ms, letters = C.c_float(0), C.c_int64(0)
+        _check(getattr(lib(), name)(self._h, C.byref(ms), C.byref(letters)), name)
+        return float(ms.value), int(letters.value)
+
 
 class EndsPlan(_PairsPlan):
     """Pairs resident on the GPU (codes uploaded once) for the end-anchored modes of K1g -- 'global', 'semiglobal' (the whole query in
@@ -889,12 +925,17 @@ class EndsPlan(_PairsPlan):
     m x n) in the workspace; 'recompute' keeps the last column of every chunk of 512 reference columns, computes the decisions again
     one chunk at a time and resumes the walk chunk after chunk (CLH_ENDS_CIGAR_RECOMPUTE): the same rows and CIGARs, bit for bit, from
     a 32nd to a 43rd of the memory per chunk, at the price of computing the cells the walk can reach twice.  It pays from about four
-    chunks on; no routing is made between the two."""
+    chunks on; no routing is made between the two.
+    windows=(genome, offsets, lengths, flags) stands for refs and ref_off (both None then; giving both is a ValueError): reference k
+    is lengths[k] bases of the resident hip.Genome from the genome-wide offset offsets[k], reversed where flags[k] & 1 and
+    complemented where flags[k] & 2 (3: the minus strand), gathered on the device when the plan is made
+    (clh_ends_plan_create_windows); one piece, two pieces and splice alike, DNA matrix only.  Lower-case bases ARE complemented
+    here, unlike in Genome.ssw_windows, which keeps the reference's revcomp() quirk (include/ciri_long_hip.h)."""
     _destroy = 'clh_ends_plan_destroy'
     _c, _dtype = 'ends', ENDS_DTYPE
 
     def __init__(self, ctx, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode='global', want_cigar=True, workspace_bytes=0,
-                 gap_open2=None, gap_extend2=None, splice=None, strand=None, traceback='stored'):
+                 gap_open2=None, gap_extend2=None, splice=None, strand=None, traceback='stored', windows=None):
         _Handle.__init__(self, ctx)
         if mode not in ENDS_MODES:
             raise ValueError('mode must be one of global, semiglobal, overlap, prefix, extend, got %r' % (mode,))
@@ -902,6 +943,9 @@ class EndsPlan(_PairsPlan):
             raise ValueError("traceback must be 'stored' or 'recompute', got %r" % (traceback,))
         self.traceback = traceback
         gap2 = gap2_of('EndsPlan', gap_open2, gap_extend2)
+        if windows is not None:
+            self._create_windows(queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode, want_cigar, workspace_bytes, gap2, splice, strand, windows)
+            return
         if splice is not None:
             self._create_spliced(ctx, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode, want_cigar, workspace_bytes, gap2, splice, strand)
             return
@@ -917,6 +961,26 @@ class EndsPlan(_PairsPlan):
             self._h = lib().clh_ends_plan_create_gap2(*(args + (C.byref(gap2),)))
         if not self._h:
             raise ClhError('clh_ends_plan_create%s failed: %s' % ('' if gap2 is None else '_gap2', last_error()))
+
+    def _create_windows(self, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode, want_cigar, workspace_bytes, gap2, splice, strand, windows):
+        """clh_ends_plan_create_windows: one piece, two pieces or introns over windows (genome, offsets, lengths, flags)"""
+        if gap2 is not None and splice is not None:
+            raise ClhError('clh_ends_plan_create_windows failed: CLH_E_UNSUPPORTED: two-piece gap costs together with introns are not built')
+        if strand is not None and splice is None:
+            raise ValueError('EndsPlan: strand comes with splice')
+        q, q_off, genome, (off, ln, flags), mat, n_mat, _ = self._inputs(queries, query_off, refs, ref_off, mat, want_cigar, windows=windows)
+        st = None
+        if strand is not None:
+            st = np.ascontiguousarray(strand, dtype=np.int8)
+            if st.shape != (self.n,):
+                raise ValueError('EndsPlan: %d strands for %d pairs' % (st.size, self.n))
+        opts = EndsOpts(ENDS_MODES[mode], mat.ctypes.data, n_mat, int(gap_open), int(gap_extend), ENDS_TRACEBACKS[self.traceback] if self.want_cigar else 0,
+                        int(workspace_bytes))
+        self._h = lib().clh_ends_plan_create_windows(genome._h, self.n, q.ctypes.data, q_off.ctypes.data, off.ctypes.data, ln.ctypes.data, flags.ctypes.data,
+                                                     C.byref(opts), C.byref(gap2) if gap2 is not None else None,
+                                                     C.byref(splice) if splice is not None else None, st.ctypes.data if st is not None else None)
+        if not self._h:
+            raise ClhError('clh_ends_plan_create_windows failed: %s' % last_error())
 
     def _create_spliced(self, ctx, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, mode, want_cigar, workspace_bytes, gap2, splice, strand):
         if gap2 is not None:
@@ -953,20 +1017,28 @@ class BandPlan(_PairsPlan):
     free), or [diagonals[k] - band, diagonals[k] + band] with a hint per pair, clipped
     to [-m, n] and at most 512 wide.  run() any number of times, fetch() (rows BAND_DTYPE, cigars uint32).  A row carries the
     clipped band and `exact`: 1 where it is proved that EndsPlan returns the same row and CIGAR (include/ciri_long_hip.h).
-    gap_open2 and gap_extend2 are EndsPlan's two-piece gap costs (clh_band_plan_create_gap2): a byte per cell of the band."""
+    gap_open2 and gap_extend2 are EndsPlan's two-piece gap costs (clh_band_plan_create_gap2): a byte per cell of the band.
+    windows=(genome, offsets, lengths, flags) stands for refs and ref_off as in EndsPlan (clh_band_plan_create_windows)."""
     _destroy = 'clh_band_plan_destroy'
     _c, _dtype = 'band', BAND_DTYPE
 
     def __init__(self, ctx, queries, query_off, refs, ref_off, mat, gap_open, gap_extend, band, mode='global', diagonals=None, want_cigar=True,
-                 workspace_bytes=0, gap_open2=None, gap_extend2=None):
+                 workspace_bytes=0, gap_open2=None, gap_extend2=None, windows=None):
         _Handle.__init__(self, ctx)
         if mode not in ENDS_MODES:
             raise ValueError('mode must be one of global, semiglobal, prefix, extend, got %r' % (mode,))
         gap2 = gap2_of('BandPlan', gap_open2, gap_extend2)
-        q, q_off, r, r_off, mat, n_mat, diag = self._inputs(queries, query_off, refs, ref_off, mat, want_cigar, diagonals)
+        q, q_off, r, r_off, mat, n_mat, diag = self._inputs(queries, query_off, refs, ref_off, mat, want_cigar, diagonals, windows=windows)
         if not 0 <= int(band) < 2 ** 31:
             raise ValueError('BandPlan: band must be a half-width >= 0, got %r' % (band,))
         opts = BandOpts(ENDS_MODES[mode], mat.ctypes.data, n_mat, int(gap_open), int(gap_extend), int(self.want_cigar), int(workspace_bytes), int(band), 0)
+        if windows is not None:      # r is the Genome, r_off its windows' offsets, lengths and flags
+            self._h = lib().clh_band_plan_create_windows(r._h, self.n, q.ctypes.data, q_off.ctypes.data, r_off[0].ctypes.data, r_off[1].ctypes.data,
+                                                         r_off[2].ctypes.data, diag.ctypes.data if diag is not None else None, C.byref(opts),
+                                                         C.byref(gap2) if gap2 is not None else None)
+            if not self._h:
+                raise ClhError('clh_band_plan_create_windows failed: %s' % last_error())
+            return
         args = (ctx._h, self.n, q.ctypes.data, q_off.ctypes.data, r.ctypes.data, r_off.ctypes.data, diag.ctypes.data if diag is not None else None,
                 C.byref(opts))
         if gap2 is None:

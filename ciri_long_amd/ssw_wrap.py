@@ -17,6 +17,8 @@ Differences, all additive:
     of the reference) or 'overlap' (end gaps free on both sequences), and start-anchored 'prefix' or 'extend' (pinned at the
     first letters, free at the far end) -- under the same affine scores, DNA or matrix (K1g); ``extend_anchors`` extends both
     ways from an anchor between letters;
+  * ``align_windows_ends``, ``align_windows_band``, ``align_windows_spliced`` and ``extend_anchors_genome`` are the pair calls with
+    references given as windows (contig, start, end) of a genome resident on the GPU, gathered on the device;
   * ``align_pairs_matrix`` aligns over any alphabet of up to 32 letters with its own substitution matrix (``BLOSUM62`` for
     proteins), what the reference's ssw_init / ssw_align take and its Python wrapper does not expose.
 """
@@ -605,6 +607,13 @@ def extend_anchors(ref_seqs, query_seqs, anchors, band=None, seed_len=0, match=2
     if traceback != 'stored':
         kw['traceback'] = traceback
     halves = align_pairs_ends(refs2, queries2, **kw) if band is None else align_pairs_band(refs2, queries2, int(band), **kw)
+    return _stitch_halves(halves, [(int(a[0]), int(a[1])) for a in anchors], [len(q) for q in query_seqs], seed_len, seed_scores, report_cigar, band is not None)
+
+
+def _stitch_halves(halves, anchors, query_lens, seed_len, seed_scores, report_cigar, banded):
+    """the results of extend_anchors from the 'extend' results of its 2 n halves (left of pair k at 2 k, right at 2 k + 1);
+    anchors[k] = (ref_pos, query_pos)"""
+    n = len(anchors)
     out = []
     for k in range(n):
         parts = []
@@ -620,15 +629,268 @@ def extend_anchors(ref_seqs, query_seqs, anchors, band=None, seed_len=0, match=2
                             ops.append((ch, int(num)))
                         num = ''
             parts.append((h.score, h.ref_end, h.query_end, ops))
-        score, rb, re_, qb, qe, ops = _stitch_anchor(parts[0], parts[1], int(anchors[k][0]), int(anchors[k][1]), seed_len, seed_scores[k])
+        score, rb, re_, qb, qe, ops = _stitch_anchor(parts[0], parts[1], anchors[k][0], anchors[k][1], seed_len, seed_scores[k])
         res = PyAlignRes.__new__(PyAlignRes)
         res.score, res.ref_begin, res.ref_end, res.query_begin, res.query_end = score, rb, re_, qb, qe
         res.score2 = res.ref_end2 = None
         res.cigar_string = None
         if report_cigar:
-            tail = len(query_seqs[k]) - qe - 1
+            tail = query_lens[k] - qe - 1
             res.cigar_string = ('%dS' % qb if qb > 0 else '') + ''.join('%d%s' % (c, o) for o, c in ops) + ('%dS' % tail if tail else '')
-        if band is not None:
+        if banded:
             res.band_exact = bool(halves[2 * k].band_exact and halves[2 * k + 1].band_exact)
         out.append(res)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the pair family against windows of the resident genome (hip.Genome): K1g, K1gb, spliced, extension from anchors
+# ---------------------------------------------------------------------------------------------------------------------------
+GATHER_REVERSE, GATHER_COMPLEMENT = 1, 2      # window flags of hip.EndsPlan(windows=...) / hip.BandPlan(windows=...); 3: the minus strand
+
+
+def _window_spans(who, genome, windows):
+    """[(contig, start, end)] -> (genome-wide offsets int64, lengths int64); ValueError names the first window that is not
+    0 <= start <= end <= length of a resident contig"""
+    off = np.zeros(len(windows), dtype=np.int64); ln = np.zeros(len(windows), dtype=np.int64)
+    for k, w in enumerate(windows):
+        ctg, a, b = w[0], int(w[1]), int(w[2])
+        if ctg not in genome.offset:
+            raise ValueError('%s: window %d %r: contig %r is not resident' % (who, k, tuple(w), ctg))
+        if not 0 <= a <= b <= genome.length[ctg]:
+            raise ValueError('%s: window %d %r lies outside contig %r of %d bases (0 <= start <= end <= length)' % (who, k, tuple(w), ctg, genome.length[ctg]))
+        off[k] = genome.offset[ctg] + a; ln[k] = b - a
+    return off, ln
+
+
+def _window_coords(res, contig, start, length, minus):
+    """contig, minus, genome_begin, genome_end on a result whose ref_begin / ref_end are relative to the window [start, start + length)
+    as it was read: forwards, or as the minus strand (letter t = base start + length - 1 - t).  0-based, inclusive, forward-strand
+    contig coordinates; a span without a letter keeps genome_end == genome_begin - 1"""
+    res.contig, res.minus = contig, bool(minus)
+    if minus:
+        res.genome_begin, res.genome_end = start + length - 1 - res.ref_end, start + length - 1 - res.ref_begin
+    else:
+        res.genome_begin, res.genome_end = start + res.ref_begin, start + res.ref_end
+    return res
+
+
+def _exons_of(cigar_string, genome_begin):
+    """the exons of a spliced CIGAR whose first reference letter is contig position genome_begin (forward strand): [(start, end)],
+    inclusive, ascending, split at N; M and D lie inside an exon, I and S take no reference letter"""
+    exons, pos, first, num = [], genome_begin, genome_begin, ''
+    for ch in cigar_string or '':
+        if ch.isdigit():
+            num += ch
+            continue
+        k, num = int(num), ''
+        if ch in 'MD=X':
+            pos += k
+        elif ch == 'N':
+            if pos > first:
+                exons.append((first, pos - 1))
+            pos += k
+            first = pos
+    if pos > first:
+        exons.append((first, pos - 1))
+    return exons
+
+
+def _genome_context(who, genome, context):
+    if context is not None and context is not genome.ctx:
+        raise ValueError('%s: the genome lives on another context' % who)
+    return genome.ctx
+
+
+def align_windows_ends(genome, windows, minus, query_seqs, mode='global', match=2, mismatch=2, gap_open=3, gap_extend=1, report_cigar=False,
+                       context=None, gap_open2=None, gap_extend2=None, traceback='stored'):
+    """``align_pairs_ends`` with reference k = window (contig, start, end) of a genome resident on the GPU (hip.Genome), read as the
+    minus strand where minus[k]: element k equals ``align_pairs_ends`` on the window's string, upper-cased and, where minus[k],
+    reverse-complemented -- the same scores, ties and CIGARs, with no string sliced, reversed, encoded or uploaded: the device
+    gathers the windows into the plan's reference buffer (csrc/genome_gather.h).  Unlike ``align_windows``, which keeps the
+    reference's revcomp() quirk, lower-case bases ARE complemented on the minus strand: a soft-masked exon aligns.  DNA match /
+    mismatch only (no `matrix`, no `alphabet`); every other keyword is ``align_pairs_ends``'s.
+
+    ref_begin and ref_end are relative to the window as read.  Each result also carries ``contig``, ``minus``, ``genome_begin`` and
+    ``genome_end``: 0-based, inclusive, forward-strand contig coordinates (on a minus window genome_begin = start + L - 1 -
+    ref_end); an empty span keeps genome_end == genome_begin - 1.  A window that is not 0 <= start <= end <= genome.length[contig],
+    or whose contig is not resident, is a ValueError that names it."""
+    who = 'align_windows_ends'
+    two = {} if hip.gap2_of(who, gap_open2, gap_extend2) is None else dict(gap_open2=gap_open2, gap_extend2=gap_extend2)
+    if traceback not in hip.ENDS_TRACEBACKS:
+        raise ValueError("%s: traceback must be 'stored' or 'recompute', got %r" % (who, traceback))
+    if mode not in hip.ENDS_MODES:
+        raise ValueError("%s: mode must be 'global', 'semiglobal', 'overlap', 'prefix' or 'extend', got %r" % (who, mode))
+    n = len(windows)
+    if len(query_seqs) != n or len(minus) != n:
+        raise ValueError('%s: %d windows vs %d strands vs %d queries' % (who, n, len(minus), len(query_seqs)))
+    off, ln = _window_spans(who, genome, windows)
+    ctx = _genome_context(who, genome, context)
+    if not n:
+        return []
+    mat, (qd, qo), _ = _pairs_inputs(who, [], query_seqs, match, mismatch, None, None)
+    flags = np.where(np.asarray(minus, dtype=bool), GATHER_REVERSE | GATHER_COMPLEMENT, 0).astype(np.uint8)
+    walk = bool(report_cigar) or mode in ('semiglobal', 'overlap')
+    rows, cig = ctx.ends_batch(qd, qo, None, None, mat, gap_open, gap_extend, mode=mode, want_cigar=walk, traceback=traceback, windows=(genome, off, ln, flags), **two)
+    out = _pairs_results(rows, cig, qo, walk, report_cigar)
+    for k, res in enumerate(out):
+        _window_coords(res, windows[k][0], int(windows[k][1]), int(ln[k]), minus[k])
+    return out
+
+
+def align_windows_band(genome, windows, minus, query_seqs, band, mode='global', diagonals=None, match=2, mismatch=2, gap_open=3, gap_extend=1,
+                       report_cigar=False, context=None, gap_open2=None, gap_extend2=None):
+    """``align_pairs_band`` with reference k = window (contig, start, end) of a resident genome, read as the minus strand where
+    minus[k] (diagonals are those of the window as read): the results of ``align_pairs_band`` on the windows' strings, ``band`` and
+    ``band_exact`` included, with the genome coordinates and the lower-case rule of ``align_windows_ends``."""
+    who = 'align_windows_band'
+    two = {} if hip.gap2_of(who, gap_open2, gap_extend2) is None else dict(gap_open2=gap_open2, gap_extend2=gap_extend2)
+    if mode not in ('global', 'semiglobal', 'prefix', 'extend'):
+        raise ValueError("%s: mode must be 'global', 'semiglobal', 'prefix' or 'extend'%s, got %r"
+                         % (who, " ('overlap' with a band is not built)" if mode == 'overlap' else '', mode))
+    n = len(windows)
+    if len(query_seqs) != n or len(minus) != n:
+        raise ValueError('%s: %d windows vs %d strands vs %d queries' % (who, n, len(minus), len(query_seqs)))
+    if diagonals is not None and len(diagonals) != n:
+        raise ValueError('%s: %d diagonals vs %d pairs' % (who, len(diagonals), n))
+    if int(band) != band or band < 0:
+        raise ValueError('%s: band is a half-width in diagonals, an integer >= 0, got %r' % (who, band))
+    off, ln = _window_spans(who, genome, windows)
+    ctx = _genome_context(who, genome, context)
+    if not n:
+        return []
+    mat, (qd, qo), _ = _pairs_inputs(who, [], query_seqs, match, mismatch, None, None)
+    flags = np.where(np.asarray(minus, dtype=bool), GATHER_REVERSE | GATHER_COMPLEMENT, 0).astype(np.uint8)
+    walk = bool(report_cigar) or mode == 'semiglobal'
+    rows, cig = ctx.band_batch(qd, qo, None, None, mat, gap_open, gap_extend, int(band), mode=mode, diagonals=diagonals, want_cigar=walk,
+                               windows=(genome, off, ln, flags), **two)
+    out = _pairs_results(rows, cig, qo, walk, report_cigar)
+    for k, (r, res) in enumerate(zip(rows, out)):
+        res.band = (int(r['band_lo']), int(r['band_hi']))
+        res.band_exact = bool(r['exact'])
+        _window_coords(res, windows[k][0], int(windows[k][1]), int(ln[k]), minus[k])
+    return out
+
+
+def align_windows_spliced(genome, windows, query_seqs, mode='semiglobal', strand='+', match=2, mismatch=2, gap_open=3, gap_extend=1, intron_open=12,
+                          noncanonical=6, donor_costs=None, acceptor_costs=None, report_cigar=False, context=None, traceback='stored'):
+    """``align_pairs_spliced`` with reference k = window (contig, start, end) of a resident genome.  The window is always read on the
+    forward strand; `strand` is the transcript's, exactly as in ``align_pairs_spliced`` ('+', '-', one per pair, or 'both': pairs k
+    and n + k of one plan, each window gathered twice, the higher score kept, ties to '+').  The results are those of
+    ``align_pairs_spliced`` on the windows' upper-cased strings, ``strand`` included, with ``contig``, ``minus`` (False),
+    ``genome_begin`` and ``genome_end`` as ``align_windows_ends`` gives them; with report_cigar also ``exons``: the forward-strand
+    contig intervals [(start, end), ...], inclusive and ascending, that the CIGAR's N ops split the alignment into -- what
+    ``align.get_exons`` would be asked for next."""
+    who = 'align_windows_spliced'
+    if traceback not in hip.ENDS_TRACEBACKS:
+        raise ValueError("%s: traceback must be 'stored' or 'recompute', got %r" % (who, traceback))
+    if mode not in hip.ENDS_MODES:
+        raise ValueError("%s: mode must be 'global', 'semiglobal', 'overlap', 'prefix' or 'extend', got %r" % (who, mode))
+    n = len(windows)
+    if len(query_seqs) != n:
+        raise ValueError('%s: %d windows vs %d queries' % (who, n, len(query_seqs)))
+    if min(int(match), int(mismatch), int(gap_open), int(gap_extend)) < 0:
+        raise ValueError('%s: match, mismatch and the gap costs must not be negative' % who)
+    splice = hip.splice_of(who, intron_open, noncanonical, donor_costs, acceptor_costs)
+    both = isinstance(strand, str) and strand == 'both'
+    st = np.concatenate([np.ones(n, dtype=np.int8), -np.ones(n, dtype=np.int8)]) if both else _strands(strand, n)
+    off, ln = _window_spans(who, genome, windows)
+    ctx = _genome_context(who, genome, context)
+    if not n:
+        return []
+    queries = list(query_seqs) * 2 if both else query_seqs
+    if both:
+        off, ln = np.concatenate([off, off]), np.concatenate([ln, ln])
+    mat, (qd, qo), _ = _pairs_inputs(who, [], queries, match, mismatch, None, None)
+    walk = bool(report_cigar) or mode in ('semiglobal', 'overlap')
+    rows, cig = ctx.ends_batch(qd, qo, None, None, mat, gap_open, gap_extend, mode=mode, want_cigar=walk, splice=splice, strand=st, traceback=traceback,
+                               windows=(genome, off, ln, np.zeros(len(off), dtype=np.uint8)))
+    out = _pairs_results(rows, cig, qo, walk, report_cigar)
+    for k, (res, s) in enumerate(zip(out, st)):
+        res.strand = '+' if s > 0 else '-'
+        w = windows[k % n]
+        _window_coords(res, w[0], int(w[1]), int(ln[k]), False)
+        if report_cigar:
+            res.exons = _exons_of(res.cigar_string, res.genome_begin)
+    if both:
+        out = [out[k] if out[k].score >= out[n + k].score else out[n + k] for k in range(n)]
+    return out
+
+
+def _anchor_flanks(contig_len, pos, query_pos, query_len, slack, minus):
+    """(left_flank, right_flank, start): the reference letters in front of and behind the anchor as the query reads them, and the
+    first base of the contig interval [start, start + left_flank + right_flank) they come from.  A side holds the query letters on
+    that side plus `slack`, or what the contig has.  On the plus strand the query's left is towards base 0; on the minus strand the
+    query reads the reverse complement, so its left is towards the contig's end"""
+    lo_room, hi_room = pos, contig_len - pos
+    left = min(hi_room if minus else lo_room, query_pos + slack)
+    right = min(lo_room if minus else hi_room, query_len - query_pos + slack)
+    return left, right, pos - (right if minus else left)
+
+
+def extend_anchors_genome(genome, anchors, minus, query_seqs, band=None, slack=None, match=2, mismatch=2, gap_open=3, gap_extend=1, report_cigar=False,
+                          context=None, gap_open2=None, gap_extend2=None, traceback='stored'):
+    """``extend_anchors`` along a resident genome: anchors[k] = (contig, pos, query_pos) is a point between letters, `pos` on the
+    forward strand of the contig (between bases pos - 1 and pos), query_pos in the query; where minus[k] the query reads the minus
+    strand.  On each side of the anchor, as the query reads it, the reference flank is min(letters to the contig's edge, query
+    letters on that side + slack); slack defaults to 64, with a band to `band`.  The 2 n flanks are 2 n windows of one plan, none of
+    them a string: the left half of a plus-strand anchor is gathered reversed (flags 1), its right half as it stands; for a
+    minus-strand anchor the right half is the bases below pos reversed and complemented (flags 3) and the left half the bases from
+    pos on complemented (flags 2).  Only the query's left part is reversed on the host.  There is no seed_len: a seed's letters are
+    the first columns of the right half.
+
+    Definition: with (left, right) the two flanks, the result equals ``extend_anchors`` on the strand-resolved string of the contig
+    interval [pos - left, pos + right) -- on the minus strand the reverse complement of [pos - right, pos + left) -- upper-cased,
+    with anchor (left, query_pos): ref_begin and ref_end are relative to that string, ``band_exact`` as there.  ``contig``,
+    ``minus``, ``genome_begin`` and ``genome_end`` are those of ``align_windows_ends`` for that interval."""
+    who = 'extend_anchors_genome'
+    two = {} if hip.gap2_of(who, gap_open2, gap_extend2) is None else dict(gap_open2=gap_open2, gap_extend2=gap_extend2)
+    if traceback not in hip.ENDS_TRACEBACKS:
+        raise ValueError("%s: traceback must be 'stored' or 'recompute', got %r" % (who, traceback))
+    if traceback != 'stored' and band is not None:
+        raise ValueError("%s: traceback=%r goes with band=None: K1gb has the stored route alone" % (who, traceback))
+    n = len(anchors)
+    if len(query_seqs) != n or len(minus) != n:
+        raise ValueError('%s: %d anchors vs %d strands vs %d queries' % (who, n, len(minus), len(query_seqs)))
+    if band is not None and (int(band) != band or band < 0):
+        raise ValueError('%s: band is a half-width in diagonals, an integer >= 0, got %r' % (who, band))
+    if slack is None:
+        slack = 64 if band is None else int(band)
+    if int(slack) != slack or slack < 0:
+        raise ValueError('%s: slack is a number of letters >= 0, got %r' % (who, slack))
+    windows2, flags2, queries2, spans, local = [], [], [], [], []
+    for k in range(n):
+        ctg, pos, qp = anchors[k][0], int(anchors[k][1]), int(anchors[k][2])
+        q = query_seqs[k]
+        if ctg not in genome.offset:
+            raise ValueError('%s: anchor %d %r: contig %r is not resident' % (who, k, tuple(anchors[k]), ctg))
+        if not (0 <= pos <= genome.length[ctg] and 0 <= qp <= len(q)):
+            raise ValueError('%s: anchor %d %r lies outside contig %r of %d bases or the query of %d letters'
+                             % (who, k, tuple(anchors[k]), ctg, genome.length[ctg], len(q)))
+        left, right, start = _anchor_flanks(genome.length[ctg], pos, qp, len(q), int(slack), bool(minus[k]))
+        if minus[k]:
+            windows2 += [(ctg, pos, pos + left), (ctg, pos - right, pos)]
+            flags2 += [GATHER_COMPLEMENT, GATHER_REVERSE | GATHER_COMPLEMENT]
+        else:
+            windows2 += [(ctg, pos - left, pos), (ctg, pos, pos + right)]
+            flags2 += [GATHER_REVERSE, 0]
+        queries2 += [q[:qp][::-1], q[qp:]]
+        spans.append((ctg, start, left + right)); local.append((left, qp))
+    off, ln = _window_spans(who, genome, windows2)
+    ctx = _genome_context(who, genome, context)
+    if not n:
+        return []
+    mat, (qd, qo), _ = _pairs_inputs(who, [], queries2, match, mismatch, None, None)
+    wins = (genome, off, ln, np.array(flags2, dtype=np.uint8))
+    if band is None:
+        rows, cig = ctx.ends_batch(qd, qo, None, None, mat, gap_open, gap_extend, mode='extend', want_cigar=bool(report_cigar), traceback=traceback, windows=wins, **two)
+    else:
+        rows, cig = ctx.band_batch(qd, qo, None, None, mat, gap_open, gap_extend, int(band), mode='extend', want_cigar=bool(report_cigar), windows=wins, **two)
+    halves = _pairs_results(rows, cig, qo, bool(report_cigar), report_cigar)
+    if band is not None:
+        for r, res in zip(rows, halves):
+            res.band_exact = bool(r['exact'])
+    out = _stitch_halves(halves, local, [len(q) for q in query_seqs], 0, [0] * n, report_cigar, band is not None)
+    for k, res in enumerate(out):
+        _window_coords(res, spans[k][0], spans[k][1], spans[k][2], minus[k])
     return out

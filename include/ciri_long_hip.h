@@ -566,6 +566,30 @@ clh_band_plan* clh_band_plan_create_gap2(clh_ctx* ctx, int32_t n, const int8_t* 
 int clh_band_batch_gap2(clh_ctx* ctx, int32_t n, const int8_t* q, const int64_t* q_off, const int8_t* r, const int64_t* r_off, const int32_t* diag,
                         const clh_band_opts* opts, const clh_gap2* gap2, clh_band_row* rows, uint32_t* cigar, int64_t cigar_cap, int64_t* cigar_used);
 
+/* ---- K1g and K1gb against windows of the resident genome ---------------------------------------------------------------------------
+ * The plans above with reference k = the win_len[k] bases of the genome from win_off[k] (genome-wide offsets, as clh_ssw_plan_windows
+ * takes them), read as win_flags[k] says: bit 0 reversed (letter t of the reference is base win_len - 1 - t of the window), bit 1
+ * complemented; 3 is the minus strand, 1 the reversed flank of an extension to the left.  create gathers the windows on the device
+ * into the plan's reference buffer (once; not per run) and returns a plan of the existing type: run, fetch, timing, info and destroy
+ * are those above, and rows, ties and CIGARs are those of the strings form on the same letters.  The letters: A/a 0, C/c 1, G/g 2,
+ * T/t 3, anything else 4, and complementing maps 0..3 to 3 - code WHATEVER THE CASE.  This differs on purpose from the windows of
+ * clh_ssw_plan_windows, which leave a lower-case base of a minus-strand window uncomplemented as the reference's revcomp() does:
+ * these modes have no call site in the reference to be bit-equal with, and a soft-masked minus-strand exon must align.
+ * gap2, splice and strand may each be NULL (strand only comes with splice; gap2 together with splice is CLH_E_UNSUPPORTED, as
+ * in the strings form).  The plan lives on the genome's context.  Refusals beyond those of the strings form: CLH_E_ARG for a null
+ * genome, and, naming the first such pair, for win_len < 0, win_off < 0, win_off + win_len > clh_genome_length and flags above 3;
+ * CLH_E_UNSUPPORTED for n_mat != 5 (substitution matrices over other alphabets take their references as strings). */
+clh_ends_plan* clh_ends_plan_create_windows(clh_genome* genome, int32_t n, const int8_t* q, const int64_t* q_off, const int64_t* win_off,
+                                            const int32_t* win_len, const uint8_t* win_flags, const clh_ends_opts* opts, const clh_gap2* gap2,
+                                            const clh_splice* splice, const int8_t* strand);
+clh_band_plan* clh_band_plan_create_windows(clh_genome* genome, int32_t n, const int8_t* q, const int64_t* q_off, const int64_t* win_off,
+                                            const int32_t* win_len, const uint8_t* win_flags, const int32_t* diag, const clh_band_opts* opts,
+                                            const clh_gap2* gap2);
+/* HIP events around the gather that create ran, and the letters it moved (each read once and written once); CLH_E_ARG for a plan
+ * whose references are strings or whose windows hold no letter. */
+int clh_ends_plan_gather_timing(clh_ends_plan* plan, float* ms, int64_t* letters);
+int clh_band_plan_gather_timing(clh_band_plan* plan, float* ms, int64_t* letters);
+
 
 /* ASCII -> codes exactly as ssw_wrap.py:234-252 (A/a C/c G/g T/t N/n, anything else 4), on the host. */
 void clh_encode_dna(const char* seq, int64_t len, int8_t* out);
