@@ -3407,3 +3407,393 @@ extern "C" int clh_poa_batch(clh_ctx* ctx, int32_t ngroups, const int8_t* seqs, 
     delete pl;
     return rc;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// K7: minimizer index of the resident genome, seeds and chains (seed.hip, seed_sort.hip; definitions in seed_device.h)
+// ---------------------------------------------------------------------------------------------------------------
+#include "seed_device.h"
+
+// device blocks of one call: given back, after the stream has drained, when the call returns
+struct SdBlocks {
+    clh_ctx* ctx;
+    std::vector<void*> v;
+    size_t refused = 0;                                 // bytes of the first allocation the device refused
+    explicit SdBlocks(clh_ctx* c) : ctx(c) {}
+    SdBlocks(const SdBlocks&) = delete;
+    ~SdBlocks() { (void)hipStreamSynchronize(ctx->stream); for (void* p : v) ctx->release(p); }
+    template <class T> T* get(size_t count)
+    {
+        void* p = ctx->alloc(sizeof(T) * (count ? count : 1));
+        if (p) v.push_back(p); else if (!refused) refused = sizeof(T) * count;
+        return (T*)p;
+    }
+    template <class T> T* put(const std::vector<T>& h)
+    {
+        T* p = get<T>(h.size());
+        if (p && !h.empty() && hipMemcpyAsync(p, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return nullptr;
+        return p;
+    }
+};
+static int sd_refused(const std::string& me, const SdBlocks& B)
+{
+    return fail(CLH_E_CAPACITY, me + "the device refused an allocation" + (B.refused ? " of " + std::to_string(B.refused) + " bytes" : std::string()));
+}
+static int sd_bits(uint64_t v) { int b = 1; while (v >>= 1) ++b; return b; }
+
+struct clh_seed_index : clh_owned {
+    using clh_owned::clh_owned;
+    clh_genome* genome = nullptr;
+    int k = 0, w = 0, max_occ = 0, last_shares = 0;
+    std::vector<int64_t> c_off, c_len;
+    int64_t *d_coff = nullptr, *d_clen = nullptr;
+    uint64_t *d_keys = nullptr, *d_vals = nullptr;
+    int64_t n = 0, distinct = 0, over = 0, bytes = 0;
+    float ms[4] = {0, 0, 0, 0};
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    std::vector<uint64_t> h_mkeys, h_mvals, h_k1, h_k2;          // what the last minimizers / seeds call left for its fetch
+};
+
+extern "C" void clh_seed_index_destroy(clh_seed_index* x) { delete x; }
+
+// the sketch of nseq sequences of d_codes: entries in (sequence, position) order, in blocks of B
+// The host tables that are uploaded asynchronously live here too: an SdEntries (and every other host buffer of an asynchronous copy) is
+// declared BEFORE the call's SdBlocks, whose destructor drains the stream, so that on every return, early ones included, no copy in
+// flight outlives its host side.
+struct SdEntries {
+    uint64_t *keys = nullptr, *vals = nullptr; int32_t* seq_of = nullptr; int64_t n = 0; int64_t *d_item_off = nullptr, *d_seq_item0 = nullptr;
+    std::vector<int64_t> h_item0; std::vector<int32_t> h_item_seq;
+};
+static int sd_sketch(const std::string& me, clh_seed_index* x, SdBlocks& B, const uint8_t* d_codes, int64_t codes_len, const std::vector<int64_t>& off,
+                     const std::vector<int64_t>& len, bool global_pos, bool want_seq, SdEntries* o)
+{
+    hipStream_t st = x->ctx->stream;
+    const int32_t nseq = (int32_t)off.size();
+    std::vector<int64_t>& item0 = o->h_item0;
+    std::vector<int32_t>& item_seq = o->h_item_seq;
+    item0.assign((size_t)nseq + 1, 0); item_seq.clear();
+    for (int32_t s = 0; s < nseq; ++s) {
+        const int64_t P = len[s] - x->k + 1, items = P > 0 ? (P + clh::kSdItem - 1) / clh::kSdItem : 0;
+        item0[s + 1] = item0[s] + items;
+        item_seq.insert(item_seq.end(), (size_t)items, s);
+    }
+    const int64_t nitems = item0[nseq];
+    clh::SdSketch S;
+    S.codes = d_codes; S.codes_len = codes_len; S.nseq = nseq; S.nitems = nitems; S.k = x->k; S.w = x->w; S.global_pos = global_pos ? 1 : 0;
+    S.off = B.put(off); S.len = B.put(len); S.item_seq = B.put(item_seq); S.seq_item0 = o->d_seq_item0 = B.put(item0);
+    int32_t* d_count = B.get<int32_t>((size_t)nitems + 1);
+    o->d_item_off = B.get<int64_t>((size_t)nitems + 1);
+    const size_t tb = clh::seed_scan_temp_bytes(nitems + 1);
+    void* d_temp = B.get<uint8_t>(tb);
+    if (!S.off || !S.len || !S.item_seq || !S.seq_item0 || !d_count || !o->d_item_off || !d_temp) return sd_refused(me, B);
+    HIPCHK(hipMemsetAsync(d_count, 0, sizeof(int32_t) * ((size_t)nitems + 1), st));
+    HIPCHK(clh::launch_seed_sketch_count(S, d_count, st));
+    HIPCHK(clh::seed_scan_counts(d_temp, tb, d_count, o->d_item_off, nitems + 1, st));
+    HIPCHK(hipMemcpyAsync(&o->n, o->d_item_off + nitems, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (o->n < 0) return fail(CLH_E_HIP, me + "the count pass left a negative total");
+    o->keys = B.get<uint64_t>((size_t)o->n); o->vals = B.get<uint64_t>((size_t)o->n);
+    if (want_seq) o->seq_of = B.get<int32_t>((size_t)o->n);
+    if (!o->keys || !o->vals || (want_seq && !o->seq_of)) return sd_refused(me, B);
+    HIPCHK(clh::launch_seed_sketch_fill(S, o->d_item_off, o->keys, o->vals, o->seq_of, o->n, st));
+    return 0;
+}
+
+static int sd_build(const std::string& me, clh_seed_index* x)
+{
+    clh_ctx* ctx = x->ctx;
+    hipStream_t st = ctx->stream;
+    SdEntries E;                                        // before B: see SdEntries
+    SdBlocks B(ctx);
+    HIPCHK(hipEventRecord(x->ev[0], st));
+    if (int rc = sd_sketch(me, x, B, (const uint8_t*)x->genome->d_codes, x->genome->len, x->c_off, x->c_len, true, false, &E)) return rc;
+    HIPCHK(hipEventRecord(x->ev[1], st));
+    x->n = E.n;
+    x->d_keys = (uint64_t*)x->alloc(sizeof(uint64_t) * (size_t)(E.n ? E.n : 1));
+    x->d_vals = (uint64_t*)x->alloc(sizeof(uint64_t) * (size_t)(E.n ? E.n : 1));
+    const size_t tb = clh::seed_sort_temp_bytes(E.n);
+    void* d_temp = B.get<uint8_t>(tb);
+    unsigned long long* d_stats = B.get<unsigned long long>(2);
+    if (!x->d_keys || !x->d_vals || !d_temp || !d_stats)
+        return fail(CLH_E_CAPACITY, me + "the device refused the " + std::to_string(16 * (size_t)E.n + tb) + " bytes of the sorted index of " + std::to_string(E.n) + " entries");
+    HIPCHK(clh::seed_sort_pairs(d_temp, tb, E.keys, x->d_keys, E.vals, x->d_vals, E.n, 2 * x->k, st));
+    HIPCHK(hipEventRecord(x->ev[2], st));
+    HIPCHK(hipMemsetAsync(d_stats, 0, 16, st));
+    HIPCHK(clh::launch_seed_index_stats(x->d_keys, E.n, x->max_occ, d_stats, st));
+    unsigned long long stats[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(stats, d_stats, 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipEventElapsedTime(&x->ms[0], x->ev[0], x->ev[1]));
+    HIPCHK(hipEventElapsedTime(&x->ms[1], x->ev[1], x->ev[2]));
+    x->distinct = (int64_t)stats[0]; x->over = (int64_t)stats[1];
+    x->bytes = 16 * (E.n ? E.n : 1) + 16 * (int64_t)x->c_off.size();
+    return 0;
+}
+
+extern "C" clh_seed_index* clh_seed_index_create(clh_genome* g, int32_t k, int32_t w, int32_t n_contigs, const int64_t* contig_off, const int64_t* contig_len,
+                                                 int32_t max_occ)
+{
+    const std::string me = "clh_seed_index_create: ";
+    if (!g || n_contigs < 0 || (n_contigs > 0 && (!contig_off || !contig_len))) { fail(CLH_E_ARG, me + "null argument"); return nullptr; }
+    if (k < clh::kSdKMin || k > clh::kSdKMax) { fail(CLH_E_ARG, me + "k must be 4..28, got " + std::to_string(k)); return nullptr; }
+    if (w < clh::kSdWMin || w > clh::kSdWMax) { fail(CLH_E_ARG, me + "w must be 1..64, got " + std::to_string(w)); return nullptr; }
+    if (max_occ < 1) { fail(CLH_E_ARG, me + "max_occ must be at least 1"); return nullptr; }
+    if (g->len >= ((int64_t)1 << 39)) { fail(CLH_E_CAPACITY, me + "a genome of 2^39 bases or more"); return nullptr; }
+    for (int32_t c = 0; c < n_contigs; ++c)
+        if (contig_off[c] < 0 || contig_len[c] < 0 || contig_off[c] + contig_len[c] > g->len || (c > 0 && contig_off[c] < contig_off[c - 1] + contig_len[c - 1])) {
+            fail(CLH_E_ARG, me + "contig " + std::to_string(c) + " lies outside the genome or before the end of the contig in front of it"); return nullptr;
+        }
+    if (hipSetDevice(g->ctx->device) != hipSuccess) { fail(CLH_E_HIP, "hipSetDevice failed"); return nullptr; }
+    clh_seed_index* x = new clh_seed_index(g->ctx);
+    x->genome = g; x->k = k; x->w = w; x->max_occ = max_occ;
+    x->c_off.assign(contig_off, contig_off + n_contigs); x->c_len.assign(contig_len, contig_len + n_contigs);
+    bool ok = true;
+    for (auto& e : x->ev) ok = ok && x->event(&e) == hipSuccess;
+    x->d_coff = (int64_t*)x->upload(x->c_off.data(), sizeof(int64_t) * (size_t)n_contigs);
+    x->d_clen = (int64_t*)x->upload(x->c_len.data(), sizeof(int64_t) * (size_t)n_contigs);
+    if (!ok || !x->d_coff || !x->d_clen) { fail(CLH_E_HIP, me + "out of device memory"); delete x; return nullptr; }
+    if (sd_build(me, x)) { (void)hipStreamSynchronize(g->ctx->stream); delete x; return nullptr; }
+    return x;
+}
+
+extern "C" int clh_seed_index_info(clh_seed_index* x, int64_t* out)
+{
+    if (!x || !out) return fail(CLH_E_ARG, "clh_seed_index_info: null argument");
+    const int64_t v[12] = {x->n, x->distinct, x->over, x->bytes, x->k, x->w, x->max_occ, x->last_shares, clh::kSdRound, clh::kSdItem, clh::kSdItemsPerBlock, 0};
+    for (int i = 0; i < 12; ++i) out[i] = v[i];
+    return 0;
+}
+
+extern "C" int clh_seed_index_timing(clh_seed_index* x, float* ms)
+{
+    if (!x || !ms) return fail(CLH_E_ARG, "clh_seed_index_timing: null argument");
+    for (int i = 0; i < 4; ++i) ms[i] = x->ms[i];
+    return 0;
+}
+
+extern "C" int clh_seed_index_dump(clh_seed_index* x, int64_t first, int64_t count, uint64_t* keys, int64_t* pos, uint8_t* strand)
+{
+    if (!x || count < 0 || (count > 0 && (!keys || !pos || !strand))) return fail(CLH_E_ARG, "clh_seed_index_dump: null argument");
+    if (first < 0 || first + count > x->n) return fail(CLH_E_ARG, "clh_seed_index_dump: the range leaves the " + std::to_string(x->n) + " entries");
+    if (count == 0) return 0;
+    HIPCHK(hipSetDevice(x->ctx->device));
+    std::vector<uint64_t> v((size_t)count);
+    HIPCHK(hipMemcpy(keys, x->d_keys + first, sizeof(uint64_t) * (size_t)count, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(v.data(), x->d_vals + first, sizeof(uint64_t) * (size_t)count, hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < count; ++i) { pos[i] = (int64_t)(v[i] >> 1); strand[i] = (uint8_t)(v[i] & 1); }
+    return 0;
+}
+
+// the reads of a call on the device and their sketch
+struct SdReads { std::vector<int64_t> off, len; uint8_t* d_codes = nullptr; int64_t total = 0; SdEntries E; };
+static int sd_reads(const std::string& me, clh_seed_index* x, SdBlocks& B, int32_t n, const int8_t* reads, const int64_t* read_off, SdReads* R)
+{
+    if (!x || n < 0 || !read_off) return fail(CLH_E_ARG, me + "null argument");
+    if (read_off[0] < 0) return fail(CLH_E_ARG, me + "offsets must ascend from 0 or above");
+    R->off.assign(read_off, read_off + n); R->len.resize((size_t)n);
+    for (int32_t r = 0; r < n; ++r) {
+        const int64_t L = read_off[r + 1] - read_off[r];
+        if (L < 0) return fail(CLH_E_ARG, me + "offsets must ascend");
+        if (L >= ((int64_t)1 << clh::kSdYBits)) return fail(CLH_E_ARG, me + "read " + std::to_string(r) + " has 2^24 letters or more");
+        R->len[r] = L;
+    }
+    R->total = read_off[n];
+    if (R->total > 0 && !reads) return fail(CLH_E_ARG, me + "null argument");
+    for (int32_t r = 0; r < n; ++r)
+        for (int64_t i = read_off[r]; i < read_off[r + 1]; ++i)
+            if (reads[i] < 0 || reads[i] > 4) return fail(CLH_E_ARG, me + "read " + std::to_string(r) + " holds a code outside 0..4");
+    HIPCHK(hipSetDevice(x->ctx->device));
+    R->d_codes = B.get<uint8_t>((size_t)R->total);
+    if (!R->d_codes) return sd_refused(me, B);
+    if (R->total > 0) HIPCHK(hipMemcpyAsync(R->d_codes, reads, (size_t)R->total, hipMemcpyHostToDevice, x->ctx->stream));
+    HIPCHK(hipEventRecord(x->ev[0], x->ctx->stream));
+    return sd_sketch(me, x, B, R->d_codes, R->total, R->off, R->len, false, true, &R->E);
+}
+
+extern "C" int clh_seed_minimizers(clh_seed_index* x, int32_t n, const int8_t* seqs, const int64_t* seq_off, int64_t* min_off)
+{
+    const std::string me = "clh_seed_minimizers: ";
+    if (!x || !min_off) return fail(CLH_E_ARG, me + "null argument");
+    SdReads R;                                          // before B: see SdEntries
+    std::vector<int64_t> item0, item_off;
+    SdBlocks B(x->ctx);
+    if (int rc = sd_reads(me, x, B, n, seqs, seq_off, &R)) return rc;
+    hipStream_t st = x->ctx->stream;
+    HIPCHK(hipEventRecord(x->ev[1], st));
+    // min_off[r] = item_off[seq_item0[r]]: both tables come back, the host does the look-up
+    item0.resize((size_t)n + 1);
+    HIPCHK(hipMemcpyAsync(item0.data(), R.E.d_seq_item0, sizeof(int64_t) * ((size_t)n + 1), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    item_off.resize((size_t)item0[n] + 1);
+    HIPCHK(hipMemcpyAsync(item_off.data(), R.E.d_item_off, sizeof(int64_t) * item_off.size(), hipMemcpyDeviceToHost, st));
+    x->h_mkeys.assign((size_t)R.E.n, 0); x->h_mvals.assign((size_t)R.E.n, 0);
+    if (R.E.n > 0) {
+        HIPCHK(hipMemcpyAsync(x->h_mkeys.data(), R.E.keys, sizeof(uint64_t) * (size_t)R.E.n, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(x->h_mvals.data(), R.E.vals, sizeof(uint64_t) * (size_t)R.E.n, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipEventElapsedTime(&x->ms[2], x->ev[0], x->ev[1]));
+    for (int32_t r = 0; r <= n; ++r) min_off[r] = item_off[(size_t)item0[r]];
+    return 0;
+}
+
+extern "C" int clh_seed_minimizers_fetch(clh_seed_index* x, int64_t cap, int64_t* pos, uint64_t* keys, uint8_t* strand)
+{
+    if (!x) return fail(CLH_E_ARG, "clh_seed_minimizers_fetch: null argument");
+    const int64_t m = (int64_t)x->h_mkeys.size();
+    if (cap < m) return fail(CLH_E_CAPACITY, "clh_seed_minimizers_fetch: cap too small");
+    if (m > 0 && (!pos || !keys || !strand)) return fail(CLH_E_ARG, "clh_seed_minimizers_fetch: null argument");
+    for (int64_t i = 0; i < m; ++i) { keys[i] = x->h_mkeys[i]; pos[i] = (int64_t)(x->h_mvals[i] >> 1); strand[i] = (uint8_t)(x->h_mvals[i] & 1); }
+    return 0;
+}
+
+// seeds, and chains where o is given: the anchors of a share stay on the device between the two
+static int sd_seeds(const std::string& me, clh_seed_index* x, int32_t n, const int8_t* reads, const int64_t* read_off, int64_t workspace_bytes, int64_t* anchor_off,
+                    int32_t* repetitive, const clh_chain_opts* o, int64_t* seg_out, int64_t* rows_out)
+{
+    clh_ctx* ctx = x->ctx;
+    hipStream_t st = ctx->stream;
+    SdReads R;                                          // before B: see SdEntries
+    std::vector<int64_t> rm, ra;
+    std::vector<int32_t> rrep;
+    SdBlocks B(ctx);
+    if (int rc = sd_reads(me, x, B, n, reads, read_off, &R)) return rc;
+    const int64_t nmin = R.E.n;
+    int64_t* d_lo = B.get<int64_t>((size_t)nmin);
+    int32_t* d_cnt = B.get<int32_t>((size_t)nmin + 1);
+    uint8_t* d_rep = B.get<uint8_t>((size_t)nmin);
+    int64_t* d_aoff = B.get<int64_t>((size_t)nmin + 1);
+    int64_t* d_rlen = B.put(R.len);
+    int64_t* d_rm = B.get<int64_t>((size_t)n + 1);
+    int64_t* d_ra = B.get<int64_t>((size_t)n + 1);
+    int32_t* d_rrep = B.get<int32_t>((size_t)n);
+    const size_t tb = clh::seed_scan_temp_bytes(nmin + 1);
+    void* d_temp = B.get<uint8_t>(tb);
+    if (!d_lo || !d_cnt || !d_rep || !d_aoff || !d_rlen || !d_rm || !d_ra || !d_rrep || !d_temp) return sd_refused(me, B);
+    HIPCHK(hipMemsetAsync(d_cnt, 0, sizeof(int32_t) * ((size_t)nmin + 1), st));
+    HIPCHK(clh::launch_seed_lookup(x->d_keys, x->n, x->max_occ, R.E.keys, nmin, d_lo, d_cnt, d_rep, st));
+    HIPCHK(clh::seed_scan_counts(d_temp, tb, d_cnt, d_aoff, nmin + 1, st));
+    HIPCHK(clh::launch_seed_per_read(R.E.d_seq_item0, R.E.d_item_off, d_aoff, d_rep, n, d_rm, d_ra, d_rrep, st));
+    HIPCHK(hipEventRecord(x->ev[1], st));
+    rm.resize((size_t)n + 1); ra.resize((size_t)n + 1); rrep.resize((size_t)n);
+    HIPCHK(hipMemcpyAsync(rm.data(), d_rm, sizeof(int64_t) * ((size_t)n + 1), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(ra.data(), d_ra, sizeof(int64_t) * ((size_t)n + 1), hipMemcpyDeviceToHost, st));
+    if (n > 0) HIPCHK(hipMemcpyAsync(rrep.data(), d_rrep, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    float t = 0;
+    HIPCHK(hipEventElapsedTime(&t, x->ev[0], x->ev[1]));
+    x->ms[2] = t;
+    if (o) x->ms[3] = 0;
+    // shares of whole reads, 64 bytes an anchor: four sort words, the sort's own space, f, p and the used mark
+    const int64_t ws = workspace_bytes > 0 ? workspace_bytes : (int64_t)1 << 30, cap = ws / 64;
+    std::vector<int32_t> cut(1, 0);
+    int64_t share_max = 0;
+    int32_t reads_max = 0;
+    for (int32_t a = 0; a < n;) {
+        int32_t b = a;
+        while (b < n && ra[b + 1] - ra[a] <= cap) ++b;
+        if (b == a)
+            return fail(CLH_E_CAPACITY, me + "read " + std::to_string(a) + " alone has " + std::to_string(ra[a + 1] - ra[a]) + " anchors, workspace_bytes holds " +
+                                            std::to_string(cap));
+        share_max = std::max(share_max, ra[b] - ra[a]); reads_max = std::max(reads_max, b - a);
+        cut.push_back(b); a = b;
+    }
+    x->last_shares = (int)cut.size() - 1;
+    const int64_t total = ra[n];
+    if (!o) {
+        x->h_k1.assign((size_t)total, 0); x->h_k2.assign((size_t)total, 0);
+        for (int32_t r = 0; r <= n; ++r) anchor_off[r] = ra[r];
+        for (int32_t r = 0; r < n; ++r) repetitive[r] = rrep[r];
+    }
+    uint64_t* d_k[4];
+    for (auto& p : d_k) p = B.get<uint64_t>((size_t)share_max);
+    const size_t sb = clh::seed_sort_temp_bytes(share_max);
+    void* d_sort = B.get<uint8_t>(sb);
+    if (!d_k[0] || !d_k[1] || !d_k[2] || !d_k[3] || !d_sort) return sd_refused(me, B);
+    clh::ChParams C;
+    memset(&C, 0, sizeof C);
+    size_t seg_bytes = 0, row_bytes = 0;
+    if (o) {
+        C.ctg_off = x->d_coff; C.ctg_len = x->d_clen; C.n_contigs = (int32_t)x->c_off.size();
+        C.k = x->k; C.lookback = o->lookback; C.max_chains = o->max_chains; C.max_attempts = o->max_attempts; C.min_score = o->min_score; C.min_anchors = o->min_anchors;
+        C.max_gap = o->max_gap; C.max_skew = o->max_skew;
+        seg_bytes = sizeof(int64_t) * clh::kChSeg * 2 * (size_t)reads_max; row_bytes = sizeof(int64_t) * clh::kChRow * (size_t)o->max_chains * 2 * (size_t)reads_max;
+        C.seg_bounds = B.get<int64_t>(2 * (size_t)reads_max + 1);
+        C.f = B.get<int32_t>((size_t)share_max); C.p = B.get<int32_t>((size_t)share_max); C.used = B.get<uint8_t>((size_t)share_max);
+        C.seg = (int64_t*)B.get<uint8_t>(seg_bytes); C.rows = (int64_t*)B.get<uint8_t>(row_bytes);
+        if (!C.seg_bounds || !C.f || !C.p || !C.used || !C.seg || !C.rows) return sd_refused(me, B);
+    }
+    const int bits_x = sd_bits((uint64_t)(x->genome->len > 0 ? x->genome->len : 1)) + clh::kSdYBits, bits_r = sd_bits(2 * (uint64_t)(n > 0 ? n : 1));
+    for (size_t s = 0; s + 1 < cut.size(); ++s) {
+        const int32_t a = cut[s], b = cut[s + 1];
+        const int64_t A = ra[b] - ra[a];
+        HIPCHK(hipEventRecord(x->ev[0], st));
+        HIPCHK(clh::launch_seed_anchor_fill(x->d_vals, x->n, R.E.vals, R.E.seq_of, d_rlen, d_lo, d_cnt, d_aoff, rm[a], rm[b], ra[a], x->k, d_k[0], d_k[1], A, st));
+        // least significant first: (x, y), then (read, minus); both sorts stable
+        HIPCHK(clh::seed_sort_pairs(d_sort, sb, d_k[1], d_k[3], d_k[0], d_k[2], A, bits_x, st));
+        HIPCHK(clh::seed_sort_pairs(d_sort, sb, d_k[2], d_k[0], d_k[3], d_k[1], A, bits_r, st));
+        HIPCHK(hipEventRecord(x->ev[1], st));
+        if (!o) {
+            if (A > 0) {
+                HIPCHK(hipMemcpyAsync(x->h_k1.data() + ra[a], d_k[0], sizeof(uint64_t) * (size_t)A, hipMemcpyDeviceToHost, st));
+                HIPCHK(hipMemcpyAsync(x->h_k2.data() + ra[a], d_k[1], sizeof(uint64_t) * (size_t)A, hipMemcpyDeviceToHost, st));
+            }
+        } else {
+            C.k1 = d_k[0]; C.k2 = d_k[1]; C.n_anchors = A; C.read0 = a; C.nseg = 2 * (b - a);
+            const size_t sg = sizeof(int64_t) * clh::kChSeg * (size_t)C.nseg, rw = sizeof(int64_t) * clh::kChRow * (size_t)o->max_chains * (size_t)C.nseg;
+            HIPCHK(hipMemsetAsync(C.seg, 0x80, sg, st));
+            HIPCHK(hipMemsetAsync(C.rows, 0x80, rw, st));
+            HIPCHK(clh::launch_seed_segments(C, st));
+            HIPCHK(clh::launch_seed_chain(C, st));
+            HIPCHK(hipEventRecord(x->ev[2], st));
+            HIPCHK(hipMemcpyAsync(seg_out + (size_t)clh::kChSeg * 2 * (size_t)a, C.seg, sg, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(rows_out + (size_t)clh::kChRow * (size_t)o->max_chains * 2 * (size_t)a, C.rows, rw, hipMemcpyDeviceToHost, st));
+        }
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipEventElapsedTime(&t, x->ev[0], x->ev[1]));
+        x->ms[2] += t;
+        if (o) { HIPCHK(hipEventElapsedTime(&t, x->ev[1], x->ev[2])); x->ms[3] += t; }
+    }
+    if (o)
+        for (int64_t s = 0; s < 2 * (int64_t)n; ++s) {
+            const int64_t* h = seg_out + clh::kChSeg * s;
+            if (h[0] == clh::kChUnwritten || h[0] < 0 || h[0] > o->max_chains || h[3] != 0)
+                return fail(CLH_E_HIP, me + "the chain kernel left segment " + std::to_string(s) + (h[0] == clh::kChUnwritten ? " unwritten" : " with status " + std::to_string(h[3])));
+            for (int64_t c = 0; c < h[0]; ++c)
+                if (rows_out[((s * o->max_chains) + c) * clh::kChRow + 9] != 0) return fail(CLH_E_HIP, me + "the chain kernel left a row of segment " + std::to_string(s) + " unwritten");
+        }
+    return 0;
+}
+
+extern "C" int clh_seed_batch(clh_seed_index* x, int32_t n, const int8_t* reads, const int64_t* read_off, int64_t workspace_bytes, int64_t* anchor_off,
+                              int32_t* repetitive)
+{
+    const std::string me = "clh_seed_batch: ";
+    if (!x || !anchor_off || (n > 0 && !repetitive)) return fail(CLH_E_ARG, me + "null argument");
+    x->h_k1.clear(); x->h_k2.clear();
+    const int rc = sd_seeds(me, x, n, reads, read_off, workspace_bytes, anchor_off, repetitive, nullptr, nullptr, nullptr);
+    if (rc) { x->h_k1.clear(); x->h_k2.clear(); }
+    return rc;
+}
+
+extern "C" int clh_seed_batch_fetch(clh_seed_index* x, int64_t cap, int32_t* read, uint8_t* minus, int64_t* xs, int32_t* ys)
+{
+    if (!x) return fail(CLH_E_ARG, "clh_seed_batch_fetch: null argument");
+    const int64_t m = (int64_t)x->h_k1.size();
+    if (cap < m) return fail(CLH_E_CAPACITY, "clh_seed_batch_fetch: cap too small");
+    if (m > 0 && (!read || !minus || !xs || !ys)) return fail(CLH_E_ARG, "clh_seed_batch_fetch: null argument");
+    for (int64_t i = 0; i < m; ++i) {
+        read[i] = (int32_t)(x->h_k1[i] >> 1); minus[i] = (uint8_t)(x->h_k1[i] & 1);
+        xs[i] = (int64_t)(x->h_k2[i] >> clh::kSdYBits); ys[i] = (int32_t)(x->h_k2[i] & (((uint64_t)1 << clh::kSdYBits) - 1));
+    }
+    return 0;
+}
+
+extern "C" int clh_seed_chain_batch(clh_seed_index* x, int32_t n, const int8_t* reads, const int64_t* read_off, const clh_chain_opts* o, int64_t* seg, int64_t* rows)
+{
+    const std::string me = "clh_seed_chain_batch: ";
+    if (!x || !o || (n > 0 && (!seg || !rows))) return fail(CLH_E_ARG, me + "null argument");
+    if (o->lookback < 1 || o->lookback > clh::kChLookbackMax) return fail(CLH_E_ARG, me + "lookback must be 1..64");
+    if (o->max_chains < 1 || o->max_chains > clh::kChMaxChains) return fail(CLH_E_ARG, me + "max_chains must be 1..64");
+    if (o->max_attempts < 1 || o->max_gap < 0 || o->max_skew < 0) return fail(CLH_E_ARG, me + "max_attempts must be at least 1, max_gap and max_skew not negative");
+    return sd_seeds(me, x, n, reads, read_off, o->workspace_bytes, nullptr, nullptr, o, seg, rows);
+}

@@ -1,0 +1,132 @@
+// seed_device.h -- K7: what the host side, the sketch, look-up and chain kernels (seed.hip), the sort plumbing (seed_sort.hip) and the
+// stand-alone host program tests/seed_host.hip share.  The definitions are those of DESIGN.md section 4 (K7): they are independent of
+// the order in which positions are visited, so that the kernels and the plain checker tests/seed_check.py agree bit for bit.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace clh {
+
+static constexpr int kSdKMin = 4, kSdKMax = 28, kSdWMin = 1, kSdWMax = 64;
+static constexpr int kSdRound = 64;                     // positions a wave decides at once: lane l takes position round * 64 + l
+static constexpr int kSdItem = 16 * kSdRound;           // positions of one work item (one wave)
+static constexpr int kSdItemsPerBlock = 4;              // work items of one workgroup (256 threads)
+static constexpr int kSdKeysCap = kSdItem + 2 * (kSdWMax - 1);      // keys an item holds in LDS: its positions and w' - 1 on either side
+static constexpr int kSdLettersCap = kSdKeysCap + kSdKMax - 1;      // letters under those keys
+static constexpr uint64_t kSdNoKey = ~(uint64_t)0;      // a position without a valid k-mer; as (key << 1 | strand) it is above every valid one
+static constexpr int kSdYBits = 24;                     // an anchor's sort word is x << 24 | y: reads of 2^24 letters and more are refused
+static constexpr int kChLookbackMax = 64, kChMaxChains = 64;
+static constexpr int64_t kChUnwritten = (int64_t)0x8080808080808080ull;    // what the chain rows are filled with before a run
+static constexpr int kChRow = 10, kChSeg = 4;           // int64 per chain row / per segment header
+
+// the 64-bit integer mix with every step masked to 2k bits: a bijection on [0, 2^2k)
+__host__ __device__ inline uint64_t sd_mix(uint64_t h, uint64_t m)
+{
+    h = (~h + (h << 21)) & m;
+    h ^= h >> 24;
+    h = (h + (h << 3) + (h << 8)) & m;
+    h ^= h >> 14;
+    h = (h + (h << 2) + (h << 4)) & m;
+    h ^= h >> 28;
+    h = (h + (h << 31)) & m;
+    return h;
+}
+
+// The rolling state of one stretch of letters: f the forward packing of the last k letters (first base most significant), r that of
+// their reverse complement, run the letters since the last code >= 4.
+struct SdRoll { uint64_t f, r; int run; };
+__host__ __device__ inline void sd_roll_init(SdRoll* s) { s->f = s->r = 0; s->run = 0; }
+// code: bits 0-2 of a resident genome byte or a read code; anything above 3 is no base
+__host__ __device__ inline void sd_roll_push(SdRoll* s, int code, int k, uint64_t m)
+{
+    const int c = code & 7;
+    if (c > 3) { s->run = 0; s->f = s->r = 0; return; }
+    s->f = ((s->f << 2) | (uint64_t)c) & m;
+    s->r = (s->r >> 2) | ((uint64_t)(3 - c) << (2 * (k - 1)));
+    s->run = s->run < k ? s->run + 1 : k;
+}
+// after the letter at position p + k - 1 was pushed: (key << 1 | strand) of position p, kSdNoKey where there is no valid k-mer
+__host__ __device__ inline uint64_t sd_roll_key(const SdRoll& s, int k, uint64_t m)
+{
+    if (s.run < k || s.f == s.r) return kSdNoKey;
+    return (sd_mix(s.f < s.r ? s.f : s.r, m) << 1) | (uint64_t)(s.f > s.r);
+}
+
+// The selection rule for one position: v[i] = (key << 1 | strand) or kSdNoKey for the positions [lo, hi) of the sequence that the caller
+// holds, v[0] being position lo; p in [lo, hi); wp = min(w, P).  The caller holds at least the wp - 1 positions on either side of p that
+// exist.  a and b are the runs left and right of p whose key is invalid or >= key[p], each at most wp - 1.
+__host__ __device__ inline bool sd_selected(const uint64_t* v, int64_t lo, int64_t hi, int64_t p, int wp)
+{
+    const uint64_t me = v[p - lo];
+    if (me == kSdNoKey) return false;
+    const uint64_t key = me >> 1;
+    int a = 0, b = 0;
+    while (a < wp - 1 && p - a - 1 >= lo && (v[p - a - 1 - lo] >> 1) >= key) ++a;
+    while (a + b < wp - 1 && p + b + 1 < hi && (v[p + b + 1 - lo] >> 1) >= key) ++b;
+    return a + b + 1 >= wp;
+}
+
+// chain transition: what anchor j adds to anchor i at distances dx, dy (both > 0): min(dx, dy, k) - beta(|dx - dy|)
+__host__ __device__ inline int64_t ch_beta(int64_t d, int k)
+{
+    if (d <= 0) return 0;
+    const int lg = 63 - __builtin_clzll((unsigned long long)d);      // floor(log2 d)
+    return ((int64_t)k * d + 99) / 100 + lg / 2;
+}
+__host__ __device__ inline int64_t ch_gain(int64_t dx, int64_t dy, int k)
+{
+    int64_t g = dx < dy ? dx : dy;
+    if (g > k) g = k;
+    return g - ch_beta(dx > dy ? dx - dy : dy - dx, k);
+}
+
+// ---- launches (seed.hip) ------------------------------------------------------------------------------------------------------
+// The sequences of one sketch: sequence s is the len[s] bytes from off[s] of `codes`; its positions [0, len - k] are cut into work items of
+// kSdItem positions; item_seq[i] names the sequence of item i and seq_item0[s] its first item (seq_item0[nseq] = items).  All device pointers.
+struct SdSketch {
+    const uint8_t* codes; int64_t codes_len;
+    const int64_t* off; const int64_t* len; int32_t nseq;
+    const int32_t* item_seq; const int64_t* seq_item0; int64_t nitems;
+    int32_t k, w;
+    int32_t global_pos;                                 // 1: a position is written genome-wide (off[s] + p), 0: inside its sequence
+};
+// count: item_count[i] = minimizers of item i.  fill: with item_off the exclusive scan of the counts, entry e gets keys[e] = key, vals[e] =
+// position << 1 | strand, and, where seq_of is given, seq_of[e] = the sequence; entries are in (sequence, position) order; cap = entries
+hipError_t launch_seed_sketch_count(const SdSketch& s, int32_t* item_count, hipStream_t stream);
+hipError_t launch_seed_sketch_fill(const SdSketch& s, const int64_t* item_off, uint64_t* keys, uint64_t* vals, int32_t* seq_of, int64_t cap, hipStream_t stream);
+// sorted keys of n entries: stats[0] += distinct keys, stats[1] += keys with more than max_occ entries (stats zeroed by the caller)
+hipError_t launch_seed_index_stats(const uint64_t* keys, int64_t n, int32_t max_occ, unsigned long long* stats, hipStream_t stream);
+// per minimizer e of the reads: lo[e] = first entry of the index with its key, cnt[e] = anchors it gives (0 where there are more than max_occ),
+// rep[e] = 1 where there are more than max_occ
+hipError_t launch_seed_lookup(const uint64_t* idx_keys, int64_t n_idx, int32_t max_occ, const uint64_t* rkeys, int64_t nmin, int64_t* lo, int32_t* cnt,
+                              uint8_t* rep, hipStream_t stream);
+// per read r (n + 1 of them, the last for the totals): read_aoff[r] = aoff[item_off[seq_item0[r]]], and for r < n repetitive[r] = the sum of rep over its minimizers
+hipError_t launch_seed_per_read(const int64_t* seq_item0, const int64_t* item_off, const int64_t* aoff, const uint8_t* rep, int32_t n, int64_t* read_moff,
+                                int64_t* read_aoff, int32_t* repetitive, hipStream_t stream);
+// anchors of the minimizers [m0, m1): anchor aoff[e] - a0 + t (t-th entry of the index from lo[e]) gets k1 = read << 1 | minus, k2 = x << kSdYBits | y; cap = anchors of the share
+hipError_t launch_seed_anchor_fill(const uint64_t* idx_vals, int64_t n_idx, const uint64_t* rvals, const int32_t* seq_of, const int64_t* read_len, const int64_t* lo,
+                                   const int32_t* cnt, const int64_t* aoff, int64_t m0, int64_t m1, int64_t a0, int32_t k, uint64_t* k1, uint64_t* k2, int64_t cap,
+                                   hipStream_t stream);
+
+struct ChParams {
+    const uint64_t* k1; const uint64_t* k2; int64_t n_anchors;       // the share's anchors in (read, minus, x, y) order
+    int32_t read0, nseg;                                             // segment s of the share is (read0 + s / 2, s & 1)
+    const int64_t* ctg_off; const int64_t* ctg_len; int32_t n_contigs;
+    int32_t k, lookback, max_chains, max_attempts, min_score, min_anchors;
+    int64_t max_gap, max_skew;
+    int64_t* seg_bounds;                                             // [nseg + 1], made by launch_seed_segments
+    int32_t* f; int32_t* p; uint8_t* used;                           // [n_anchors] each
+    int64_t* seg; int64_t* rows;                                     // [nseg][kChSeg], [nseg][max_chains][kChRow], marker-filled by the caller
+};
+hipError_t launch_seed_segments(const ChParams& c, hipStream_t stream);
+hipError_t launch_seed_chain(const ChParams& c, hipStream_t stream);
+
+// ---- plumbing (seed_sort.hip): rocPRIM's device radix sort and scan -------------------------------------------------------------
+size_t seed_sort_temp_bytes(int64_t n);
+// stable sort of (keys, vals) on key bits [0, bits): the result is in keys_out / vals_out
+hipError_t seed_sort_pairs(void* temp, size_t temp_bytes, const uint64_t* keys_in, uint64_t* keys_out, const uint64_t* vals_in, uint64_t* vals_out, int64_t n, int bits,
+                           hipStream_t stream);
+size_t seed_scan_temp_bytes(int64_t n);
+hipError_t seed_scan_counts(void* temp, size_t temp_bytes, const int32_t* counts, int64_t* out, int64_t n, hipStream_t stream);     // exclusive, 64-bit sums
+
+}  // namespace clh

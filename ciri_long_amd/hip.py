@@ -107,6 +107,11 @@ class BandOpts(C.Structure):
                 ('want_cigar', C.c_int32), ('workspace_bytes', C.c_int64), ('band', C.c_int32), ('reserved', C.c_int32)]
 
 
+class ChainOpts(C.Structure):
+    _fields_ = [('lookback', C.c_int32), ('max_chains', C.c_int32), ('max_attempts', C.c_int32), ('min_score', C.c_int32), ('min_anchors', C.c_int32),
+                ('reserved', C.c_int32), ('max_gap', C.c_int64), ('max_skew', C.c_int64), ('workspace_bytes', C.c_int64)]
+
+
 BAND_DTYPE = np.dtype([('score', '<i4'), ('ref_begin', '<i4'), ('ref_end', '<i4'), ('query_begin', '<i4'), ('query_end', '<i4'),
                        ('cigar_len', '<i4'), ('cigar_off', '<i8'), ('band_lo', '<i4'), ('band_hi', '<i4'), ('exact', '<i4'), ('reserved', '<i4')])
 EDIT_SEARCH_DTYPE = np.dtype([('distance', '<i4'), ('start', '<i4'), ('end', '<i4'), ('last_end', '<i4'), ('nlocs', '<i4')])
@@ -252,6 +257,19 @@ def lib():
             L.clh_band_plan_create_windows.restype = C.c_void_p
             L.clh_band_plan_create_windows.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                        C.POINTER(BandOpts), C.POINTER(Gap2)]
+        if hasattr(L, 'clh_seed_index_create'):          # absent from a CLH_LIB build older than the minimizer index (K7): SeedIndex raises there
+            L.clh_seed_index_create.restype = C.c_void_p
+            L.clh_seed_index_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
+            L.clh_seed_index_destroy.restype = None
+            L.clh_seed_index_destroy.argtypes = [C.c_void_p]
+            L.clh_seed_index_info.argtypes = [C.c_void_p, C.c_void_p]
+            L.clh_seed_index_timing.argtypes = [C.c_void_p, C.c_void_p]
+            L.clh_seed_index_dump.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.clh_seed_minimizers.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.clh_seed_minimizers_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.clh_seed_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+            L.clh_seed_batch_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.clh_seed_chain_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(ChainOpts), C.c_void_p, C.c_void_p]
         L.clh_band_plan_create.restype = C.c_void_p
         L.clh_band_plan_create.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BandOpts)]
         L.clh_band_plan_destroy.restype = None
@@ -1186,6 +1204,101 @@ class Genome(_Handle):
                                            ml.ctypes.data if ml is not None else None, C.byref(o), out.ctypes.data,
                                            cig.ctypes.data if want_cigar else None, cap, C.byref(used)), 'clh_ssw_windows_batch')
         return out, cig[:used.value]
+
+
+def _packed(reads):
+    """reads as libclh takes them: a (codes, offsets) pair as hip.pack gives it, or a list of str / int8 arrays, which is packed"""
+    if isinstance(reads, tuple) and len(reads) == 2 and isinstance(reads[1], np.ndarray):
+        return np.ascontiguousarray(reads[0], dtype=np.int8), np.ascontiguousarray(reads[1], dtype=np.int64)
+    return pack(reads)
+
+
+class SeedIndex(_Handle):
+    """K7: the minimizer index of a resident genome (every contig a sequence of its own), sorted by (key, position) on the device, and
+    the two steps that turn reads into loci with it: seeds() and chains().  The definitions -- minimizers with all ties selected,
+    anchors, the chain score and the extraction -- are those of include/ciri_long_hip.h; tests/seed_check.py states them in plain
+    Python and every array here equals what it gives.  Close the index before its genome."""
+    _destroy = 'clh_seed_index_destroy'
+
+    def __init__(self, genome, k=15, w=5, max_occ=64):
+        self._h = None
+        if not isinstance(genome, Genome) or not genome._h:
+            raise ValueError('SeedIndex: genome is an open hip.Genome')
+        _Handle.__init__(self, genome.ctx)
+        if not hasattr(lib(), 'clh_seed_index_create'):
+            raise ClhError('SeedIndex: this libclh.so is older than the minimizer index')
+        self.genome, self.k, self.w, self.max_occ = genome, int(k), int(w), int(max_occ)
+        self.contigs = list(genome.offset)                  # in the order of the concatenation
+        off = np.array([genome.offset[c] for c in self.contigs], dtype=np.int64)
+        ln = np.array([genome.length[c] for c in self.contigs], dtype=np.int64)
+        self.contig_off = off
+        self._h = lib().clh_seed_index_create(genome._h, self.k, self.w, len(off), off.ctypes.data, ln.ctypes.data, self.max_occ)
+        if not self._h:
+            raise ClhError('clh_seed_index_create failed: %s' % last_error())
+
+    def info(self):
+        """entries, distinct keys, keys with more than max_occ entries, device bytes, shares of the last seeds() / chains(), and the
+        sketch's geometry: positions a wave decides per round, positions of a work item (one wave), work items of a workgroup"""
+        out = (C.c_int64 * 12)()
+        _check(lib().clh_seed_index_info(self._h, out), 'clh_seed_index_info')
+        return {'entries': int(out[0]), 'distinct': int(out[1]), 'repetitive_keys': int(out[2]), 'bytes': int(out[3]), 'k': int(out[4]), 'w': int(out[5]),
+                'max_occ': int(out[6]), 'shares': int(out[7]), 'round': int(out[8]), 'item': int(out[9]), 'items_per_block': int(out[10])}
+
+    def timing(self):
+        """HIP-event milliseconds: sketch and sort of the build, the last minimizers() / seeds() on the device, the chain kernels of the last chains()"""
+        ms = (C.c_float * 4)()
+        _check(lib().clh_seed_index_timing(self._h, ms), 'clh_seed_index_timing')
+        return {'sketch': float(ms[0]), 'sort': float(ms[1]), 'seeds': float(ms[2]), 'chain': float(ms[3])}
+
+    def dump(self, first=0, count=None):
+        """entries [first, first + count) of the sorted index -> (keys uint64, genome-wide positions int64, strands uint8)"""
+        count = self.info()['entries'] - first if count is None else int(count)
+        keys, pos, strand = np.zeros(max(count, 0), dtype=np.uint64), np.zeros(max(count, 0), dtype=np.int64), np.zeros(max(count, 0), dtype=np.uint8)
+        _check(lib().clh_seed_index_dump(self._h, int(first), count, keys.ctypes.data, pos.ctypes.data, strand.ctypes.data), 'clh_seed_index_dump')
+        return keys, pos, strand
+
+    def minimizers(self, seqs):
+        """the index's own sketch on other sequences -> per sequence (positions int64, keys uint64, strands uint8), by position"""
+        data, off = _packed(seqs)
+        n = len(off) - 1
+        moff = np.zeros(n + 1, dtype=np.int64)
+        _check(lib().clh_seed_minimizers(self._h, n, data.ctypes.data, off.ctypes.data, moff.ctypes.data), 'clh_seed_minimizers')
+        m = int(moff[n])
+        pos, keys, strand = np.zeros(m, dtype=np.int64), np.zeros(m, dtype=np.uint64), np.zeros(m, dtype=np.uint8)
+        _check(lib().clh_seed_minimizers_fetch(self._h, m, pos.ctypes.data, keys.ctypes.data, strand.ctypes.data), 'clh_seed_minimizers_fetch')
+        return [(pos[moff[r]:moff[r + 1]], keys[moff[r]:moff[r + 1]], strand[moff[r]:moff[r + 1]]) for r in range(n)]
+
+    def seeds(self, reads, workspace_bytes=0):
+        """the anchors of a batch of reads, in ascending (read, minus, x, y) order -> dict of arrays: anchor_off [n + 1], repetitive [n]
+        (minimizers of the read whose key has more than max_occ entries: no anchors), read, minus, x (genome-wide), y"""
+        data, off = _packed(reads)
+        n = len(off) - 1
+        aoff, rep = np.zeros(n + 1, dtype=np.int64), np.zeros(n, dtype=np.int32)
+        _check(lib().clh_seed_batch(self._h, n, data.ctypes.data, off.ctypes.data, int(workspace_bytes), aoff.ctypes.data, rep.ctypes.data), 'clh_seed_batch')
+        m = int(aoff[n])
+        read, minus, x, y = np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.uint8), np.zeros(m, dtype=np.int64), np.zeros(m, dtype=np.int32)
+        _check(lib().clh_seed_batch_fetch(self._h, m, read.ctypes.data, minus.ctypes.data, x.ctypes.data, y.ctypes.data), 'clh_seed_batch_fetch')
+        return {'anchor_off': aoff, 'repetitive': rep, 'read': read, 'minus': minus, 'x': x, 'y': y}
+
+    def chains(self, reads, lookback=64, max_gap=5000, max_skew=500, min_score=40, min_anchors=3, max_chains=4, max_attempts=None, workspace_bytes=0):
+        """seeds, then colinear chains per (read, strand) on the device -> (chains, truncated): chains[r] the chains of read r, both
+        strands merged, ordered by (-score, minus, x_first), each a dict of minus, contig (its index), score, anchors, x_first, y_first,
+        x_end, y_end (x inside the contig, y in the read as the strand reads it, ends = start of the last anchor + k); truncated
+        [n, 2]: the segment (read, strand) used max_attempts (default 8 max_chains) attempts with a chain end of min_score still unused"""
+        data, off = _packed(reads)
+        n = len(off) - 1
+        o = ChainOpts(int(lookback), int(max_chains), int(8 * max_chains if max_attempts is None else max_attempts), int(min_score), int(min_anchors), 0,
+                      int(max_gap), int(max_skew), int(workspace_bytes))
+        seg = np.zeros((2 * n, 4), dtype=np.int64)
+        rows = np.zeros((2 * n, max(int(max_chains), 1), 10), dtype=np.int64)
+        _check(lib().clh_seed_chain_batch(self._h, n, data.ctypes.data, off.ctypes.data, C.byref(o), seg.ctypes.data, rows.ctypes.data), 'clh_seed_chain_batch')
+        out = []
+        for r in range(n):
+            got = [rows[s, c] for s in (2 * r, 2 * r + 1) for c in range(int(seg[s, 0]))]
+            got = [{'minus': int(v[1]), 'contig': int(v[2]), 'score': int(v[3]), 'anchors': int(v[4]), 'x_first': int(v[5]), 'y_first': int(v[6]),
+                    'x_end': int(v[7]), 'y_end': int(v[8])} for v in got]
+            out.append(sorted(got, key=lambda c: (-c['score'], c['minus'], c['x_first'])))
+        return out, seg[:, 1].reshape(n, 2).astype(bool)
 
 
 class Plan(_Handle):

@@ -590,6 +590,75 @@ clh_band_plan* clh_band_plan_create_windows(clh_genome* genome, int32_t n, const
 int clh_ends_plan_gather_timing(clh_ends_plan* plan, float* ms, int64_t* letters);
 int clh_band_plan_gather_timing(clh_band_plan* plan, float* ms, int64_t* letters);
 
+/* ---- K7: minimizer index of the resident genome, seeds and chains (csrc/seed.hip) ---------------------------
+ * The producer of the loci the plans above take.  Nothing of it exists in the reference, whose mapper is an external package; the
+ * definitions are this project's own, independent of the order positions are visited in, and stated in plain Python by
+ * tests/seed_check.py, with which every array below is compared for equality.
+ *
+ * Minimizers, 4 <= k <= 28, 1 <= w <= 64.  A sequence is base codes (bits 0-2 of a resident byte, or a read code 0..4; 4 is no base).
+ * Position p of a sequence of n letters (P = n - k + 1 positions) has a valid k-mer if its k codes are below 4 and its forward packing f
+ * (2 bits per base, first base most significant) differs from the packing r of its reverse complement; strand = (f > r), key =
+ * mix(min(f, r)), mix the 64-bit integer mix of seed_device.h (sd_mix) with every step masked to 2k bits.  With w' = min(w, P), p is a
+ * minimizer iff it is valid and some window of w' consecutive positions inside [0, P) holds p and no valid key below key[p]: all ties
+ * are selected.  A contig is a sequence of its own; no k-mer and no window spans two.
+ *
+ * clh_seed_index_create sketches the contigs [contig_off[c], contig_off[c] + contig_len[c]) of the genome (ascending, not overlapping,
+ * inside it) on the device and sorts the entries by (key, genome-wide position).  Buffers are sized from the count pass.  CLH_E_ARG:
+ * k, w or max_occ (>= 1) out of range, contigs out of order or outside the genome; CLH_E_CAPACITY with the bytes asked for: the
+ * device refused an allocation.  The index lives on the genome's context and reads the genome in place: destroy it before the genome.
+ *
+ * clh_seed_index_info, out[12]: entries, distinct keys, keys with more than max_occ entries, device bytes held, k, w, max_occ, shares
+ * of the last seeds / chains call, then the sketch's geometry: positions a wave decides per round, positions of a work item, work items
+ * of a workgroup, and 0.  clh_seed_index_timing, ms[4] (HIP events): sketch and sort of the build, the last clh_seed_minimizers /
+ * clh_seed_batch (sketch, look-up, sorts; no transfers to the host), the chain kernels of the last clh_seed_chain_batch.
+ * clh_seed_index_dump: entries [first, first + count) of the sorted arrays.
+ *
+ * clh_seed_minimizers: the same sketch on n sequences of codes 0..4; min_off[n + 1]; then clh_seed_minimizers_fetch(cap >= min_off[n])
+ * gives position (inside the sequence), key and strand of each, in (sequence, position) order.
+ *
+ * clh_seed_batch: per read its minimizers, each looked up in the sorted keys; a key with more than max_occ entries gives no anchors and
+ * counts in repetitive[read]; every other entry gives the anchor (read, minus, x, y): minus = strand of the read's k-mer XOR that of the
+ * genome's, x the genome-wide start of the genome k-mer, y = q (the k-mer's start in the read) on the plus strand and L - k - q on the
+ * minus strand (L the read's length): the start in the reverse-complemented read, so that on either strand a true alignment is a run
+ * ascending in x and y.  anchor_off[n + 1]; clh_seed_batch_fetch(cap >= anchor_off[n]) gives the anchors in ascending (read, minus, x,
+ * y) order.  A batch whose anchors need more than workspace_bytes (<= 0: 1 GiB; 64 bytes an anchor) is cut into shares of whole reads,
+ * with the same arrays; one read above it is CLH_E_CAPACITY.  CLH_E_ARG, naming the first read: a code outside 0..4, a read of 2^24
+ * letters or more.
+ *
+ * The two fetches read what their call parked on the index in host memory (16 B per minimizer or anchor), held until the next call of
+ * the same kind or the index's destruction: a fetch follows its call directly, and one index serves one caller at a time -- two threads
+ * sharing an index would overwrite each other's results; give each its own index or serialise call and fetch as a pair.
+ *
+ * clh_seed_chain_batch: the seeds step, then per segment (read, minus), anchors i = 0.. in the order above,
+ *   f(i) = max(k, max_j f(j) + min(dx, dy, k) - beta(|dx - dy|)) over j in [i - lookback, i) on the same contig with dx = x_i - x_j > 0,
+ *   dy = y_i - y_j > 0, dx, dy <= max_gap, |dx - dy| <= max_skew; beta(0) = 0, beta(d) = (k d + 99) / 100 + floor(log2 d) / 2;
+ *   p(i) the nearest j attaining a value strictly above k, else -1.
+ * Extraction, at most max_attempts times and until max_chains are out: e = the unused anchor of greatest f (ties: smallest index); stop
+ * if f(e) < min_score; walk e, p(e), ... while unused, marking; score = f(e) - f(the used anchor the walk stopped on, if any); the chain
+ * is emitted if score >= min_score and it holds >= min_anchors anchors.  A segment that has used max_attempts with such an e still
+ * there is `truncated`.  seg[2 n][4]: chains, truncated, anchors, 0; rows[2 n][max_chains][10], the first `chains` of a segment written:
+ * read, minus, contig, score, anchors, x_first, y_first, x_last + k, y_last + k, 0 (x relative to the contig; segment 2 r + minus).
+ * 1 <= lookback <= 64, 1 <= max_chains <= 64, max_attempts >= 1, max_gap, max_skew >= 0, else CLH_E_ARG.  A row or header the kernel
+ * left unwritten is CLH_E_HIP from this call, never returned. */
+typedef struct clh_seed_index clh_seed_index;
+typedef struct {
+    int32_t lookback, max_chains, max_attempts, min_score, min_anchors, reserved;
+    int64_t max_gap, max_skew, workspace_bytes;
+} clh_chain_opts;
+clh_seed_index* clh_seed_index_create(clh_genome* genome, int32_t k, int32_t w, int32_t n_contigs, const int64_t* contig_off, const int64_t* contig_len,
+                                      int32_t max_occ);
+void clh_seed_index_destroy(clh_seed_index* index);
+int clh_seed_index_info(clh_seed_index* index, int64_t* out);
+int clh_seed_index_timing(clh_seed_index* index, float* ms);
+int clh_seed_index_dump(clh_seed_index* index, int64_t first, int64_t count, uint64_t* keys, int64_t* pos, uint8_t* strand);
+int clh_seed_minimizers(clh_seed_index* index, int32_t n, const int8_t* seqs, const int64_t* seq_off, int64_t* min_off);
+int clh_seed_minimizers_fetch(clh_seed_index* index, int64_t cap, int64_t* pos, uint64_t* keys, uint8_t* strand);
+int clh_seed_batch(clh_seed_index* index, int32_t n, const int8_t* reads, const int64_t* read_off, int64_t workspace_bytes, int64_t* anchor_off,
+                   int32_t* repetitive);
+int clh_seed_batch_fetch(clh_seed_index* index, int64_t cap, int32_t* read, uint8_t* minus, int64_t* x, int32_t* y);
+int clh_seed_chain_batch(clh_seed_index* index, int32_t n, const int8_t* reads, const int64_t* read_off, const clh_chain_opts* opts, int64_t* seg,
+                         int64_t* rows);
+
 
 /* ASCII -> codes exactly as ssw_wrap.py:234-252 (A/a C/c G/g T/t N/n, anything else 4), on the host. */
 void clh_encode_dna(const char* seq, int64_t len, int8_t* out);
