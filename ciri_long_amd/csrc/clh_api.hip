@@ -789,6 +789,8 @@ extern "C" int clh_splice_signal_batch(clh_genome* g, int32_t n, const int64_t* 
     for (int i = 0; i < n; ++i) {
         if (ctg_off[i] < 0 || ctg_len[i] < 0 || ctg_off[i] + ctg_len[i] > g->len) return fail(CLH_E_ARG, "clh_splice_signal_batch: contig outside the genome");
         if (clip_base[i] < 0 || clip_base[i] > 4096) return fail(CLH_E_ARG, "clh_splice_signal_batch: clip_base out of range");
+        if ((int64_t)clip_base[i] + search_extra > clh::kSpliceMaxSearch)     // the ranking key's fields would overflow (clh_device.h)
+            return fail(CLH_E_ARG, "clh_splice_signal_batch: clip_base + search_extra above 16284");
         clh::SpliceTask& t = tasks[(size_t)i];
         t.ctg_off = ctg_off[i]; t.ctg_len = ctg_len[i]; t.start = start[i]; t.end = end[i]; t.clip_base = clip_base[i]; t.host_mask = host_mask[i];
     }

@@ -221,6 +221,13 @@ struct SpliceSites {
     const int64_t* pos[4];
     int64_t n[4];
 };
+// site_key (splice_scan.hip) packs clip_alt, alt, w and tot into fields of kSpliceKeyBits bits.  With sl = clip_base + search_extra
+// and both free slides below kSpliceSlideCap: alt = |i - j| <= us_len + ds_len <= 2 sl + 2 (kSpliceSlideCap - 1), clip_alt <=
+// max(alt, clip_base) <= that (clip_base <= sl), tot <= 2 max(sl, kSpliceSlideCap - 1) <= that, w <= 3.  So no field overflows while
+// 2 sl + 2 (kSpliceSlideCap - 1) < 2^kSpliceKeyBits: sl <= kSpliceMaxSearch = 16284.
+static constexpr int kSpliceKeyBits = 15;
+static constexpr int kSpliceSlideCap = 100;
+static constexpr int kSpliceMaxSearch = ((1 << kSpliceKeyBits) - 1 - 2 * (kSpliceSlideCap - 1)) / 2;
 hipError_t launch_splice_scan(const uint8_t* codes, const uint8_t* ascii, const SpliceTask* tasks, int n, int search_extra, int shift_threshold, int canonical,
                               const SpliceSites& sites, int32_t* out, hipStream_t stream);
 hipError_t launch_genome_count_n(const uint8_t* codes, const unsigned int* pre_n, const long long* off, const long long* len, long long* out, int n, hipStream_t stream);

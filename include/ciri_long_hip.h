@@ -257,7 +257,10 @@ int clh_genome_set_splice_sites(clh_genome* genome, const int64_t* pos, const in
  * index into GT-AG, GC-AG, AT-AC, GT-AC, AT-AG).
  * is_canonical: bit 0 = search GT-AG only; bit 1 = the two search windows are cut the way a minimap2 index serves sequences
  * (mappy.Aligner.seq, env.GENOME of the reference's main pass, find_bsj.py:340-341: no sequence for a start outside the contig,
- * end clipped) instead of the way Python slices a string (align.Fasta.seq, the short-read pass, find_bsj.py:455,462). */
+ * end clipped) instead of the way Python slices a string (align.Fasta.seq, the short-read pass, find_bsj.py:455,462).
+ * CLH_E_ARG for clip_base outside [0, 4096], a negative search_extra or shift_threshold, and clip_base + search_extra above
+ * 16284 (the ranking key keeps 15 bits per component).  With annotated sites set, a candidate away from the contig ends whose
+ * 2 (clip_base + search_extra) exceeds 64 gets status 1 as well. */
 int clh_splice_signal_batch(clh_genome* genome, int32_t n, const int64_t* ctg_off, const int64_t* ctg_len, const int64_t* start,
                             const int64_t* end, const int32_t* clip_base, const int32_t* host_mask, int32_t search_extra,
                             int32_t shift_threshold, int32_t is_canonical, int32_t* out);

@@ -73,11 +73,12 @@ static int key_less(const int* a, const int* b)
     return 0;
 }
 
-/* align.py:705-733; returns the index of the winner (the list is never empty here) */
-static int sort_ss(const list_t* l, int us, int ds, int cb)
+/* align.py:705-733; returns the index of the winner (the list is never empty here); rec (optional): the winner's tier, its four
+ * key components and how many sites of that tier carry the same four */
+static int sort_ss(const list_t* l, int us, int ds, int cb, int32_t* rec)
 {
     for (int tier = 0; tier < 4; ++tier) {
-        int best = -1, bk[4] = {0, 0, 0, 0};
+        int best = -1, bk[4] = {0, 0, 0, 0}, same = 0;
         for (int k = 0; k < l->n; ++k) {
             const site_t* s = &l->v[k];
             /* a site belongs to the first tier that accepts it */
@@ -90,25 +91,33 @@ static int sort_ss(const list_t* l, int us, int ds, int cb)
             if (tier == 0) { key[0] = s->clip_alt; key[1] = s->alt; key[2] = s->w; key[3] = s->tot; }
             else if (tier == 1) { key[0] = s->alt; key[1] = s->w; key[2] = s->clip_alt; key[3] = s->tot; }
             else { key[0] = s->w; key[1] = s->alt; key[2] = s->clip_alt; key[3] = s->tot; }
-            if (best < 0 || key_less(key, bk)) { best = k; memcpy(bk, key, sizeof(bk)); }     /* stable: first seen wins ties */
+            if (best < 0 || key_less(key, bk)) { best = k; memcpy(bk, key, sizeof(bk)); same = 1; }     /* stable: first seen wins ties */
+            else if (!key_less(bk, key)) ++same;
         }
-        if (best >= 0) return best;
+        if (best >= 0) {
+            if (rec) { rec[0] = tier; for (int k = 0; k < 4; ++k) rec[1 + k] = bk[k]; rec[5] = same; }
+            return best;
+        }
     }
     return -1;
 }
 
 /* the same range as a minimap2 index serves it (mappy.Aligner.seq -> mappy_fetch_seq: env.GENOME of the reference's main pass,
  * find_bsj.py:340-341): no sequence (n = -1, Python's None) for a start outside [0, L) or an empty range; the end is clipped */
-static void idxslice(int64_t L, int64_t a, int64_t b, int64_t* lo, int64_t* n)
+static void idxslice(int64_t L, int64_t a, int64_t b, int64_t* lo, int64_t* n, int* wrapped, int* clipped)
 {
+    *wrapped = 0; *clipped = 0;
     if (a < 0 || a >= L || a >= b) { *lo = 0; *n = -1; return; }
+    *clipped = b > L;
     *lo = a; *n = (b > L ? L : b) - a;
 }
 
-/* Python's s[a:b] on a string of length L: first index and length */
-static void pyslice(int64_t L, int64_t a, int64_t b, int64_t* lo, int64_t* n)
+/* Python's s[a:b] on a string of length L: first index and length; wrapped: 1 = a negative start counted from the end, 2 = and
+ * clamped to 0 there; clipped: the end lay beyond L */
+static void pyslice(int64_t L, int64_t a, int64_t b, int64_t* lo, int64_t* n, int* wrapped, int* clipped)
 {
-    if (a < 0) { a += L; if (a < 0) a = 0; } else if (a > L) a = L;
+    *wrapped = 0; *clipped = b > L;
+    if (a < 0) { a += L; *wrapped = 1; if (a < 0) { a = 0; *wrapped = 2; } } else if (a > L) a = L;
     if (b < 0) { b += L; if (b < 0) b = 0; } else if (b > L) b = L;
     *lo = a; *n = b > a ? b - a : 0;
 }
@@ -119,12 +128,21 @@ static void pyslice(int64_t L, int64_t a, int64_t b, int64_t* lo, int64_t* n)
  * out[8] = status (0 done, 1 = invalid coordinates),
  * us_free, ds_free, found (0 none, 1 de novo, 2 annotated pair), strand (0 '+', 1 '-'), us_shift, ds_shift, motif.
  * is_canonical: bit 0 = GT-AG only; bit 1 = the search windows of find_denovo_signal are cut as a minimap2 index serves sequences
- * (g must then be the text as the index holds it: upper case, anything but ACGT an N) instead of as Python slices a string. */
-int clo_splice_signal(const char* g, int64_t L, int64_t start, int64_t end, int32_t clip_base, int32_t host_mask,
-                      int32_t search_extra, int32_t shift_threshold, int32_t is_canonical,
-                      const int64_t* site_pos, const int64_t* site_cnt, int32_t* out)
+ * (g must then be the text as the index holds it: upper case, anything but ACGT an N) instead of as Python slices a string.
+ *
+ * clo_splice_trace is the same run with a record (tr, optional) of what it met -- int32, CLO_SPLICE_TRACE_HEAD + 4 * (4 * sl + 4) long:
+ *   0 edge | 1-4 upstream slice: first index, length (-1 = no sequence), wrapped, clipped | 5-8 downstream slice alike |
+ *   9 short_seq | 10 need = ds_len - us_len + 2 | 11 searched: bit 2 * round + strand | 12 sites materialised |
+ *   13 winning tier (-1 = none) | 14-17 the winner's four key components in its tier's order | 18 sites of that tier with the same four |
+ *   19 annotation consulted | 20 us_len | 21 ds_len | 24-27 lengths of the annotated shift lists: '+' upstream, '+' downstream,
+ *   '-' upstream, '-' downstream | from CLO_SPLICE_TRACE_HEAD on: those four lists, each starts then ends */
+#define CLO_SPLICE_TRACE_HEAD 32
+int clo_splice_trace(const char* g, int64_t L, int64_t start, int64_t end, int32_t clip_base, int32_t host_mask,
+                     int32_t search_extra, int32_t shift_threshold, int32_t is_canonical,
+                     const int64_t* site_pos, const int64_t* site_cnt, int32_t* out, int32_t* tr)
 {
     memset(out, 0, sizeof(int32_t) * 8);
+    if (tr) { memset(tr, 0, sizeof(int32_t) * CLO_SPLICE_TRACE_HEAD); tr[13] = -1; }
     const int index_slices = (is_canonical & 2) != 0;
     is_canonical &= 1;
     if (start < 0 || start >= end || end > L) { out[0] = 1; return 0; }
@@ -149,6 +167,7 @@ int clo_splice_signal(const char* g, int64_t L, int64_t start, int64_t end, int3
     const int64_t* run[4]; int64_t cnt[4] = {0, 0, 0, 0};
     { int64_t at = 0; for (int k = 0; k < 4; ++k) { run[k] = site_pos ? site_pos + at : NULL; cnt[k] = site_cnt ? site_cnt[k] : 0; at += cnt[k]; } }
     const int have_anno = !edge && cnt[0] + cnt[1] + cnt[2] + cnt[3] > 0;
+    if (tr) { tr[0] = edge; tr[19] = have_anno; tr[20] = sl + us_free; tr[21] = sl + ds_free; }
     int* us_anno[2]; int* ds_anno[2]; int n_us[2] = {0, 0}, n_ds[2] = {0, 0};
     for (int s = 0; s < 2; ++s) { us_anno[s] = (int*)malloc(sizeof(int) * (size_t)(4 * sl + 4)); ds_anno[s] = (int*)malloc(sizeof(int) * (size_t)(4 * sl + 4)); }
     list_t found = {NULL, 0, 0};
@@ -172,20 +191,33 @@ int clo_splice_signal(const char* g, int64_t L, int64_t start, int64_t end, int3
                 }
         }
         if (found.n) rc_found = 2;
+        if (tr) {
+            int at = CLO_SPLICE_TRACE_HEAD;
+            for (int s = 0; s < 2; ++s) {
+                tr[24 + 2 * s] = n_us[s]; tr[25 + 2 * s] = n_ds[s];
+                for (int a = 0; a < n_us[s]; ++a) tr[at++] = us_anno[s][a];
+                for (int b = 0; b < n_ds[s]; ++b) tr[at++] = ds_anno[s][b];
+            }
+        }
     }
 
     /* ---- de-novo search (align.py:571-695) ---- */
     if (!rc_found) {
         const int us_len = sl + us_free, ds_len = sl + ds_free;
         int64_t ua, nu, da, nd;
-        if (index_slices) { idxslice(L, start - us_len - 2, start + ds_len, &ua, &nu); idxslice(L, end - us_len, end + ds_len + 2, &da, &nd); }
+        int wu, cu, wd, cd;
+        if (index_slices) { idxslice(L, start - us_len - 2, start + ds_len, &ua, &nu, &wu, &cu); idxslice(L, end - us_len, end + ds_len + 2, &da, &nd, &wd, &cd); }
         else {
-            pyslice(L, start - us_len - 2, start + ds_len, &ua, &nu);   /* genome[start - us_len - 2 : start + ds_len] */
-            pyslice(L, end - us_len, end + ds_len + 2, &da, &nd);       /* genome[end - us_len : end + ds_len + 2]     */
+            pyslice(L, start - us_len - 2, start + ds_len, &ua, &nu, &wu, &cu);   /* genome[start - us_len - 2 : start + ds_len] */
+            pyslice(L, end - us_len, end + ds_len + 2, &da, &nd, &wd, &cd);       /* genome[end - us_len : end + ds_len + 2]     */
         }
         const char* us_seq = g + ua;
         const char* ds_seq = g + da;
         const int short_seq = nu < 0 || nd < 0 || nu < ds_len - us_len + 2 || nd < ds_len - us_len + 2;      /* align.py:580-583: None or too short: no search */
+        if (tr) {
+            tr[1] = (int32_t)ua; tr[2] = (int32_t)nu; tr[3] = wu; tr[4] = cu; tr[5] = (int32_t)da; tr[6] = (int32_t)nd; tr[7] = wd; tr[8] = cd;
+            tr[9] = short_seq; tr[10] = ds_len - us_len + 2;
+        }
         const int OFF = us_len + sl + 2;                                /* shift -> index of the flag arrays */
         const int nflag = OFF + ds_len + sl + 4;
         char* fu = (char*)malloc((size_t)nflag); char* fd = (char*)malloc((size_t)nflag);
@@ -196,6 +228,7 @@ int clo_splice_signal(const char* g, int64_t L, int64_t start, int64_t end, int3
             else { if (!host) break; strands = 3 & ~host; }
             for (int s = 0; s < 2; ++s) {
                 if (!((strands >> s) & 1)) continue;
+                if (tr) tr[11] |= 1 << (2 * round + s);
                 for (int m = 0; m < (is_canonical ? 1 : 5); ++m) {
                     char us_motif[2], ds_motif[2];
                     if (s == 0) { memcpy(ds_motif, DONOR[m], 2); memcpy(us_motif, ACCEPTOR[m], 2); }
@@ -224,10 +257,18 @@ int clo_splice_signal(const char* g, int64_t L, int64_t start, int64_t end, int3
     }
 
     if (rc_found) {
-        const site_t* s = &found.v[sort_ss(&found, us_free, ds_free, cb)];
+        if (tr) tr[12] = found.n;
+        const site_t* s = &found.v[sort_ss(&found, us_free, ds_free, cb, tr ? tr + 13 : NULL)];
         out[3] = rc_found; out[4] = s->strand; out[5] = s->i; out[6] = s->j; out[7] = s->motif;
     }
     for (int s = 0; s < 2; ++s) { free(us_anno[s]); free(ds_anno[s]); }
     free(found.v);
     return 0;
+}
+
+int clo_splice_signal(const char* g, int64_t L, int64_t start, int64_t end, int32_t clip_base, int32_t host_mask,
+                      int32_t search_extra, int32_t shift_threshold, int32_t is_canonical,
+                      const int64_t* site_pos, const int64_t* site_cnt, int32_t* out)
+{
+    return clo_splice_trace(g, L, start, end, clip_base, host_mask, search_extra, shift_threshold, is_canonical, site_pos, site_cnt, out, NULL);
 }

@@ -326,21 +326,60 @@ def _rc_upper(s):
     return ''.join(t.get(c, c) for c in reversed(s))
 
 
-def oracle_splice_signal(contig, start, end, clip_base, host, is_canonical=True, site_runs=None, index_slices=False):
+def _splice_call(contig, start, end, clip_base, host, is_canonical, site_runs, index_slices, search_extra, shift_threshold, trace):
+    L = oracle()
+    sig = [C.c_char_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.clo_splice_signal.argtypes = sig
+    L.clo_splice_trace.argtypes = sig + [C.c_void_p]
+    raw = contig if isinstance(contig, bytes) else contig.encode('latin-1')
+    hm = host if isinstance(host, int) else (1 if host and '+' in host else 0) | (2 if host and '-' in host else 0)
+    out = np.zeros(8, dtype=np.int32)
+    pos, cnt = site_runs if site_runs is not None else (np.zeros(1, dtype=np.int64), np.zeros(4, dtype=np.int64))
+    pos = np.ascontiguousarray(pos, dtype=np.int64); cnt = np.ascontiguousarray(cnt, dtype=np.int64)
+    args = (raw, len(raw), start, end, clip_base, hm, search_extra, shift_threshold, (1 if is_canonical else 0) | (2 if index_slices else 0),
+            pos.ctypes.data, cnt.ctypes.data, out.ctypes.data)
+    if not trace:
+        L.clo_splice_signal(*args)
+        return raw, out, None
+    tr = np.zeros(32 + 4 * (4 * (clip_base + search_extra) + 4), dtype=np.int32)
+    L.clo_splice_trace(*(args + (tr.ctypes.data,)))
+    return raw, out, tr
+
+
+def oracle_splice_row(contig, start, end, clip_base, host_mask, is_canonical=True, site_runs=None, index_slices=False, search_extra=10,
+                      shift_threshold=3):
+    """clo_splice_signal's eight columns as K6 writes them: status, us_free, ds_free, found, strand, us_shift, ds_shift, motif"""
+    return [int(x) for x in _splice_call(contig, start, end, clip_base, host_mask, is_canonical, site_runs, index_slices, search_extra,
+                                         shift_threshold, False)[1]]
+
+
+def oracle_splice_trace(contig, start, end, clip_base, host_mask, is_canonical=True, site_runs=None, index_slices=False, search_extra=10,
+                        shift_threshold=3):
+    """clo_splice_trace: (row, record) -- the eight columns and a dict of what the run met: 'edge', 'us' / 'ds' (first index, length,
+    wrapped, clipped; length -1 = no sequence; wrapped 1 = counted from the end, 2 = and clamped to 0), 'short_seq', 'need',
+    'searched' (set of (round, strand)), 'sites', 'tier' (-1 = no winner), 'key' (the winner's four components in its tier's order),
+    'same_key' (sites of the tier with that key), 'anno' (annotation consulted), 'us_len', 'ds_len' and 'shifts' =
+    {strand: (upstream list, downstream list)}, each list starts then ends."""
+    _raw, out, tr = _splice_call(contig, start, end, clip_base, host_mask, is_canonical, site_runs, index_slices, search_extra,
+                                 shift_threshold, True)
+    t = [int(x) for x in tr]
+    at, shifts = 32, {}
+    for s in range(2):
+        nu, nd = t[24 + 2 * s], t[25 + 2 * s]
+        shifts[s] = (t[at:at + nu], t[at + nu:at + nu + nd]); at += nu + nd
+    return [int(x) for x in out], {
+        'edge': t[0], 'us': tuple(t[1:5]), 'ds': tuple(t[5:9]), 'short_seq': t[9], 'need': t[10],
+        'searched': {(r, s) for r in range(2) for s in range(2) if (t[11] >> (2 * r + s)) & 1}, 'sites': t[12], 'tier': t[13],
+        'key': tuple(t[14:18]), 'same_key': t[18], 'anno': t[19], 'us_len': t[20], 'ds_len': t[21], 'shifts': shifts}
+
+
+def oracle_splice_signal(contig, start, end, clip_base, host, is_canonical=True, site_runs=None, index_slices=False, search_extra=10,
+                         shift_threshold=3):
     """The splice-signal step for one candidate on the characters of its contig.  host: iterable of '+'/'-' or None;
     site_runs: (positions int64, counts int64[4]) of this contig's annotated sites (1-based, four ascending runs) or None.
     Returns (ss_site | None, us_free, ds_free) like find_annotated_signal + find_denovo_signal, or 'edge' where the
     neighbourhood leaves the contig."""
-    L = oracle()
-    L.clo_splice_signal.argtypes = [C.c_char_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                    C.c_void_p, C.c_void_p, C.c_void_p]
-    raw = contig if isinstance(contig, bytes) else contig.encode('latin-1')
-    hm = (1 if host and '+' in host else 0) | (2 if host and '-' in host else 0)
-    out = np.zeros(8, dtype=np.int32)
-    pos, cnt = site_runs if site_runs is not None else (np.zeros(1, dtype=np.int64), np.zeros(4, dtype=np.int64))
-    pos = np.ascontiguousarray(pos, dtype=np.int64); cnt = np.ascontiguousarray(cnt, dtype=np.int64)
-    L.clo_splice_signal(raw, len(raw), start, end, clip_base, hm, 10, 3, (1 if is_canonical else 0) | (2 if index_slices else 0), pos.ctypes.data,
-                        cnt.ctypes.data, out.ctypes.data)
+    raw, out, _tr = _splice_call(contig, start, end, clip_base, host, is_canonical, site_runs, index_slices, search_extra, shift_threshold, False)
     status, us_free, ds_free, found, strand, i, j, m = (int(x) for x in out)
     if status:
         return 'edge'
