@@ -3450,8 +3450,8 @@ struct clh_seed_index : clh_owned {
     int64_t *d_coff = nullptr, *d_clen = nullptr;
     uint64_t *d_keys = nullptr, *d_vals = nullptr;
     int64_t n = 0, distinct = 0, over = 0, bytes = 0;
-    float ms[4] = {0, 0, 0, 0};
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    float ms[5] = {0, 0, 0, 0, 0};
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     std::vector<uint64_t> h_mkeys, h_mvals, h_k1, h_k2;          // what the last minimizers / seeds call left for its fetch
 };
 
@@ -3568,7 +3568,7 @@ extern "C" int clh_seed_index_info(clh_seed_index* x, int64_t* out)
 extern "C" int clh_seed_index_timing(clh_seed_index* x, float* ms)
 {
     if (!x || !ms) return fail(CLH_E_ARG, "clh_seed_index_timing: null argument");
-    for (int i = 0; i < 4; ++i) ms[i] = x->ms[i];
+    for (int i = 0; i < 5; ++i) ms[i] = x->ms[i];
     return 0;
 }
 
@@ -3648,9 +3648,40 @@ extern "C" int clh_seed_minimizers_fetch(clh_seed_index* x, int64_t cap, int64_t
     return 0;
 }
 
-// seeds, and chains where o is given: the anchors of a share stay on the device between the two
+static clh::LkParams lk_params(const clh_link_opts* l)
+{
+    return clh::LkParams{l->max_query_gap, l->max_overlap, l->max_skew, l->max_intron, l->max_circle, l->intron_cost, l->backsplice_cost};
+}
+static int lk_opts_check(const std::string& me, const clh_link_opts* l)
+{
+    if (l->max_query_gap < 0 || l->max_overlap < 0 || l->max_skew < 0 || l->max_intron < 0 || l->max_circle < 0 || l->intron_cost < 0 || l->backsplice_cost < 0)
+        return fail(CLH_E_ARG, me + "no link parameter may be negative");
+    if (l->max_skew > l->max_intron) return fail(CLH_E_ARG, me + "max_skew must not be above max_intron");
+    if (l->intron_cost >= clh::kLkLimit || l->backsplice_cost >= clh::kLkLimit) return fail(CLH_E_ARG, me + "intron_cost and backsplice_cost must be below 2^40");
+    return 0;
+}
+// what the link kernel left for segments [s0, s0 + nseg), whose chain counts are in seg: every header and every row of a chain written
+static int lk_validate(const std::string& me, int64_t s0, int64_t nseg, int32_t max_chains, const int64_t* seg, const int64_t* lseg, const int64_t* lrows)
+{
+    for (int64_t s = 0; s < nseg; ++s) {
+        const int64_t* h = lseg + clh::kLkSeg * s;
+        const int64_t nc = seg[clh::kChSeg * s];
+        if (h[0] == clh::kChUnwritten || h[0] != nc || h[1] < 0 || h[1] > nc || (nc > 0 && h[1] == 0) || h[3] != 0)
+            return fail(CLH_E_HIP, me + "the link kernel left segment " + std::to_string(s0 + s) +
+                                       (h[0] == clh::kChUnwritten ? " unwritten" : " with " + std::to_string(h[0]) + " chains of " + std::to_string(nc) + ", status " + std::to_string(h[3])));
+        for (int64_t c = 0; c < nc; ++c) {
+            const int64_t* r = lrows + ((s * max_chains) + c) * clh::kLkRow;
+            if (r[7] != 0 || r[0] < 0 || r[0] >= nc || r[2] < -1 || r[2] >= nc || r[4] < 0 || r[4] >= h[1] || r[5] < 0 || r[5] >= nc)
+                return fail(CLH_E_HIP, me + "the link kernel left a row of segment " + std::to_string(s0 + s) + (r[7] != 0 ? " unwritten" : " out of range"));
+        }
+    }
+    return 0;
+}
+
+// seeds, and chains where o is given, and their links where lo is: the anchors and the chain rows of a share stay on the device between the steps
 static int sd_seeds(const std::string& me, clh_seed_index* x, int32_t n, const int8_t* reads, const int64_t* read_off, int64_t workspace_bytes, int64_t* anchor_off,
-                    int32_t* repetitive, const clh_chain_opts* o, int64_t* seg_out, int64_t* rows_out)
+                    int32_t* repetitive, const clh_chain_opts* o, int64_t* seg_out, int64_t* rows_out, const clh_link_opts* lo = nullptr, int64_t* lseg_out = nullptr,
+                    int64_t* lrows_out = nullptr)
 {
     clh_ctx* ctx = x->ctx;
     hipStream_t st = ctx->stream;
@@ -3685,6 +3716,7 @@ static int sd_seeds(const std::string& me, clh_seed_index* x, int32_t n, const i
     HIPCHK(hipEventElapsedTime(&t, x->ev[0], x->ev[1]));
     x->ms[2] = t;
     if (o) x->ms[3] = 0;
+    if (lo) x->ms[4] = 0;
     // shares of whole reads, 64 bytes an anchor: four sort words, the sort's own space, f, p and the used mark
     const int64_t ws = workspace_bytes > 0 ? workspace_bytes : (int64_t)1 << 30, cap = ws / 64;
     std::vector<int32_t> cut(1, 0);
@@ -3724,6 +3756,13 @@ static int sd_seeds(const std::string& me, clh_seed_index* x, int32_t n, const i
         C.seg = (int64_t*)B.get<uint8_t>(seg_bytes); C.rows = (int64_t*)B.get<uint8_t>(row_bytes);
         if (!C.seg_bounds || !C.f || !C.p || !C.used || !C.seg || !C.rows) return sd_refused(me, B);
     }
+    clh::LkLaunch K;
+    memset(&K, 0, sizeof K);
+    if (lo) {
+        K.seg = C.seg; K.rows = C.rows; K.max_chains = o->max_chains; K.k = x->k; K.p = lk_params(lo);
+        K.lseg = B.get<int64_t>((size_t)clh::kLkSeg * 2 * (size_t)reads_max); K.lrows = B.get<int64_t>((size_t)clh::kLkRow * (size_t)o->max_chains * 2 * (size_t)reads_max);
+        if (!K.lseg || !K.lrows) return sd_refused(me, B);
+    }
     const int bits_x = sd_bits((uint64_t)(x->genome->len > 0 ? x->genome->len : 1)) + clh::kSdYBits, bits_r = sd_bits(2 * (uint64_t)(n > 0 ? n : 1));
     for (size_t s = 0; s + 1 < cut.size(); ++s) {
         const int32_t a = cut[s], b = cut[s + 1];
@@ -3747,6 +3786,17 @@ static int sd_seeds(const std::string& me, clh_seed_index* x, int32_t n, const i
             HIPCHK(clh::launch_seed_segments(C, st));
             HIPCHK(clh::launch_seed_chain(C, st));
             HIPCHK(hipEventRecord(x->ev[2], st));
+            if (lo) {                                   // on the device rows, directly behind the chain kernel
+                const size_t lsg = sizeof(int64_t) * clh::kLkSeg * (size_t)C.nseg, lrw = sizeof(int64_t) * clh::kLkRow * (size_t)o->max_chains * (size_t)C.nseg;
+                K.nseg = C.nseg;
+                HIPCHK(hipMemsetAsync(K.lseg, 0x80, lsg, st));
+                HIPCHK(hipMemsetAsync(K.lrows, 0x80, lrw, st));
+                HIPCHK(hipEventRecord(x->ev[4], st));     // the link slot times the kernel alone, not the marker fill
+                HIPCHK(clh::launch_seed_link(K, st));
+                HIPCHK(hipEventRecord(x->ev[3], st));
+                HIPCHK(hipMemcpyAsync(lseg_out + (size_t)clh::kLkSeg * 2 * (size_t)a, K.lseg, lsg, hipMemcpyDeviceToHost, st));
+                HIPCHK(hipMemcpyAsync(lrows_out + (size_t)clh::kLkRow * (size_t)o->max_chains * 2 * (size_t)a, K.lrows, lrw, hipMemcpyDeviceToHost, st));
+            }
             HIPCHK(hipMemcpyAsync(seg_out + (size_t)clh::kChSeg * 2 * (size_t)a, C.seg, sg, hipMemcpyDeviceToHost, st));
             HIPCHK(hipMemcpyAsync(rows_out + (size_t)clh::kChRow * (size_t)o->max_chains * 2 * (size_t)a, C.rows, rw, hipMemcpyDeviceToHost, st));
         }
@@ -3754,6 +3804,7 @@ static int sd_seeds(const std::string& me, clh_seed_index* x, int32_t n, const i
         HIPCHK(hipEventElapsedTime(&t, x->ev[0], x->ev[1]));
         x->ms[2] += t;
         if (o) { HIPCHK(hipEventElapsedTime(&t, x->ev[1], x->ev[2])); x->ms[3] += t; }
+        if (lo) { HIPCHK(hipEventElapsedTime(&t, x->ev[4], x->ev[3])); x->ms[4] += t; }
     }
     if (o)
         for (int64_t s = 0; s < 2 * (int64_t)n; ++s) {
@@ -3763,6 +3814,7 @@ static int sd_seeds(const std::string& me, clh_seed_index* x, int32_t n, const i
             for (int64_t c = 0; c < h[0]; ++c)
                 if (rows_out[((s * o->max_chains) + c) * clh::kChRow + 9] != 0) return fail(CLH_E_HIP, me + "the chain kernel left a row of segment " + std::to_string(s) + " unwritten");
         }
+    if (lo) return lk_validate(me, 0, 2 * (int64_t)n, o->max_chains, seg_out, lseg_out, lrows_out);
     return 0;
 }
 
@@ -3798,4 +3850,60 @@ extern "C" int clh_seed_chain_batch(clh_seed_index* x, int32_t n, const int8_t* 
     if (o->max_chains < 1 || o->max_chains > clh::kChMaxChains) return fail(CLH_E_ARG, me + "max_chains must be 1..64");
     if (o->max_attempts < 1 || o->max_gap < 0 || o->max_skew < 0) return fail(CLH_E_ARG, me + "max_attempts must be at least 1, max_gap and max_skew not negative");
     return sd_seeds(me, x, n, reads, read_off, o->workspace_bytes, nullptr, nullptr, o, seg, rows);
+}
+
+extern "C" int clh_seed_link_batch(clh_seed_index* x, int32_t n, const int8_t* reads, const int64_t* read_off, const clh_chain_opts* o, const clh_link_opts* lo,
+                                   int64_t* seg, int64_t* rows, int64_t* link_seg, int64_t* link_rows)
+{
+    const std::string me = "clh_seed_link_batch: ";
+    if (!x || !o || !lo || (n > 0 && (!seg || !rows || !link_seg || !link_rows))) return fail(CLH_E_ARG, me + "null argument");
+    if (o->lookback < 1 || o->lookback > clh::kChLookbackMax) return fail(CLH_E_ARG, me + "lookback must be 1..64");
+    if (o->max_chains < 1 || o->max_chains > clh::kChMaxChains) return fail(CLH_E_ARG, me + "max_chains must be 1..64");
+    if (o->max_attempts < 1 || o->max_gap < 0 || o->max_skew < 0) return fail(CLH_E_ARG, me + "max_attempts must be at least 1, max_gap and max_skew not negative");
+    if (int rc = lk_opts_check(me, lo)) return rc;
+    return sd_seeds(me, x, n, reads, read_off, o->workspace_bytes, nullptr, nullptr, o, seg, rows, lo, link_seg, link_rows);
+}
+
+extern "C" int clh_seed_link_rows(clh_seed_index* x, int32_t nseg, int32_t max_chains, const int64_t* seg, const int64_t* rows, const clh_link_opts* lo,
+                                  int64_t* link_seg, int64_t* link_rows)
+{
+    const std::string me = "clh_seed_link_rows: ";
+    if (!x || !lo || nseg < 0 || (nseg > 0 && (!seg || !rows || !link_seg || !link_rows))) return fail(CLH_E_ARG, me + "null argument");
+    if (max_chains < 1 || max_chains > clh::kChMaxChains) return fail(CLH_E_ARG, me + "max_chains must be 1..64");
+    if (int rc = lk_opts_check(me, lo)) return rc;
+    for (int64_t s = 0; s < nseg; ++s) {
+        const int64_t nc = seg[clh::kChSeg * s];
+        if (nc < 0 || nc > max_chains) return fail(CLH_E_ARG, me + "segment " + std::to_string(s) + " has " + std::to_string(nc) + " chains, outside 0.." + std::to_string(max_chains));
+        for (int64_t c = 0; c < nc; ++c) {
+            const int64_t* r = rows + (s * max_chains + c) * clh::kChRow;
+            for (int f = 5; f <= 8; ++f)
+                if (r[f] < 0 || r[f] >= clh::kLkLimit) return fail(CLH_E_ARG, me + "segment " + std::to_string(s) + ", chain " + std::to_string(c) + ": a coordinate outside [0, 2^40)");
+            if (r[3] <= -clh::kLkLimit || r[3] >= clh::kLkLimit) return fail(CLH_E_ARG, me + "segment " + std::to_string(s) + ", chain " + std::to_string(c) + ": a score outside (-2^40, 2^40)");
+        }
+    }
+    x->ms[4] = 0;
+    if (nseg == 0) return 0;
+    HIPCHK(hipSetDevice(x->ctx->device));
+    hipStream_t st = x->ctx->stream;
+    SdBlocks B(x->ctx);                                 // seg and rows are the caller's and outlive the call; the copies are drained by B
+    const size_t sg = (size_t)clh::kChSeg * (size_t)nseg, rw = (size_t)clh::kChRow * (size_t)max_chains * (size_t)nseg;
+    const size_t lsg = (size_t)clh::kLkSeg * (size_t)nseg, lrw = (size_t)clh::kLkRow * (size_t)max_chains * (size_t)nseg;
+    int64_t* d_seg = B.get<int64_t>(sg); int64_t* d_rows = B.get<int64_t>(rw);
+    clh::LkLaunch K;
+    memset(&K, 0, sizeof K);
+    K.lseg = B.get<int64_t>(lsg); K.lrows = B.get<int64_t>(lrw);
+    if (!d_seg || !d_rows || !K.lseg || !K.lrows) return sd_refused(me, B);
+    K.seg = d_seg; K.rows = d_rows; K.nseg = nseg; K.max_chains = max_chains; K.k = x->k; K.p = lk_params(lo);
+    HIPCHK(hipMemcpyAsync(d_seg, seg, sizeof(int64_t) * sg, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_rows, rows, sizeof(int64_t) * rw, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(K.lseg, 0x80, sizeof(int64_t) * lsg, st));
+    HIPCHK(hipMemsetAsync(K.lrows, 0x80, sizeof(int64_t) * lrw, st));
+    HIPCHK(hipEventRecord(x->ev[2], st));
+    HIPCHK(clh::launch_seed_link(K, st));
+    HIPCHK(hipEventRecord(x->ev[3], st));
+    HIPCHK(hipMemcpyAsync(link_seg, K.lseg, sizeof(int64_t) * lsg, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(link_rows, K.lrows, sizeof(int64_t) * lrw, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipEventElapsedTime(&x->ms[4], x->ev[2], x->ev[3]));
+    return lk_validate(me, 0, nseg, max_chains, seg, link_seg, link_rows);
 }

@@ -80,6 +80,40 @@ __host__ __device__ inline int64_t ch_gain(int64_t dx, int64_t dy, int k)
     return g - ch_beta(dx > dy ? dx - dy : dy - dx, k);
 }
 
+// ---- links between the chains of one segment (seed_link.hip; tests/link_check.py) --------------------------
+static constexpr int kLkRow = 8, kLkSeg = 4;            // int64 per link row / per link header
+static constexpr int64_t kLkNone = INT64_MIN;           // no link
+static constexpr int64_t kLkLimit = (int64_t)1 << 40;   // coordinates, scores and the two costs lie in [0, 2^40): no sum below can overflow
+enum { kLkColinear = 1, kLkIntron = 2, kLkBacksplice = 3 };
+struct LkChain { int64_t g, score, x0, x1, y0, y1; };
+struct LkParams { int64_t max_query_gap, max_overlap, max_skew, max_intron, max_circle, intron_cost, backsplice_cost; };
+
+// the order of the chains of a segment: (y0, y1, x0, c) ascending, c the chain's index
+__host__ __device__ inline bool lk_before(const LkChain& a, int ca, const LkChain& b, int cb)
+{
+    if (a.y0 != b.y0) return a.y0 < b.y0;
+    if (a.y1 != b.y1) return a.y1 < b.y1;
+    if (a.x0 != b.x0) return a.x0 < b.x0;
+    return ca < cb;
+}
+
+// The link j -> i (j before i in the order above, which the caller sees to): what it adds to F_j, that is -(cost + read overlap), always
+// <= 0, with its kind in *kind; kLkNone and kind 0 where the link is not admissible.
+__host__ __device__ inline int64_t lk_link(const LkChain& j, const LkChain& i, const LkParams& p, int k, int* kind)
+{
+    *kind = 0;
+    if (j.g != i.g || i.y0 <= j.y0 || i.y1 <= j.y1) return kLkNone;
+    const int64_t q = i.y0 - j.y1;
+    if (q > p.max_query_gap || -q > p.max_overlap) return kLkNone;
+    const int64_t d = (i.x0 - j.x1) - q, ad = d < 0 ? -d : d;
+    int64_t cost;
+    if (ad <= p.max_skew) { *kind = kLkColinear; cost = ch_beta(ad, k); }
+    else if (d > 0 && d <= p.max_intron) { *kind = kLkIntron; cost = p.intron_cost; }
+    else if (d < 0 && j.x1 - i.x0 > 0 && j.x1 - i.x0 <= p.max_circle) { *kind = kLkBacksplice; cost = p.backsplice_cost; }
+    else return kLkNone;
+    return -(cost + (q < 0 ? -q : 0));
+}
+
 // ---- launches (seed.hip) ------------------------------------------------------------------------------------------------------
 // The sequences of one sketch: sequence s is the len[s] bytes from off[s] of `codes`; its positions [0, len - k] are cut into work items of
 // kSdItem positions; item_seq[i] names the sequence of item i and seq_item0[s] its first item (seq_item0[nseq] = items).  All device pointers.
@@ -120,6 +154,15 @@ struct ChParams {
 };
 hipError_t launch_seed_segments(const ChParams& c, hipStream_t stream);
 hipError_t launch_seed_chain(const ChParams& c, hipStream_t stream);
+
+// Links (seed_link.hip): segment s has its chains in seg[s][0] (chain header) and rows[s][0 .. max_chains) (chain rows); lseg[nseg][kLkSeg]
+// and lrows[nseg][max_chains][kLkRow] are marker-filled by the caller.  All device pointers; max_chains in 1..64.
+struct LkLaunch {
+    const int64_t* seg; const int64_t* rows; int32_t nseg, max_chains, k;
+    LkParams p;
+    int64_t* lseg; int64_t* lrows;
+};
+hipError_t launch_seed_link(const LkLaunch& l, hipStream_t stream);
 
 // ---- plumbing (seed_sort.hip): rocPRIM's device radix sort and scan -------------------------------------------------------------
 size_t seed_sort_temp_bytes(int64_t n);

@@ -112,6 +112,11 @@ class ChainOpts(C.Structure):
                 ('reserved', C.c_int32), ('max_gap', C.c_int64), ('max_skew', C.c_int64), ('workspace_bytes', C.c_int64)]
 
 
+class LinkOpts(C.Structure):
+    _fields_ = [('max_query_gap', C.c_int64), ('max_overlap', C.c_int64), ('max_skew', C.c_int64), ('max_intron', C.c_int64), ('max_circle', C.c_int64),
+                ('intron_cost', C.c_int64), ('backsplice_cost', C.c_int64)]
+
+
 BAND_DTYPE = np.dtype([('score', '<i4'), ('ref_begin', '<i4'), ('ref_end', '<i4'), ('query_begin', '<i4'), ('query_end', '<i4'),
                        ('cigar_len', '<i4'), ('cigar_off', '<i8'), ('band_lo', '<i4'), ('band_hi', '<i4'), ('exact', '<i4'), ('reserved', '<i4')])
 EDIT_SEARCH_DTYPE = np.dtype([('distance', '<i4'), ('start', '<i4'), ('end', '<i4'), ('last_end', '<i4'), ('nlocs', '<i4')])
@@ -270,6 +275,10 @@ def lib():
             L.clh_seed_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
             L.clh_seed_batch_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             L.clh_seed_chain_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(ChainOpts), C.c_void_p, C.c_void_p]
+        if hasattr(L, 'clh_seed_link_batch'):            # absent from a CLH_LIB build older than the links between chains: links() raises there
+            L.clh_seed_link_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(ChainOpts), C.POINTER(LinkOpts), C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]
+            L.clh_seed_link_rows.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(LinkOpts), C.c_void_p, C.c_void_p]
         L.clh_band_plan_create.restype = C.c_void_p
         L.clh_band_plan_create.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BandOpts)]
         L.clh_band_plan_destroy.restype = None
@@ -1245,10 +1254,12 @@ class SeedIndex(_Handle):
                 'max_occ': int(out[6]), 'shares': int(out[7]), 'round': int(out[8]), 'item': int(out[9]), 'items_per_block': int(out[10])}
 
     def timing(self):
-        """HIP-event milliseconds: sketch and sort of the build, the last minimizers() / seeds() on the device, the chain kernels of the last chains()"""
-        ms = (C.c_float * 4)()
+        """HIP-event milliseconds: sketch and sort of the build, the last minimizers() / seeds() on the device, the chain kernels of the last
+        chains() / links(), the link kernel of the last links() / link_rows() (the kernel alone, without the
+        marker fill of its rows)"""
+        ms = (C.c_float * 5)()
         _check(lib().clh_seed_index_timing(self._h, ms), 'clh_seed_index_timing')
-        return {'sketch': float(ms[0]), 'sort': float(ms[1]), 'seeds': float(ms[2]), 'chain': float(ms[3])}
+        return {'sketch': float(ms[0]), 'sort': float(ms[1]), 'seeds': float(ms[2]), 'chain': float(ms[3]), 'link': float(ms[4])}
 
     def dump(self, first=0, count=None):
         """entries [first, first + count) of the sorted index -> (keys uint64, genome-wide positions int64, strands uint8)"""
@@ -1299,6 +1310,49 @@ class SeedIndex(_Handle):
                     'x_end': int(v[7]), 'y_end': int(v[8])} for v in got]
             out.append(sorted(got, key=lambda c: (-c['score'], c['minus'], c['x_first'])))
         return out, seg[:, 1].reshape(n, 2).astype(bool)
+
+    @staticmethod
+    def _link_opts(max_query_gap, max_overlap, max_skew, max_intron, max_circle, intron_cost, backsplice_cost):
+        if not hasattr(lib(), 'clh_seed_link_batch'):
+            raise ClhError('SeedIndex: this libclh.so is older than the links between chains')
+        return LinkOpts(int(max_query_gap), int(max_overlap), int(max_skew), int(max_intron), int(max_circle), int(intron_cost), int(backsplice_cost))
+
+    def links(self, reads, lookback=64, max_gap=5000, max_skew=500, min_score=40, min_anchors=3, max_chains=32, max_attempts=None, workspace_bytes=0,
+              max_query_gap=500, max_overlap=32, max_intron=200000, max_circle=200000, intron_cost=16, backsplice_cost=32):
+        """chains() and, behind the chain kernel on the device, the links between the chains of every (read, strand) segment (the
+        definitions: include/ciri_long_hip.h, tests/link_check.py; max_skew is the chain's and the link's) -> the raw arrays, segment
+        2 r + minus: seg [2 n, 4] (chains, truncated, anchors, 0), rows [2 n, max_chains, 10] (read, minus, contig, score, anchors, x_first,
+        y_first, x_end, y_end, 0), link_seg [2 n, 4] (chains, paths, 0, 0), link_rows [2 n, max_chains, 8] (rank, F, pred, kind 0 none /
+        1 colinear / 2 intron / 3 back-splice, path, pos, the path's score where pos == 0, 0); only the first `chains` rows of a segment
+        are written"""
+        data, off = _packed(reads)
+        n = len(off) - 1
+        lo = self._link_opts(max_query_gap, max_overlap, max_skew, max_intron, max_circle, intron_cost, backsplice_cost)
+        o = ChainOpts(int(lookback), int(max_chains), int(8 * max_chains if max_attempts is None else max_attempts), int(min_score), int(min_anchors), 0,
+                      int(max_gap), int(max_skew), int(workspace_bytes))
+        mc = max(int(max_chains), 1)
+        seg, rows = np.zeros((2 * n, 4), dtype=np.int64), np.zeros((2 * n, mc, 10), dtype=np.int64)
+        lseg, lrows = np.zeros((2 * n, 4), dtype=np.int64), np.zeros((2 * n, mc, 8), dtype=np.int64)
+        _check(lib().clh_seed_link_batch(self._h, n, data.ctypes.data, off.ctypes.data, C.byref(o), C.byref(lo), seg.ctypes.data, rows.ctypes.data,
+                                         lseg.ctypes.data, lrows.ctypes.data), 'clh_seed_link_batch')
+        return {'seg': seg, 'rows': rows, 'link_seg': lseg, 'link_rows': lrows}
+
+    def link_rows(self, counts, rows, max_query_gap=500, max_overlap=32, max_skew=500, max_intron=200000, max_circle=200000, intron_cost=16,
+                  backsplice_cost=32):
+        """the links of chain rows the caller gives (another mapper's hits): counts [nseg], rows [nseg, max_chains, 10] in the layout of
+        links(), of which contig, score, x_first, y_first, x_end, y_end are read -> link_seg, link_rows as links() gives them"""
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+        if rows.ndim != 3 or rows.shape[0] != len(counts) or rows.shape[2] != 10:
+            raise ValueError('link_rows: rows is [nseg, max_chains, 10] beside counts [nseg], got %r beside %d' % (rows.shape, len(counts)))
+        nseg, mc = int(rows.shape[0]), int(rows.shape[1])
+        lo = self._link_opts(max_query_gap, max_overlap, max_skew, max_intron, max_circle, intron_cost, backsplice_cost)
+        seg = np.zeros((nseg, 4), dtype=np.int64)
+        seg[:, 0] = counts
+        lseg, lrows = np.zeros((nseg, 4), dtype=np.int64), np.zeros((nseg, max(mc, 1), 8), dtype=np.int64)
+        _check(lib().clh_seed_link_rows(self._h, nseg, mc, seg.ctypes.data, rows.ctypes.data, C.byref(lo), lseg.ctypes.data, lrows.ctypes.data),
+               'clh_seed_link_rows')
+        return {'link_seg': lseg, 'link_rows': lrows}
 
 
 class Plan(_Handle):

@@ -4,7 +4,14 @@ it covers, and its first anchor in the form ``ssw_wrap.extend_anchors_genome`` t
 ``reads -> map_reads -> extend_anchors_genome / align_windows_spliced`` stays on the device from letters to CIGARs.
 
 The definitions (minimizers with all ties selected, anchors, chain score, extraction) are the project's own and are not those of
-minimap2: include/ciri_long_hip.h states them, tests/seed_check.py restates them in plain Python."""
+minimap2: include/ciri_long_hip.h states them, tests/seed_check.py restates them in plain Python.
+
+One chain comes out per exon.  ``link_reads`` links the chains of a read into paths across introns and back-splice junctions, still on
+the device (csrc/seed_link.hip; tests/link_check.py is its plain statement), and ``map_spliced`` carries the best path through
+``ssw_wrap.align_windows_spliced``: ``reads -> chains -> paths -> exons and circle`` with no external mapper and no host loop over
+rotations of the read."""
+import numpy as np
+
 from . import hip
 
 
@@ -12,6 +19,19 @@ def index(genome, k=15, w=5, max_occ=64):
     """the minimizer index of a ``hip.Genome``: every contig sketched as a sequence of its own, entries sorted by (key, position);
     a key with more than max_occ entries seeds nothing"""
     return hip.SeedIndex(genome, k=k, w=w, max_occ=max_occ)
+
+
+def _map_style(index, c, L):
+    """a chain of SeedIndex.chains (or a chain row as a dict) of a read of L letters as map_reads gives it"""
+    name, k = index.contigs[c['contig']], index.k
+    if c['minus']:
+        qs, qe = L - c['y_end'], L - c['y_first']
+        anchor = (name, c['x_first'] + k, L - k - c['y_first'])
+    else:
+        qs, qe = c['y_first'], c['y_end']
+        anchor = (name, c['x_first'], c['y_first'])
+    return {'contig': name, 'minus': bool(c['minus']), 'score': c['score'], 'anchors': c['anchors'], 'ref_start': c['x_first'],
+            'ref_end': c['x_end'], 'query_start': qs, 'query_end': qe, 'anchor': anchor}
 
 
 def map_reads(index, reads, **chain_parameters):
@@ -27,20 +47,122 @@ def map_reads(index, reads, **chain_parameters):
                            (contig, g + k, q), read position q facing the upper edge of the genome k-mer"""
     data, off = hip._packed(reads)
     chains, _ = index.chains((data, off), **chain_parameters)
-    k = index.k
+    return [[_map_style(index, c, int(off[r + 1] - off[r])) for c in mine] for r, mine in enumerate(chains)]
+
+
+LINK_KINDS = {1: 'colinear', 2: 'intron', 3: 'backsplice'}
+_ROW = ('read', 'minus', 'contig', 'score', 'anchors', 'x_first', 'y_first', 'x_end', 'y_end')
+_LINK_KEYS = ('max_query_gap', 'max_overlap', 'max_skew', 'max_intron', 'max_circle', 'intron_cost', 'backsplice_cost')
+_ALIGN_KEYS = ('match', 'mismatch', 'gap_open', 'gap_extend', 'intron_open', 'noncanonical', 'donor_costs', 'acceptor_costs', 'traceback')
+
+
+def _path(chains, kinds, score):
+    """one path: its map_reads-style chains in the strand's read order and the kind of the link into each chain but the first"""
+    minus = chains[0]['minus']
+    links = [LINK_KINDS[int(v)] for v in kinds]
+    runs = [[chains[0]]]
+    for c, name in zip(chains[1:], links):
+        if name == 'backsplice':
+            runs.append([])
+        runs[-1].append(c)
+    pieces = [{'ref_start': run[0]['ref_start'], 'ref_end': run[-1]['ref_end'], 'query_start': (run[-1] if minus else run[0])['query_start'],
+               'query_end': (run[0] if minus else run[-1])['query_end']} for run in runs]
+    path = {'contig': chains[0]['contig'], 'minus': minus, 'score': score, 'chains': chains, 'links': links, 'pieces': pieces}
+    back = [t for t, name in enumerate(links) if name == 'backsplice']
+    if back:
+        path['circle'] = (path['contig'], min(chains[t + 1]['ref_start'] for t in back), max(chains[t]['ref_end'] for t in back))
+        target = chains[back[0] + 1]
+        path['rotation'] = target['query_end'] if minus else target['query_start']
+    return path
+
+
+def _paths(index, counts, rows, link_rows, lengths, min_path_score):
+    """the raw arrays of SeedIndex.links / link_rows (segment 2 r + minus) -> per read its paths, best first"""
     out = []
-    for r, mine in enumerate(chains):
-        L = int(off[r + 1] - off[r])
-        rows = []
-        for c in mine:
-            name = index.contigs[c['contig']]
-            if c['minus']:
-                qs, qe = L - c['y_end'], L - c['y_first']
-                anchor = (name, c['x_first'] + k, L - k - c['y_first'])
-            else:
-                qs, qe = c['y_first'], c['y_end']
-                anchor = (name, c['x_first'], c['y_first'])
-            rows.append({'contig': name, 'minus': bool(c['minus']), 'score': c['score'], 'anchors': c['anchors'], 'ref_start': c['x_first'],
-                         'ref_end': c['x_end'], 'query_start': qs, 'query_end': qe, 'anchor': anchor})
-        out.append(rows)
+    for r, L in enumerate(lengths):
+        mine = []
+        for s in (2 * r, 2 * r + 1):
+            n = int(counts[s])
+            lr = link_rows[s, :n]
+            for p in range(int(lr[:, 4].max()) + 1 if n else 0):
+                walk = sorted(np.flatnonzero(lr[:, 4] == p).tolist(), key=lambda c: int(lr[c, 5]))
+                score = int(lr[walk[0], 6])
+                if score >= min_path_score:
+                    chains = [_map_style(index, dict(zip(_ROW, (int(v) for v in rows[s, c, :9]))), L) for c in walk]
+                    mine.append(_path(chains, [lr[c, 3] for c in walk[1:]], score))
+        out.append(sorted(mine, key=lambda v: (-v['score'], v['minus'], v['chains'][0]['ref_start'])))
     return out
+
+
+def link_reads(index, reads, min_path_score=0, **parameters):
+    """map_reads, and the chains of each (read, strand) linked on the device into paths whose links are colinear, introns or
+    back-splices (``SeedIndex.links`` and its parameters: those of map_reads with max_chains=32, and max_query_gap, max_overlap,
+    max_intron, max_circle, intron_cost, backsplice_cost; max_skew is the chain's and the link's).  Per read the list of its paths over
+    both strands with a score of at least min_path_score, ordered by (-score, minus, ref_start of the first chain), each a dict:
+
+    contig, minus, score   of the path; the score is that of its last chain's F less what the walk stopped on
+    chains                 map_reads-style dicts in the strand's read order (on the minus strand: descending in the read as given)
+    links                  'colinear' | 'intron' | 'backsplice', one fewer than chains
+    pieces                 the maximal runs of chains between back-splice links, each with ref_start (of its first chain), ref_end
+                           (of its last), query_start, query_end (in the read as given)
+    circle, rotation       only with at least one back-splice: (contig, the lowest ref_start of a back-splice's target, the highest
+                           ref_end of a back-splice's source), and the position in the read as given at which the first back-splice's
+                           target begins: what find_bsj's rotate-and-map-again loop converges towards, with no mapper call."""
+    data, off = hip._packed(reads)
+    got = index.links((data, off), **parameters)
+    return _paths(index, got['seg'][:, 0], got['rows'], got['link_rows'], np.diff(off).tolist(), min_path_score)
+
+
+def link_chains(index, chain_lists, read_lengths, min_path_score=0, **link_parameters):
+    """link_reads for chains the caller gives (another mapper's hits), through ``SeedIndex.link_rows``: chain_lists[r] holds the
+    map_reads-style dicts of read r (contig, minus, score, ref_start, ref_end, query_start, query_end; anchors if known), each strand's in
+    the order given, which is the order ties fall back on; read_lengths[r] its length.  At most 64 chains per (read, strand)."""
+    n = len(chain_lists)
+    if len(read_lengths) != n:
+        raise ValueError('link_chains: %d chain lists vs %d read lengths' % (n, len(read_lengths)))
+    segs = [[c for c in mine if bool(c['minus']) == bool(s & 1)] for mine in chain_lists for s in (0, 1)]
+    most = max([len(s) for s in segs] + [1])
+    if most > 64:
+        raise ValueError('link_chains: %d chains in one (read, strand), at most 64 are linked' % most)
+    rows = np.zeros((2 * n, most, 10), dtype=np.int64)
+    for s, mine in enumerate(segs):
+        L = int(read_lengths[s >> 1])
+        for c, v in enumerate(mine):
+            y0, y1 = (L - v['query_end'], L - v['query_start']) if s & 1 else (v['query_start'], v['query_end'])
+            rows[s, c, :9] = (s >> 1, s & 1, index.contigs.index(v['contig']), v['score'], v.get('anchors', 0), v['ref_start'], y0, v['ref_end'], y1)
+    counts = np.array([len(s) for s in segs], dtype=np.int64)
+    got = index.link_rows(counts, rows, **link_parameters)
+    return _paths(index, counts, rows, got['link_rows'], [int(v) for v in read_lengths], min_path_score)
+
+
+def map_spliced(index, reads, context=None, **parameters):
+    """reads -> chains -> paths -> exons: link_reads (its parameters), then for the best path of each read every piece aligned between
+    its outer anchors -- the query is the strand's read letters from the start of the piece's first chain to the end of its last, the
+    window (contig, ref_start, ref_end) of the piece -- all pieces of all reads in one ``ssw_wrap.align_windows_spliced(mode='global',
+    strand='both', report_cigar=True)`` (its scoring keywords pass through).  Per read None where it has no path, else its best path
+    with, on every piece, exons [(start, end)] (inclusive, forward strand), strand ('+' / '-': the transcript's, from the splice
+    signals), score and cigar_string; a piece whose ref_end lies below its ref_start (chains that run backwards inside a colinear
+    link's skew) is not aligned and carries None.
+
+    The ends of a piece are those of its outer anchors and are not refined: a back-splice junction lies up to w - 1 + the letters an
+    error took beyond them.  Refining the junction itself stays with the clip alignment and the splice scan (K6)."""
+    from . import ssw_wrap
+    align = {name: parameters.pop(name) for name in _ALIGN_KEYS if name in parameters}
+    data, off = hip._packed(reads)
+    best = [dict(paths[0]) if paths else None for paths in link_reads(index, (data, off), **parameters)]
+    windows, queries, where = [], [], []
+    for r, path in enumerate(best):
+        if path is None:
+            continue
+        path['pieces'] = [dict(p, exons=None, strand=None, score=None, cigar_string=None) for p in path['pieces']]
+        for piece in path['pieces']:
+            if piece['ref_end'] < piece['ref_start']:
+                continue
+            q = data[off[r] + piece['query_start']:off[r] + piece['query_end']]
+            queries.append(np.where(q < 4, 3 - q, q)[::-1].astype(np.int8) if path['minus'] else q)
+            windows.append((path['contig'], piece['ref_start'], piece['ref_end']))
+            where.append(piece)
+    got = ssw_wrap.align_windows_spliced(index.genome, windows, queries, mode='global', strand='both', report_cigar=True, context=context, **align)
+    for piece, res in zip(where, got):
+        piece.update(exons=res.exons, strand=res.strand, score=res.score, cigar_string=res.cigar_string)
+    return best

@@ -612,8 +612,9 @@ int clh_band_plan_gather_timing(clh_band_plan* plan, float* ms, int64_t* letters
  *
  * clh_seed_index_info, out[12]: entries, distinct keys, keys with more than max_occ entries, device bytes held, k, w, max_occ, shares
  * of the last seeds / chains call, then the sketch's geometry: positions a wave decides per round, positions of a work item, work items
- * of a workgroup, and 0.  clh_seed_index_timing, ms[4] (HIP events): sketch and sort of the build, the last clh_seed_minimizers /
- * clh_seed_batch (sketch, look-up, sorts; no transfers to the host), the chain kernels of the last clh_seed_chain_batch.
+ * of a workgroup, and 0.  clh_seed_index_timing, ms[5] (HIP events): sketch and sort of the build, the last clh_seed_minimizers /
+ * clh_seed_batch (sketch, look-up, sorts; no transfers to the host), the chain kernels of the last clh_seed_chain_batch, the link
+ * kernels of the last clh_seed_link_batch / clh_seed_link_rows (below).
  * clh_seed_index_dump: entries [first, first + count) of the sorted arrays.
  *
  * clh_seed_minimizers: the same sketch on n sequences of codes 0..4; min_off[n + 1]; then clh_seed_minimizers_fetch(cap >= min_off[n])
@@ -642,7 +643,32 @@ int clh_band_plan_gather_timing(clh_band_plan* plan, float* ms, int64_t* letters
  * there is `truncated`.  seg[2 n][4]: chains, truncated, anchors, 0; rows[2 n][max_chains][10], the first `chains` of a segment written:
  * read, minus, contig, score, anchors, x_first, y_first, x_last + k, y_last + k, 0 (x relative to the contig; segment 2 r + minus).
  * 1 <= lookback <= 64, 1 <= max_chains <= 64, max_attempts >= 1, max_gap, max_skew >= 0, else CLH_E_ARG.  A row or header the kernel
- * left unwritten is CLH_E_HIP from this call, never returned. */
+ * left unwritten is CLH_E_HIP from this call, never returned.
+ *
+ * Links (csrc/seed_link.hip; the plain statement is tests/link_check.py): the chains of one segment, c = 0 .. n - 1 in the order the rows
+ * hold them (n <= max_chains <= 64), each with g = contig, score, x0 = x_first, x1 = x_last + k, y0 = y_first, y1 = y_last + k, are
+ * linked into paths.  The chains are ranked by the key (y0, y1, x0, c) ascending.  A link j -> i needs rank j < rank i and
+ *   g_j == g_i, y0_i > y0_j, y1_i > y1_j; with q = y0_i - y1_j: q <= max_query_gap and -q <= max_overlap;
+ *   with d = (x0_i - x1_j) - q exactly one kind: 1 colinear, |d| <= max_skew, cost beta(|d|) as above; 2 intron, max_skew < d <=
+ *   max_intron, cost intron_cost; 3 back-splice, d < -max_skew and 0 < x1_j - x0_i <= max_circle, cost backsplice_cost; anything else
+ *   is no link.
+ * v(j, i) = F_j - cost - max(0, -q); F_i = score_i + max(0, max_j v(j, i)); pred_i the j of the maximum and kind_i its kind, -1 and 0
+ * where no link has v > 0; among equal maxima the j of greatest rank.  Paths, until every chain is in one: e = the chain in no path of
+ * greatest F (ties: smallest rank); walk e, pred(e), ... up to a chain already in a path or to none; the chains walked are path p = 0,
+ * 1, ... in the order of extraction, pos counting from the path's first chain (the last one walked); the path's score is F_e - F of the
+ * chain the walk stopped on (0 where on none).  No threshold is applied.
+ * link_seg[nseg][4]: chains, paths, 0, 0; link_rows[nseg][max_chains][8], the first `chains` of a segment written: rank, F, pred, kind,
+ * path, pos, the path's score where pos == 0 else 0, 0.
+ * clh_link_opts: every field >= 0, max_skew <= max_intron, the two costs below 2^40, else CLH_E_ARG.
+ * clh_seed_link_batch: clh_seed_chain_batch, then the links of every segment (2 r + minus) on the device rows, in the same shares and
+ * with no trip to the host between the two; seg and rows are those of clh_seed_chain_batch.  clh_seed_index_timing gives ms[5]: the
+ * four above and the link kernels of the last clh_seed_link_batch / clh_seed_link_rows (the kernels alone: the marker fill of their
+ * rows lies outside the interval).
+ * clh_seed_link_rows: the links of nseg segments of chain rows that the caller gives (another mapper's hits): seg[nseg][4] with the
+ * count in its first word, rows[nseg][max_chains][10] in the layout above, of which contig, score, x_first, y_first, x_end and y_end
+ * are read.  The index gives its context and k.  CLH_E_ARG, naming the segment: a count outside 0..max_chains, a coordinate outside
+ * [0, 2^40), a score outside (-2^40, 2^40).  Every buffer is sized from the arguments.  As above, a header or row the kernel left
+ * unwritten, or a walk that would have left the segment, is CLH_E_HIP, never returned. */
 typedef struct clh_seed_index clh_seed_index;
 typedef struct {
     int32_t lookback, max_chains, max_attempts, min_score, min_anchors, reserved;
@@ -661,6 +687,13 @@ int clh_seed_batch(clh_seed_index* index, int32_t n, const int8_t* reads, const 
 int clh_seed_batch_fetch(clh_seed_index* index, int64_t cap, int32_t* read, uint8_t* minus, int64_t* x, int32_t* y);
 int clh_seed_chain_batch(clh_seed_index* index, int32_t n, const int8_t* reads, const int64_t* read_off, const clh_chain_opts* opts, int64_t* seg,
                          int64_t* rows);
+typedef struct {
+    int64_t max_query_gap, max_overlap, max_skew, max_intron, max_circle, intron_cost, backsplice_cost;
+} clh_link_opts;
+int clh_seed_link_batch(clh_seed_index* index, int32_t n, const int8_t* reads, const int64_t* read_off, const clh_chain_opts* chain_opts,
+                        const clh_link_opts* link_opts, int64_t* seg, int64_t* rows, int64_t* link_seg, int64_t* link_rows);
+int clh_seed_link_rows(clh_seed_index* index, int32_t nseg, int32_t max_chains, const int64_t* seg, const int64_t* rows, const clh_link_opts* link_opts,
+                       int64_t* link_seg, int64_t* link_rows);
 
 
 /* ASCII -> codes exactly as ssw_wrap.py:234-252 (A/a C/c G/g T/t N/n, anything else 4), on the host. */

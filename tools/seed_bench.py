@@ -9,9 +9,13 @@ its own device work (SeedIndex.timing), the median of R runs after a warm-up.  S
       scan, anchor fill and the two sorts; no transfer to the host is in the interval.  Anchors per second, and the look-ups per second
       (two binary searches of log2(entries) dependent loads each).
   (c) chains of the same reads: the seeds step again, and the chain kernels apart.
+  (d) links of the same reads (clh_seed_link_batch: seeds, chains, and the link kernel behind the chain kernel): the three steps
+      apart, and their sum beside what clh_seed_chain_batch takes on the same reads with the same chain options (max_chains 32) -- the
+      one figure the link step has a predecessor for.  The link slot is the kernel alone; the marker fill of its rows is outside it.  Linear reads give one chain each, so the link kernel's work here is its floor: header, rank
+      and one extraction per segment.
 
 There is no parent-commit or reference figure for a step that did not exist: no ratio is printed.
-usage: python tools/seed_bench.py [G=100] [N=100000] [runs=10] [shapes=abc] [--hbm GBPS]"""
+usage: python tools/seed_bench.py [G=100] [N=100000] [runs=10] [shapes=abcd] [--hbm GBPS]"""
 import json
 import math
 import os
@@ -31,7 +35,7 @@ if '--hbm' in ARGS:
 G = int(ARGS[0]) if len(ARGS) > 0 else 100
 N = int(ARGS[1]) if len(ARGS) > 1 else 100000
 R = int(ARGS[2]) if len(ARGS) > 2 else 10
-SHAPES = ARGS[3] if len(ARGS) > 3 else 'abc'
+SHAPES = ARGS[3] if len(ARGS) > 3 else 'abcd'
 K, W = 15, 5
 
 
@@ -57,7 +61,7 @@ def main():
                           'index_bytes': info['bytes'], 'sketch_ms': round(sk, 3), 'sort_ms': round(so, 3), 'sketch_gbases_per_s': round(8 * per / sk / 1e6, 2),
                           'sketch_bytes_moved': moved, 'sketch_bound_ms_at_%g_GBps' % HBM: round(moved / HBM / 1e6, 3),
                           'sort_entries_per_s': round(info['entries'] / so * 1e3)}), flush=True)
-    if 'b' in SHAPES or 'c' in SHAPES:
+    if 'b' in SHAPES or 'c' in SHAPES or 'd' in SHAPES:
         reads = []
         for r in range(N):
             v = codes[r % 8]
@@ -90,6 +94,23 @@ def main():
             print(json.dumps({'shape': 'c: chains of the same reads, defaults', 'anchors': anchors, 'chains': sum(len(c) for c in chains),
                               'reads_with_a_chain': sum(1 for c in chains if c), 'seeds_ms': round(se, 3), 'chain_ms': round(ms, 3),
                               'reads_per_s': round(N / (ms + se) * 1e3), 'chain_anchors_per_s': round(anchors / ms * 1e3)}), flush=True)
+        if 'd' in SHAPES:
+            got = idx.links(packed)                     # warm-up
+            both = {'chain_batch': [], 'link_batch': [], 'link': [], 'chain': [], 'seeds': []}
+            for _ in range(R):
+                idx.chains(packed, max_chains=32)       # the same chain options as links(): the difference is the link step alone
+                t = idx.timing()
+                both['chain_batch'].append(t['seeds'] + t['chain'])
+                idx.links(packed)
+                t = idx.timing()
+                both['link_batch'].append(t['seeds'] + t['chain'] + t['link'])
+                for name in ('seeds', 'chain', 'link'):
+                    both[name].append(t[name])
+            med = {name: float(np.median(v)) for name, v in both.items()}
+            print(json.dumps({'shape': 'd: links of the same reads, defaults (max_chains 32)', 'segments': 2 * N, 'chains': int(got['seg'][:, 0].sum()),
+                              'paths': int(got['link_seg'][:, 1].sum()), 'seeds_ms': round(med['seeds'], 3), 'chain_ms': round(med['chain'], 3),
+                              'link_ms': round(med['link'], 3), 'link_batch_ms': round(med['link_batch'], 3),
+                              'chain_batch_ms': round(med['chain_batch'], 3), 'segments_per_s': round(2 * N / med['link'] * 1e3)}), flush=True)
     idx.close()
     genome.close()
 
