@@ -2458,6 +2458,17 @@ static int64_t sp_site(const int32_t* site, int soff, int which, int x, int y)
     return site[((x | y) > 3 || (x | y) < 0) ? clh::kSpOther : soff + which + 4 * x + y];
 }
 
+// the table of both strands that ssw_ends.hip's spliced kernels and seed_junction.hip take (clh_device.h)
+static void sp_table(const clh_splice* sp, int32_t* site)
+{
+    for (int x = 0; x < 4; ++x)
+        for (int y = 0; y < 4; ++y) {      // strand -: the transcript reads the complement of (y, x)
+            site[4 * x + y] = sp->donor[4 * x + y]; site[16 + 4 * x + y] = sp->acceptor[4 * x + y];
+            site[32 + 4 * x + y] = sp->acceptor[4 * (3 - y) + (3 - x)]; site[48 + 4 * x + y] = sp->donor[4 * (3 - y) + (3 - x)];
+        }
+    site[clh::kSpOther] = sp->other;
+}
+
 // what the spliced create refuses beyond pairs_check_opts, and the table of both strands -> 0, or the code
 static int sp_check(const std::string& me, const clh_ends_opts* o, const clh_splice* sp, const int8_t* strand, int32_t n, int32_t* site, int64_t* site_max)
 {
@@ -2482,12 +2493,7 @@ static int sp_check(const std::string& me, const clh_ends_opts* o, const clh_spl
         for (int k = 0; k < n; ++k)
             if (strand[k] != 1 && strand[k] != -1) return fail(CLH_E_ARG, me + "pair " + std::to_string(k) + ": strand must be +1 or -1, got " + std::to_string((int)strand[k]));
     *site_max = (int64_t)sp->intron_open + dmax + amax;
-    for (int x = 0; x < 4; ++x)
-        for (int y = 0; y < 4; ++y) {      // strand -: the transcript reads the complement of (y, x)
-            site[4 * x + y] = sp->donor[4 * x + y]; site[16 + 4 * x + y] = sp->acceptor[4 * x + y];
-            site[32 + 4 * x + y] = sp->acceptor[4 * (3 - y) + (3 - x)]; site[48 + 4 * x + y] = sp->donor[4 * (3 - y) + (3 - x)];
-        }
-    site[clh::kSpOther] = sp->other;
+    sp_table(sp, site);
     return 0;
 }
 
@@ -3906,4 +3912,131 @@ extern "C" int clh_seed_link_rows(clh_seed_index* x, int32_t nseg, int32_t max_c
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipEventElapsedTime(&x->ms[4], x->ev[2], x->ev[3]));
     return lk_validate(me, 0, nseg, max_chains, seg, link_seg, link_rows);
+}
+
+// ---- K7j: back-splice junctions refined to the base (seed_junction.hip; the definitions in seed_device.h and the header) ----------
+static_assert(clh::kJxSiteOther == clh::kSpOther && clh::kJxSites == clh::kSpSites, "K7j reads the spliced kernels' site table");
+
+extern "C" int clh_seed_junction_info(int64_t* out)
+{
+    if (!out) return fail(CLH_E_ARG, "clh_seed_junction_info: null argument");
+    static_assert(clh::kJxClasses == 4, "out[0..3] are the class bounds");
+    const int64_t v[8] = {clh::jx_class_bound(0), clh::jx_class_bound(1), clh::jx_class_bound(2), clh::jx_class_bound(3), clh::kJxMaxSpan, clh::kJxMaxSlack,
+                          clh::kJxWaves, clh::kJxClasses};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+    return 0;
+}
+
+extern "C" int clh_seed_junction_batch(clh_seed_index* x, int32_t n_reads, const int8_t* reads, const int64_t* read_off, int64_t n_tasks, const int64_t* task,
+                                       const clh_junction_opts* o, const clh_splice* sp, int64_t* out, float* kernel_ms)
+{
+    const std::string me = "clh_seed_junction_batch: ";
+    if (kernel_ms) *kernel_ms = 0;
+    if (!x || !o || !sp || n_reads < 0 || n_tasks < 0 || !read_off || (n_tasks > 0 && (!task || !out))) return fail(CLH_E_ARG, me + "null argument");
+    if (o->max_span < 1 || o->max_span > clh::kJxMaxSpan) return fail(CLH_E_ARG, me + "max_span must be 1.." + std::to_string(clh::kJxMaxSpan));
+    if (o->slack < 0 || o->slack > clh::kJxMaxSlack) return fail(CLH_E_ARG, me + "slack must be 0.." + std::to_string(clh::kJxMaxSlack));
+    int64_t dmax = sp->other, amax = sp->other;
+    bool neg = o->match < 0 || o->mismatch < 0 || o->gap_open < 0 || o->gap_extend < 0 || sp->intron_open < 0 || sp->other < 0;
+    for (int k = 0; k < 16; ++k) {
+        neg = neg || sp->donor[k] < 0 || sp->acceptor[k] < 0;
+        dmax = std::max<int64_t>(dmax, sp->donor[k]); amax = std::max<int64_t>(amax, sp->acceptor[k]);
+    }
+    if (neg) return fail(CLH_E_ARG, me + "match, mismatch, the gap costs, intron_open, the donor and acceptor costs and `other` must not be negative");
+    if (o->gap_open < o->gap_extend) return fail(CLH_E_UNSUPPORTED, me + "gap_open < gap_extend is not built");
+    const int64_t cmax = std::max<int64_t>(std::max(o->match, o->mismatch), std::max(o->gap_open, o->gap_extend));
+    if ((2 * (int64_t)o->max_span + o->slack) * cmax + sp->intron_open + dmax + amax >= clh::kJxBound)
+        return fail(CLH_E_ARG, me + "(2 max_span + slack) max(match, mismatch, gap_open, gap_extend) + intron_open + dmax + amax must stay below 2^20: a side score "
+                                    "less a site cost and a column index share one 32-bit key");
+    if (read_off[0] < 0) return fail(CLH_E_ARG, me + "offsets must ascend from 0 or above");
+    for (int32_t r = 0; r < n_reads; ++r)
+        if (read_off[r + 1] < read_off[r]) return fail(CLH_E_ARG, me + "offsets must ascend");
+    if (read_off[n_reads] > 0 && !reads) return fail(CLH_E_ARG, me + "null argument");
+    for (int32_t r = 0; r < n_reads; ++r)
+        for (int64_t i = read_off[r]; i < read_off[r + 1]; ++i)
+            if (reads[i] < 0 || reads[i] > 4) return fail(CLH_E_ARG, me + "read " + std::to_string(r) + " holds a code outside 0..4");
+    const int64_t n_ctg = (int64_t)x->c_off.size();
+    std::vector<int64_t> order((size_t)n_tasks);        // before B: see SdEntries
+    std::vector<int32_t> site(clh::kJxSites);
+    clh::JxLaunch K;
+    memset(&K, 0, sizeof K);
+    std::vector<int8_t> cls((size_t)n_tasks);
+    int64_t count[clh::kJxClasses] = {0, 0, 0, 0};
+    for (int64_t t = 0; t < n_tasks; ++t) {
+        const int64_t* k = task + clh::kJxTask * t;
+        const std::string who = me + "task " + std::to_string(t) + ": ";
+        if (k[0] < 0 || k[0] >= n_reads) return fail(CLH_E_ARG, who + "read " + std::to_string(k[0]) + " outside the " + std::to_string(n_reads) + " reads");
+        if (k[2] < 0 || k[2] >= n_ctg) return fail(CLH_E_ARG, who + "contig " + std::to_string(k[2]) + " outside the " + std::to_string(n_ctg) + " contigs");
+        const int64_t L = read_off[k[0] + 1] - read_off[k[0]], len = x->c_len[(size_t)k[2]];
+        if (k[4] < 0 || k[4] > L || k[6] < 0 || k[6] > L) return fail(CLH_E_ARG, who + "yd or ya outside [0, " + std::to_string(L) + "]");
+        if (k[3] < 0 || k[3] > len || k[5] < 0 || k[5] > len) return fail(CLH_E_ARG, who + "xd or xa outside [0, " + std::to_string(len) + "]");
+        if (k[7] < -1 || k[7] > 1) return fail(CLH_E_ARG, who + "strand must be -1, 0 or +1, got " + std::to_string(k[7]));
+        cls[(size_t)t] = (int8_t)(clh::jx_status(k[3], k[4], k[5], k[6], o->max_span) ? 0 : clh::jx_class(k[6] - k[4]));
+        ++count[cls[(size_t)t]];
+    }
+    if (n_tasks == 0) return 0;
+    int64_t next[clh::kJxClasses];
+    for (int c = 0; c < clh::kJxClasses; ++c) { K.first[c + 1] = K.first[c] + count[c]; next[c] = K.first[c]; }
+    for (int64_t t = 0; t < n_tasks; ++t) order[(size_t)next[cls[(size_t)t]]++] = t;
+    sp_table(sp, site.data());
+    HIPCHK(hipSetDevice(x->ctx->device));
+    hipStream_t st = x->ctx->stream;
+    SdBlocks B(x->ctx);
+    const size_t total = (size_t)read_off[n_reads], nt = (size_t)n_tasks;
+    int8_t* d_reads = B.get<int8_t>(total);
+    int64_t* d_roff = B.get<int64_t>((size_t)n_reads + 1);
+    int64_t* d_task = B.get<int64_t>(nt * clh::kJxTask);
+    K.order = B.put(order); K.site = B.put(site);
+    K.out = B.get<int64_t>(nt * clh::kJxRow);
+    if (!d_reads || !d_roff || !d_task || !K.order || !K.site || !K.out) return sd_refused(me, B);
+    if (total) HIPCHK(hipMemcpyAsync(d_reads, reads, total, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_roff, read_off, sizeof(int64_t) * ((size_t)n_reads + 1), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_task, task, sizeof(int64_t) * nt * clh::kJxTask, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(K.out, 0x80, sizeof(int64_t) * nt * clh::kJxRow, st));
+    K.genome = (const uint8_t*)x->genome->d_codes; K.ctg_off = x->d_coff; K.ctg_len = x->d_clen;
+    K.reads = d_reads; K.read_off = d_roff; K.task = d_task;
+    K.match = o->match; K.mismatch = o->mismatch; K.go = o->gap_open; K.ge = o->gap_extend; K.io = sp->intron_open; K.slack = o->slack; K.max_span = o->max_span;
+    HIPCHK(hipEventRecord(x->ev[2], st));
+    HIPCHK(clh::launch_seed_junction(K, st));
+    HIPCHK(hipEventRecord(x->ev[3], st));
+    HIPCHK(hipMemcpyAsync(out, K.out, sizeof(int64_t) * nt * clh::kJxRow, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, x->ev[2], x->ev[3]));
+    if (kernel_ms) *kernel_ms = ms;
+    for (int64_t t = 0; t < n_tasks; ++t) {
+        const int64_t* r = out + clh::kJxRow * t;
+        const int64_t* k = task + clh::kJxTask * t;
+        if (r[0] == clh::kChUnwritten || r[0] != clh::jx_status(k[3], k[4], k[5], k[6], o->max_span))
+            return fail(CLH_E_HIP, me + "the junction kernel left task " + std::to_string(t) + (r[0] == clh::kChUnwritten ? " unwritten" : " with status " + std::to_string(r[0])));
+        if (r[0] == 0 && (r[3] < 0 || r[3] > k[6] - k[4] || r[4] < 0 || r[5] < 0 || r[6] > x->c_len[(size_t)k[2]] || r[7] < 0 || r[7] >= r[6]))
+            return fail(CLH_E_HIP, me + "the junction kernel left the row of task " + std::to_string(t) + " out of range");
+    }
+    return 0;
+}
+
+// the letters of n spans of the resident genome as codes 0..4 (bits 0-2 of the byte, clamped to 4): one small gather on the device, one
+// lane a span, and one copy back -- for the dinucleotides beside many refined junctions, not for windows
+extern "C" int clh_genome_letters(clh_genome* g, int32_t n, const int64_t* off, const int64_t* len, int8_t* out)
+{
+    const std::string me = "clh_genome_letters: ";
+    if (!g || n < 0 || (n > 0 && (!off || !len || !out))) return fail(CLH_E_ARG, me + "null argument");
+    std::vector<int64_t> at((size_t)n + 1, 0);          // before B: see SdEntries
+    for (int i = 0; i < n; ++i) {
+        if (off[i] < 0 || len[i] < 0 || off[i] + len[i] > g->len) return fail(CLH_E_ARG, me + "span outside the genome");
+        at[(size_t)i + 1] = at[(size_t)i] + len[i];
+    }
+    const int64_t total = at[(size_t)n];
+    if (total == 0) return 0;
+    HIPCHK(hipSetDevice(g->ctx->device));
+    hipStream_t st = g->ctx->stream;
+    SdBlocks B(g->ctx);
+    int64_t* d_off = B.get<int64_t>((size_t)n); int64_t* d_len = B.get<int64_t>((size_t)n); int64_t* d_at = B.put(at);
+    int8_t* d_out = B.get<int8_t>((size_t)total);
+    if (!d_off || !d_len || !d_at || !d_out) return sd_refused(me, B);
+    HIPCHK(hipMemcpyAsync(d_off, off, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_len, len, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, st));
+    HIPCHK(clh::launch_genome_letters((const uint8_t*)g->d_codes, g->len, d_off, d_len, d_at, n, d_out, st));
+    HIPCHK(hipMemcpyAsync(out, d_out, (size_t)total, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
 }

@@ -1,5 +1,6 @@
-// seed_device.h -- K7: what the host side, the sketch, look-up and chain kernels (seed.hip), the sort plumbing (seed_sort.hip) and the
-// stand-alone host program tests/seed_host.hip share.  The definitions are those of DESIGN.md section 4 (K7): they are independent of
+// seed_device.h -- K7: what the host side, the sketch, look-up and chain kernels (seed.hip), the link and junction kernels (seed_link.hip,
+// seed_junction.hip), the sort plumbing (seed_sort.hip) and the stand-alone host programs tests/seed_host.hip, link_host.hip and
+// junction_host.hip share.  The definitions are those of DESIGN.md section 4 (K7): they are independent of
 // the order in which positions are visited, so that the kernels and the plain checker tests/seed_check.py agree bit for bit.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -113,6 +114,81 @@ __host__ __device__ inline int64_t lk_link(const LkChain& j, const LkChain& i, c
     else return kLkNone;
     return -(cost + (q < 0 ? -q : 0));
 }
+
+// ---- a back-splice junction refined to the base (seed_junction.hip; tests/junction_check.py) ---------------
+static constexpr int kJxTask = 8, kJxRow = 12;          // int64 per task (read, minus, contig, xd, yd, xa, ya, strand) / per result row
+static constexpr int kJxMaxSpan = 512, kJxMaxSlack = 64;
+static constexpr int kJxWaves = 4;                      // tasks of one workgroup: the waves share nothing
+static constexpr int kJxClasses = 4;                    // class c takes m <= kJxClassBase << c with 1 << c rows per lane
+static constexpr int kJxClassBase = 64;                  // the rows of class 0: one per lane
+static_assert((kJxClassBase << (kJxClasses - 1)) == kJxMaxSpan, "the last class takes max_span");
+static constexpr int kJxSiteOther = 64, kJxSites = 65;  // the site table of clh_device.h (kSpOther, kSpSites): start+, end+, start-, end-, other
+// (2 max_span + slack) max(match, mismatch, gap_open, gap_extend) + intron_open + dmax + amax stays below this: a side score less a
+// site cost then lies inside (-2^20, 2^20) and stands, times 1024, above a 10-bit column index in one 32-bit key
+static constexpr int64_t kJxBound = (int64_t)1 << 20;
+static constexpr int kJxIndexBits = 10, kJxIndexMask = (1 << kJxIndexBits) - 1;      // columns 0 .. 512 + 64
+
+__host__ __device__ inline int64_t jx_class_bound(int c) { return (int64_t)kJxClassBase << c; }
+__host__ __device__ inline int jx_class(int64_t m)
+{
+    int c = 0;
+    while (c < kJxClasses - 1 && m > jx_class_bound(c)) ++c;
+    return c;
+}
+// 0: refined; 1: m = ya - yd above max_span; 2: no read letter between the anchors, or the acceptor anchor not below the donor anchor
+__host__ __device__ inline int jx_status(int64_t xd, int64_t yd, int64_t xa, int64_t ya, int64_t max_span)
+{
+    if (ya - yd > max_span) return 1;
+    if (ya - yd < 1 || xa >= xd) return 2;
+    return 0;
+}
+// the letters of D = contig[xd : min(xd + m + slack, len)) and of A = contig[max(0, xa - m - slack) : xa); 0 <= xd, xa <= len
+__host__ __device__ inline int64_t jx_nd(int64_t xd, int64_t m, int64_t slack, int64_t len)
+{
+    const int64_t e = xd + m + slack < len ? xd + m + slack : len;
+    return e > xd ? e - xd : 0;
+}
+__host__ __device__ inline int64_t jx_na(int64_t xa, int64_t m, int64_t slack)
+{
+    const int64_t s = xa - m - slack > 0 ? xa - m - slack : 0;
+    return xa > s ? xa - s : 0;
+}
+// letter x of the contig that lies at [off, off + len) of the genome, as genome_gather.h reads it: bits 0-2, clamped to 4; 4 outside
+__host__ __device__ inline int jx_letter(const uint8_t* genome, int64_t off, int64_t len, int64_t x)
+{
+    if (x < 0 || x >= len) return 4;
+    const int c = genome[off + x] & 7;
+    return c > 4 ? 4 : c;
+}
+// the cost of the dinucleotide at contig positions (p, p + 1) as a run's start (part 0, p = a) or end (part 1, p = b - 1) on strand
+// + (minus 0) or - (minus 1); `other` where it holds a code >= 4 or leaves the contig
+__host__ __device__ inline int jx_site(const int32_t* site, const uint8_t* genome, int64_t off, int64_t len, int64_t p, int part, int minus)
+{
+    const int a = jx_letter(genome, off, len, p), b = jx_letter(genome, off, len, p + 1);
+    if (a > 3 || b > 3) return site[kJxSiteOther];
+    return site[32 * minus + 16 * part + 4 * a + b];
+}
+// letter y of S, the read of L letters as the strand reads it
+__host__ __device__ inline int jx_read_letter(const int8_t* read, int64_t L, int64_t y, int minus)
+{
+    if (y < 0 || y >= L) return 4;
+    const int c = minus ? read[L - 1 - y] : read[y];
+    return minus && c < 4 ? 3 - c : c;
+}
+
+// All device pointers.  Tasks order[first[c] .. first[c + 1]) are those of class c; out[n][kJxRow] is marker-filled by the caller.
+struct JxLaunch {
+    const uint8_t* genome; const int64_t* ctg_off; const int64_t* ctg_len;
+    const int8_t* reads; const int64_t* read_off;
+    const int64_t* task; const int64_t* order; int64_t first[kJxClasses + 1];
+    const int32_t* site;                                // kJxSites costs
+    int32_t match, mismatch, go, ge, io, slack, max_span;
+    int64_t* out;
+};
+hipError_t launch_seed_junction(const JxLaunch& l, hipStream_t stream);
+// the letters (jx_letter's codes) of n short spans of the genome: span i is len[i] bytes from off[i] and goes to out + at[i]; one lane a span
+hipError_t launch_genome_letters(const uint8_t* genome, int64_t genome_len, const int64_t* off, const int64_t* len, const int64_t* at, int64_t n, int8_t* out,
+                                 hipStream_t stream);
 
 // ---- launches (seed.hip) ------------------------------------------------------------------------------------------------------
 // The sequences of one sketch: sequence s is the len[s] bytes from off[s] of `codes`; its positions [0, len - k] are cut into work items of

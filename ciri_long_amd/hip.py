@@ -117,6 +117,10 @@ class LinkOpts(C.Structure):
                 ('intron_cost', C.c_int64), ('backsplice_cost', C.c_int64)]
 
 
+class JunctionOpts(C.Structure):
+    _fields_ = [('match', C.c_int32), ('mismatch', C.c_int32), ('gap_open', C.c_int32), ('gap_extend', C.c_int32), ('slack', C.c_int32), ('max_span', C.c_int32)]
+
+
 BAND_DTYPE = np.dtype([('score', '<i4'), ('ref_begin', '<i4'), ('ref_end', '<i4'), ('query_begin', '<i4'), ('query_end', '<i4'),
                        ('cigar_len', '<i4'), ('cigar_off', '<i8'), ('band_lo', '<i4'), ('band_hi', '<i4'), ('exact', '<i4'), ('reserved', '<i4')])
 EDIT_SEARCH_DTYPE = np.dtype([('distance', '<i4'), ('start', '<i4'), ('end', '<i4'), ('last_end', '<i4'), ('nlocs', '<i4')])
@@ -279,6 +283,11 @@ def lib():
             L.clh_seed_link_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(ChainOpts), C.POINTER(LinkOpts), C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p]
             L.clh_seed_link_rows.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(LinkOpts), C.c_void_p, C.c_void_p]
+        if hasattr(L, 'clh_seed_junction_batch'):        # absent from a CLH_LIB build older than the junction refinement: junctions() raises there
+            L.clh_seed_junction_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(JunctionOpts), C.POINTER(Splice),
+                                                  C.c_void_p, C.POINTER(C.c_float)]
+            L.clh_seed_junction_info.argtypes = [C.c_void_p]
+            L.clh_genome_letters.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.clh_band_plan_create.restype = C.c_void_p
         L.clh_band_plan_create.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BandOpts)]
         L.clh_band_plan_destroy.restype = None
@@ -1155,6 +1164,16 @@ class Genome(_Handle):
         _check(lib().clh_genome_count_n(self._h, n, off.ctypes.data, ln.ctypes.data, out.ctypes.data), 'clh_genome_count_n')
         return out
 
+    def letters(self, windows):
+        """the letters of windows [(contig, start, end)] as upper-case strings over ACGTN (short spans such as dinucleotides, any number of them: one gather on the device, one lane a span)"""
+        if not hasattr(lib(), 'clh_genome_letters'):
+            raise ClhError('Genome.letters: this libclh.so is older than the junction refinement')
+        off, ln = self._spans(windows)
+        out = np.zeros(max(int(ln.sum()), 1), dtype=np.int8)
+        _check(lib().clh_genome_letters(self._h, len(off), off.ctypes.data, ln.ctypes.data, out.ctypes.data), 'clh_genome_letters')
+        text, at = ''.join('ACGTN'[c] for c in out[:int(ln.sum())]), np.concatenate([[0], np.cumsum(ln)])
+        return [text[at[k]:at[k + 1]] for k in range(len(off))]
+
     def set_splice_sites(self, ss_index):
         """Annotated splice sites for splice_signals(): ss_index = {contig: {pos: {strand: {'start'|'end': 1}}}} (the
         reference's splice_site_index, align.py:235-252) or None.  Contigs that are not resident are ignored."""
@@ -1353,6 +1372,35 @@ class SeedIndex(_Handle):
         _check(lib().clh_seed_link_rows(self._h, nseg, mc, seg.ctypes.data, rows.ctypes.data, C.byref(lo), lseg.ctypes.data, lrows.ctypes.data),
                'clh_seed_link_rows')
         return {'link_seg': lseg, 'link_rows': lrows}
+
+    @staticmethod
+    def junction_info():
+        """K7j's geometry: class_bounds (the greatest m of each class; a class of bound 64 c gives a lane c rows), max_span, max_slack, the
+        waves (tasks) of a workgroup"""
+        if not hasattr(lib(), 'clh_seed_junction_info'):
+            raise ClhError('SeedIndex: this libclh.so is older than the junction refinement')
+        out = (C.c_int64 * 8)()
+        _check(lib().clh_seed_junction_info(out), 'clh_seed_junction_info')
+        return {'class_bounds': [int(v) for v in out[:int(out[7])]], 'max_span': int(out[4]), 'max_slack': int(out[5]), 'waves': int(out[6])}
+
+    def junctions(self, reads, tasks, match=2, mismatch=2, gap_open=3, gap_extend=1, intron_open=12, noncanonical=6, donor_costs=None, acceptor_costs=None,
+                  slack=16, max_span=512):
+        """back-splice junctions refined to the base (K7j; the definition: include/ciri_long_hip.h, tests/junction_check.py).  tasks [n, 8]:
+        read, minus, contig (its index), xd, yd, xa, ya, strand (+1, -1, 0 both) -> [n, 12] int64: status (0 refined, 1 m above max_span,
+        2 the anchors cross), score, strand (0 '+', 1 '-'), t, u, v, donor_end, acceptor_start, HL, HR, the start cost, the end cost.  The
+        costs are those of ``ssw_wrap.align_windows_spliced``.  last_junction_ms holds the kernels' HIP-event time."""
+        if not hasattr(lib(), 'clh_seed_junction_batch'):
+            raise ClhError('SeedIndex: this libclh.so is older than the junction refinement')
+        data, off = _packed(reads)
+        tasks = np.ascontiguousarray(tasks, dtype=np.int64).reshape(-1, 8)
+        sp = splice_of('junctions', intron_open, noncanonical, donor_costs, acceptor_costs)
+        o = JunctionOpts(int(match), int(mismatch), int(gap_open), int(gap_extend), int(slack), int(max_span))
+        out = np.zeros((len(tasks), 12), dtype=np.int64)
+        ms = C.c_float(0)
+        _check(lib().clh_seed_junction_batch(self._h, len(off) - 1, data.ctypes.data, off.ctypes.data, len(tasks), tasks.ctypes.data, C.byref(o), C.byref(sp),
+                                             out.ctypes.data, C.byref(ms)), 'clh_seed_junction_batch')
+        self.last_junction_ms = float(ms.value)
+        return out
 
 
 class Plan(_Handle):

@@ -9,7 +9,9 @@ minimap2: include/ciri_long_hip.h states them, tests/seed_check.py restates them
 One chain comes out per exon.  ``link_reads`` links the chains of a read into paths across introns and back-splice junctions, still on
 the device (csrc/seed_link.hip; tests/link_check.py is its plain statement), and ``map_spliced`` carries the best path through
 ``ssw_wrap.align_windows_spliced``: ``reads -> chains -> paths -> exons and circle`` with no external mapper and no host loop over
-rotations of the read."""
+rotations of the read.  ``refine_junctions`` names every back-splice junction of a path to the base (csrc/seed_junction.hip, K7j;
+tests/junction_check.py is its plain statement), ``call_circles`` makes ``contig:start-end`` with strand and splice signal of it, and
+``map_spliced(refine=True)`` cuts the pieces there."""
 import numpy as np
 
 from . import hip
@@ -135,7 +137,93 @@ def link_chains(index, chain_lists, read_lengths, min_path_score=0, **link_param
     return _paths(index, counts, rows, got['link_rows'], [int(v) for v in read_lengths], min_path_score)
 
 
-def map_spliced(index, reads, context=None, **parameters):
+_JUNCTION_KEYS = ('match', 'mismatch', 'gap_open', 'gap_extend', 'intron_open', 'noncanonical', 'donor_costs', 'acceptor_costs', 'slack', 'max_span')
+_COMPLEMENT = str.maketrans('ACGT', 'TGCA')
+
+
+def _junction_tasks(index, number, r, L, path):
+    """the task rows of SeedIndex.junctions for the back-splice links of one path of read r (L letters): the donor anchor is the start
+    of the source chain's last k-mer, the acceptor anchor the end of the target chain's first k-mer, both strands asked for; number:
+    contig name -> index"""
+    k, minus, out = index.k, path['minus'], []
+    for t, name in enumerate(path['links']):
+        if name == 'backsplice':
+            j, i = path['chains'][t], path['chains'][t + 1]
+            y1_j = L - j['query_start'] if minus else j['query_end']
+            y0_i = L - i['query_end'] if minus else i['query_start']
+            out.append((r, int(minus), number[path['contig']], j['ref_end'] - k, y1_j - k, i['ref_start'] + k, y0_i + k, 0))
+    return out
+
+
+def refine_junctions(index, reads, paths, **scoring):
+    """paths: what ``link_reads`` gave for these reads.  Every back-splice link of every path is refined to the base on the device
+    (``SeedIndex.junctions`` and its scoring keywords; K7j, the definition: include/ciri_long_hip.h) in one batch.  -> the paths, each
+    with ``junctions``: one dict per back-splice link, in the path's order:
+
+    status          0 refined; 1 more than max_span read letters between the anchors; 2 the anchors cross (then the rest is None)
+    score, strand   J of the definition; '+' / '-', the transcript's strand, from the splice signals
+    circle          (contig, acceptor_start, donor_end): the circle's 0-based start and exclusive end
+    read_pos        the split in the read as given: the first read_pos letters lie on one side of the junction
+    donor, acceptor the dinucleotides beside the circle as the transcript reads them, 'GT' and 'AG' at a canonical junction"""
+    data, off = hip._packed(reads)
+    lengths = np.diff(off).tolist()
+    out = [[dict(path) for path in mine] for mine in paths]
+    tasks, where = [], []
+    number = {name: c for c, name in enumerate(index.contigs)}
+    for r, mine in enumerate(out):
+        for path in mine:
+            path['junctions'] = []
+            for task in _junction_tasks(index, number, r, lengths[r], path):
+                tasks.append(task)
+                where.append(path)
+    if not tasks:
+        return out
+    rows = index.junctions((data, off), np.array(tasks, dtype=np.int64), **scoring)
+    windows = []
+    for task, row in zip(tasks, rows.tolist()):
+        if row[0] == 0:
+            name = index.contigs[task[2]]
+            size = index.genome.length[name]
+            windows += [(name, row[6], min(row[6] + 2, size)), (name, max(row[7] - 2, 0), row[7])]
+    flanks = iter(index.genome.letters(windows) if windows else [])
+    for task, row, path in zip(tasks, rows.tolist(), where):
+        if row[0] != 0:
+            path['junctions'].append({'status': row[0], 'score': None, 'strand': None, 'circle': None, 'read_pos': None, 'donor': None, 'acceptor': None})
+            continue
+        after, before = next(flanks), next(flanks)
+        if row[2]:
+            donor, acceptor = before.translate(_COMPLEMENT)[::-1], after.translate(_COMPLEMENT)[::-1]
+        else:
+            donor, acceptor = after, before
+        y = task[4] + row[3]
+        path['junctions'].append({'status': 0, 'score': row[1], 'strand': '-' if row[2] else '+', 'circle': (path['contig'], row[7], row[6]),
+                                  'read_pos': lengths[task[0]] - y if task[1] else y, 'donor': donor, 'acceptor': acceptor})
+    return out
+
+
+def call_circles(index, reads, **parameters):
+    """reads -> circles with no external mapper: ``link_reads`` (its parameters), then the back-splice junctions of each read's best path
+    refined (``refine_junctions`` and its scoring keywords).  Per read None where it has no path or no refined junction, else a dict from
+    the best-scoring refined junction of that path (the first among equals): circ_id 'contig:start-end' (1-based, inclusive), contig,
+    start (0-based), end (exclusive), strand, signal ('GT-AG' or the like: donor-acceptor as the transcript reads them), score, read_pos and
+    path (the refined path)."""
+    scoring = {name: parameters.pop(name) for name in _JUNCTION_KEYS if name in parameters}
+    data, off = hip._packed(reads)
+    best = [paths[:1] for paths in link_reads(index, (data, off), **parameters)]
+    out = []
+    for mine in refine_junctions(index, (data, off), best, **scoring):
+        done = [j for j in mine[0]['junctions'] if j['status'] == 0] if mine else []
+        if not done:
+            out.append(None)
+            continue
+        j = max(done, key=lambda v: v['score'])
+        contig, start, end = j['circle']
+        out.append({'circ_id': '%s:%d-%d' % (contig, start + 1, end), 'contig': contig, 'start': start, 'end': end, 'strand': j['strand'],
+                    'signal': '%s-%s' % (j['donor'], j['acceptor']), 'score': j['score'], 'read_pos': j['read_pos'], 'path': mine[0]})
+    return out
+
+
+def map_spliced(index, reads, context=None, refine=False, **parameters):
     """reads -> chains -> paths -> exons: link_reads (its parameters), then for the best path of each read every piece aligned between
     its outer anchors -- the query is the strand's read letters from the start of the piece's first chain to the end of its last, the
     window (contig, ref_start, ref_end) of the piece -- all pieces of all reads in one ``ssw_wrap.align_windows_spliced(mode='global',
@@ -144,12 +232,28 @@ def map_spliced(index, reads, context=None, **parameters):
     signals), score and cigar_string; a piece whose ref_end lies below its ref_start (chains that run backwards inside a colinear
     link's skew) is not aligned and carries None.
 
-    The ends of a piece are those of its outer anchors and are not refined: a back-splice junction lies up to w - 1 + the letters an
-    error took beyond them.  Refining the junction itself stays with the clip alignment and the splice scan (K6)."""
+    By default the ends of a piece are those of its outer anchors and are not refined: a back-splice junction lies up to w - 1 + the
+    letters an error took beyond them.  refine=True refines every back-splice of the best path first (``refine_junctions`` with the
+    alignment's scoring keywords, and slack, max_span): the path carries ``junctions``, and a piece that ends at a refined back-splice
+    (status 0) ends at its donor_end and at the split in the read, the piece behind it begins at acceptor_start and the split, so that
+    the exons of a circle tile it to the base; each piece is then aligned as before."""
     from . import ssw_wrap
+    junction = {name: parameters.pop(name) for name in ('slack', 'max_span') if refine and name in parameters}      # without refine: unknown keywords, as before
     align = {name: parameters.pop(name) for name in _ALIGN_KEYS if name in parameters}
     data, off = hip._packed(reads)
     best = [dict(paths[0]) if paths else None for paths in link_reads(index, (data, off), **parameters)]
+    if refine:
+        junction.update({name: v for name, v in align.items() if name in _JUNCTION_KEYS})
+        best = [mine[0] if mine else None for mine in refine_junctions(index, (data, off), [[p] if p else [] for p in best], **junction)]
+        for path in best:
+            if path is None:
+                continue
+            path['pieces'] = [dict(p) for p in path['pieces']]
+            for t, j in enumerate(path['junctions']):
+                if j['status'] == 0:
+                    left, right = path['pieces'][t], path['pieces'][t + 1]
+                    left['ref_end'], right['ref_start'] = j['circle'][2], j['circle'][1]
+                    left['query_start' if path['minus'] else 'query_end'] = right['query_end' if path['minus'] else 'query_start'] = j['read_pos']
     windows, queries, where = [], [], []
     for r, path in enumerate(best):
         if path is None:

@@ -242,6 +242,10 @@ const void* clh_genome_codes(const clh_genome* genome);      /* device pointer *
 int64_t clh_genome_length(const clh_genome* genome);
 /* out[k] = number of upper-case 'N' in [off[k], off[k]+len[k]) -- Counter(window)['N'] of find_bsj.py:199 */
 int clh_genome_count_n(clh_genome* genome, int32_t n, const int64_t* off, const int64_t* len, int64_t* out);
+/* the letters of the spans [off[k], off[k]+len[k]) as codes 0..4 (bits 0-2 of the resident byte, clamped to 4), packed one span behind
+ * the other into out: one gather on the device (one lane a span, so meant for short spans such as the dinucleotides beside refined
+ * junctions, many of them at once) and one copy back.  CLH_E_ARG: a span outside the genome. */
+int clh_genome_letters(clh_genome* genome, int32_t n, const int64_t* off, const int64_t* len, int8_t* out);
 /* Annotated splice sites for clh_splice_signal_batch: the reference's splice_site_index / circ_ss_idx
  * (CIRI_long/align.py:235-252, 275-316: index[contig][pos][strand]['start'|'end']) flattened to four runs of genome-wide
  * positions (contig offset in the resident genome + pos), each strictly ascending, concatenated in `pos` in the order
@@ -694,6 +698,45 @@ int clh_seed_link_batch(clh_seed_index* index, int32_t n, const int8_t* reads, c
                         const clh_link_opts* link_opts, int64_t* seg, int64_t* rows, int64_t* link_seg, int64_t* link_rows);
 int clh_seed_link_rows(clh_seed_index* index, int32_t nseg, int32_t max_chains, const int64_t* seg, const int64_t* rows, const clh_link_opts* link_opts,
                        int64_t* link_seg, int64_t* link_rows);
+
+/* ---- K7j: a back-splice junction refined to the base (csrc/seed_junction.hip) -------------------------------
+ * The plain statement is tests/junction_check.py.  The definition is the project's own; parity with find_bsj.py's rotate-and-map loop,
+ * clip alignment and sliding signal search is neither sought nor claimed.
+ *
+ * A task (8 int64: read, minus, contig, xd, yd, xa, ya, strand) is one back-splice, given by two anchor points on one contig and one
+ * strand of one read.  S is the read as the strand reads it: for minus != 0 the reverse complement of the read as given (codes below 4
+ * complemented, 4 stays 4), K7's y frame.  The donor anchor (xd, yd) is a point known to be aligned on the side the read leaves, the
+ * acceptor anchor (xa, ya) one on the side it re-enters; both x are relative to the contig.  From a link j -> i of kind 3 the anchors
+ * are xd = x1_j - k, yd = y1_j - k (the start of the source chain's last k-mer) and xa = x0_i + k, ya = y0_i + k (the end of the target
+ * chain's first k-mer).  With m = ya - yd:
+ *   Q = S[yd : ya);  D = contig[xd : min(xd + m + slack, contig_len)), nD letters forward from the donor anchor;
+ *   A = contig[max(0, xa - m - slack) : xa), nA letters up to the acceptor anchor.
+ * Genome letters are bits 0-2 of the resident byte, clamped to 4, the case dropped; no letter of a neighbouring contig is read.
+ *   HL[t][u], 0 <= t <= m, 0 <= u <= nD: the global affine score of Q[0:t) against D[0:u);
+ *   HR[t][v], 0 <= v <= nA: the global affine score of Q[t:m) against the last v letters of A;
+ * equal codes below 4 score +match, everything else (code 4 on either side included) -mismatch; a gap of g letters costs gap_open +
+ * (g - 1) gap_extend, gap_open >= gap_extend: K1g's one-piece recurrences with global boundaries.
+ * The skipped run starts at a = xd + u and ends at b = xa - v - 1, and clh_splice prices it as in clh_ends_plan_create_spliced: strand +:
+ * start = donor[r[a], r[a + 1]], end = acceptor[r[b - 1], r[b]]; strand -: start = acceptor[c(r[a + 1]), c(r[a])], end = donor[c(r[b]),
+ * c(r[b - 1])]; a dinucleotide that holds a code >= 4 or leaves the contig costs `other`.
+ *   J(s, t, u, v) = HL[t][u] + HR[t][v] - start_s(xd + u) - end_s(xa - v - 1) - intron_open
+ * and the answer is its maximum over the task's strands (strand +1, -1, or 0 for both); ties go to strand +, then the smallest t, then
+ * the smallest u, then the smallest v.
+ * out[n_tasks][12]: status, score, strand (0 +, 1 -), t, u, v, donor_end = xd + u (the circle's exclusive end), acceptor_start = xa - v
+ * (its 0-based start), HL[t][u], HR[t][v], the start cost, the end cost.  status 0: refined; 1: m > max_span, not attempted; 2: m < 1 or
+ * xa >= xd, the anchors cross (where both hold, 1); for 1 and 2 the other eleven words are 0.  With xa < xd, acceptor_start < donor_end.
+ * Limits: 1 <= max_span <= 512, 0 <= slack <= 64, every cost >= 0, and (2 max_span + slack) max(match, mismatch, gap_open, gap_extend) +
+ * intron_open + dmax + amax < 2^20 (dmax, amax the greatest donor and acceptor cost, `other` included): under it a side score less a site
+ * cost lies inside (-2^20, 2^20), and such a value and a column index share one 32-bit key in the kernel.  Outside these CLH_E_ARG;
+ * gap_open < gap_extend is CLH_E_UNSUPPORTED.  CLH_E_ARG, naming the first read or task: a read code outside 0..4; a read index or
+ * contig out of range, yd or ya outside [0, L], xd or xa outside [0, contig_len], a strand outside {-1, 0, 1}.  A row the kernel left
+ * unwritten is CLH_E_HIP, never returned.  n_tasks == 0 is success.  kernel_ms (may be NULL): HIP events around the kernels alone.
+ * clh_seed_junction_info, out[8]: the four class bounds on m (a class of bound 64 c gives a lane c rows), the greatest max_span, the
+ * greatest slack, the waves (tasks) of a workgroup, the number of classes. */
+typedef struct { int32_t match, mismatch, gap_open, gap_extend, slack, max_span; } clh_junction_opts;
+int clh_seed_junction_batch(clh_seed_index* index, int32_t n_reads, const int8_t* reads, const int64_t* read_off, int64_t n_tasks,
+                            const int64_t* task, const clh_junction_opts* opts, const clh_splice* splice, int64_t* out, float* kernel_ms);
+int clh_seed_junction_info(int64_t* out);
 
 
 /* ASCII -> codes exactly as ssw_wrap.py:234-252 (A/a C/c G/g T/t N/n, anything else 4), on the host. */
