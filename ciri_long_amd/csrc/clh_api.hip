@@ -3459,6 +3459,8 @@ struct clh_seed_index : clh_owned {
     float ms[5] = {0, 0, 0, 0, 0};
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     std::vector<uint64_t> h_mkeys, h_mvals, h_k1, h_k2;          // what the last minimizers / seeds call left for its fetch
+    hipEvent_t cev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // around the kernels of clh_seed_circle_batch
+    std::vector<int64_t> h_table;                                // what the last circles call left for clh_seed_circle_table_fetch
 };
 
 extern "C" void clh_seed_index_destroy(clh_seed_index* x) { delete x; }
@@ -3556,6 +3558,7 @@ extern "C" clh_seed_index* clh_seed_index_create(clh_genome* g, int32_t k, int32
     x->c_off.assign(contig_off, contig_off + n_contigs); x->c_len.assign(contig_len, contig_len + n_contigs);
     bool ok = true;
     for (auto& e : x->ev) ok = ok && x->event(&e) == hipSuccess;
+    for (auto& e : x->cev) ok = ok && x->event(&e) == hipSuccess;
     x->d_coff = (int64_t*)x->upload(x->c_off.data(), sizeof(int64_t) * (size_t)n_contigs);
     x->d_clen = (int64_t*)x->upload(x->c_len.data(), sizeof(int64_t) * (size_t)n_contigs);
     if (!ok || !x->d_coff || !x->d_clen) { fail(CLH_E_HIP, me + "out of device memory"); delete x; return nullptr; }
@@ -3684,10 +3687,165 @@ static int lk_validate(const std::string& me, int64_t s0, int64_t nseg, int32_t 
     return 0;
 }
 
+// what K7j admits of its scoring: clh_seed_junction_batch and clh_seed_circle_batch refuse the same
+static int jx_opts_check(const std::string& me, const clh_junction_opts* o, const clh_splice* sp)
+{
+    if (o->max_span < 1 || o->max_span > clh::kJxMaxSpan) return fail(CLH_E_ARG, me + "max_span must be 1.." + std::to_string(clh::kJxMaxSpan));
+    if (o->slack < 0 || o->slack > clh::kJxMaxSlack) return fail(CLH_E_ARG, me + "slack must be 0.." + std::to_string(clh::kJxMaxSlack));
+    int64_t dmax = sp->other, amax = sp->other;
+    bool neg = o->match < 0 || o->mismatch < 0 || o->gap_open < 0 || o->gap_extend < 0 || sp->intron_open < 0 || sp->other < 0;
+    for (int k = 0; k < 16; ++k) {
+        neg = neg || sp->donor[k] < 0 || sp->acceptor[k] < 0;
+        dmax = std::max<int64_t>(dmax, sp->donor[k]); amax = std::max<int64_t>(amax, sp->acceptor[k]);
+    }
+    if (neg) return fail(CLH_E_ARG, me + "match, mismatch, the gap costs, intron_open, the donor and acceptor costs and `other` must not be negative");
+    if (o->gap_open < o->gap_extend) return fail(CLH_E_UNSUPPORTED, me + "gap_open < gap_extend is not built");
+    const int64_t cmax = std::max<int64_t>(std::max(o->match, o->mismatch), std::max(o->gap_open, o->gap_extend));
+    if ((2 * (int64_t)o->max_span + o->slack) * cmax + sp->intron_open + dmax + amax >= clh::kJxBound)
+        return fail(CLH_E_ARG, me + "(2 max_span + slack) max(match, mismatch, gap_open, gap_extend) + intron_open + dmax + amax must stay below 2^20: a side score "
+                                    "less a site cost and a column index share one 32-bit key");
+    return 0;
+}
+
+// ---- K7c: what clh_seed_circle_batch adds to sd_seeds (seed_circle.hip) ------------------------------------------------------------
+// Declared by the caller BEFORE the call, as an SdEntries is: its host tables are uploaded asynchronously and outlive sd_seeds' SdBlocks.
+struct SdCircle {
+    const clh_junction_opts* jo = nullptr; const clh_splice* sp = nullptr;
+    int64_t min_path_score = 0;
+    int64_t* circle_out = nullptr; int64_t* cor_out = nullptr; int64_t* n_circles = nullptr;
+    std::vector<int64_t> h_roff;
+    std::vector<int32_t> site;
+    unsigned long long h_count[clh::kJxClasses] = {0, 0, 0, 0};
+    int64_t h_total = 0;
+    float ms[3] = {0, 0, 0};
+    clh::CcLaunch L; clh::JxLaunch J;
+    int64_t* d_jout = nullptr;
+    size_t slots_max = 0;                               // task slots of the largest share
+};
+
+// the buffers of the largest share and of the whole batch's circle rows
+static int cc_prepare(const std::string& me, clh_seed_index* x, SdBlocks& B, const uint8_t* d_reads, int32_t n, int32_t reads_max, int32_t max_chains, SdCircle* cc)
+{
+    hipStream_t st = x->ctx->stream;
+    memset(&cc->L, 0, sizeof cc->L); memset(&cc->J, 0, sizeof cc->J);
+    clh::CcLaunch& L = cc->L;
+    L.max_chains = max_chains; L.slots = max_chains > 1 ? max_chains - 1 : 1; L.k = x->k; L.n_contigs = (int32_t)x->c_off.size(); L.max_span = cc->jo->max_span;
+    L.min_path_score = cc->min_path_score;
+    cc->slots_max = (size_t)reads_max * (size_t)L.slots;
+    cc->site.assign(clh::kJxSites, 0);
+    sp_table(cc->sp, cc->site.data());
+    L.read_off = B.put(cc->h_roff);
+    L.genome = (const uint8_t*)x->genome->d_codes; L.ctg_off = x->d_coff; L.ctg_len = x->d_clen;
+    L.sel = B.get<int64_t>((size_t)clh::kCcSel * (size_t)reads_max);
+    L.task = B.get<int64_t>((size_t)clh::kJxTask * cc->slots_max);
+    L.cls = B.get<int32_t>(cc->slots_max);
+    L.count = B.get<unsigned long long>(2 * clh::kJxClasses);
+    L.order = B.get<int64_t>(cc->slots_max);
+    cc->d_jout = B.get<int64_t>((size_t)clh::kJxRow * cc->slots_max);
+    L.junction = cc->d_jout;
+    L.circle = B.get<int64_t>((size_t)clh::kCcRow * (size_t)n);
+    const int32_t* d_site = B.put(cc->site);
+    if (!L.read_off || !L.sel || !L.task || !L.cls || !L.count || !L.order || !cc->d_jout || !L.circle || !d_site) return sd_refused(me, B);
+    HIPCHK(hipMemsetAsync(L.circle, 0x80, sizeof(int64_t) * clh::kCcRow * (size_t)n, st));
+    clh::JxLaunch& J = cc->J;
+    J.genome = L.genome; J.ctg_off = L.ctg_off; J.ctg_len = L.ctg_len;
+    J.reads = (const int8_t*)d_reads; J.read_off = L.read_off; J.task = L.task; J.order = L.order; J.site = d_site; J.out = cc->d_jout;
+    const clh_junction_opts* o = cc->jo;
+    J.match = o->match; J.mismatch = o->mismatch; J.go = o->gap_open; J.ge = o->gap_extend; J.io = cc->sp->intron_open; J.slack = o->slack; J.max_span = o->max_span;
+    return 0;
+}
+
+// reads [a, b) of the batch, whose chain and link rows the two kernels in front have just left on the device: the best path and its tasks,
+// the class routing, K7j on them, the circle rows.  One copy of kJxClasses counters comes back in between: the junction launches are sized by them.
+static int cc_share(const std::string& me, clh_seed_index* x, SdCircle* cc, const clh::ChParams& C, const clh::LkLaunch& K, int32_t a, int32_t b)
+{
+    hipStream_t st = x->ctx->stream;
+    clh::CcLaunch& L = cc->L;
+    L.seg = C.seg; L.rows = C.rows; L.lseg = K.lseg; L.lrows = K.lrows; L.nreads = b - a; L.read0 = a;
+    const size_t slots = (size_t)L.nreads * (size_t)L.slots;
+    HIPCHK(hipMemsetAsync(L.count, 0, sizeof(unsigned long long) * 2 * clh::kJxClasses, st));
+    HIPCHK(hipMemsetAsync(L.sel, 0x80, sizeof(int64_t) * clh::kCcSel * (size_t)L.nreads, st));
+    HIPCHK(hipMemsetAsync(cc->d_jout, 0x80, sizeof(int64_t) * clh::kJxRow * slots, st));
+    HIPCHK(hipEventRecord(x->cev[0], st));
+    HIPCHK(clh::launch_seed_circle_select(L, st));
+    HIPCHK(clh::launch_seed_circle_route(L, st));
+    HIPCHK(hipEventRecord(x->cev[1], st));
+    HIPCHK(hipMemcpyAsync(cc->h_count, L.count, sizeof(unsigned long long) * clh::kJxClasses, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    clh::JxLaunch& J = cc->J;
+    J.first[0] = 0;
+    for (int c = 0; c < clh::kJxClasses; ++c) J.first[c + 1] = J.first[c] + (int64_t)cc->h_count[c];
+    if (J.first[clh::kJxClasses] < 0 || (size_t)J.first[clh::kJxClasses] > slots)
+        return fail(CLH_E_HIP, me + "the select kernel counted " + std::to_string(J.first[clh::kJxClasses]) + " tasks in " + std::to_string(slots) + " slots");
+    cc->h_total += J.first[clh::kJxClasses];
+    HIPCHK(hipEventRecord(x->cev[2], st));
+    HIPCHK(clh::launch_seed_junction(J, st));
+    HIPCHK(hipEventRecord(x->cev[3], st));
+    HIPCHK(clh::launch_seed_circle_finalise(L, st));
+    HIPCHK(hipEventRecord(x->cev[4], st));
+    return 0;
+}
+
+// after the last share: the table of the whole batch's rows, and everything that goes back to the host
+static int cc_table(const std::string& me, clh_seed_index* x, SdBlocks& B, int32_t n, SdCircle* cc)
+{
+    hipStream_t st = x->ctx->stream;
+    *cc->n_circles = 0;
+    x->h_table.clear();
+    if (n <= 0) return 0;
+    const size_t N = (size_t)n;
+    const int64_t* d_circle = cc->L.circle;
+    uint64_t* d_w[5];                                   // key_lo, key_hi, reads; two more for the sorts' outputs
+    for (auto& p : d_w) p = B.get<uint64_t>(N);
+    uint64_t* d_perm = B.get<uint64_t>(N);
+    int32_t* d_head = B.get<int32_t>(N + 1);
+    int64_t* d_first = B.get<int64_t>(N + 1);
+    int64_t* d_table = B.get<int64_t>((size_t)clh::kCcTable * N);
+    int64_t* d_cor = B.get<int64_t>(N);
+    const size_t sb = clh::seed_sort_temp_bytes(n), tb = clh::seed_scan_temp_bytes(n + 1);
+    void* d_sort = B.get<uint8_t>(sb);
+    void* d_scan = B.get<uint8_t>(tb);
+    if (!d_w[0] || !d_w[1] || !d_w[2] || !d_w[3] || !d_w[4] || !d_perm || !d_head || !d_first || !d_table || !d_cor || !d_sort || !d_scan) return sd_refused(me, B);
+    HIPCHK(hipMemsetAsync(d_cor, 0x80, sizeof(int64_t) * N, st));
+    HIPCHK(hipEventRecord(x->cev[5], st));
+    HIPCHK(clh::launch_seed_circle_keys(d_circle, n, d_w[0], d_w[1], d_w[2], st));
+    // least significant first: (end, strand), then (contig, start) with the rows of another status last; both sorts stable
+    HIPCHK(clh::seed_sort_pairs(d_sort, sb, d_w[0], d_w[3], d_w[2], d_w[4], n, 42, st));
+    HIPCHK(clh::launch_seed_circle_gather(d_w[1], d_w[4], n, d_w[0], st));
+    HIPCHK(clh::seed_sort_pairs(d_sort, sb, d_w[0], d_w[3], d_w[4], d_perm, n, 64, st));
+    HIPCHK(clh::launch_seed_circle_heads(d_circle, d_perm, n, d_head, st));
+    HIPCHK(clh::seed_scan_counts(d_scan, tb, d_head, d_first, (int64_t)n + 1, st));
+    HIPCHK(clh::launch_seed_circle_table(d_circle, d_perm, d_head, d_first, n, d_table, d_cor, st));
+    HIPCHK(hipEventRecord(x->cev[6], st));
+    int64_t groups = 0;
+    HIPCHK(hipMemcpyAsync(&groups, d_first + n, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(cc->circle_out, d_circle, sizeof(int64_t) * clh::kCcRow * N, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(cc->cor_out, d_cor, sizeof(int64_t) * N, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    float t = 0;
+    HIPCHK(hipEventElapsedTime(&t, x->cev[5], x->cev[6]));
+    cc->ms[2] += t;
+    if (groups < 0 || groups > n) return fail(CLH_E_HIP, me + "the table step left " + std::to_string(groups) + " circles of " + std::to_string(n) + " reads");
+    int64_t found = 0;
+    for (int32_t r = 0; r < n; ++r) {
+        const int64_t* c = cc->circle_out + (size_t)clh::kCcRow * (size_t)r;
+        if (c[0] < clh::kCcFound || c[0] > clh::kCcNoJunction || c[15] != 0)
+            return fail(CLH_E_HIP, me + "the circle kernels left read " + std::to_string(r) + (c[0] == clh::kChUnwritten ? " unwritten" : " with status " + std::to_string(c[0])));
+        const int64_t g = cc->cor_out[r];
+        if (c[0] == clh::kCcFound ? (g < 0 || g >= groups) : g != -1) return fail(CLH_E_HIP, me + "the table step left read " + std::to_string(r) + " in row " + std::to_string(g));
+        found += c[0] == clh::kCcFound;
+    }
+    if ((found > 0) != (groups > 0)) return fail(CLH_E_HIP, me + "the table step left " + std::to_string(groups) + " circles of " + std::to_string(found) + " reads with one");
+    x->h_table.assign((size_t)clh::kCcTable * (size_t)groups, 0);
+    if (groups > 0) HIPCHK(hipMemcpy(x->h_table.data(), d_table, sizeof(int64_t) * clh::kCcTable * (size_t)groups, hipMemcpyDeviceToHost));
+    *cc->n_circles = groups;
+    return 0;
+}
+
 // seeds, and chains where o is given, and their links where lo is: the anchors and the chain rows of a share stay on the device between the steps
 static int sd_seeds(const std::string& me, clh_seed_index* x, int32_t n, const int8_t* reads, const int64_t* read_off, int64_t workspace_bytes, int64_t* anchor_off,
                     int32_t* repetitive, const clh_chain_opts* o, int64_t* seg_out, int64_t* rows_out, const clh_link_opts* lo = nullptr, int64_t* lseg_out = nullptr,
-                    int64_t* lrows_out = nullptr)
+                    int64_t* lrows_out = nullptr, SdCircle* cc = nullptr)
 {
     clh_ctx* ctx = x->ctx;
     hipStream_t st = ctx->stream;
@@ -3769,6 +3927,8 @@ static int sd_seeds(const std::string& me, clh_seed_index* x, int32_t n, const i
         K.lseg = B.get<int64_t>((size_t)clh::kLkSeg * 2 * (size_t)reads_max); K.lrows = B.get<int64_t>((size_t)clh::kLkRow * (size_t)o->max_chains * 2 * (size_t)reads_max);
         if (!K.lseg || !K.lrows) return sd_refused(me, B);
     }
+    if (cc)
+        if (int rc = cc_prepare(me, x, B, R.d_codes, n, reads_max, o->max_chains, cc)) return rc;
     const int bits_x = sd_bits((uint64_t)(x->genome->len > 0 ? x->genome->len : 1)) + clh::kSdYBits, bits_r = sd_bits(2 * (uint64_t)(n > 0 ? n : 1));
     for (size_t s = 0; s + 1 < cut.size(); ++s) {
         const int32_t a = cut[s], b = cut[s + 1];
@@ -3800,18 +3960,30 @@ static int sd_seeds(const std::string& me, clh_seed_index* x, int32_t n, const i
                 HIPCHK(hipEventRecord(x->ev[4], st));     // the link slot times the kernel alone, not the marker fill
                 HIPCHK(clh::launch_seed_link(K, st));
                 HIPCHK(hipEventRecord(x->ev[3], st));
-                HIPCHK(hipMemcpyAsync(lseg_out + (size_t)clh::kLkSeg * 2 * (size_t)a, K.lseg, lsg, hipMemcpyDeviceToHost, st));
-                HIPCHK(hipMemcpyAsync(lrows_out + (size_t)clh::kLkRow * (size_t)o->max_chains * 2 * (size_t)a, K.lrows, lrw, hipMemcpyDeviceToHost, st));
+                if (cc) {                               // the rows stay where they are: select, tasks, K7j and the circle rows behind the link kernel
+                    if (int rc = cc_share(me, x, cc, C, K, a, b)) return rc;
+                } else {
+                    HIPCHK(hipMemcpyAsync(lseg_out + (size_t)clh::kLkSeg * 2 * (size_t)a, K.lseg, lsg, hipMemcpyDeviceToHost, st));
+                    HIPCHK(hipMemcpyAsync(lrows_out + (size_t)clh::kLkRow * (size_t)o->max_chains * 2 * (size_t)a, K.lrows, lrw, hipMemcpyDeviceToHost, st));
+                }
             }
-            HIPCHK(hipMemcpyAsync(seg_out + (size_t)clh::kChSeg * 2 * (size_t)a, C.seg, sg, hipMemcpyDeviceToHost, st));
-            HIPCHK(hipMemcpyAsync(rows_out + (size_t)clh::kChRow * (size_t)o->max_chains * 2 * (size_t)a, C.rows, rw, hipMemcpyDeviceToHost, st));
+            if (!cc) {
+                HIPCHK(hipMemcpyAsync(seg_out + (size_t)clh::kChSeg * 2 * (size_t)a, C.seg, sg, hipMemcpyDeviceToHost, st));
+                HIPCHK(hipMemcpyAsync(rows_out + (size_t)clh::kChRow * (size_t)o->max_chains * 2 * (size_t)a, C.rows, rw, hipMemcpyDeviceToHost, st));
+            }
         }
         HIPCHK(hipStreamSynchronize(st));
+        if (cc) {
+            HIPCHK(hipEventElapsedTime(&t, x->cev[0], x->cev[1])); cc->ms[0] += t;
+            HIPCHK(hipEventElapsedTime(&t, x->cev[2], x->cev[3])); cc->ms[1] += t;
+            HIPCHK(hipEventElapsedTime(&t, x->cev[3], x->cev[4])); cc->ms[2] += t;
+        }
         HIPCHK(hipEventElapsedTime(&t, x->ev[0], x->ev[1]));
         x->ms[2] += t;
         if (o) { HIPCHK(hipEventElapsedTime(&t, x->ev[1], x->ev[2])); x->ms[3] += t; }
         if (lo) { HIPCHK(hipEventElapsedTime(&t, x->ev[4], x->ev[3])); x->ms[4] += t; }
     }
+    if (cc) return cc_table(me, x, B, n, cc);          // the select kernel checked the headers and rows where they lay
     if (o)
         for (int64_t s = 0; s < 2 * (int64_t)n; ++s) {
             const int64_t* h = seg_out + clh::kChSeg * s;
@@ -3933,20 +4105,7 @@ extern "C" int clh_seed_junction_batch(clh_seed_index* x, int32_t n_reads, const
     const std::string me = "clh_seed_junction_batch: ";
     if (kernel_ms) *kernel_ms = 0;
     if (!x || !o || !sp || n_reads < 0 || n_tasks < 0 || !read_off || (n_tasks > 0 && (!task || !out))) return fail(CLH_E_ARG, me + "null argument");
-    if (o->max_span < 1 || o->max_span > clh::kJxMaxSpan) return fail(CLH_E_ARG, me + "max_span must be 1.." + std::to_string(clh::kJxMaxSpan));
-    if (o->slack < 0 || o->slack > clh::kJxMaxSlack) return fail(CLH_E_ARG, me + "slack must be 0.." + std::to_string(clh::kJxMaxSlack));
-    int64_t dmax = sp->other, amax = sp->other;
-    bool neg = o->match < 0 || o->mismatch < 0 || o->gap_open < 0 || o->gap_extend < 0 || sp->intron_open < 0 || sp->other < 0;
-    for (int k = 0; k < 16; ++k) {
-        neg = neg || sp->donor[k] < 0 || sp->acceptor[k] < 0;
-        dmax = std::max<int64_t>(dmax, sp->donor[k]); amax = std::max<int64_t>(amax, sp->acceptor[k]);
-    }
-    if (neg) return fail(CLH_E_ARG, me + "match, mismatch, the gap costs, intron_open, the donor and acceptor costs and `other` must not be negative");
-    if (o->gap_open < o->gap_extend) return fail(CLH_E_UNSUPPORTED, me + "gap_open < gap_extend is not built");
-    const int64_t cmax = std::max<int64_t>(std::max(o->match, o->mismatch), std::max(o->gap_open, o->gap_extend));
-    if ((2 * (int64_t)o->max_span + o->slack) * cmax + sp->intron_open + dmax + amax >= clh::kJxBound)
-        return fail(CLH_E_ARG, me + "(2 max_span + slack) max(match, mismatch, gap_open, gap_extend) + intron_open + dmax + amax must stay below 2^20: a side score "
-                                    "less a site cost and a column index share one 32-bit key");
+    if (int rc = jx_opts_check(me, o, sp)) return rc;
     if (read_off[0] < 0) return fail(CLH_E_ARG, me + "offsets must ascend from 0 or above");
     for (int32_t r = 0; r < n_reads; ++r)
         if (read_off[r + 1] < read_off[r]) return fail(CLH_E_ARG, me + "offsets must ascend");
@@ -4011,6 +4170,42 @@ extern "C" int clh_seed_junction_batch(clh_seed_index* x, int32_t n_reads, const
         if (r[0] == 0 && (r[3] < 0 || r[3] > k[6] - k[4] || r[4] < 0 || r[5] < 0 || r[6] > x->c_len[(size_t)k[2]] || r[7] < 0 || r[7] >= r[6]))
             return fail(CLH_E_HIP, me + "the junction kernel left the row of task " + std::to_string(t) + " out of range");
     }
+    return 0;
+}
+
+// ---- K7c: the circles of a read batch in one device pass (seed_circle.hip; the definitions in seed_device.h and the header) --------
+extern "C" int clh_seed_circle_batch(clh_seed_index* x, int32_t n, const int8_t* reads, const int64_t* read_off, const clh_chain_opts* o, const clh_link_opts* lo,
+                                     const clh_junction_opts* jo, const clh_splice* sp, int64_t min_path_score, int64_t* circle, int64_t* circle_of_read,
+                                     int64_t* n_circles, float* kernel_ms)
+{
+    const std::string me = "clh_seed_circle_batch: ";
+    if (kernel_ms) kernel_ms[0] = kernel_ms[1] = kernel_ms[2] = 0;
+    if (!x || !o || !lo || !jo || !sp || !n_circles || !read_off || n < 0 || (n > 0 && (!circle || !circle_of_read))) return fail(CLH_E_ARG, me + "null argument");
+    *n_circles = 0;
+    x->h_table.clear();
+    if (o->lookback < 1 || o->lookback > clh::kChLookbackMax) return fail(CLH_E_ARG, me + "lookback must be 1..64");
+    if (o->max_chains < 1 || o->max_chains > clh::kChMaxChains) return fail(CLH_E_ARG, me + "max_chains must be 1..64");
+    if (o->max_attempts < 1 || o->max_gap < 0 || o->max_skew < 0) return fail(CLH_E_ARG, me + "max_attempts must be at least 1, max_gap and max_skew not negative");
+    if (int rc = lk_opts_check(me, lo)) return rc;
+    if (int rc = jx_opts_check(me, jo, sp)) return rc;
+    if (x->c_off.size() >= ((size_t)1 << clh::kCcContigBits)) return fail(CLH_E_CAPACITY, me + "an index of 2^23 contigs or more: the table's sort word holds 23 bits of them");
+    if (n == 0) return read_off[0] < 0 ? fail(CLH_E_ARG, me + "offsets must ascend from 0 or above") : 0;
+    SdCircle cc;                                        // before sd_seeds' SdBlocks: see SdEntries
+    cc.jo = jo; cc.sp = sp; cc.min_path_score = min_path_score; cc.circle_out = circle; cc.cor_out = circle_of_read; cc.n_circles = n_circles;
+    cc.h_roff.assign(read_off, read_off + (size_t)n + 1);
+    const int rc = sd_seeds(me, x, n, reads, read_off, o->workspace_bytes, nullptr, nullptr, o, nullptr, nullptr, lo, nullptr, nullptr, &cc);
+    if (rc) { x->h_table.clear(); *n_circles = 0; return rc; }
+    if (kernel_ms) for (int i = 0; i < 3; ++i) kernel_ms[i] = cc.ms[i];
+    return 0;
+}
+
+extern "C" int clh_seed_circle_table_fetch(clh_seed_index* x, int64_t cap, int64_t* table)
+{
+    if (!x) return fail(CLH_E_ARG, "clh_seed_circle_table_fetch: null argument");
+    const int64_t m = (int64_t)(x->h_table.size() / clh::kCcTable);
+    if (cap < m) return fail(CLH_E_CAPACITY, "clh_seed_circle_table_fetch: cap too small");
+    if (m > 0 && !table) return fail(CLH_E_ARG, "clh_seed_circle_table_fetch: null argument");
+    for (size_t i = 0; i < x->h_table.size(); ++i) table[i] = x->h_table[i];
     return 0;
 }
 

@@ -1,6 +1,6 @@
-// seed_device.h -- K7: what the host side, the sketch, look-up and chain kernels (seed.hip), the link and junction kernels (seed_link.hip,
-// seed_junction.hip), the sort plumbing (seed_sort.hip) and the stand-alone host programs tests/seed_host.hip, link_host.hip and
-// junction_host.hip share.  The definitions are those of DESIGN.md section 4 (K7): they are independent of
+// seed_device.h -- K7: what the host side, the sketch, look-up and chain kernels (seed.hip), the link, junction and circle kernels
+// (seed_link.hip, seed_junction.hip, seed_circle.hip), the sort plumbing (seed_sort.hip) and the stand-alone host programs
+// tests/seed_host.hip, link_host.hip, junction_host.hip and circle_host.hip share.  The definitions are those of DESIGN.md section 4 (K7): they are independent of
 // the order in which positions are visited, so that the kernels and the plain checker tests/seed_check.py agree bit for bit.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -189,6 +189,117 @@ hipError_t launch_seed_junction(const JxLaunch& l, hipStream_t stream);
 // the letters (jx_letter's codes) of n short spans of the genome: span i is len[i] bytes from off[i] and goes to out + at[i]; one lane a span
 hipError_t launch_genome_letters(const uint8_t* genome, int64_t genome_len, const int64_t* off, const int64_t* len, const int64_t* at, int64_t n, int8_t* out,
                                  hipStream_t stream);
+
+// ---- the circles of a read batch (seed_circle.hip; tests/circle_check.py) ---------------------------------
+static constexpr int kCcRow = 16, kCcTable = 10;        // int64 per circle row (one per read) / per table row (one per distinct circle)
+static constexpr int kCcSel = 8;                        // int64 per read between select and finalise: state, minus, score, chains, links, 0, 0, 0
+static constexpr int kCcWaves = 4;                      // reads of one workgroup of the select kernel: the waves share nothing
+static constexpr int kCcContigBits = 23;                // the table's sort word is (another status) << 63 | contig << 40 | start
+enum { kCcFound = 0, kCcNoPath = 1, kCcNoBacksplice = 2, kCcNoJunction = 3, kCcBad = 4 };      // kCcBad never leaves the device: the row stays unwritten
+static constexpr int64_t kCcNoScore = INT64_MIN;        // a lane without a candidate path
+
+// The best path of a read is the least under (-score, minus, x_first of its pos-0 chain, path index); the last three make one word.
+__host__ __device__ inline uint64_t cc_tie_key(int minus, int64_t x_first, int path)
+{
+    return ((uint64_t)(minus != 0) << 46) | ((uint64_t)x_first << 6) | (uint64_t)path;       // x_first in [0, 2^40), path in [0, 64)
+}
+__host__ __device__ inline bool cc_path_before(int64_t score_a, uint64_t key_a, int64_t score_b, uint64_t key_b)
+{
+    return score_a != score_b ? score_a > score_b : key_a < key_b;
+}
+// The best of the candidate paths of one read, stated serially over its two segments one after the other (the statement that
+// tests/circle_host.hip runs; seed_circle_select_kernel reduces the same (score, key) pairs per lane and across the wave): lrows_m / rows_m are the link and the
+// chain rows of segment m (n_m of them); a candidate is a chain with pos == 0 whose path scores at least min_path_score.
+// -> true and (score, key) of the best, or false
+__host__ __device__ inline bool cc_best_path(const int64_t* const lrows[2], const int64_t* const rows[2], const int n[2], int64_t min_path_score, int64_t* score,
+                                             uint64_t* key)
+{
+    bool any = false;
+    for (int m = 0; m < 2; ++m)
+        for (int c = 0; c < n[m]; ++c) {
+            const int64_t* lr = lrows[m] + (int64_t)c * kLkRow;
+            if (lr[5] != 0 || lr[6] < min_path_score) continue;
+            const uint64_t kc = cc_tie_key(m, rows[m][(int64_t)c * kChRow + 5], (int)lr[4]);
+            if (!any || cc_path_before(lr[6], kc, *score, *key)) { *score = lr[6]; *key = kc; any = true; }
+        }
+    return any;
+}
+// the K7j task of the back-splice link j -> i of read `read` on strand `minus`: row_j, row_i are the two chain rows (kChRow)
+__host__ __device__ inline void cc_task(int64_t read, int minus, const int64_t* row_j, const int64_t* row_i, int k, int64_t* task)
+{
+    task[0] = read; task[1] = minus; task[2] = row_i[2];
+    task[3] = row_j[7] - k; task[4] = row_j[8] - k;     // the donor anchor: the start of the source chain's last k-mer
+    task[5] = row_i[5] + k; task[6] = row_i[6] + k;     // the acceptor anchor: the end of the target chain's first k-mer
+    task[7] = 0;
+}
+// what clh_seed_junction_batch admits of a task: L the read's letters, len the contig's
+__host__ __device__ inline bool cc_task_ok(const int64_t* task, int64_t L, int64_t len)
+{
+    return task[4] >= 0 && task[4] <= L && task[6] >= 0 && task[6] <= L && task[3] >= 0 && task[3] <= len && task[5] >= 0 && task[5] <= len;
+}
+// the ordinal of the link into the chain at `pos` among the path's back-splice links: mask has bit p set for every such chain at pos p
+__host__ __device__ inline int cc_ordinal(uint64_t mask, int pos) { return __builtin_popcountll(mask & (((uint64_t)1 << pos) - 1)); }
+// the winner among the cnt K7j rows of a path, in path order: the greatest J of status 0, the first among equals; -1 where none is refined
+__host__ __device__ inline int cc_winner(const int64_t* jrows, int cnt, int* refined)
+{
+    int best = -1;
+    *refined = 0;
+    for (int t = 0; t < cnt; ++t) {
+        const int64_t* r = jrows + (int64_t)t * kJxRow;
+        if (r[0] != 0) continue;
+        ++*refined;
+        if (best < 0 || r[1] > jrows[(int64_t)best * kJxRow + 1]) best = t;
+    }
+    return best;
+}
+// the dinucleotide at contig positions (p, p + 1) as 5 c0 + c1 (jx_letter's codes); -1 where fewer than two of its letters lie inside the contig
+__host__ __device__ inline int cc_dinuc(const uint8_t* genome, int64_t off, int64_t len, int64_t p)
+{
+    if (p < 0 || p + 2 > len) return -1;
+    return 5 * jx_letter(genome, off, len, p) + jx_letter(genome, off, len, p + 1);
+}
+__host__ __device__ inline int cc_dinuc_revcomp(int code)
+{
+    if (code < 0) return -1;
+    const int c0 = code / 5, c1 = code % 5;
+    return 5 * (c1 < 4 ? 3 - c1 : 4) + (c0 < 4 ? 3 - c0 : 4);
+}
+// donor and acceptor codes of the circle [start, end) on transcript strand `sminus`, as the transcript reads them
+__host__ __device__ inline void cc_flanks(const uint8_t* genome, int64_t off, int64_t len, int64_t start, int64_t end, int sminus, int* donor, int* acceptor)
+{
+    const int after = cc_dinuc(genome, off, len, end), before = cc_dinuc(genome, off, len, start - 2);
+    *donor = sminus ? cc_dinuc_revcomp(before) : after;
+    *acceptor = sminus ? cc_dinuc_revcomp(after) : before;
+}
+// the split in the read as given: y = yd + t in the read as the strand reads it
+__host__ __device__ inline int64_t cc_read_pos(int64_t L, int64_t yd, int64_t t, int minus) { return minus ? L - (yd + t) : yd + t; }
+
+// All device pointers.  The share holds reads [read0, read0 + nreads): seg, rows, lseg, lrows are the chain and link rows of its 2 nreads
+// segments; read r of the share owns the task slots [r slots, (r + 1) slots), slots = max(max_chains - 1, 1), of which the first
+// sel[r][4] are filled in path order.  cls[slot] is the K7j class of a filled slot and -1 of an empty one; count[c] (zeroed by the caller)
+// receives the tasks of class c; order and first[] of the JxLaunch are made of them by launch_seed_circle_route.
+struct CcLaunch {
+    const int64_t* seg; const int64_t* rows; const int64_t* lseg; const int64_t* lrows;
+    int32_t nreads, read0, max_chains, slots, k, n_contigs, max_span;
+    int64_t min_path_score;
+    const int64_t* read_off;                            // [reads of the batch + 1]
+    const uint8_t* genome; const int64_t* ctg_off; const int64_t* ctg_len;
+    int64_t* sel; int64_t* task; int32_t* cls;
+    unsigned long long* count;                          // [2 kJxClasses]: the tasks of each class, then the route kernel's cursors
+    int64_t* order;                                     // [nreads slots]
+    const int64_t* junction;                            // [nreads slots][kJxRow]: what K7j left
+    int64_t* circle;                                    // [reads of the batch][kCcRow], marker-filled by the caller
+};
+hipError_t launch_seed_circle_select(const CcLaunch& l, hipStream_t stream);
+hipError_t launch_seed_circle_route(const CcLaunch& l, hipStream_t stream);
+hipError_t launch_seed_circle_finalise(const CcLaunch& l, hipStream_t stream);
+// The table of n circle rows: sort words, the gather between the two sort passes, head flags, and the scatter.  perm is the reads in
+// ascending (contig, start, end, strand) with the rows of another status last; head[n + 1] and first[n + 1] its flags and their exclusive scan.
+hipError_t launch_seed_circle_keys(const int64_t* circle, int64_t n, uint64_t* key_lo, uint64_t* key_hi, uint64_t* read, hipStream_t stream);
+hipError_t launch_seed_circle_gather(const uint64_t* key_hi, const uint64_t* perm, int64_t n, uint64_t* out, hipStream_t stream);
+hipError_t launch_seed_circle_heads(const int64_t* circle, const uint64_t* perm, int64_t n, int32_t* head, hipStream_t stream);
+hipError_t launch_seed_circle_table(const int64_t* circle, const uint64_t* perm, const int32_t* head, const int64_t* first, int64_t n, int64_t* table,
+                                    int64_t* circle_of_read, hipStream_t stream);
 
 // ---- launches (seed.hip) ------------------------------------------------------------------------------------------------------
 // The sequences of one sketch: sequence s is the len[s] bytes from off[s] of `codes`; its positions [0, len - k] are cut into work items of

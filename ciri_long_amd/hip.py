@@ -288,6 +288,10 @@ def lib():
                                                   C.c_void_p, C.POINTER(C.c_float)]
             L.clh_seed_junction_info.argtypes = [C.c_void_p]
             L.clh_genome_letters.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, 'clh_seed_circle_batch'):          # absent from a CLH_LIB build older than the circles of a batch: circles() raises there
+            L.clh_seed_circle_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(ChainOpts), C.POINTER(LinkOpts), C.POINTER(JunctionOpts),
+                                                C.POINTER(Splice), C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p]
+            L.clh_seed_circle_table_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
         L.clh_band_plan_create.restype = C.c_void_p
         L.clh_band_plan_create.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BandOpts)]
         L.clh_band_plan_destroy.restype = None
@@ -1401,6 +1405,35 @@ class SeedIndex(_Handle):
                                              out.ctypes.data, C.byref(ms)), 'clh_seed_junction_batch')
         self.last_junction_ms = float(ms.value)
         return out
+
+    def circles(self, reads, min_path_score=0, lookback=64, max_gap=5000, max_skew=500, min_score=40, min_anchors=3, max_chains=32, max_attempts=None,
+                workspace_bytes=0, max_query_gap=500, max_overlap=32, max_intron=200000, max_circle=200000, intron_cost=16, backsplice_cost=32, match=2,
+                mismatch=2, gap_open=3, gap_extend=1, intron_open=12, noncanonical=6, donor_costs=None, acceptor_costs=None, slack=16, max_span=512):
+        """the circles of a batch of reads in one device pass (K7c; the definition: include/ciri_long_hip.h, tests/circle_check.py): links()
+        and its keywords, the best path of every read with a score of at least min_path_score, junctions() and its keywords on that path's
+        back-splice links, the winner's flanks, and the table of the distinct circles; the paths and the tasks stay on the device ->
+        dict of arrays: circle [n, 16] int64 (status 0 a circle / 1 no path / 2 no back-splice in the best path / 3 none refined, contig,
+        start, end, strand, donor code, acceptor code, J, read_pos, the path's minus, score, chains, back-splice links, those refined, the
+        winner's ordinal, 0; a dinucleotide code is 5 c0 + c1, -1 where it leaves the contig), circle_of_read [n] (the read's row of the
+        table, -1 without a circle), table [n_circles, 10] (contig, start, end, strand, donor, acceptor, reads, the greatest J, the lowest
+        read, 0; ascending), kernel_ms (HIP events: select and task build, the junction kernels, finalise and table)"""
+        if not hasattr(lib(), 'clh_seed_circle_batch'):
+            raise ClhError('SeedIndex: this libclh.so is older than the circles of a batch')
+        data, off = _packed(reads)
+        n = len(off) - 1
+        lo = self._link_opts(max_query_gap, max_overlap, max_skew, max_intron, max_circle, intron_cost, backsplice_cost)
+        o = ChainOpts(int(lookback), int(max_chains), int(8 * max_chains if max_attempts is None else max_attempts), int(min_score), int(min_anchors), 0,
+                      int(max_gap), int(max_skew), int(workspace_bytes))
+        sp = splice_of('circles', intron_open, noncanonical, donor_costs, acceptor_costs)
+        jo = JunctionOpts(int(match), int(mismatch), int(gap_open), int(gap_extend), int(slack), int(max_span))
+        circle, of_read = np.zeros((n, 16), dtype=np.int64), np.zeros(n, dtype=np.int64)
+        count = C.c_int64(0)
+        ms = (C.c_float * 3)()
+        _check(lib().clh_seed_circle_batch(self._h, n, data.ctypes.data, off.ctypes.data, C.byref(o), C.byref(lo), C.byref(jo), C.byref(sp), int(min_path_score),
+                                           circle.ctypes.data, of_read.ctypes.data, C.byref(count), ms), 'clh_seed_circle_batch')
+        table = np.zeros((int(count.value), 10), dtype=np.int64)
+        _check(lib().clh_seed_circle_table_fetch(self._h, int(count.value), table.ctypes.data), 'clh_seed_circle_table_fetch')
+        return {'circle': circle, 'circle_of_read': of_read, 'table': table, 'kernel_ms': np.array([float(v) for v in ms], dtype=np.float32)}
 
 
 class Plan(_Handle):

@@ -223,6 +223,53 @@ def call_circles(index, reads, **parameters):
     return out
 
 
+def _signals(index, rows):
+    """rows [m, >= 6] of contig, start, end, strand, donor code, acceptor code (a circle row from word 1, or a table row) -> 'GT-AG' or
+    the like per row.  A code is 5 c0 + c1; -1 stands where the dinucleotide leaves the contig, and the letters that remain inside it are
+    then read from the resident genome as ``refine_junctions`` reads them"""
+    text = [['ACGTN'[c // 5] + 'ACGTN'[c % 5] if c >= 0 else None for c in (int(row[4]), int(row[5]))] for row in rows]
+    windows, where = [], []
+    for t, row in enumerate(rows):
+        if None in text[t]:
+            name = index.contigs[int(row[0])]
+            windows += [(name, int(row[2]), min(int(row[2]) + 2, index.genome.length[name])), (name, max(int(row[1]) - 2, 0), int(row[1]))]
+            where.append(t)
+    flanks = iter(index.genome.letters(windows) if windows else [])
+    for t in where:
+        after, before = next(flanks), next(flanks)
+        text[t] = [before.translate(_COMPLEMENT)[::-1], after.translate(_COMPLEMENT)[::-1]] if rows[t][3] else [after, before]
+    return ['%s-%s' % (d, a) for d, a in text]
+
+
+def call_circles_batch(index, reads, **parameters):
+    """reads -> the sample's circles in one device pass (``SeedIndex.circles`` and its keywords: those of ``link_reads`` with
+    min_path_score, and the scoring keywords of ``refine_junctions``; K7c, the definition: include/ciri_long_hip.h).  The reads are
+    uploaded once and neither paths nor tasks come back.  -> the dict of arrays of ``SeedIndex.circles`` (circle [n, 16],
+    circle_of_read [n], table [n_circles, 10], kernel_ms), and under 'circles' the table as a list of dicts, ascending in (contig, start,
+    end, strand): circ_id 'contig:start-end' (1-based, inclusive), contig, start (0-based), end (exclusive), strand, signal, reads (how
+    many reads of the batch name this circle), score (the greatest J among them) and first_read (the lowest of their indices).  A
+    read's circle is the one ``call_circles`` gives it; ``circle_dicts`` turns the rows into its dicts."""
+    got = index.circles(hip._packed(reads), **parameters)
+    table = got['table']
+    out = dict(got)
+    out['circles'] = [{'circ_id': '%s:%d-%d' % (index.contigs[int(row[0])], int(row[1]) + 1, int(row[2])), 'contig': index.contigs[int(row[0])], 'start': int(row[1]),
+                       'end': int(row[2]), 'strand': '-' if row[3] else '+', 'signal': signal, 'reads': int(row[6]), 'score': int(row[7]), 'first_read': int(row[8])}
+                      for row, signal in zip(table, _signals(index, table))]
+    return out
+
+
+def circle_dicts(index, result):
+    """what ``call_circles_batch`` (or ``SeedIndex.circles``) gave -> per read None, or the dict ``call_circles`` gives without its 'path'"""
+    rows = result['circle']
+    found = [r for r in range(len(rows)) if rows[r, 0] == 0]
+    out = [None] * len(rows)
+    for r, signal in zip(found, _signals(index, [rows[r, 1:] for r in found])):
+        contig, start, end = index.contigs[int(rows[r, 1])], int(rows[r, 2]), int(rows[r, 3])
+        out[r] = {'circ_id': '%s:%d-%d' % (contig, start + 1, end), 'contig': contig, 'start': start, 'end': end, 'strand': '-' if rows[r, 4] else '+',
+                  'signal': signal, 'score': int(rows[r, 7]), 'read_pos': int(rows[r, 8])}
+    return out
+
+
 def map_spliced(index, reads, context=None, refine=False, **parameters):
     """reads -> chains -> paths -> exons: link_reads (its parameters), then for the best path of each read every piece aligned between
     its outer anchors -- the query is the strand's read letters from the start of the piece's first chain to the end of its last, the

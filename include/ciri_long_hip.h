@@ -738,6 +738,43 @@ int clh_seed_junction_batch(clh_seed_index* index, int32_t n_reads, const int8_t
                             const int64_t* task, const clh_junction_opts* opts, const clh_splice* splice, int64_t* out, float* kernel_ms);
 int clh_seed_junction_info(int64_t* out);
 
+/* ---- K7c: the circles of a read batch in one device pass, with read counts (csrc/seed_circle.hip) ---------
+ * The plain statement is tests/circle_check.py.  The reads are uploaded once; sketch, look-up, chains, links, the best path of every read,
+ * its K7j tasks, K7j, the flanking dinucleotides and the table of the distinct circles all run on the device, in the shares of
+ * clh_seed_link_batch, and what comes back is one row of 16 words per read and one row per distinct circle.  The definitions restate what
+ * clh_seed_link_batch, the host steps of ciri_long_amd.seed.call_circles and clh_seed_junction_batch compute between them, k the index's
+ * k-mer length.  For read r of L letters, its segments 2 r (plus) and 2 r + 1 (minus) linked as clh_seed_link_batch links them:
+ *   Best path.  The candidates are the paths of both segments whose score (link_rows[..][6] at pos == 0) is at least min_path_score (which
+ *     may be negative); the best is the least under (-score, minus, x_first of the path's pos-0 chain, path index).  None: status 1.
+ *   Tasks.  Every chain i of that path with kind == 3 and j = pred_i, in ascending pos, gives the task
+ *     (r, minus, contig, x1_j - k, y1_j - k, x0_i + k, y0_i + k, 0).  None: status 2.
+ *   Junctions.  Each task is answered by K7j exactly as clh_seed_junction_batch answers it (above).
+ *   Winner.  Among the tasks of K7j status 0 the one of greatest J, among equals the first in path order.  None: status 3.
+ *   Flanks.  after = contig[donor_end : donor_end + 2), before = contig[acceptor_start - 2 : acceptor_start), letters as K7j reads them.
+ *     Strand +: donor = after, acceptor = before; strand -: donor = revcomp(before), acceptor = revcomp(after), code 4 stays 4.  A
+ *     dinucleotide is coded 5 c0 + c1, and -1 where fewer than two of its letters lie inside the contig.
+ *   read_pos.  With y = yd + t: L - y on the minus strand, y otherwise: the split in the read as given.
+ * circle[n][16]: status 0-3, contig, start (acceptor_start), end (donor_end, exclusive), strand (0 +, 1 -), donor code, acceptor code, J,
+ * read_pos, the path's minus, the path's score, chains in the path, its back-splice links, how many of those K7j refined, the winner's
+ * ordinal among them, 0.  At status 1 words 1-14 are 0; at status 2 and 3 words 9-13 are filled and the rest are 0.
+ * The table groups the status-0 rows by (contig, start, end, strand) exactly: table[n_circles][10] = contig, start, end, strand, donor,
+ * acceptor, reads (the count), the greatest J, the lowest read index, 0, ascending in (contig, start, end, strand);
+ * circle_of_read[n] is a read's row in the table, or -1.  The grouping runs over the rows of the whole batch after the last share and does
+ * not depend on how the batch was cut.  clh_seed_circle_table_fetch(cap >= n_circles) gives the table of the last call (the convention
+ * of clh_seed_batch_fetch); a cap too small is CLH_E_CAPACITY.
+ * The call refuses what clh_seed_link_batch and clh_seed_junction_batch refuse, with their codes; an index of 2^23 contigs or more is
+ * CLH_E_CAPACITY; n == 0 is success with n_circles = 0.  Capacity goes through chain_opts->workspace_bytes as in clh_seed_link_batch;
+ * a read owns max(max_chains - 1, 1) task slots (160 bytes each) of its share, and an allocation the device refuses is CLH_E_CAPACITY
+ * with its byte count.  Every index a kernel takes from a row is checked before it is followed; a read whose rows fail, and any row left
+ * unwritten, is CLH_E_HIP, never returned.  kernel_ms (float[3], may be NULL): HIP events around the select / task-build kernels, the
+ * junction kernels, and the finalise and table kernels alone, summed over the shares.  Between the first two, kJxClasses task counters
+ * come back to the host per share, by which the junction launches are sized; the paths and the tasks do not come back.
+ * clh_seed_index_timing keeps its five slots: seeds, chain and link are those of this call's shares. */
+int clh_seed_circle_batch(clh_seed_index* index, int32_t n, const int8_t* reads, const int64_t* read_off, const clh_chain_opts* chain_opts,
+                          const clh_link_opts* link_opts, const clh_junction_opts* junction_opts, const clh_splice* splice, int64_t min_path_score,
+                          int64_t* circle, int64_t* circle_of_read, int64_t* n_circles, float* kernel_ms);
+int clh_seed_circle_table_fetch(clh_seed_index* index, int64_t cap, int64_t* table);
+
 
 /* ASCII -> codes exactly as ssw_wrap.py:234-252 (A/a C/c G/g T/t N/n, anything else 4), on the host. */
 void clh_encode_dna(const char* seq, int64_t len, int8_t* out);
