@@ -96,11 +96,22 @@ def label(name):
     return [r for r, (lab, _) in enumerate(reads()) if lab == name][0]
 
 
+def link_of(max_chains=None):
+    """LINK, with another max_chains where one is given"""
+    return dict(LINK) if max_chains is None else dict(LINK, max_chains=max_chains)
+
+
+@functools.lru_cache(maxsize=None)
+def indexed():
+    """-> (sc.Genome, its index)"""
+    genome = sc.Genome(world()[0])
+    return genome, sc.index(genome.codes, K, W)
+
+
 @functools.lru_cache(maxsize=None)
 def checked():
     """-> (sc.Genome, its index, per read the checker's link_reads paths at LINK): computed once"""
-    genome = sc.Genome(world()[0])
-    idx = sc.index(genome.codes, K, W)
+    genome, idx = indexed()
     return genome, idx, [jcases.lc.link_read(genome, idx, sc.encode(t), K, W, MAX_OCC, **dict(LINK)) for t in texts()]
 
 
@@ -112,18 +123,19 @@ def refined(scoring=False):
 
 
 @functools.lru_cache(maxsize=None)
-def segments():
-    """-> per read the raw chains of its two segments at LINK's chain parameters"""
-    genome, idx, _ = checked()
-    chain_p, _, _ = cc.split(LINK)
+def segments(max_chains=None):
+    """-> per read the raw chains of its two segments at LINK's chain parameters (max_chains: another than LINK's)"""
+    genome, idx = indexed()
+    chain_p, _, _ = cc.split(link_of(max_chains))
     return [jcases.lc.segment_chains(genome, idx, sc.encode(t), K, W, MAX_OCC, **chain_p) for t in texts()]
 
 
 @functools.lru_cache(maxsize=None)
-def want(scoring=False, min_path_score=0):
-    """-> (circle rows, circle_of_read, table) of the planted reads by the checker"""
-    genome, _, _ = checked()
-    _, link_p, junction_p = cc.split(dict(LINK, **(SCORING if scoring else {})))
-    rows = [cc.row(genome, sc.encode(t), r, segs, K, min_path_score, link_p, junction_p) for r, (t, segs) in enumerate(zip(texts(), segments()))]
+def want(scoring=False, min_path_score=0, max_chains=None):
+    """-> (circle rows, circle_of_read, table) of the planted reads by the checker (max_chains: another than LINK's)"""
+    genome, _ = indexed()
+    _, link_p, junction_p = cc.split(dict(link_of(max_chains), **(SCORING if scoring else {})))
+    rows = [cc.row(genome, sc.encode(t), r, segs, K, min_path_score, link_p, junction_p)
+            for r, (t, segs) in enumerate(zip(texts(), segments(max_chains)))]
     tab, where = cc.table(rows)
     return rows, where, tab

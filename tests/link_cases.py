@@ -182,9 +182,12 @@ def isolated_case(n=64):
     return [chain(t, 40 + t % 3, 100, 200, 10, 110) for t in range(n)]
 
 
-def fuzz_segments(seed, count, most=64, wide=False):
+FUZZ_SCORES = (0, 1, 5, 17, 17, 40, 40, 90)
+
+
+def fuzz_segments(seed, count, most=64, wide=False, scores=FUZZ_SCORES):
     """segments of 0..most chains drawn from small ranges, so that equal keys, equal values and equal F abound (for FUZZ_SMALL); wide: the
-    chains are spread far enough for introns and back-splices at the defaults"""
+    chains are spread far enough for introns and back-splices at the defaults; scores: what a chain's score is drawn from"""
     rng = random.Random(seed)
     out = []
     for s in range(count):
@@ -192,7 +195,7 @@ def fuzz_segments(seed, count, most=64, wide=False):
         mine = []
         for _ in range(n):
             x0, y0 = rng.randrange(0, 400000 if wide else 40), rng.randrange(0, 3000 if wide else 24)
-            mine.append(chain(rng.randrange(2), rng.choice((0, 1, 5, 17, 17, 40, 40, 90)), x0, x0 + rng.randint(1, 300 if wide else 9), y0,
+            mine.append(chain(rng.randrange(2), rng.choice(scores), x0, x0 + rng.randint(1, 300 if wide else 9), y0,
                               y0 + rng.randint(1, 300 if wide else 9)))
         out.append(mine)
     return out

@@ -123,8 +123,12 @@ def test_refusals(world):
         bad[1, 2, field] = value
         with pytest.raises(hip.ClhError, match=r'\(-2\).*segment 1, chain 2'):
             world.link_rows(np.array([3, 3]), bad)
-        bad[1, 2, field] = (1 << 40) - 1 if value > 0 else 0 if field != 3 else 1 - (1 << 40)      # on the bound: taken
-        world.link_rows(np.array([3, 3]), bad)
+        bad[1, 2, field] = (1 << 40) - 1 if value > 0 else 0 if field != 3 else 1 - (1 << 40)      # on the bound: taken, and answered as the checker does
+        got = world.link_rows(np.array([3, 3]), bad)
+        for s in (0, 1):
+            mine = [cases.chain(*(int(bad[s, c, f]) for f in (2, 3, 5, 7, 6, 8))) for c in range(3)]
+            want, paths = lc.rows(mine, world.k)
+            assert got['link_seg'][s].tolist() == [3, paths, 0, 0] and got['link_rows'][s].tolist() == want, (field, value, s)
     assert_rows(world, [cases.shared_predecessor_case()], max_skew=0, max_intron=0, max_circle=0, max_query_gap=0, max_overlap=0, intron_cost=0,
                 backsplice_cost=0)
 
